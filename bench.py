@@ -23,7 +23,11 @@ off); every rank reports its device (`config.devices`: PCI bus ids, asserted dis
 (`rank_ms`: [min, median, max] over the ranks of the HIP-event time of the engine's launches, so a straggler is visible
 beside the max-over-ranks wall time that `value` is computed from).
 
-Extra objects in the line:
+A plain run does only what the headline needs: set up, warm up, time the --steps steps, write the outputs (--dump-outputs
+DIR: what the timed path returned in its last step, as DIR/<name>.npy; the inputs are seeded, so two builds compare output
+for output) and print the line.  The objects below are null in it; --full measures them after the timed steps.
+
+Extra objects in the line (--full):
   other_configs the other single-GPU configurations of BASELINE.json (default N = 1 run only): a2j_b64 (config 2), fcos_b16
                 (config 3), pipeline_b1 (the reference caller's own batch, ros_demo.py:270) -- hipGraph replay, median of five
                 groups of steps; value, ms_per_step and the dominant kernel's roofline fraction of each -- and pipeline_b32_f32:
@@ -99,8 +103,14 @@ def parse():
                          "replayed step, the form rehearsed since round 3)")
     ap.add_argument("--init-timeout", type=float, default=180.0,
                     help="--gpus > 1: seconds the process group may take to start (rendezvous + first collective) per attempt")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: also the roofline, other_configs, dropin and cpu_baseline objects (a plain run "
+                         "leaves them null); the --no-* switches below drop single objects of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all; rank 0)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the other single-GPU BASELINE configurations (a2j_b64, fcos_b16, pipeline_b1) of the default run")
+                    help="skip the other single-GPU BASELINE configurations (a2j_b64, fcos_b16, pipeline_b1) of the --full run")
     ap.add_argument("--stub-engine", action="store_true",
                     help="TEST ONLY: a CPU stand-in for the engine (sleeps, deterministic records) so that the N-rank plumbing of "
                          "this file -- ladder, rendezvous, gather, line -- runs on gloo without a GPU; the line says so")
@@ -873,10 +883,81 @@ def other_configs_leg(args, info, dev, sds=None, hip=None):
     return out
 
 
+DUMP_BUDGET = 64 << 20     # bytes that --dump-outputs may write in all
+DUMP_LEFT_OUT = ("candidates", "host_record", "host")
+
+
+def step_outputs(out):
+    """What a caller of the timed path receives from one step, as named host arrays: a tensor as it is (float64 for float64
+    and for integer results, which it holds exactly; float32 otherwise), a result object field by field, a tuple element by
+    element.  Left out: the detector's internal candidates (rows beyond their count are never written) and the pinned byte
+    copies of results that are already there (host_record).  Detection rows at or beyond count[i] are undefined
+    (ops.alloc_detections) and are written as zeros."""
+    import dataclasses
+
+    import numpy as np
+    arrays = {}
+
+    def fields(v):
+        if dataclasses.is_dataclass(v):
+            return [(f.name, getattr(v, f.name)) for f in dataclasses.fields(v)]
+        if hasattr(type(v), "__slots__"):
+            return [(k, getattr(v, k)) for k in type(v).__slots__]
+        return list(getattr(v, "__dict__", {}).items())
+
+    def walk(name, v):
+        if v is None or type(v).__name__ == "Candidates":
+            return
+        if torch.is_tensor(v):
+            t = v.detach().cpu()
+            arrays[name or "out"] = t.numpy().astype(np.float32 if t.is_floating_point() and t.dtype != torch.float64
+                                                      else np.float64)
+        elif isinstance(v, (tuple, list)):
+            for i, x in enumerate(v):
+                walk(f"{name or 'out'}{i}", x)
+        else:
+            sub = {k: x for k, x in fields(v) if k not in DUMP_LEFT_OUT}
+            if type(v).__name__ == "Detections":
+                n, cap = sub["scores"].shape[:2]
+                written = torch.arange(cap)[None, :] < sub["count"].cpu()[:, None]
+                for k, x in sub.items():
+                    if torch.is_tensor(x) and tuple(x.shape[:2]) == (n, cap):
+                        x = x.detach().cpu().clone()
+                        x[~written] = 0
+                        sub[k] = x
+            for k, x in sub.items():
+                walk(f"{name}_{k}" if name else k, x)
+    walk("", out)
+    return arrays
+
+
+def dump_outputs(arrays, out_dir):
+    """--dump-outputs: DIR/<name>.npy per array.  Above DUMP_BUDGET in all, every array keeps the same fixed, seeded sample of
+    its leading rows (arrays of equal length keep the same rows; DIR/<name>.rows.npy holds their indices)."""
+    import numpy as np
+    out_dir.mkdir(parents=True, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, 0.95 * DUMP_BUDGET / max(1, total))
+    picks = {}
+    for name in sorted(arrays):
+        a = arrays[name]
+        if frac < 1.0 and a.ndim >= 1 and a.shape[0] > 1:
+            n = a.shape[0]
+            if n not in picks:
+                picks[n] = np.sort(np.random.default_rng(n).choice(n, max(1, int(n * frac)), replace=False))
+            a = a[picks[n]]
+            np.save(out_dir / f"{name}.rows.npy", picks[n].astype(np.float64))
+        np.save(out_dir / f"{name}.npy", a)
+    print(f"[bench] --dump-outputs: {len(arrays)} arrays of the last timed step in {out_dir}"
+          + (f" (a seeded sample of {frac:.0%} of the rows: {total} bytes in all)" if frac < 1.0 else ""), file=sys.stderr, flush=True)
+
+
 def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "HN_BENCH_WORKER" not in os.environ:
         sys.exit(supervise(args))
     worker(args)
@@ -1001,10 +1082,13 @@ def worker(args):
     ev["on"] = world > 1
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        full_step()
+        last = full_step()
     fence()
     elapsed = time.perf_counter() - t0
     ev["on"] = False
+    if args.dump_outputs and rank == 0:
+        # (before anything else runs: a replayed step's static outputs would be overwritten by the legs below)
+        dump_outputs(step_outputs(last), Path(args.dump_outputs))
     rank_ms = None
     if world > 1:
         on_dev = args.dist_backend == "nccl" and on_gpu
@@ -1049,10 +1133,10 @@ def worker(args):
         if rccl_ranks != world or not bool(gathered["rows"].all()):
             raise SystemExit(f"all-gather returned {gathered['rows'].numel()} rows for {world} ranks x {batch} frames")
     roof = None
-    if on_gpu and not args.no_roofline and not args.native and (not args.graph or "eager_step" in info):
+    if args.full and on_gpu and not args.no_roofline and not args.native and (not args.graph or "eager_step" in info):
         roof = roofline_leg(info.get("eager_step", step) if args.graph else step, max(1, min(args.steps, 3)),
                             1e3 * elapsed / args.steps, not args.no_clock_sample, terms=1 if args.precision == "f16x1" else 3)
-    single = rank == 0 and world == 1 and on_gpu
+    single = args.full and rank == 0 and world == 1 and on_gpu
     dropin = None
     if single and args.workload == "pipeline" and not args.no_dropin and not args.native and not args.graph:
         dropin = dropin_leg(args, sds, dev, batch)

@@ -95,10 +95,10 @@ def test_bench_refuses_world_size_mismatch():
 
 def test_bench_line_contract():
     """The one JSON line of the driver contract: metric / value / unit / n_gpus / steps / warmup / ms_per_step /
-    higher_is_better / scaling / vs_baseline / dtype / data / config.workload, plus the roofline and cpu_baseline
+    higher_is_better / scaling / vs_baseline / dtype / data / config.workload, plus (--full) the roofline and cpu_baseline
     objects with their required keys; clock sampled in-kernel; parity figures over the CPU sample."""
     r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--cpu-frames", "2"], capture_output=True, text=True, timeout=900)
+                        "--cpu-frames", "2", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -157,6 +157,36 @@ def test_bench_line_contract():
     assert "ONE pass" in cpu["sample"] and cpu["batch1"]["value"] > 0 and "median of 5" in cpu["batch1"]["sample"]
     assert cpu["parity"]["keypoints_within_tolerance"] is True
     assert cpu["live_batch1"]["value"] > 0 and 0 < cpu["live_batch1"]["lifter_ms"] < cpu["live_batch1"]["ms_per_frame"]
+
+
+def test_bench_plain_run_dumps_what_the_engine_returns(tmp_path, fcos_sd, a2j_sd):
+    """The plain line (no --full): the headline only, the other objects null; --dump-outputs holds the last timed step's
+    results, bit for bit what the same engine returns for the same seeded frames in this process."""
+    import numpy as np
+    from hn_amd import synth
+    from hn_amd.a2j_engine import A2JEngine
+    from hn_amd.fcos_engine import FCOSEngine
+    from hn_amd.pipeline import HandNetEngine
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "2",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "frames/s"
+    assert d["roofline"] is None and d["other_configs"] is None and d["dropin"] is None and d["cpu_baseline"] is None
+    eng = HandNetEngine(FCOSEngine(fcos_sd, 3, device="cuda"), A2JEngine(a2j_sd, device="cuda"), 3)
+    ref = eng.forward_device(synth.make_rgb(2, seed=1000).cuda(), synth.make_depth(2, seed=2000).cuda())
+    torch.cuda.synchronize()
+    for name in ("keypoints", "crop_box", "has_hand", "crops_nhwc"):
+        got, want = np.load(out / f"{name}.npy"), getattr(ref, name).cpu().numpy()
+        assert got.dtype in (np.float32, np.float64) and got.shape == want.shape, name
+        assert np.array_equal(got, want.astype(got.dtype), equal_nan=True), name
+    cnt = ref.detections.count.cpu().numpy()
+    boxes = np.load(out / "detections_boxes.npy")
+    for i, k in enumerate(cnt):
+        assert np.array_equal(boxes[i, :k], ref.detections.boxes[i, :k].cpu().numpy()) and not boxes[i, k:].any()
 
 
 def test_four_ranks_equal_single_process_batch(tmp_path, fcos_sd, a2j_sd):

@@ -5,7 +5,7 @@ for rep in 1 2; do
   echo "range: $(HN_HALO_STAGGER_RANGE=1 $P 2>&1 | tail -1)"
   echo "odd:   $(HN_HALO_STAGGER_ODD=1 $P 2>&1 | tail -1)"
 done
-B="python bench.py --no-dropin --no-cpu-baseline --no-other-configs --steps 10 --warmup 3"
+B="python bench.py --full --no-dropin --no-cpu-baseline --no-other-configs --steps 10 --warmup 3"
 for rep in 1 2; do
   echo "bench base:  $($B 2>/dev/null | python -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["ms_per_step"], d["roofline"]["stages"]["resnet34_body"])')"
   echo "bench range: $(HN_HALO_STAGGER_RANGE=1 $B 2>/dev/null | python -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["ms_per_step"], d["roofline"]["stages"]["resnet34_body"])')"

@@ -10,7 +10,7 @@ done
 J='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["value"], d["ms_per_step"], {k: v["ms_per_step"] for k, v in (d["roofline"] or {}).get("stages", {}).items()})'
 for rep in 1 2; do
   for f in "" "HN_CONV_NO_STREAM=1"; do
-    echo "pipeline b32 ${f:-stream}: $(env $f python bench.py --no-dropin --no-cpu-baseline --no-other-configs --steps 10 --warmup 3 2>/dev/null | python -c "$J")"
-    echo "a2j b64 ${f:-stream}: $(env $f python bench.py --workload a2j --no-cpu-baseline --steps 50 --warmup 10 2>/dev/null | python -c "$J")"
+    echo "pipeline b32 ${f:-stream}: $(env $f python bench.py --full --no-dropin --no-cpu-baseline --no-other-configs --steps 10 --warmup 3 2>/dev/null | python -c "$J")"
+    echo "a2j b64 ${f:-stream}: $(env $f python bench.py --full --workload a2j --no-cpu-baseline --steps 50 --warmup 10 2>/dev/null | python -c "$J")"
   done
 done
