@@ -8,6 +8,7 @@
 //   hn_fcos_nms / hn_nms   : torchvision.ops.batched_nms / nms (call site fcos.py:635),
 //                            resize_boxes (fcos.py:770-783)
 //   hn_crop_resize         : handnet_pipeline/handnet_pipeline.py:74-105
+//   hn_crop_resize_hands   : the same rule for the first K hand detections of each frame (K crops per frame)
 #include "hn_common.h"
 
 #pragma clang fp contract(off)
@@ -936,6 +937,111 @@ __global__ __launch_bounds__(256) void crop_gather_kernel(const float* __restric
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// hands: slot k of frame i = the k-th hand-label detection of the frame's score-ordered list
+// ---------------------------------------------------------------------------------------
+constexpr int kMaxHands = 16;
+
+// crop_box_kernel's padding for one detection box: handnet_pipeline.py:88-97 in fp32 (no contraction in this file);
+// returns 0 when the clamped inclusive slice is empty (o[] then zero)
+__device__ __forceinline__ int pad_hand_box(const float* b, int h, int w, long long o[4]) {
+  long long b0 = (long long)b[0], b1 = (long long)b[1], b2 = (long long)b[2], b3 = (long long)b[3];
+  const long long bw = b2 - b0, bh = b3 - b1;
+  const float pw = 0.4f * (float)bw, phh = 0.4f * (float)bh;
+  const float t0 = (float)b0 - pw, t1 = (float)b1 - phh;
+  const float t2 = (float)b2 + pw, t3 = (float)b3 + phh;
+  b0 = t0 > 0.f ? (long long)t0 : 0;
+  b1 = t1 > 0.f ? (long long)t1 : 0;
+  b2 = t2 < (float)w ? (long long)t2 : (long long)w;
+  b3 = t3 < (float)h ? (long long)t3 : (long long)h;
+  const long long ch = (b3 + 1 < h ? b3 + 1 : h) - b1, cwid = (b2 + 1 < w ? b2 + 1 : w) - b0;
+  const int ok = (ch > 0 && cwid > 0 && b1 >= 0 && b0 >= 0) ? 1 : 0;
+  o[0] = ok ? b0 : 0; o[1] = ok ? b1 : 0; o[2] = ok ? b2 : 0; o[3] = ok ? b3 : 0;
+  return ok;
+}
+
+__device__ __forceinline__ void write_slot(long slot, const long long b[4], int ok, float sc, int idx,
+                                           long long* __restrict__ crop_box, int* __restrict__ has_hand,
+                                           float* __restrict__ score, int* __restrict__ det_index) {
+  typedef long long i64x2 __attribute__((ext_vector_type(2)));
+  i64x2* cb = reinterpret_cast<i64x2*>(crop_box + slot * 4);
+  cb[0] = i64x2{b[0], b[1]};
+  cb[1] = i64x2{b[2], b[3]};
+  has_hand[slot] = ok;
+  score[slot] = ok ? sc : 0.f;
+  det_index[slot] = ok ? idx : -1;
+}
+
+// One wave64 per frame.  The survivor list is walked 64 entries at a time: a ballot of the hand-label lanes, and a
+// lane's rank among the frame's hand detections is the popcount of the matching lanes below it plus those of earlier
+// chunks.  The walk ends as soon as max_hands are found (real frames: the first chunk); slots left over are zeroed.
+__global__ __launch_bounds__(64) void hand_slots_kernel(const float* __restrict__ det_boxes,
+                                                        const float* __restrict__ det_scores,
+                                                        const int* __restrict__ det_labels,
+                                                        const int* __restrict__ det_count, int cap, int hand_label,
+                                                        int max_hands, int h, int w, long long* __restrict__ crop_box,
+                                                        int* __restrict__ has_hand, float* __restrict__ score,
+                                                        int* __restrict__ det_index) {
+  const int img = blockIdx.x, lane = threadIdx.x;
+  const int cnt = min(det_count[img], cap);
+  const long row = (long)img * cap;
+  int found = 0;
+  for (int base = 0; base < cnt && found < max_hands; base += 64) {
+    const int i = base + lane;
+    const bool hand = i < cnt && det_labels[row + i] == hand_label;
+    const unsigned long long mask = __ballot(hand);
+    const int rank = found + __popcll(mask & ((1ull << lane) - 1ull));
+    if (hand && rank < max_hands) {
+      long long b[4];
+      const int ok = pad_hand_box(det_boxes + (row + i) * 4, h, w, b);
+      write_slot((long)img * max_hands + rank, b, ok, det_scores[row + i], i, crop_box, has_hand, score, det_index);
+    }
+    found += __popcll(mask);
+  }
+  if (lane >= found && lane < max_hands) {
+    const long long z[4] = {0, 0, 0, 0};
+    write_slot((long)img * max_hands + lane, z, 0, 0.f, -1, crop_box, has_hand, score, det_index);
+  }
+}
+
+// crop_gather_kernel over n * max_hands crops: crop `slot` reads frame slot / max_hands
+__global__ __launch_bounds__(256) void hand_crop_gather_kernel(const float* __restrict__ depth,
+                                                               const long long* __restrict__ crop_box,
+                                                               const int* __restrict__ has_hand, int n, int max_hands,
+                                                               int h, int w, int in_ch, int reorder, int out, int c4,
+                                                               float* __restrict__ crops) {
+  const long total = (long)n * max_hands * out * out;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int ox = (int)(i % out);
+    const long t = i / out;
+    const int oy = (int)(t % out);
+    const long slot = t / out;
+    const long img = slot / max_hands;
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    if (has_hand[slot]) {
+      const long long* b = crop_box + slot * 4;
+      const int x1 = (int)b[0], y1 = (int)b[1];
+      const int cw = (int)((b[2] + 1 < w ? b[2] + 1 : w) - b[0]);
+      const int ch = (int)((b[3] + 1 < h ? b[3] + 1 : h) - b[1]);
+      int sy, sx;
+      if (ch == out) sy = oy; else if (out == 2 * ch) sy = oy >> 1;
+      else sy = min((int)floorf((float)oy * ((float)ch / (float)out)), ch - 1);
+      if (cw == out) sx = ox; else if (out == 2 * cw) sx = ox >> 1;
+      else sx = min((int)floorf((float)ox * ((float)cw / (float)out)), cw - 1);
+      const long pix = (long)(y1 + sy) * w + (x1 + sx);
+      for (int c = 0; c < in_ch; ++c) {
+        const int src_c = (reorder && c < 3) ? 2 - c : c;
+        o[c] = depth[(img * in_ch + src_c) * h * w + pix];
+      }
+    }
+    *reinterpret_cast<f32x4*>(crops + i * c4 * 4) = o;
+    for (int q = 1; q < c4; ++q) {
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<f32x4*>(crops + i * c4 * 4 + q * 4) = z;
+    }
+  }
+}
+
 int grid_for(long total, int block) {
   const long g = (total + block - 1) / block;
   return (int)(g < 8192 ? (g > 0 ? g : 1) : 8192);
@@ -1196,5 +1302,26 @@ extern "C" int hn_crop_resize(const float* det_boxes, const int32_t* det_labels,
   hipLaunchKernelGGL(crop_gather_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, depth,
                      (const long long*)crop_box, has_hand, n, h, w, in_ch, reorder_bgr, out, cpad / 4, crops);
   HN_CHECK_LAUNCH("crop_gather_kernel");
+  return HN_OK;
+}
+
+extern "C" int hn_crop_resize_hands(const float* det_boxes, const float* det_scores, const int32_t* det_labels,
+                                    const int32_t* det_count, int cap, int hand_label, int max_hands, const float* depth,
+                                    int n, int in_ch, int reorder_bgr, int h, int w, int out, int cpad, int64_t* crop_box,
+                                    int32_t* has_hand, float* score, int32_t* det_index, float* crops, void* stream) {
+  HN_CHECK_ARG(det_boxes && det_scores && det_labels && det_count && depth && crop_box && has_hand && score && det_index && crops,
+               "hn_crop_resize_hands: null pointer");
+  HN_CHECK_ARG(max_hands >= 1 && max_hands <= kMaxHands, "max_hands must be 1..%d (got %d)", kMaxHands, max_hands);
+  HN_CHECK_ARG(n > 0 && h > 0 && w > 0 && out > 0 && cap > 0 && cpad >= 4 && cpad % 4 == 0, "bad dims");
+  HN_CHECK_ARG(in_ch >= 1 && in_ch <= 4, "depth image must have 1..4 channels (got %d)", in_ch);
+  HN_CHECK_ARG((uintptr_t)crop_box % 16 == 0 && (uintptr_t)crops % 16 == 0, "crop_box / crops must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(hand_slots_kernel, dim3(n), dim3(64), 0, st, det_boxes, det_scores, det_labels, det_count, cap,
+                     hand_label, max_hands, h, w, (long long*)crop_box, has_hand, score, det_index);
+  HN_CHECK_LAUNCH("hand_slots_kernel");
+  const long total = (long)n * max_hands * out * out;
+  hipLaunchKernelGGL(hand_crop_gather_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, depth,
+                     (const long long*)crop_box, has_hand, n, max_hands, h, w, in_ch, reorder_bgr, out, cpad / 4, crops);
+  HN_CHECK_LAUNCH("hand_crop_gather_kernel");
   return HN_OK;
 }

@@ -1461,6 +1461,38 @@ extern "C" int hn_handnet_forward(hn_model* m, const float* rgb, const float* de
   });
 }
 
+extern "C" int hn_handnet_forward_hands(hn_model* m, const float* rgb, const float* depth, int n, int h, int w, int max_hands,
+                                        float* keypoints, int64_t* crop_box, int32_t* has_hand, float* score, void* stream) {
+  HN_CHECK_ARG(m && rgb && depth && keypoints && crop_box && has_hand && score, "hn_handnet_forward_hands: null pointer");
+  HN_CHECK_ARG((m->cfg.parts & (HN_MODEL_FCOS | HN_MODEL_A2J)) == (HN_MODEL_FCOS | HN_MODEL_A2J), "model needs both HN_MODEL_FCOS and HN_MODEL_A2J");
+  HN_CHECK_ARG(n > 0 && h > 0 && w > 0, "bad image batch");
+  HN_CHECK_ARG(max_hands >= 1 && max_hands <= 16, "max_hands must be 1..16 (got %d)", max_hands);
+  const int cap = (int)hn_fcos_capacity(m, h, w);
+  const int k = n * max_hands;
+  const std::string key = "hands:" + std::to_string(n) + "x" + std::to_string(max_hands) + "x" + std::to_string(h) + "x" +
+                          std::to_string(w);
+  return run_planned(m, key, stream, [&](Ctx& cx) -> int {
+    FcosOut out;
+    out.cap = cap;
+    out.boxes = (float*)alloc_bytes(cx, (size_t)n * cap * 16);
+    out.scores = (float*)alloc_bytes(cx, (size_t)n * cap * 4);
+    out.labels = (int32_t*)alloc_bytes(cx, (size_t)n * cap * 4);
+    out.sides = (int32_t*)alloc_bytes(cx, (size_t)n * cap * 4);
+    out.level = (int32_t*)alloc_bytes(cx, (size_t)n * cap * 4);
+    out.count = (int32_t*)alloc_bytes(cx, (size_t)n * 4);
+    HN_TRY(fcos_graph(cx, rgb, n, h, w, out));
+    int32_t* det_index = (int32_t*)alloc_bytes(cx, (size_t)k * 4);
+    T crops;
+    crops.n = k; crops.h = kCrop; crops.w = kCrop; crops.c = 4; crops.ps = 4; crops.split = false;
+    crops.p = alloc_bytes(cx, (size_t)k * kCrop * kCrop * 16);
+    if (!cx.dry)
+      HN_TRY(hn_crop_resize_hands(out.boxes, out.scores, out.labels, out.count, cap, m->cfg.num_classes - 1, max_hands, depth, n,
+                                  m->cfg.rgbd ? 4 : 1, m->cfg.rgbd ? 1 : 0, h, w, kCrop, 4, crop_box, has_hand, score,
+                                  det_index, (float*)crops.p, cx.stream));
+    return a2j_graph(cx, crops, has_hand, keypoints, has_hand);
+  });
+}
+
 extern "C" int hn_handnet_forward_xyz(hn_model* m, const float* rgb, const float* depth, int n, int h, int w, const float* paras,
                                       const hn_convert_opts* opts, float* keypoints, float* image_uvd, float* xyz_mm,
                                       int64_t* crop_box, int32_t* has_hand, void* stream) {

@@ -11,6 +11,10 @@ Constructor and call contract of handnet_pipeline/handnet_pipeline.py:38-116:
   no frame with a hand: (zeros[N,21,3], zeros_like(depth_images), zeros[N,4] float32 on the CPU)
   is_detect or is_3D: returns None (the reference has no such branch either).
 
+Beyond the reference: net.forward_hands(images, depth, max_hands=K) poses the first K hand detections of every frame
+(the reference keeps the first, :84-85) -> keypoints [N,K,21,3], depth_batch of the filled slots, boxes [N,K,4], hand_mask
+[N,K], scores [N,K].
+
 Documented deviations: a batch that MIXES frames with and without a hand raises in the
 reference (torch.stack of a list containing None, :82,111) and an empty crop slice reuses
 the previous frame's crop (:100-105); here such frames simply count as "no hand".
@@ -134,14 +138,17 @@ class HandNet(EngineOwner):
             self._auto_graph_allowed = True
         return self
 
-    def _auto_graph(self, image_shape, depth_shape, on_gpu=True) -> bool:
-        """Whether this call of forward() should run as a graph replay (capturing first if need be)."""
+    def _auto_graph(self, image_shape, depth_shape, on_gpu=True, hands=None) -> bool:
+        """Whether this call of forward() (hands = K: of forward_hands()) should run as a graph replay (capturing first if
+        need be)."""
         eng = self.engine()
-        if not self._auto_graph_allowed or eng.check_range or getattr(self, "_last_sparse", False) or not on_gpu:
+        sparse = getattr(self, "_last_sparse" if hands is None else "_last_sparse_hands", False)
+        if not self._auto_graph_allowed or eng.check_range or sparse or not on_gpu:
             return False
-        if eng.has_graph(image_shape, depth_shape, to_host=True):
+        if (eng.has_graph(image_shape, depth_shape, to_host=True) if hands is None
+                else eng.has_graph_hands(image_shape, depth_shape, hands, to_host=True)):
             return True
-        key = (tuple(image_shape), tuple(depth_shape))
+        key = (tuple(image_shape), tuple(depth_shape)) + (() if hands is None else (hands,))
         if key == getattr(self, "_streak_key", None):
             self._streak += 1
         else:
@@ -198,6 +205,72 @@ class HandNet(EngineOwner):
         else:
             out = self.forward_device(images, depth_images, _to_host=True)
         return self._finish(out, n, depth_images)
+
+    def forward_hands(self, images, depth_images, max_hands: int = 2, is_3D: bool = False, is_detect: bool = False):
+        """forward() for up to max_hands (1..16) hands per frame.  Slot k of frame i is the k-th hand-class detection of
+        frame i in the detector's score order (the reference keeps slot 0 only, handnet_pipeline.py:84-85), padded and
+        cropped as forward() crops it.  images / depth_images as forward() takes them.  Returns
+          keypoints   [N,K,21,3] fp32 on the CPU (zero rows for empty slots)
+          depth_batch [M,1,176,176] (RGB-D: [M,4,176,176]) on the model device: the crops of the M filled slots, frame-major
+                      then rank order ([0,...] when no slot is filled)
+          boxes       [N,K,4] int64 on the CPU (padded, clamped x1,y1,x2,y2; zeros for empty slots)
+          hand_mask   [N,K] bool on the CPU
+          scores      [N,K] fp32 on the CPU (the detections' scores; 0 for empty slots)
+        One device -> host copy and one sync per call; repeated shapes switch to graph replay as forward() does."""
+        if is_detect or is_3D:
+            return None
+        if depth_images is None:
+            raise ValueError("depth_images is required for the ensemble inference branch")
+        k = ops.check_max_hands(max_hands)
+        eng = self.engine()
+        n = len(images)
+        dev = eng.device
+        batch = images if torch.is_tensor(images) else torch.stack([i.float() for i in images])
+        batch, depth = batch.to(dev).float().contiguous(), depth_images.to(dev).float().contiguous()
+        mode = getattr(self, "use_graph", None)
+        graph = bool(mode) if mode is not None else self._auto_graph(batch.shape, depth.shape, True, hands=k)
+        out = None
+        if graph:
+            try:
+                run, s_img, s_dep, out = eng.graphed_hands(batch, depth, k, to_host=True, limit=self.AUTO_GRAPH_MAX_SHAPES)
+                s_img.copy_(batch)
+                s_dep.copy_(depth)
+                run()
+            except ops.RangeError:
+                raise
+            except Exception as e:  # noqa: BLE001 -- whatever made the capture fail, this call would succeed eagerly
+                if mode:
+                    raise
+                self._capture_failed(e)
+                out = None
+        if out is None:
+            out = eng.forward_hands(batch, depth, k, to_host=True)
+        return self._finish_hands(out, n, k, depth)
+
+    def _finish_hands(self, out, n, k, depth):
+        """forward_hands()'s tuple from the step's one host record (see _finish)."""
+        from hn_amd.pipeline import read_hands_tail, read_host_record
+        rows = n * k
+        sel = out.crops_nhwc
+        depth_all = (sel.permute(0, 3, 1, 2) if self.RGBD else sel[..., 0].unsqueeze(1)).contiguous()
+        torch.cuda.current_stream(out.keypoints.device).synchronize()
+        joints = out.keypoints.shape[2]
+        if out.image_uvd is not None:
+            kp, has, box, words, more = read_host_record(out.host_record, rows, joints, extras=True)
+            self.last_converted = {"image_uvd": more[0].view(n, k, joints, 3),
+                                   "xyz_mm": more[1].view(n, k, joints, 3) if len(more) > 1 else None}
+        else:
+            kp, has, box, words = read_host_record(out.host_record, rows, joints)
+        scores, _ = read_hands_tail(out.host_record, rows)
+        mask = has != 0
+        filled = int(mask.sum())
+        self._last_sparse_hands = rows >= 8 and filled * 2 < rows     # (the engine's own threshold for compaction)
+        check_range_contract(kp, words if out.range_flags is not None else None, depth, has_hand=has)
+        if filled == rows:
+            depth_batch = depth_all
+        else:
+            depth_batch = depth_all.index_select(0, mask.nonzero().flatten().to(depth_all.device))
+        return kp.view(n, k, joints, 3), depth_batch, box.view(n, k, 4), mask.view(n, k), scores.view(n, k)
 
     def forward_raw(self, bgr_u8, depth_raw, is_3D: bool = False, is_detect: bool = False):
         """The reference caller's ingest AND its network call in one (ros_demo.py:227-231,266-273): bgr_u8 = the cv_bridge

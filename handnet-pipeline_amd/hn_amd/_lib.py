@@ -12,7 +12,7 @@ from pathlib import Path
 
 from . import build as _build
 
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 TILE_AUTO, TILE_128x128, TILE_128x64, TILE_64x64, TILE_128x32, _TILE_RETIRED_5, TILE_64x128 = range(7)
 HN_FCOS_MAX_LEVELS = 5
@@ -172,6 +172,7 @@ SIGNATURES = {
     "hn_fcos_nms_ratios": (C.c_int, [VP] * 6 + [C.c_int, C.c_int, C.c_double, VP] + [VP] * 9),
     "hn_nms": (C.c_int, [VP, VP, C.c_int, C.c_double, VP, VP, VP, VP]),
     "hn_crop_resize": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, VP] + [C.c_int] * 7 + [VP, VP, VP, VP]),
+    "hn_crop_resize_hands": (C.c_int, [VP, VP, VP, VP] + [C.c_int] * 3 + [VP] + [C.c_int] * 7 + [VP] * 6),
     "hn_stem_image_nhwc4": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP]),
     "hn_stem_image_nhwc4_valid": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP]),
     "hn_pack_depth_nhwc": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, VP]),
@@ -187,6 +188,7 @@ SIGNATURES = {
                                        VP, VP, VP, VP, VP, VP, C.c_int, VP]),
     "hn_a2j_forward": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, VP]),
     "hn_handnet_forward": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP]),
+    "hn_handnet_forward_hands": (C.c_int, [VP, VP, VP] + [C.c_int] * 4 + [VP] * 5),
     "hn_destroy": (C.c_int, [VP]),
     "hn_groupnorm_finalize_rows32_levels": (C.c_int, [C.POINTER(GnLevels), VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, VP]),
     "hn_affine_split_f32_levels": (C.c_int, [C.POINTER(SplitLevels)] + [C.c_int] * 6 + [VP]),

@@ -1,5 +1,5 @@
 """ctypes binding of the MODEL-level C ABI (include/handnet_hip.h: hn_create / hn_load_weight / hn_finalize /
-hn_fcos_forward / hn_a2j_forward / hn_handnet_forward / hn_destroy).
+hn_fcos_forward / hn_a2j_forward / hn_handnet_forward(_hands) / hn_destroy).
 
 The layer graphs live in C++ (csrc/model.hip) and issue the same launches as the Python engines, so this class and
 `HandNetEngine` return bit-identical tensors (tests/test_model_abi_gpu.py); it exists to exercise that ABI from the
@@ -139,6 +139,22 @@ class NativeModel:
             check(self.lib.hn_handnet_forward(self._h, ptr(rgb), ptr(depth), n, h, w, ptr(kp), ptr(box), ptr(has), _stream()),
                   "hn_handnet_forward")
         return kp, box, has
+
+    def handnet_hands(self, rgb, depth, max_hands=2):
+        """hn_handnet_forward_hands: rgb [N,3,H,W], depth [N,1|4,H,W] fp32 GPU -> (keypoints [N,K,J,3], crop_box [N,K,4] int64,
+        has_hand [N,K] int32, score [N,K] fp32); slot k = the k-th hand detection of the frame, K = max_hands.  The count is
+        checked by the library (1..16: RuntimeError otherwise)."""
+        rgb, depth = rgb.float().contiguous(), depth.float().contiguous()
+        n, _, h, w = rgb.shape
+        k = max(int(max_hands), 1)
+        with on_device(self.device):
+            kp = torch.empty((n, k, self.num_joints, 3), device=self.device)
+            box = torch.empty((n, k, 4), device=self.device, dtype=torch.int64)
+            has = torch.empty((n, k), device=self.device, dtype=torch.int32)
+            score = torch.empty((n, k), device=self.device)
+            check(self.lib.hn_handnet_forward_hands(self._h, ptr(rgb), ptr(depth), n, h, w, int(max_hands), ptr(kp), ptr(box),
+                                                    ptr(has), ptr(score), _stream()), "hn_handnet_forward_hands")
+        return kp, box, has, score
 
     def handnet_xyz(self, rgb, depth, paras=None, clamp=False):
         """hn_handnet_forward_xyz: handnet() + the aggregation epilogue's image (u,v,d) and -- with paras = (fx, fy, cx, cy) --

@@ -1195,6 +1195,50 @@ def crop_resize(det: Detections, hand_label, depth, out_size=176, cpad=4, crop_b
     return crop_box, has_hand, crops
 
 
+MAX_HANDS = 16
+
+
+def check_max_hands(max_hands) -> int:
+    """max_hands as an int in 1..MAX_HANDS (the bound of the crop batch: N * K crops of 176 x 176), else ValueError."""
+    try:
+        k = int(max_hands)
+    except (TypeError, ValueError):
+        k = None
+    if k is None or k != max_hands or not 1 <= k <= MAX_HANDS:
+        raise ValueError(f"max_hands must be an integer in 1..{MAX_HANDS} (got {max_hands!r})")
+    return k
+
+
+def crop_resize_hands(det: Detections, hand_label, depth, max_hands, out_size=176, cpad=4, crop_box=None, has_hand=None,
+                      score=None, det_index=None, crops=None, reorder_bgr=False):
+    """crop_resize for the first max_hands hand detections of each frame: slot k of frame i is the k-th detection with label
+    hand_label in frame i's score-ordered list, padded and cut as crop_resize cuts the first.  -> (crop_box [N,K,4] int64,
+    has_hand [N,K] int32, score [N,K] fp32, det_index [N,K] int32 (-1: empty slot), crops [N*K,out,out,cpad] NHWC).
+    An empty slot (no such detection, or an empty padded slice) has zeros everywhere and still uses up its rank."""
+    k = check_max_hands(max_hands)
+    _req(depth, name="depth")
+    n, c, h, w = depth.shape
+    if c not in (1, 4):
+        raise ValueError("depth must be [N,1,H,W] or [N,4,H,W]")
+    cap = det.scores.shape[1]
+    dev = depth.device
+    if crop_box is None:
+        crop_box = torch.empty((n, k, 4), device=dev, dtype=torch.int64)
+    if has_hand is None:
+        has_hand = torch.empty((n, k), device=dev, dtype=torch.int32)
+    if score is None:
+        score = torch.empty((n, k), device=dev, dtype=torch.float32)
+    if det_index is None:
+        det_index = torch.empty((n, k), device=dev, dtype=torch.int32)
+    if crops is None:
+        crops = torch.empty((n * k, out_size, out_size, cpad), device=dev, dtype=torch.float32)
+    check(_lib.load().hn_crop_resize_hands(ptr(det.boxes), ptr(det.scores), ptr(det.labels), ptr(det.count), cap,
+                                           int(hand_label), k, ptr(depth), n, c, 1 if reorder_bgr else 0, h, w, out_size, cpad,
+                                           ptr(crop_box), ptr(has_hand), ptr(score), ptr(det_index), ptr(crops), _stream()),
+          "hn_crop_resize_hands")
+    return crop_box, has_hand, score, det_index, crops
+
+
 def stem_image_nhwc4(x, border=3, out=None, valid=None):
     """fp32 [N,H,W,4] -> stem image fp16 [2 (hi, lo), N, H+2b, W+2b, 4] with a zero border (input of conv_stem_*_split).
     valid [N] int32 (optional): images with valid == 1 that hold a non-finite pixel get valid = 2 (a2j_aggregate then writes

@@ -39,6 +39,26 @@ class HandNetOutput:
     #                                    hn_pack_records rows (crop box 32 B | has_hand | 1 | keypoints), row N = the range words
 
 
+@dataclass
+class HandsOutput:
+    """HandNetEngine.forward_hands: up to K hands per frame.  Slot k of frame i is the k-th hand-label detection of frame i
+    (score order); empty slots (fewer hand detections, or an empty padded slice) are zeros with det_index -1."""
+    keypoints: torch.Tensor   # [N,K,21,3] fp32 device, crop (u,v,d); zero rows for empty slots
+    crops_nhwc: torch.Tensor  # [N*K,176,176,4] fp32 device, frame-major (crop i*K + k = slot k of frame i)
+    crop_box: torch.Tensor    # [N,K,4] int64 device
+    has_hand: torch.Tensor    # [N,K] int32 device: 0 empty, 1 hand, 2 hand whose crop holds non-finite pixels (NaN row)
+    score: torch.Tensor       # [N,K] fp32 device: the slot's detection score (0 when empty)
+    det_index: torch.Tensor   # [N,K] int32 device: the slot's row in `detections` (-1 when empty)
+    #                           (to_host steps: both are views of the device record, rewritten by the engine's next such step)
+    detections: ops.Detections
+    candidates: ops.Candidates
+    range_flags: torch.Tensor = None
+    image_uvd: torch.Tensor = None     # [N,K,21,3] after set_convert()
+    xyz_mm: torch.Tensor = None        # [N,K,21,3] after set_convert(paras=...)
+    host_record: torch.Tensor = None   # to_host steps: pinned uint8; rows 0..N*K-1 = one record per slot, row N*K = the range
+    #                                    words, then score [N*K] fp32 and det_index [N*K] int32 (read_hands_tail)
+
+
 RECORD_BYTES = 296      # hn_amd.dist's per-frame record (box 32 + flags 8 + 21 x 3 fp32 keypoints, padded to 8)
 RECORD_FIELD = 252      # one [21,3] fp32 field; the WIDE record of a converting step appends image (u,v,d) and camera xyz
 
@@ -68,6 +88,24 @@ def read_host_record(rec: torch.Tensor, n: int, joints: int = 21, extras: bool =
         lo = 40 + 4 * j3 * f
         more.append(torch.from_numpy(a[:n, lo:lo + 4 * j3].copy().view(np.float32).reshape(n, joints, 3)))
     return kp, has, box, words, more
+
+
+def hands_record_rows(slots: int, rec_bytes: int) -> int:
+    """Rows of a forward_hands record: one per slot, the range-word row, then the slots' scores and detection ranks."""
+    return slots + 1 + (8 * slots + rec_bytes - 1) // rec_bytes
+
+
+def _hands_tail(rec: torch.Tensor, slots: int):
+    """(score [slots] fp32, det_index [slots] int32) views of a forward_hands record (device or host)."""
+    flat = rec.view(-1)
+    base = (slots + 1) * rec.shape[1]
+    return (flat[base:base + 4 * slots].view(torch.float32), flat[base + 4 * slots:base + 8 * slots].view(torch.int32))
+
+
+def read_hands_tail(rec: torch.Tensor, slots: int):
+    """A synchronised forward_hands host_record -> (score [slots] fp32, det_index [slots] int32), fresh CPU tensors."""
+    score, index = _hands_tail(rec, slots)
+    return score.clone(), index.clone()
 
 
 def range_message(bits: int) -> str:
@@ -187,6 +225,20 @@ class HandNetEngine:
         _tail(keypoints, image_uvd, xyz_mm, has_hand): more launches of the SAME step, issued inside its range scope -- before
         the flag words are collected, so their split producers are covered by the step's range contract (the live step's
         lifter, hn_amd/live.py); its return value is HandNetOutput.tail."""
+        return self._step(images, depth, None, to_host, _record, _tail)
+
+    @ops.device_guarded
+    def forward_hands(self, images, depth: torch.Tensor, max_hands: int = 2, to_host: bool = False, _record=None) -> HandsOutput:
+        """forward_device for up to max_hands (1..16) hands per frame: slot k of frame i is the k-th hand-label detection of
+        frame i in the detector's score order, cropped as forward_device crops the first (max_hands = 1 IS forward_device's
+        crop); A2J runs on the N * max_hands crops with the slots' has_hand mask (capturable), or -- eager, when the previous
+        step filled fewer than half of its slots -- on the filled slots only.  to_host: one record row per slot, the range
+        words, then the scores and detection ranks, in ONE device -> host copy (HandsOutput.host_record; read_host_record /
+        read_hands_tail after a sync)."""
+        return self._step(images, depth, ops.check_max_hands(max_hands), to_host, _record, None)
+
+    def _step(self, images, depth, hands, to_host, _record, _tail):
+        """The body of forward_device (hands None: the top-1 crop, HandNetOutput) and forward_hands (hands = K)."""
         want_c = 4 if self.a2j.rgbd else 1
         if depth.dim() != 4 or depth.shape[1] != want_c or depth.shape[0] != len(images):
             raise ValueError(f"depth_images must be [N,{want_c},H,W] matching images"
@@ -194,35 +246,55 @@ class HandNetEngine:
         noting = self.note_range or self.check_range
         if noting and self._range_block is None:
             self._range_block = torch.zeros((4,), device=self.device, dtype=torch.int32)
+        n = len(images)
+        rows = n if hands is None else n * hands
+        record = None
+        if hands is not None and (to_host or _record is not None):
+            # (fetched first: the crop stage writes the scores and ranks straight into the record)
+            record = _record if _record is not None else self._host_record_buffers(n, hands)
         # (the scope is this host thread's: another engine on another thread keeps its own switch and block)
         with ops.range_scope(self._range_block, on=noting):
             det, cand = self.fcos.detect(images)
-            crop_box, has_hand, crops = ops.crop_resize(det, self.num_classes - 1, depth.float().contiguous(), CROP, 4,
-                                                        reorder_bgr=self.a2j.rgbd)
-            conv = self._convert_spec(crop_box, tuple(depth.shape[-2:]))
-            kp = self._a2j_sparse(crops, has_hand, conv) if self._use_compaction(len(images)) else None
+            if hands is None:
+                crop_box, has_hand, crops = ops.crop_resize(det, self.num_classes - 1, depth.float().contiguous(), CROP, 4,
+                                                            reorder_bgr=self.a2j.rgbd)
+                box_rows, has_rows = crop_box, has_hand
+            else:
+                score, det_index = _hands_tail(record[1], rows) if record is not None else (None, None)
+                crop_box, has_hand, score, det_index, crops = ops.crop_resize_hands(
+                    det, self.num_classes - 1, depth.float().contiguous(), hands, CROP, 4, score=score, det_index=det_index,
+                    reorder_bgr=self.a2j.rgbd)
+                box_rows, has_rows = crop_box.view(rows, 4), has_hand.view(rows)
+            conv = self._convert_spec(box_rows, tuple(depth.shape[-2:]))
+            kp = self._a2j_sparse(crops, has_rows, conv) if self._use_compaction(rows) else None
             if kp is None:
-                kp = self.a2j.forward_nhwc(crops, valid=has_hand, convert=conv)
+                kp = self.a2j.forward_nhwc(crops, valid=has_rows, convert=conv)
             img_uvd = xyz = None
             if conv is not None:
                 kp, img_uvd, xyz = kp
             tail = _tail(kp, img_uvd, xyz, has_hand) if _tail is not None else None
             host_rec = None
             if to_host or _record is not None:
-                n = len(images)
-                host_rec, dev_rec = _record if _record is not None else self._host_record_buffers(n)
-                ops.pack_records(kp, crop_box, has_hand, n + 1, dev_rec.shape[1], out=dev_rec, extras=(img_uvd, xyz))   # (row n: zeros)
-                flags = ops.range_check_collect(self._range_block, out=dev_rec[n, :16].view(torch.int32)) if noting else None
+                host_rec, dev_rec = record if record is not None else (
+                    _record if _record is not None else self._host_record_buffers(n))
+                ops.pack_records(kp, box_rows, has_rows, rows + 1, dev_rec.shape[1], out=dev_rec[:rows + 1],
+                                 extras=(img_uvd, xyz))   # (row `rows`: zeros)
+                flags = ops.range_check_collect(self._range_block, out=dev_rec[rows, :16].view(torch.int32)) if noting else None
                 if host_rec is not None:      # (None: the caller copies a larger buffer that holds the records -- the live step)
                     host_rec.copy_(dev_rec, non_blocking=True)
             else:
                 flags = ops.range_check_collect(self._range_block) if noting else None
-        self._note_hand_count(has_hand, len(images))
+        self._note_hand_count(has_rows, rows)
         if self.check_range:
             bits = ops.range_bits(flags.cpu().tolist())
             if bits:
                 raise ops.RangeError(range_message(bits))
-        return HandNetOutput(kp, crops, crop_box, has_hand, det, cand, flags, img_uvd, xyz, tail, host_rec)
+        if hands is None:
+            return HandNetOutput(kp, crops, crop_box, has_hand, det, cand, flags, img_uvd, xyz, tail, host_rec)
+        per_slot = (n, hands) + tuple(kp.shape[1:])
+        return HandsOutput(kp.view(per_slot), crops, crop_box, has_hand, score, det_index, det, cand, flags,
+                           None if img_uvd is None else img_uvd.view(per_slot), None if xyz is None else xyz.view(per_slot),
+                           host_rec)
 
     # -------------------------------------------------------------------------------
     # sparse streams: A2J on the frames with a hand only
@@ -271,13 +343,19 @@ class HandNetEngine:
     # -------------------------------------------------------------------------------
     # hipGraph replay for a fixed batch shape (launch-bound at small batch)
     # -------------------------------------------------------------------------------
-    def _host_record_buffers(self, n):
-        buf = self._host_records.get(n)
+    def _new_record(self, n, hands=None):
+        """(pinned host, device) record buffers of a step over n frames (hands: forward_hands with that many slots per frame)."""
+        rb = record_bytes(self._fields())
+        rows = n + 1 if hands is None else hands_record_rows(n * hands, rb)
+        return (torch.zeros((rows, rb), dtype=torch.uint8, pin_memory=True),
+                torch.zeros((rows, rb), dtype=torch.uint8, device=self.device))
+
+    def _host_record_buffers(self, n, hands=None):
+        key = n if hands is None else ("hands", n, hands)
+        buf = self._host_records.get(key)
         if buf is None:
             with torch.inference_mode(False):   # ordinary tensors: written in place by later calls in any mode
-                rb = record_bytes(self._fields())
-                buf = self._host_records[n] = (torch.zeros((n + 1, rb), dtype=torch.uint8, pin_memory=True),
-                                               torch.zeros((n + 1, rb), dtype=torch.uint8, device=self.device))
+                buf = self._host_records[key] = self._new_record(n, hands)
         return buf
 
     @ops.device_guarded
@@ -287,11 +365,29 @@ class HandNetEngine:
         the device -> host copy of forward_device(to_host=True) (static_output.host_record).  limit: at most that many
         captured steps are kept -- capturing one more evicts the least recently used (its static activation pool is freed)."""
         key = (tuple(images.shape), tuple(depth.shape), bool(to_host))
+        return self._graphed(key, images, depth, to_host, limit, None)
+
+    @ops.device_guarded
+    def graphed_hands(self, images: torch.Tensor, depth: torch.Tensor, max_hands: int = 2, to_host: bool = False,
+                      limit: int | None = None):
+        """graphed() for forward_hands(images, depth, max_hands, to_host): (run, static_images, static_depth, static
+        HandsOutput).  Its captures are keyed apart from graphed()'s and share their eviction order (limit)."""
+        k = ops.check_max_hands(max_hands)
+        return self._graphed(self._hands_key(images.shape, depth.shape, k, to_host), images, depth, to_host, limit, k)
+
+    @staticmethod
+    def _hands_key(image_shape, depth_shape, max_hands, to_host):
+        return ("hands", tuple(image_shape), tuple(depth_shape), int(max_hands), bool(to_host))
+
+    def has_graph_hands(self, image_shape, depth_shape, max_hands, to_host: bool = False) -> bool:
+        return self._hands_key(image_shape, depth_shape, max_hands, to_host) in self._graphs
+
+    def _graphed(self, key, images, depth, to_host, limit, hands):
         if key not in self._graphs:
             while limit is not None and len(self._graphs) >= max(1, limit):
                 self._graphs.popitem(last=False)
             with torch.inference_mode(False), torch.no_grad():
-                return self._capture(key, images, depth, to_host)
+                return self._capture(key, images, depth, to_host, hands)
         self._graphs.move_to_end(key)
         g, s_img, s_dep, out = self._graphs[key]
         return g.replay, s_img, s_dep, out
@@ -395,28 +491,30 @@ class HandNetEngine:
         self._staged_done(staged)
         return self.forward_device(rgb, d4 if self.a2j.rgbd else d1, to_host=to_host)
 
-    def _capture(self, key, images, depth, to_host=False):
+    def _capture(self, key, images, depth, to_host=False, hands=None):
         # static buffers are ordinary (non-inference) tensors so that later copy_() works in any mode
         s_img, s_dep = torch.empty_like(images), torch.empty_like(depth)
         s_img.copy_(images)
         s_dep.copy_(depth)
-        record = None
-        if to_host:     # the capture's own record buffers (addresses are baked into the graph)
-            n = images.shape[0]
-            rb = record_bytes(self._fields())
-            record = (torch.zeros((n + 1, rb), dtype=torch.uint8, pin_memory=True),
-                      torch.zeros((n + 1, rb), dtype=torch.uint8, device=self.device))
+        # the capture's own record buffers (addresses are baked into the graph)
+        record = self._new_record(images.shape[0], hands) if to_host else None
+
+        def step():
+            if hands is None:
+                return self.forward_device(s_img, s_dep, _record=record)
+            return self.forward_hands(s_img, s_dep, hands, _record=record)
+
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with ops.launch_cost_hidden():
             with torch.cuda.stream(side):
                 for _ in range(2):  # warm-up (allocator, lazy module load) outside capture
-                    self.forward_device(s_img, s_dep, _record=record)
+                    step()
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
             # thread_local: GPU work another thread of the host process issues meanwhile (a ROS node's other callbacks)
             # does not invalidate the capture
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                out = self.forward_device(s_img, s_dep, _record=record)
+                out = step()
         self._graphs[key] = (g, s_img, s_dep, out)
         return g.replay, s_img, s_dep, out

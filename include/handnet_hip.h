@@ -33,7 +33,7 @@ extern "C" {
 #define HN_ERR_HIP 2
 
 /* ABI version; bumped whenever a struct below changes. */
-#define HN_ABI_VERSION 35
+#define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
 
@@ -507,6 +507,19 @@ int hn_crop_resize(const float* det_boxes, const int32_t* det_labels, const int3
                    int h, int w, int out, int cpad, int64_t* crop_box, int32_t* has_hand, float* crops,
                    void* stream);
 
+/* The crop stage for up to max_hands (1..16, else HN_ERR_ARG) hands per frame.  Slot k of frame i is the k-th detection
+ * with label == hand_label in frame i's score-ordered list; its box is padded, clamped and cut exactly as hn_crop_resize
+ * does for the first one (max_hands = 1 gives hn_crop_resize's crop_box / has_hand / crops bit for bit).  A slot whose
+ * padded box gives an empty slice, and every slot beyond the frame's hand detections, is empty: zero box, has_hand 0,
+ * score 0, det_index -1, zero crop (an empty slot still uses up its rank).  Outputs, frame-major (slot = i * max_hands + k):
+ *   crop_box [n][max_hands][4] int64, has_hand [n][max_hands] int32, score [n][max_hands] fp32 (det_scores of the slot's
+ *   detection), det_index [n][max_hands] int32 (its row in the detection list), crops [n * max_hands][out][out][cpad] fp32.
+ * det_scores [n][cap] as written by hn_fcos_nms; other arguments as in hn_crop_resize. */
+int hn_crop_resize_hands(const float* det_boxes, const float* det_scores, const int32_t* det_labels,
+                         const int32_t* det_count, int cap, int hand_label, int max_hands, const float* depth, int n,
+                         int in_ch, int reorder_bgr, int h, int w, int out, int cpad, int64_t* crop_box, int32_t* has_hand,
+                         float* score, int32_t* det_index, float* crops, void* stream);
+
 /* fp32 NHWC(4) image [n][h][w][4] -> the stem image of hn_conv_stem_f16x3 / hn_conv_stem_pool_f16x3 (two fp16 planes hi, lo of
  * [n][h + 2*border][w + 2*border][4], zero border): the A2J crops on their way to the split-precision stem
  * (a2j/resnet.py:155-158 conv1 -> bn1 -> relu -> maxpool). */
@@ -743,6 +756,11 @@ int hn_a2j_forward(hn_model* m, const float* crops, int k, int h, int w, const i
                    float* keypoints, void* stream);
 int hn_handnet_forward(hn_model* m, const float* rgb, const float* depth, int n, int h, int w, float* keypoints,
                        int64_t* crop_box, int32_t* has_hand, void* stream);
+/* hn_handnet_forward for up to max_hands (1..16) hands per frame: the detector, hn_crop_resize_hands, then A2J on the
+ * n * max_hands crops.  keypoints [n][max_hands][J][3], crop_box [n][max_hands][4] int64, has_hand [n][max_hands] int32,
+ * score [n][max_hands] fp32, all device; empty slots give zero rows.  max_hands = 1 is hn_handnet_forward. */
+int hn_handnet_forward_hands(hn_model* m, const float* rgb, const float* depth, int n, int h, int w, int max_hands,
+                             float* keypoints, int64_t* crop_box, int32_t* has_hand, float* score, void* stream);
 /* hn_handnet_forward + what the reference's caller computes from its results right away (ros_demo.py:289,329-330;
  * a2j/a2j.py:17-43): image (u,v,d) and / or camera xyz in mm per joint, written by the aggregation's epilogue
  * (hn_a2j_aggregate_convert_f32) -- same launches as hn_handnet_forward.  image_uvd / xyz_mm [n][J][3] device, either may be
