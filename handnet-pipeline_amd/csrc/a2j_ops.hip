@@ -429,6 +429,100 @@ extern "C" int hn_joints2d_standardize_f32(const float* image_uvd, const int32_t
 }
 
 // ---------------------------------------------------------------------------------------
+// The lifter's input with the live caller's skip rule (include/handnet_hip.h): ros_demo.py:288-300 drops a hand when
+// process_bbox(get_bbox(joints2d)) is None (pose2mesh/lib/coord_utils.py:21-49).  One wave per slot: the bounding box from
+// exact wave min / max reductions, the rule in fp32 one rounding per numpy operation (no contraction: this file is built with
+// the compiler's default), then joints2d_standardize_kernel's statistics for the accepted slots, restated line by line.
+// ---------------------------------------------------------------------------------------
+namespace {
+__device__ __forceinline__ void wave_minmax(float& lo, float& hi) {
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, o));
+    hi = fmaxf(hi, __shfl_xor(hi, o));
+  }
+}
+
+// get_bbox along one axis (coord_utils.py:21-40): center = (min + max) / 2., half = 0.5 * (max - min), start = center - half,
+// size = (center + half) - start; numpy 2 keeps every step in float32 (a Python float operand does not widen it)
+__device__ __forceinline__ void bbox_axis(float lo, float hi, float& start, float& size) {
+#pragma clang fp contract(off)
+  const float center = (lo + hi) * 0.5f;      // (/ 2. and * 0.5 round identically: one rounding of the same exact value)
+  const float half = 0.5f * (hi - lo);
+  start = center - half;
+  size = (center + half) - start;
+}
+
+// process_bbox's test (coord_utils.py:42-49): w * h > 0 and x + (w - 1) >= x and y + (h - 1) >= y, in float32
+__device__ __forceinline__ bool bbox_kept(float x, float y, float w, float h) {
+#pragma clang fp contract(off)
+  const float x2 = x + (w - 1.f), y2 = y + (h - 1.f);
+  return w * h > 0.f && x2 >= x && y2 >= y;
+}
+
+__global__ __launch_bounds__(64) void lifter_input_gated_kernel(const float* __restrict__ uvd, const int* __restrict__ valid,
+                                                                int J, float* __restrict__ out, int* __restrict__ lifted) {
+  const int img = blockIdx.x, lane = threadIdx.x;
+  float* o = out + (long)img * J * 2;
+  const float* p = uvd + (long)img * J * 3;
+  bool keep = !valid || valid[img] == 1;
+  if (keep) {
+    float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+    bool finite = true;
+    for (int j = lane; j < J; j += 64) {
+      const float u = p[j * 3 + 0], v = p[j * 3 + 1];
+      finite = finite && isfinite(u) && isfinite(v);
+      x0 = fminf(x0, u);
+      x1 = fmaxf(x1, u);
+      y0 = fminf(y0, v);
+      y1 = fmaxf(y1, v);
+    }
+    wave_minmax(x0, x1);
+    wave_minmax(y0, y1);
+    float bx, bw, by, bh;
+    bbox_axis(x0, x1, bx, bw);
+    bbox_axis(y0, y1, by, bh);
+    // (a non-finite joint is refused outright: the reference's min() over NaN depends on the joint order)
+    keep = __ballot(!finite) == 0ull && bbox_kept(bx, by, bw, bh);
+  }
+  if (lane == 0) lifted[img] = keep ? 1 : 0;
+  if (!keep) {
+    for (int i = lane; i < J * 2; i += 64) o[i] = 0.f;
+    return;
+  }
+  // joints2d_standardize_kernel's body from here on: the same operations in the same order (bit-identical rows)
+  double m0 = 0.0, m1 = 0.0;
+  for (int j = 0; j < J; ++j) {
+    m0 += (double)p[j * 3 + 0];
+    m1 += (double)p[j * 3 + 1];
+  }
+  m0 /= J;
+  m1 /= J;
+  double v0 = 0.0, v1 = 0.0;
+  for (int j = 0; j < J; ++j) {
+    const double a = (double)p[j * 3 + 0] - m0, b = (double)p[j * 3 + 1] - m1;
+    v0 += a * a;
+    v1 += b * b;
+  }
+  const double s0 = sqrt(v0 / J), s1 = sqrt(v1 / J);
+  for (int j = lane; j < J; j += 64) {
+    o[j * 2 + 0] = (float)(((double)p[j * 3 + 0] - m0) / s0);
+    o[j * 2 + 1] = (float)(((double)p[j * 3 + 1] - m1) / s1);
+  }
+}
+}  // namespace
+
+extern "C" int hn_lifter_input_gated_f32(const float* image_uvd, const int32_t* valid, int n, int joints, float* out,
+                                         int32_t* lifted, void* stream) {
+  HN_CHECK_ARG(image_uvd && out && lifted, "hn_lifter_input_gated_f32: null pointer");
+  HN_CHECK_ARG(n >= 0 && joints > 1, "bad dims");
+  if (n == 0) return HN_OK;
+  hipLaunchKernelGGL(lifter_input_gated_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, image_uvd, valid, joints, out,
+                     lifted);
+  HN_CHECK_LAUNCH("lifter_input_gated_kernel");
+  return HN_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // Per-frame result records of the N > 1 all-gather (hn_amd/dist.py) and the always-on non-finite check
 // ---------------------------------------------------------------------------------------
 namespace {

@@ -112,6 +112,17 @@ class HandNet(EngineOwner):
         self._convert_cfg = (tuple(paras), bool(clamp))
         return LiveHandEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, clamp, perm_reverse)
 
+    def live_hands(self, lifter, paras, max_hands: int = 2, clamp: bool = True, perm_reverse=None):
+        """live() for up to max_hands (1..16) hands per frame (hn_amd.live.LiveHandsEngine): forward_hands' slots, the
+        caller's clamp + convert_joints, the lifter's input with the caller's skip rule per slot (a hand whose 2D box
+        process_bbox refuses is not lifted: ros_demo.py:288-300), Pose2Mesh on every slot, one device -> host copy.
+        read() of a step's output gives keypoints / boxes / scores per slot, `lifted` [N,K] and the mesh [N,K,V,3]."""
+        from hn_amd.live import LiveHandsEngine
+        k = ops.check_max_hands(max_hands)
+        self._convert_cfg = (tuple(paras), bool(clamp))
+        return LiveHandsEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, k, clamp,
+                               perm_reverse)
+
     # forward() switches ITSELF to hipGraph replay once the same input shapes have come in a few times in a row -- the live
     # caller's case (ros_demo.py:270-273: one 640x480 frame per call, ~150 dependent launches whose host cost is 8 % of the
     # call; at batch 32 the replay saves the ~0.3 ms the GPU idles while Python issues the first launches after the sync).

@@ -208,6 +208,7 @@ SIGNATURES = {
     "hn_a2j_aggregate_convert_f32": (C.c_int, [VP, VP, VP, VP] + [C.c_int] * 5 + [VP, C.c_float, C.c_float, c_f32p,
                                                C.POINTER(ConvertOpts), VP, VP, VP, VP]),
     "hn_joints2d_standardize_f32": (C.c_int, [VP, VP, C.c_int, C.c_int, VP, VP]),
+    "hn_lifter_input_gated_f32": (C.c_int, [VP, VP, C.c_int, C.c_int, VP, VP, VP]),
     "hn_handnet_forward_xyz": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_int, c_f32p, C.POINTER(ConvertOpts),
                                          VP, VP, VP, VP, VP, VP]),
 }

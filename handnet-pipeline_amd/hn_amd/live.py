@@ -17,12 +17,14 @@ crops + the dataset's float32 boxes + per-sample intrinsics -> A2J -> clip + con
 """
 from __future__ import annotations
 
+import collections
 from dataclasses import dataclass
 
 import torch
 
 from . import ops
-from .pipeline import HandNetEngine, HandNetOutput, read_host_record, record_bytes
+from .pipeline import (HandNetEngine, HandNetOutput, HandsOutput, hands_record_rows, read_hands_tail, read_host_record,
+                       record_bytes)
 from .pose2mesh_engine import Pose2MeshEngine
 
 
@@ -55,13 +57,12 @@ class LiveOutput:
         return kp, has, box, words, more, mesh
 
 
-class LiveHandEngine:
+class _LiveStep:
+    """What the one-hand and the K-hand live steps share: the engines, the caller's conversion, the final-mesh permutation,
+    the output buffers of a batch size, the camera feed (forward_raw) and the capture (graphed).  A subclass gives _nbytes(n)
+    and forward_device(images, depth, _buffers)."""
+
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None):
-        """paras = (fx, fy, cx, cy) of the depth camera (ros_demo.py:191-196); clamp: the caller's clamps before the
-        conversion (ros_demo.py:279-283).  perm_reverse: graph_perm_reverse[:V] (int64, V = vertices of the real mesh,
-        ros_demo.py:162) -- given, the step also does the caller's last three lines (vertex order, camera offset by the first
-        joint, y / z negated: ros_demo.py:332-337) and `mesh` of the outputs IS out['mesh'], [N,V,3]; else the lifter's raw
-        [N,V0,3] vertices in coarsening order."""
         if not _same_device(hand.device, lifter.device):
             raise ValueError(f"HandNet on {hand.device} but the lifter on {lifter.device}")
         self.hand, self.lifter, self.device = hand, lifter, hand.device
@@ -79,37 +80,11 @@ class LiveHandEngine:
         key = (n, v0)
         b = self._buffers.get(key)
         if b is None:
-            rb = record_bytes(3)
-            nbytes = (n + 1) * rb + n * v0 * 12
+            nbytes = self._nbytes(n)
             with torch.inference_mode(False):
                 b = self._buffers[key] = (torch.zeros((nbytes,), dtype=torch.uint8, device=self.device),
                                           torch.zeros((nbytes,), dtype=torch.uint8, pin_memory=True))
         return b
-
-    @ops.device_guarded
-    def forward_device(self, images, depth, _buffers=None) -> LiveOutput:
-        """images [N,3,H,W] 0..1 (or a list), depth [N,1,H,W] metres on the GPU -> LiveOutput (no sync)."""
-        n = len(images)
-        v0 = self.vertices
-        dev, host = _buffers if _buffers is not None else self._out_buffers(n, v0)
-        rb = record_bytes(3)
-        rec = dev[: (n + 1) * rb].view(n + 1, rb)
-        mesh_buf = dev[(n + 1) * rb:].view(torch.float32).view(n, v0, 3)
-
-        def lift(_kp, image_uvd, xyz, has_hand):
-            # (inside the step's range scope: the lifter's split producers note into the step's flag words, which the step's one
-            # collect launch hands over -- an overflowing activation of the lifter raises like one of the pose network)
-            p2d = ops.joints2d_standardize(image_uvd, valid=has_hand)
-            if self.perm is None:
-                mesh, pose3d = self.lifter.forward(p2d, mesh_out=mesh_buf)          # the last layer writes into the copy buffer
-                return p2d, mesh, pose3d, mesh
-            raw, pose3d = self.lifter.forward(p2d)
-            return p2d, ops.mesh_finish(raw, self.perm, xyz, valid=has_hand, out=mesh_buf), pose3d, raw
-        # the step packs its wide records and its range words straight into `rec`; ONE copy moves records + mesh
-        out = self.hand.forward_device(images, depth, _record=(None, rec), _tail=lift)
-        p2d, mesh, pose3d, raw = out.tail
-        host.copy_(dev, non_blocking=True)
-        return LiveOutput(out, p2d, mesh, pose3d, host, n, raw)
 
     @ops.device_guarded
     def forward_raw(self, bgr_u8, depth_raw) -> LiveOutput:
@@ -140,9 +115,7 @@ class LiveHandEngine:
                 s_img, s_dep = torch.empty_like(images), torch.empty_like(depth)
                 s_img.copy_(images)
                 s_dep.copy_(depth)
-                n = images.shape[0]
-                v0 = self.vertices
-                nbytes = (n + 1) * record_bytes(3) + n * v0 * 12
+                nbytes = self._nbytes(images.shape[0])
                 bufs = (torch.zeros((nbytes,), dtype=torch.uint8, device=self.device),
                         torch.zeros((nbytes,), dtype=torch.uint8, pin_memory=True))
                 side = torch.cuda.Stream()
@@ -158,6 +131,128 @@ class LiveHandEngine:
             hit = self._graphs[key] = (g, s_img, s_dep, out)
         g, s_img, s_dep, out = hit
         return g.replay, s_img, s_dep, out
+
+
+class LiveHandEngine(_LiveStep):
+    def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None):
+        """paras = (fx, fy, cx, cy) of the depth camera (ros_demo.py:191-196); clamp: the caller's clamps before the
+        conversion (ros_demo.py:279-283).  perm_reverse: graph_perm_reverse[:V] (int64, V = vertices of the real mesh,
+        ros_demo.py:162) -- given, the step also does the caller's last three lines (vertex order, camera offset by the first
+        joint, y / z negated: ros_demo.py:332-337) and `mesh` of the outputs IS out['mesh'], [N,V,3]; else the lifter's raw
+        [N,V0,3] vertices in coarsening order."""
+        super().__init__(hand, lifter, paras, clamp, perm_reverse)
+
+    def _nbytes(self, n):
+        return (n + 1) * record_bytes(3) + n * self.vertices * 12
+
+    @ops.device_guarded
+    def forward_device(self, images, depth, _buffers=None) -> LiveOutput:
+        """images [N,3,H,W] 0..1 (or a list), depth [N,1,H,W] metres on the GPU -> LiveOutput (no sync)."""
+        n = len(images)
+        v0 = self.vertices
+        dev, host = _buffers if _buffers is not None else self._out_buffers(n, v0)
+        rb = record_bytes(3)
+        rec = dev[: (n + 1) * rb].view(n + 1, rb)
+        mesh_buf = dev[(n + 1) * rb:].view(torch.float32).view(n, v0, 3)
+
+        def lift(_kp, image_uvd, xyz, has_hand):
+            # (inside the step's range scope: the lifter's split producers note into the step's flag words, which the step's one
+            # collect launch hands over -- an overflowing activation of the lifter raises like one of the pose network)
+            p2d = ops.joints2d_standardize(image_uvd, valid=has_hand)
+            if self.perm is None:
+                mesh, pose3d = self.lifter.forward(p2d, mesh_out=mesh_buf)          # the last layer writes into the copy buffer
+                return p2d, mesh, pose3d, mesh
+            raw, pose3d = self.lifter.forward(p2d)
+            return p2d, ops.mesh_finish(raw, self.perm, xyz, valid=has_hand, out=mesh_buf), pose3d, raw
+        # the step packs its wide records and its range words straight into `rec`; ONE copy moves records + mesh
+        out = self.hand.forward_device(images, depth, _record=(None, rec), _tail=lift)
+        p2d, mesh, pose3d, raw = out.tail
+        host.copy_(dev, non_blocking=True)
+        return LiveOutput(out, p2d, mesh, pose3d, host, n, raw)
+
+
+def live_hands_layout(slots: int, vertices: int):
+    """Byte layout of the K-hand live step's one buffer for `slots` = N*K hand slots: (record rows, record bytes, offset of
+    `lifted` (int32 [slots]), offset of the mesh (fp32 [slots,V,3]), total bytes).  The record is forward_hands' wide record
+    unchanged (one row per slot, the range-word row, the scores and detection ranks: hands_record_rows)."""
+    rb = record_bytes(3)
+    rows = hands_record_rows(slots, rb)
+    lifted = rows * rb
+    mesh = lifted + 4 * slots
+    return rows, rb, lifted, mesh, mesh + slots * vertices * 12
+
+
+LiveHandsRead = collections.namedtuple(
+    "LiveHandsRead", "keypoints has_hand crop_box score det_index image_uvd xyz_mm lifted mesh words")
+
+
+@dataclass
+class LiveHandsOutput:
+    hands: HandsOutput           # the step's forward_hands results (image_uvd and xyz_mm included), on the device
+    pose2d: torch.Tensor         # [N*K,21,2] the lifter's input; zero rows where not lifted
+    lifted: torch.Tensor         # [N,K] int32: 1 where the slot's hand went through the lifter (the caller's skip rule)
+    mesh: torch.Tensor           # [N,K,V,3] as LiveOutput.mesh, per slot; zero rows where not lifted
+    pose3d: torch.Tensor         # [N*K,21,3] PoseNet's lifted joints (every row: rows not lifted are the lifter on zeros)
+    host: torch.Tensor           # pinned uint8 (live_hands_layout): records, lifted, mesh -- ONE copy, enqueued by the step
+    n: int = 0
+    k: int = 0
+    raw_mesh: torch.Tensor = None   # [N*K,V0,3] the lifter's own output on the device
+
+    def read(self) -> LiveHandsRead:
+        """After the stream is synchronised: the step's results per frame and slot as fresh CPU tensors (LiveHandsRead;
+        lifted as bool, words = the step's range words)."""
+        n, k, s = self.n, self.k, self.n * self.k
+        rows, rb, lo, mo, nbytes = live_hands_layout(s, self.mesh.shape[2])
+        rec = self.host[:lo].view(rows, rb)
+        kp, has, box, words, (img, xyz) = read_host_record(rec, s, extras=True)
+        score, index = read_hands_tail(rec, s)
+        lifted = self.host[lo:mo].view(torch.int32).reshape(n, k) != 0
+        mesh = self.host[mo:nbytes].view(torch.float32).reshape(n, k, -1, 3).clone()
+        per = lambda t: t.reshape((n, k) + tuple(t.shape[1:]))
+        return LiveHandsRead(per(kp), per(has), per(box), per(score), per(index), per(img), per(xyz), lifted, mesh, words)
+
+
+class LiveHandsEngine(_LiveStep):
+    """LiveHandEngine for up to max_hands hands per frame: HandNet's forward_hands step (slot k of frame i = frame i's k-th
+    hand detection) -> clamp + convert in the aggregation's epilogue -> the lifter's input WITH the caller's skip rule per
+    slot (ros_demo.py:288-300: a hand whose 2D box process_bbox refuses is not lifted; hn_lifter_input_gated_f32) ->
+    Pose2Mesh on all N*K rows (dense: rejected rows are zeros, so the step stays capturable and its activations finite) ->
+    the final mesh (perm_reverse) -> ONE device -> host copy of records + lifted + mesh (live_hands_layout)."""
+
+    def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, max_hands: int = 2, clamp: bool = True,
+                 perm_reverse=None):
+        self.max_hands = ops.check_max_hands(max_hands)
+        super().__init__(hand, lifter, paras, clamp, perm_reverse)
+
+    def _nbytes(self, n):
+        return live_hands_layout(n * self.max_hands, self.vertices)[4]
+
+    @ops.device_guarded
+    def forward_device(self, images, depth, _buffers=None) -> LiveHandsOutput:
+        """images [N,3,H,W] 0..1 (or a list), depth [N,1,H,W] metres on the GPU -> LiveHandsOutput (no sync).  Eager steps
+        may run A2J on the filled slots only (HandNetEngine.forward_hands); the lifter always runs on all N*K rows."""
+        n, k = len(images), self.max_hands
+        s, v = n * k, self.vertices
+        dev, host = _buffers if _buffers is not None else self._out_buffers(n, v)
+        rows, rb, lo, mo, nbytes = live_hands_layout(s, v)
+        rec = dev[:lo].view(rows, rb)
+        lifted = dev[lo:mo].view(torch.int32)
+        mesh_buf = dev[mo:nbytes].view(torch.float32).view(s, v, 3)
+
+        def lift(_kp, image_uvd, xyz, has_hand):
+            # (inside the step's range scope, as LiveHandEngine's lifter)
+            p2d, _ = ops.lifter_input_gated(image_uvd, valid=has_hand, lifted=lifted)
+            raw, pose3d = self.lifter.forward(p2d)
+            if self.perm is None:
+                mesh = torch.mul(raw, lifted.view(s, 1, 1), out=mesh_buf)       # (x * 1 is x: rows not lifted -> zeros)
+            else:
+                mesh = ops.mesh_finish(raw, self.perm, xyz, valid=lifted, out=mesh_buf)
+            return p2d, mesh, pose3d, raw
+        # the step packs its per-slot records, range words, scores and ranks straight into `rec`; ONE copy moves it all
+        out = self.hand.forward_hands(images, depth, k, _record=(None, rec), _tail=lift)
+        p2d, mesh, pose3d, raw = out.tail
+        host.copy_(dev, non_blocking=True)
+        return LiveHandsOutput(out, p2d, lifted.view(n, k), mesh.view(n, k, v, 3), pose3d, host, n, k, raw)
 
 
 @dataclass

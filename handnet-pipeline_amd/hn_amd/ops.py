@@ -1336,6 +1336,29 @@ def joints2d_standardize(image_uvd, valid=None, out=None):
     return out
 
 
+def lifter_input_gated(image_uvd, valid=None, out=None, lifted=None):
+    """joints2d_standardize with the live caller's skip rule (ros_demo.py:288-300): image (u,v,d) [N,J,3] -> (the lifter's
+    input [N,J,2], lifted [N] int32).  A row is lifted (1, and joints2d_standardize's row bit for bit) iff valid is None or 1
+    there, its (u,v) are finite and process_bbox(get_bbox(uv)) is not None (coord_utils.py:21-49, fp32 as numpy evaluates
+    it); every other row is zeros with lifted 0 -- so a degenerate hand never reaches the lifter as inf / NaN."""
+    _req(image_uvd, name="image_uvd")
+    n, j, _ = image_uvd.shape
+    if out is None:
+        out = torch.empty((n, j, 2), device=image_uvd.device, dtype=torch.float32)
+    if lifted is None:
+        lifted = torch.empty((n,), device=image_uvd.device, dtype=torch.int32)
+    _req(out, name="out"); _req(lifted, torch.int32, "lifted")
+    if tuple(out.shape) != (n, j, 2) or lifted.numel() != n:
+        raise ValueError("out must be [N,J,2] and lifted [N]")
+    if valid is not None:
+        _req(valid, torch.int32, "valid")
+        if valid.numel() != n:
+            raise ValueError("valid must hold one flag per row")
+    check(_lib.load().hn_lifter_input_gated_f32(ptr(image_uvd), ptr(valid), n, j, ptr(out), ptr(lifted), _stream()),
+          "hn_lifter_input_gated_f32")
+    return out, lifted
+
+
 def convert_joints(kp, crop_box, valid=None, paras=None, crop=176, out=None):
     """kp [N,J,3] crop-(u,v,d), crop_box [N,4] int64 -> image (u,v,d), or camera xyz in mm when
     paras = (fx, fy, cx, cy) is given (convert_joints + uvd2xyz of the reference, on the device)."""

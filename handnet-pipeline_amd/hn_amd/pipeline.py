@@ -57,6 +57,7 @@ class HandsOutput:
     xyz_mm: torch.Tensor = None        # [N,K,21,3] after set_convert(paras=...)
     host_record: torch.Tensor = None   # to_host steps: pinned uint8; rows 0..N*K-1 = one record per slot, row N*K = the range
     #                                    words, then score [N*K] fp32 and det_index [N*K] int32 (read_hands_tail)
+    tail: object = None                # what forward_hands' `_tail` callable returned (the multi-hand live step, hn_amd/live.py)
 
 
 RECORD_BYTES = 296      # hn_amd.dist's per-frame record (box 32 + flags 8 + 21 x 3 fp32 keypoints, padded to 8)
@@ -228,14 +229,16 @@ class HandNetEngine:
         return self._step(images, depth, None, to_host, _record, _tail)
 
     @ops.device_guarded
-    def forward_hands(self, images, depth: torch.Tensor, max_hands: int = 2, to_host: bool = False, _record=None) -> HandsOutput:
+    def forward_hands(self, images, depth: torch.Tensor, max_hands: int = 2, to_host: bool = False, _record=None,
+                      _tail=None) -> HandsOutput:
         """forward_device for up to max_hands (1..16) hands per frame: slot k of frame i is the k-th hand-label detection of
         frame i in the detector's score order, cropped as forward_device crops the first (max_hands = 1 IS forward_device's
         crop); A2J runs on the N * max_hands crops with the slots' has_hand mask (capturable), or -- eager, when the previous
         step filled fewer than half of its slots -- on the filled slots only.  to_host: one record row per slot, the range
         words, then the scores and detection ranks, in ONE device -> host copy (HandsOutput.host_record; read_host_record /
-        read_hands_tail after a sync)."""
-        return self._step(images, depth, ops.check_max_hands(max_hands), to_host, _record, None)
+        read_hands_tail after a sync).  _tail(keypoints, image_uvd, xyz_mm, has_hand), all per slot ([N*K,...]): as for
+        forward_device; its return value is HandsOutput.tail."""
+        return self._step(images, depth, ops.check_max_hands(max_hands), to_host, _record, _tail)
 
     def _step(self, images, depth, hands, to_host, _record, _tail):
         """The body of forward_device (hands None: the top-1 crop, HandNetOutput) and forward_hands (hands = K)."""
@@ -272,7 +275,7 @@ class HandNetEngine:
             img_uvd = xyz = None
             if conv is not None:
                 kp, img_uvd, xyz = kp
-            tail = _tail(kp, img_uvd, xyz, has_hand) if _tail is not None else None
+            tail = _tail(kp, img_uvd, xyz, has_rows) if _tail is not None else None
             host_rec = None
             if to_host or _record is not None:
                 host_rec, dev_rec = record if record is not None else (
@@ -294,7 +297,7 @@ class HandNetEngine:
         per_slot = (n, hands) + tuple(kp.shape[1:])
         return HandsOutput(kp.view(per_slot), crops, crop_box, has_hand, score, det_index, det, cand, flags,
                            None if img_uvd is None else img_uvd.view(per_slot), None if xyz is None else xyz.view(per_slot),
-                           host_rec)
+                           host_rec, tail)
 
     # -------------------------------------------------------------------------------
     # sparse streams: A2J on the frames with a hand only

@@ -32,7 +32,8 @@ extern "C" {
 #define HN_ERR_ARG 1
 #define HN_ERR_HIP 2
 
-/* ABI version; bumped whenever a struct below changes. */
+/* ABI version; bumped whenever a struct below changes (functions added without touching a struct or an existing signature
+ * keep it: hn_lifter_input_gated_f32 came under 36). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -600,6 +601,13 @@ int hn_a2j_aggregate_convert_f32(const float* cls, const float* reg, const float
  * image_uvd [n][J][3] (columns 0, 1 are read) -> out [n][J][2] fp32; rows with valid[i] != 1 are zeros. */
 int hn_joints2d_standardize_f32(const float* image_uvd, const int32_t* valid /* or NULL */, int n, int joints, float* out,
                                 void* stream);
+/* The same with the live caller's skip rule (ros_demo.py:288-300): a row is lifted -- lifted[i] = 1 and out[i] is exactly what
+ * hn_joints2d_standardize_f32 writes for it -- iff valid[i] == 1 (or valid is NULL), its (u,v) are finite and
+ * process_bbox(get_bbox(uv)) is not None (pose2mesh/lib/coord_utils.py:21-49, evaluated in fp32 one rounding per numpy
+ * operation); otherwise lifted[i] = 0 and out[i] is zeros.  One launch, one wave per row (the multi-hand live step:
+ * hn_amd.live.LiveHandsEngine).  Added under ABI 36: a new function only, no struct or existing signature changed. */
+int hn_lifter_input_gated_f32(const float* image_uvd /* [n][joints][3] */, const int32_t* valid /* or NULL */, int n,
+                              int joints, float* out /* [n][joints][2] */, int32_t* lifted /* [n] */, void* stream);
 
 /* Per-frame result records for the N > 1 all-gather (ONE collective of fixed-size records per step).
  * Record layout (rec_bytes >= 40 + 12*joints, multiple of 8): bytes 0..31 crop box 4 x int64, 32..35 has_hand,
