@@ -7,7 +7,10 @@
 
 Weights are the seeded synthetic checkpoints of the tests (the published models/*.pth are not redistributable); with real
 checkpoints pass their paths in `args` and reload_detector / reload_a2j = True, as ros_demo.py:370-388 does.
-usage (GPU box): python examples/live_demo.py [frames]"""
+With --overlay out.png the step also draws the mesh over the frame (the caller's render(), ros_demo.py:86-116,341) and the last
+frame's overlay is written with PIL; --mano FILE reads the face list from a MANO pickle's 'f' entry, else a synthetic face list
+over the 778 vertices is used (a seeded Delaunay triangulation, as tests/golden/make_golden_p2m.py builds one).
+usage (GPU box): python examples/live_demo.py [frames] [--overlay out.png] [--mano MANO_RIGHT.pkl]"""
 import sys
 import time
 import types
@@ -28,8 +31,25 @@ from hn_amd import synth  # noqa: E402
 PARAS = (617.343, 617.343, 312.42, 241.42)        # fx, fy, cx, cy of the depth camera (ros_demo.py:191-196)
 
 
+def _faces(mano_file):
+    if mano_file:
+        import pickle
+        with open(mano_file, "rb") as f:
+            return np.asarray(pickle.load(f, encoding="latin1")["f"], dtype=np.int64)
+    from scipy.spatial import Delaunay
+    return Delaunay(np.random.default_rng(7).random((778, 2))).simplices.astype(np.int64)
+
+
 def main():
-    frames = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+    argv = sys.argv[1:]
+    opt = {}
+    for flag in ("--overlay", "--mano"):
+        if flag in argv:
+            i = argv.index(flag)
+            opt[flag] = argv[i + 1]
+            del argv[i:i + 2]
+    frames = int(argv[0]) if argv else 20
+    faces = _faces(opt.get("--mano")) if "--overlay" in opt else None
     args = types.SimpleNamespace(pretrained_fcos="-", pretrained_a2j="-")
     net = HandNet(args, reload_detector=False, num_classes=3, reload_a2j=False)           # ros_demo.py:374-388
     net.detector.load_state_dict(synth.make_fcos_state_dict(0, 3), strict=False)
@@ -54,7 +74,7 @@ def main():
         print("2. set_convert: joints2d[0] =", conv["image_uvd"][0, 0, :2].tolist(), " joints3d[0] (mm) =", conv["xyz_mm"][0, 0].tolist())
         # 3. the live chain as one captured step
         rev = torch.from_numpy(g["perm_reverse"][:778].astype(np.int64))                  # graph_perm_reverse[:V], ros_demo.py:162
-        live = net.live(model, PARAS, clamp=True, perm_reverse=rev)                      # -> the step hands over out['mesh']
+        live = net.live(model, PARAS, clamp=True, perm_reverse=rev, faces=faces)         # -> the step hands over out['mesh']
         run, s_img, s_dep, out = live.graphed(rgb, depth)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -63,11 +83,17 @@ def main():
             s_dep.copy_(synth.make_depth(1, seed=2000 + i).cuda())
             run()
             torch.cuda.current_stream().synchronize()
-            kp, has_hand, crop_box, _words, (image_uvd, xyz_mm), mesh = out.read()
+            res = out.read()
+            kp, has_hand, crop_box, _words, (image_uvd, xyz_mm), mesh = res[:6]
         dt = time.perf_counter() - t0
         cam_mesh = mesh[0]                                                                # out['mesh'] of ros_demo.py:332-337
         print(f"3. live step: {frames} frames, {1e3 * dt / frames:.2f} ms per frame incl. synthetic frame generation; "
               f"mesh {tuple(out.raw_mesh.shape)} -> {tuple(cam_mesh.shape)} camera-frame vertices; has_hand = {has_hand.tolist()}")
+        if faces is not None:                                                             # ros_demo.py:341: the mesh_label image
+            from PIL import Image
+            Image.fromarray(res.overlay[0].numpy()).save(opt["--overlay"])
+            changed = int((res.overlay[0] != (s_img[0] * 255).round().byte().permute(1, 2, 0).cpu()).any(dim=2).sum())
+            print(f"4. overlay: {tuple(res.overlay.shape)} uint8 RGB in the same copy, {changed} pixels drawn -> {opt['--overlay']}")
 
 
 if __name__ == "__main__":

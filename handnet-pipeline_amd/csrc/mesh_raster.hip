@@ -1,0 +1,261 @@
+// The live loop's last call, render(out, paras, h, w, full_image, face) of ros_demo.py:86-116,329-337, as two launches:
+// the lifted meshes of all N*K hand slots rasterised over the camera frame, one depth buffer per frame.
+//
+//   mesh_raster_setup  one workgroup per slot, one thread per face (strided): projects the face's three vertices with the
+//                      plain pinhole (fp32, one rounding per operation), snaps them to 1/256 pixel, and writes the face's
+//                      record (snapped corners wound so that the doubled area is positive, the three Z, 1 / area, the flat
+//                      8-bit colour) and its pixel bounding box; reduces the slot's pixel bounding box.
+//   mesh_raster_tiles  one wave per 8x8 pixel tile, one pixel per lane.  The tile walks the K slots of its frame, skips a
+//                      slot whose box misses it, tests 64 face boxes at a time (one per lane, one ballot) and evaluates
+//                      only the faces whose box touches the tile: 64-bit integer edge functions with the top-left rule,
+//                      fp32 barycentric depth, nearest Z kept in registers.  Each pixel is written once: the nearest
+//                      face's colour, or the frame's own pixel.
+//
+// No atomics, no order dependence between workgroups: the image is a pure function of the inputs (slot-major, then face
+// order decides an exact depth tie).  The rule itself is stated in DESIGN.md ("The overlay") and restated in numpy by
+// tests/raster_ref.py.
+#include "hn_common.h"
+
+namespace {
+
+constexpr int kSub = 256;           // sub-pixel grid: 1/256 pixel
+constexpr int kHalf = 128;          // a pixel's sample point: (256 col + 128, 256 row + 128)
+constexpr float kSnapLimit = 16777216.f;   // |snapped coordinate| < 2^24
+constexpr float kNear = 0.05f, kFar = 100.f;
+
+struct __attribute__((aligned(16))) FaceRec {
+  int ax, ay, bx, by, cx, cy;       // snapped corners, wound so that (bx-ax)(cy-ay) - (cx-ax)(by-ay) > 0
+  float za, zb, zc;                 // camera Z of the corners (metres, > 0 in front)
+  float inv_area;                   // 1 / doubled area
+  unsigned rgb;                     // r | g << 8 | b << 16
+  int pad;
+};
+static_assert(sizeof(FaceRec) == 48, "face record");
+
+struct Box { short x0, x1, y0, y1; };   // inclusive pixel range; x0 > x1: nothing to draw
+static_assert(sizeof(Box) == 8, "face box");
+
+struct SlotBox { int x0, x1, y0, y1; };
+
+__host__ __device__ inline size_t rec_offset(int s) { return (size_t)s * sizeof(SlotBox); }
+__host__ __device__ inline size_t box_offset(int s, int f) { return rec_offset(s) + (size_t)s * f * sizeof(FaceRec); }
+__host__ __device__ inline size_t scratch_total(int s, int f) { return box_offset(s, f) + (size_t)s * f * sizeof(Box); }
+
+struct Snapped { int x, y; float z; bool ok; };
+
+// (x, y, z) of out['mesh'] (OpenGL camera: y up, z towards the viewer) -> (X, Y, Z) = (x, -y, -z) -> u = (fx X) / Z + cx,
+// v = (fy Y) / Z + cy -> rint(256 u), rint(256 v); every operation rounded on its own
+__device__ __forceinline__ Snapped project(const float* __restrict__ p, float fx, float fy, float cx, float cy) {
+#pragma clang fp contract(off)
+  const float X = p[0], Y = -p[1], Z = -p[2];
+  Snapped r;
+  r.z = Z;
+  r.ok = (fabsf(X) <= 3.402823466e38f) && (fabsf(Y) <= 3.402823466e38f) && (Z >= kNear) && (Z <= kFar);
+  const float zs = r.ok ? Z : 1.f;
+  const float u = __fadd_rn(__fdiv_rn(__fmul_rn(fx, X), zs), cx);
+  const float v = __fadd_rn(__fdiv_rn(__fmul_rn(fy, Y), zs), cy);
+  const float xs = rintf(__fmul_rn(u, (float)kSub)), ys = rintf(__fmul_rn(v, (float)kSub));
+  r.ok = r.ok && (fabsf(xs) < kSnapLimit) && (fabsf(ys) < kSnapLimit);     // (false for NaN / inf as well)
+  r.x = r.ok ? (int)xs : 0;
+  r.y = r.ok ? (int)ys : 0;
+  return r;
+}
+
+// shade = min(1, 0.3 + 2.4 l / pi), l = |n_z| / |n| of the face's camera-space normal; base colour (1, 1, 0.9)
+__device__ __forceinline__ unsigned face_colour(const float* a, const float* b, const float* c) {
+  const float e1x = b[0] - a[0], e1y = b[1] - a[1], e1z = b[2] - a[2];
+  const float e2x = c[0] - a[0], e2y = c[1] - a[1], e2z = c[2] - a[2];
+  const float nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+  const float len = sqrtf(nx * nx + ny * ny + nz * nz);
+  const float l = len > 0.f ? fabsf(nz) / len : 0.f;
+  const float shade = fminf(1.f, 0.3f + 2.4f * l / 3.14159265358979323846f);
+  const float base[3] = {1.f, 1.f, 0.9f};
+  unsigned rgb = 0;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const float q = floorf(255.f * shade * base[ch] + 0.5f);
+    rgb |= (unsigned)fminf(fmaxf(q, 0.f), 255.f) << (8 * ch);
+  }
+  return rgb;
+}
+
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+__global__ __launch_bounds__(256) void mesh_raster_setup(const float* __restrict__ mesh, const int* __restrict__ faces,
+                                                         const int* __restrict__ lifted, int v, int f, float fx, float fy,
+                                                         float cx, float cy, int h, int w, unsigned char* __restrict__ scratch,
+                                                         int slots) {
+  const int slot = blockIdx.x;
+  SlotBox* slot_box = reinterpret_cast<SlotBox*>(scratch + (size_t)slot * sizeof(SlotBox));
+  FaceRec* recs = reinterpret_cast<FaceRec*>(scratch + rec_offset(slots)) + (size_t)slot * f;
+  Box* boxes = reinterpret_cast<Box*>(scratch + box_offset(slots, f)) + (size_t)slot * f;
+  const bool drawn = !lifted || lifted[slot] != 0;        // (uniform over the workgroup)
+  int bx0 = w, bx1 = -1, by0 = h, by1 = -1;
+  for (int i = threadIdx.x; i < f && drawn; i += blockDim.x) {
+    const int i0 = faces[3 * i], i1 = faces[3 * i + 1], i2 = faces[3 * i + 2];
+    Box box = {1, 0, 1, 0};
+    FaceRec rec = {};
+    if ((unsigned)i0 < (unsigned)v && (unsigned)i1 < (unsigned)v && (unsigned)i2 < (unsigned)v) {   // (a bad index draws nothing)
+      const float* pa = mesh + ((size_t)slot * v + i0) * 3;
+      const float* pb = mesh + ((size_t)slot * v + i1) * 3;
+      const float* pc = mesh + ((size_t)slot * v + i2) * 3;
+      const Snapped a = project(pa, fx, fy, cx, cy);
+      Snapped b = project(pb, fx, fy, cx, cy), c = project(pc, fx, fy, cx, cy);
+      const long long area = (long long)(b.x - a.x) * (c.y - a.y) - (long long)(c.x - a.x) * (b.y - a.y);
+      if (a.ok && b.ok && c.ok && area != 0) {
+        if (area < 0) { const Snapped t = b; b = c; c = t; }
+        const int lo_x = min(a.x, min(b.x, c.x)), hi_x = max(a.x, max(b.x, c.x));
+        const int lo_y = min(a.y, min(b.y, c.y)), hi_y = max(a.y, max(b.y, c.y));
+        // pixels whose sample point 256 p + 128 lies in [lo, hi] (>> is an arithmetic shift: floor for negative values too)
+        const int x0 = max((lo_x + kHalf - 1) >> 8, 0), x1 = min((hi_x - kHalf) >> 8, w - 1);
+        const int y0 = max((lo_y + kHalf - 1) >> 8, 0), y1 = min((hi_y - kHalf) >> 8, h - 1);
+        if (x0 <= x1 && y0 <= y1) {
+          box = {(short)x0, (short)x1, (short)y0, (short)y1};
+          rec.ax = a.x; rec.ay = a.y; rec.bx = b.x; rec.by = b.y; rec.cx = c.x; rec.cy = c.y;
+          rec.za = a.z; rec.zb = b.z; rec.zc = c.z;
+          rec.inv_area = 1.f / (float)(area < 0 ? -area : area);
+          rec.rgb = face_colour(pa, pb, pc);
+          bx0 = min(bx0, x0); bx1 = max(bx1, x1); by0 = min(by0, y0); by1 = max(by1, y1);
+        }
+      }
+    }
+    recs[i] = rec;
+    boxes[i] = box;
+  }
+  __shared__ int part[4][4];
+  bx0 = wave_min(bx0); bx1 = -wave_min(-bx1); by0 = wave_min(by0); by1 = -wave_min(-by1);
+  if ((threadIdx.x & 63) == 0) {
+    int* p = part[threadIdx.x >> 6];
+    p[0] = bx0; p[1] = bx1; p[2] = by0; p[3] = by1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    SlotBox sb = {part[0][0], part[0][1], part[0][2], part[0][3]};
+    for (int wv = 1; wv < 4; ++wv) {
+      sb.x0 = min(sb.x0, part[wv][0]); sb.x1 = max(sb.x1, part[wv][1]);
+      sb.y0 = min(sb.y0, part[wv][2]); sb.y1 = max(sb.y1, part[wv][3]);
+    }
+    *slot_box = sb;
+  }
+}
+
+// edge a -> b of a face with positive doubled area (clockwise on the screen, y down): the inside is E > 0, and a sample
+// exactly on the edge belongs to the face when the edge is a top edge (dy == 0, dx > 0) or a left edge (dy < 0)
+__device__ __forceinline__ long long edge(int ax, int ay, int bx, int by, int px, int py, bool& in) {
+  const int dx = bx - ax, dy = by - ay;
+  const long long e = (long long)dx * (py - ay) - (long long)dy * (px - ax);
+  const bool top_left = dy < 0 || (dy == 0 && dx > 0);
+  in = in && (e > 0 || (e == 0 && top_left));
+  return e;
+}
+
+template <int FMT>   // HN_FRAME_F32_CHW / HN_FRAME_U8_BGR_HWC
+__global__ __launch_bounds__(256) void mesh_raster_tiles(const unsigned char* __restrict__ scratch, int slots, int f, int k,
+                                                         const void* __restrict__ frame, int h, int w,
+                                                         unsigned char* __restrict__ out, float* __restrict__ depth_out) {
+  // a workgroup is 4 tiles side by side: 32 x 8 pixels
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int tx = (blockIdx.x * 4 + wave) * 8, ty = blockIdx.y * 8, n = blockIdx.z;
+  if (tx >= w) return;                                        // (wave-uniform)
+  const int col = tx + (lane & 7), row = ty + (lane >> 3);
+  const bool inside_frame = col < w && row < h;
+  const int px = col * kSub + kHalf, py = row * kSub + kHalf;
+  const FaceRec* all_recs = reinterpret_cast<const FaceRec*>(scratch + rec_offset(slots));
+  const Box* all_boxes = reinterpret_cast<const Box*>(scratch + box_offset(slots, f));
+  float best = 3.402823466e38f;
+  unsigned rgb = 0;
+  bool covered = false;
+  for (int kk = 0; kk < k; ++kk) {
+    const int slot = n * k + kk;
+    const SlotBox sb = *reinterpret_cast<const SlotBox*>(scratch + (size_t)slot * sizeof(SlotBox));
+    if (sb.x0 > tx + 7 || sb.x1 < tx || sb.y0 > ty + 7 || sb.y1 < ty) continue;      // (wave-uniform)
+    const FaceRec* recs = all_recs + (size_t)slot * f;
+    const Box* boxes = all_boxes + (size_t)slot * f;
+    for (int base = 0; base < f; base += 64) {
+      bool hit = false;
+      if (base + lane < f) {
+        const Box b = boxes[base + lane];
+        hit = b.x0 <= tx + 7 && b.x1 >= tx && b.y0 <= ty + 7 && b.y1 >= ty;
+      }
+      unsigned long long todo = __ballot(hit);
+      while (todo) {                                          // ascending face order: the lower index wins an exact tie
+        const int bit = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const FaceRec r = recs[__builtin_amdgcn_readfirstlane(base + bit)];
+        bool in = inside_frame;
+        const long long wa = edge(r.bx, r.by, r.cx, r.cy, px, py, in);      // weight of corner a
+        const long long wb = edge(r.cx, r.cy, r.ax, r.ay, px, py, in);
+        const long long wc = edge(r.ax, r.ay, r.bx, r.by, px, py, in);
+        if (in) {
+          const float z = ((float)wa * r.za + (float)wb * r.zb + (float)wc * r.zc) * r.inv_area;
+          if (z < best) { best = z; rgb = r.rgb; covered = true; }
+        }
+      }
+    }
+  }
+  if (!inside_frame) return;
+  const size_t pix = ((size_t)n * h + row) * w + col;
+  if (!covered) {
+    if (FMT == HN_FRAME_F32_CHW) {
+      const float* src = static_cast<const float*>(frame) + (size_t)n * 3 * h * w + (size_t)row * w + col;
+      rgb = 0;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const float q = rintf(255.f * src[(size_t)ch * h * w]);
+        rgb |= (unsigned)fminf(fmaxf(q, 0.f), 255.f) << (8 * ch);           // (fmaxf(NaN, 0) is 0)
+      }
+    } else {
+      const unsigned char* src = static_cast<const unsigned char*>(frame) + pix * 3;
+      rgb = (unsigned)src[2] | (unsigned)src[1] << 8 | (unsigned)src[0] << 16;   // bgr8 -> RGB
+    }
+  }
+  unsigned char* dst = out + pix * 3;
+  dst[0] = (unsigned char)(rgb & 255u);
+  dst[1] = (unsigned char)((rgb >> 8) & 255u);
+  dst[2] = (unsigned char)((rgb >> 16) & 255u);
+  if (depth_out) depth_out[pix] = covered ? best : 0.f;
+}
+
+}  // namespace
+
+extern "C" int64_t hn_mesh_render_scratch_bytes(int s, int f) {
+  if (s <= 0 || f <= 0) return 0;
+  return (int64_t)scratch_total(s, f);
+}
+
+extern "C" int hn_mesh_render_u8(const float* mesh, const int32_t* faces, const int32_t* faces_host, const int32_t* lifted, int s,
+                                 int v, int f, int k, const float* paras, const void* frame, int frame_format, int h, int w,
+                                 void* scratch, int64_t scratch_bytes, uint8_t* out_image, float* out_depth, void* stream) {
+  HN_CHECK_ARG(mesh && faces && paras && frame && scratch, "hn_mesh_render_u8: null pointer");
+  HN_CHECK_ARG(out_image, "hn_mesh_render_u8: out_image is NULL");
+  HN_CHECK_ARG(s > 0 && v > 0 && f > 0, "hn_mesh_render_u8: bad dims (s %d, v %d, f %d: all must be positive)", s, v, f);
+  HN_CHECK_ARG(k > 0 && s % k == 0, "hn_mesh_render_u8: %d slots are not a multiple of k = %d slots per frame", s, k);
+  HN_CHECK_ARG(h > 0 && w > 0 && h <= 16384 && w <= 16384, "hn_mesh_render_u8: bad frame size %d x %d (1..16384)", h, w);
+  HN_CHECK_ARG(s / k <= 65535, "hn_mesh_render_u8: more than 65535 frames");
+  HN_CHECK_ARG(frame_format == HN_FRAME_F32_CHW || frame_format == HN_FRAME_U8_BGR_HWC, "hn_mesh_render_u8: unknown frame format %d",
+               frame_format);
+  HN_CHECK_ARG(scratch_bytes >= (int64_t)scratch_total(s, f), "hn_mesh_render_u8: scratch of %lld bytes, %lld needed",
+               (long long)scratch_bytes, (long long)scratch_total(s, f));
+  HN_CHECK_ARG(((uintptr_t)scratch & 15) == 0, "hn_mesh_render_u8: scratch must be 16-byte aligned");
+  if (faces_host)
+    for (int64_t i = 0; i < (int64_t)f * 3; ++i)
+      HN_CHECK_ARG(faces_host[i] >= 0 && faces_host[i] < v, "hn_mesh_render_u8: face %lld uses vertex %d of %d", (long long)(i / 3),
+                   faces_host[i], v);
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* sc = static_cast<unsigned char*>(scratch);
+  hipLaunchKernelGGL(mesh_raster_setup, dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, paras[0], paras[1], paras[2], paras[3],
+                     h, w, sc, s);
+  HN_CHECK_LAUNCH("mesh_raster_setup");
+  const dim3 grid((w + 31) / 32, (h + 7) / 8, s / k);
+  if (frame_format == HN_FRAME_F32_CHW)
+    hipLaunchKernelGGL(mesh_raster_tiles<HN_FRAME_F32_CHW>, grid, dim3(256), 0, st, sc, s, f, k, frame, h, w, out_image, out_depth);
+  else
+    hipLaunchKernelGGL(mesh_raster_tiles<HN_FRAME_U8_BGR_HWC>, grid, dim3(256), 0, st, sc, s, f, k, frame, h, w, out_image,
+                       out_depth);
+  HN_CHECK_LAUNCH("mesh_raster_tiles");
+  return HN_OK;
+}

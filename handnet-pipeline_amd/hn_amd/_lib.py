@@ -65,6 +65,7 @@ class ModelConfig(C.Structure):  # == struct hn_model_config
 MODEL_FCOS, MODEL_A2J = 1, 2
 PRECISION_SPLIT, PRECISION_F32 = 0, 1
 RANGE_ACTIVATION, RANGE_INPUT, RANGE_INPUT_NONFINITE = 1, 2, 4
+FRAME_F32_CHW, FRAME_U8_BGR_HWC = 0, 1
 
 
 class FcosLevels(C.Structure):
@@ -152,6 +153,9 @@ SIGNATURES = {
     "hn_linear_rows_f16x3": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, VP, VP, VP, C.c_int, C.c_int, VP, VP, C.c_int, C.c_int, VP,
                                        C.c_int, VP]),
     "hn_mesh_finish_f32": (C.c_int, [VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP]),
+    "hn_mesh_render_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "hn_mesh_render_u8": (C.c_int, [VP, VP, VP, VP] + [C.c_int] * 4 + [c_f32p, VP, C.c_int, C.c_int, C.c_int, VP, C.c_int64, VP, VP,
+                                    VP]),
     "hn_pad_split_rows_f32": (C.c_int, [VP, C.c_int64, C.c_int, C.c_int, VP, VP]),
     "hn_lifter_combine_f32": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP]),
     "hn_cheby3_basis_split": (C.c_int, [VP, VP, VP, C.c_int, VP, VP, VP, C.c_int, C.c_int, C.c_int, VP]),

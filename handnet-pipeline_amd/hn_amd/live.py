@@ -35,6 +35,23 @@ def _same_device(a, b) -> bool:
     return a.type == b.type and (a.type != "cuda" or index(a) == index(b))
 
 
+class LiveRead(collections.namedtuple("LiveRead", "keypoints has_hand crop_box words more mesh")):
+    """LiveOutput.read() of a step without an overlay: unpacks as the six results it always had."""
+    __slots__ = ()
+    overlay = None
+
+
+LiveOverlayRead = collections.namedtuple("LiveOverlayRead", LiveRead._fields + ("overlay",))
+
+
+def live_overlay_layout(n: int, vertices: int, h: int, w: int):
+    """Byte layout of the one-hand live step's buffer with an overlay: (offset of the mesh, offset of the overlay (uint8
+    [n,h,w,3], appended: the records and the mesh stay where a step without one has them), total bytes)."""
+    mesh = (n + 1) * record_bytes(3)
+    overlay = mesh + n * vertices * 12
+    return mesh, overlay, overlay + n * h * w * 3
+
+
 @dataclass
 class LiveOutput:
     hand: HandNetOutput          # the step's detector / pose results (image_uvd and xyz_mm included), on the device
@@ -45,16 +62,20 @@ class LiveOutput:
     host: torch.Tensor           # pinned uint8: (N + 1) wide records, then the mesh as fp32 -- ONE copy, enqueued by the step
     n: int = 0
     raw_mesh: torch.Tensor = None   # [N,V0,3] the lifter's own output on the device (= mesh without perm_reverse)
+    overlay: torch.Tensor = None    # [N,H,W,3] uint8 RGB on the device: the mesh drawn over the frame (engines with faces=)
 
     def read(self):
         """After the stream is synchronised: (keypoints, has_hand, crop_box, range words, [image_uvd, xyz_mm], mesh) as fresh CPU
-        tensors."""
+        tensors (LiveRead; `.overlay` is None).  A step with faces= appends the overlay [N,H,W,3] uint8 (LiveOverlayRead)."""
         rb = record_bytes(3)
         n = self.n
         rec = self.host[: (n + 1) * rb].view(n + 1, rb)
         kp, has, box, words, more = read_host_record(rec, n, extras=True)
-        mesh = self.host[(n + 1) * rb:].view(torch.float32).reshape(n, -1, 3).clone()
-        return kp, has, box, words, more, mesh
+        mo, oo = (n + 1) * rb, (n + 1) * rb + self.mesh[0].numel() * 4 * n
+        mesh = self.host[mo:oo].view(torch.float32).reshape(n, -1, 3).clone()
+        if self.overlay is None:
+            return LiveRead(kp, has, box, words, more, mesh)
+        return LiveOverlayRead(kp, has, box, words, more, mesh, self.host[oo:].reshape(self.overlay.shape).clone())
 
 
 class _LiveStep:
@@ -62,7 +83,7 @@ class _LiveStep:
     the output buffers of a batch size, the camera feed (forward_raw) and the capture (graphed).  A subclass gives _nbytes(n)
     and forward_device(images, depth, _buffers)."""
 
-    def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None):
+    def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None):
         if not _same_device(hand.device, lifter.device):
             raise ValueError(f"HandNet on {hand.device} but the lifter on {lifter.device}")
         self.hand, self.lifter, self.device = hand, lifter, hand.device
@@ -73,14 +94,43 @@ class _LiveStep:
             if int(self.perm.max()) >= lifter.graphs[0].v or int(self.perm.min()) < 0:
                 raise ValueError("perm_reverse points outside the lifter's finest graph")
         self.vertices = lifter.graphs[0].v if self.perm is None else int(self.perm.shape[0])
+        # faces: the mesh's triangles (mesh_model.face) -- given, the step ends with the overlay (ops.mesh_render: the caller's
+        # render(), ros_demo.py:86-116) and the image rides behind the mesh in the step's one copy
+        self.faces, self.paras = None, tuple(float(p) for p in paras)
+        if faces is not None:
+            if self.perm is None:
+                raise ValueError("faces= needs perm_reverse=: the overlay projects out['mesh'] (camera frame, the real mesh's "
+                                 "vertex order); the lifter's raw output has no camera offset to project")
+            with ops.on_device(self.device):
+                self.faces = ops.mesh_faces(faces, self.vertices, self.device)
+        self._render_scratch = {}
         self._graphs = {}
         self._buffers = {}
 
-    def _out_buffers(self, n, v0):
-        key = (n, v0)
+    def _frames(self, images):
+        """The step's input frames as one fp32 [N,3,H,W] tensor (the overlay's background), or None without faces."""
+        if self.faces is None:
+            return None
+        frames = images if torch.is_tensor(images) else torch.stack(list(images))
+        return frames.contiguous()
+
+    def _hw(self, frames):
+        return None if frames is None else (int(frames.shape[2]), int(frames.shape[3]))
+
+    def _draw(self, mesh, lifted, frames, k, out):
+        s = mesh.shape[0]
+        scratch = self._render_scratch.get(s)
+        if scratch is None:
+            with torch.inference_mode(False):
+                scratch = self._render_scratch[s] = torch.empty(
+                    (ops.mesh_render_scratch_bytes(s, self.faces.shape[0]),), dtype=torch.uint8, device=self.device)
+        return ops.mesh_render(mesh, self.faces, self.paras, frames, lifted=lifted, k=k, out=out, scratch=scratch)
+
+    def _out_buffers(self, n, v0, hw=None):
+        key = (n, v0, hw)
         b = self._buffers.get(key)
         if b is None:
-            nbytes = self._nbytes(n)
+            nbytes = self._nbytes(n, hw)
             with torch.inference_mode(False):
                 b = self._buffers[key] = (torch.zeros((nbytes,), dtype=torch.uint8, device=self.device),
                                           torch.zeros((nbytes,), dtype=torch.uint8, pin_memory=True))
@@ -115,7 +165,7 @@ class _LiveStep:
                 s_img, s_dep = torch.empty_like(images), torch.empty_like(depth)
                 s_img.copy_(images)
                 s_dep.copy_(depth)
-                nbytes = self._nbytes(images.shape[0])
+                nbytes = self._nbytes(images.shape[0], self._hw(self._frames(images)))
                 bufs = (torch.zeros((nbytes,), dtype=torch.uint8, device=self.device),
                         torch.zeros((nbytes,), dtype=torch.uint8, pin_memory=True))
                 side = torch.cuda.Stream()
@@ -134,26 +184,30 @@ class _LiveStep:
 
 
 class LiveHandEngine(_LiveStep):
-    def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None):
+    def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None):
         """paras = (fx, fy, cx, cy) of the depth camera (ros_demo.py:191-196); clamp: the caller's clamps before the
         conversion (ros_demo.py:279-283).  perm_reverse: graph_perm_reverse[:V] (int64, V = vertices of the real mesh,
         ros_demo.py:162) -- given, the step also does the caller's last three lines (vertex order, camera offset by the first
         joint, y / z negated: ros_demo.py:332-337) and `mesh` of the outputs IS out['mesh'], [N,V,3]; else the lifter's raw
-        [N,V0,3] vertices in coarsening order."""
-        super().__init__(hand, lifter, paras, clamp, perm_reverse)
+        [N,V0,3] vertices in coarsening order.  faces: mesh_model.face ([F,3] vertex indices of the real mesh; needs perm_reverse) --
+        given, the step also draws the mesh over the frame (ros_demo.py:86-116 render(): LiveOutput.overlay, read().overlay)."""
+        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces)
 
-    def _nbytes(self, n):
-        return (n + 1) * record_bytes(3) + n * self.vertices * 12
+    def _nbytes(self, n, hw=None):
+        if hw is None:
+            return (n + 1) * record_bytes(3) + n * self.vertices * 12
+        return live_overlay_layout(n, self.vertices, *hw)[2]
 
     @ops.device_guarded
     def forward_device(self, images, depth, _buffers=None) -> LiveOutput:
         """images [N,3,H,W] 0..1 (or a list), depth [N,1,H,W] metres on the GPU -> LiveOutput (no sync)."""
         n = len(images)
         v0 = self.vertices
-        dev, host = _buffers if _buffers is not None else self._out_buffers(n, v0)
+        frames = self._frames(images)
+        dev, host = _buffers if _buffers is not None else self._out_buffers(n, v0, self._hw(frames))
         rb = record_bytes(3)
         rec = dev[: (n + 1) * rb].view(n + 1, rb)
-        mesh_buf = dev[(n + 1) * rb:].view(torch.float32).view(n, v0, 3)
+        mesh_buf = dev[(n + 1) * rb:(n + 1) * rb + n * v0 * 12].view(torch.float32).view(n, v0, 3)
 
         def lift(_kp, image_uvd, xyz, has_hand):
             # (inside the step's range scope: the lifter's split producers note into the step's flag words, which the step's one
@@ -167,8 +221,12 @@ class LiveHandEngine(_LiveStep):
         # the step packs its wide records and its range words straight into `rec`; ONE copy moves records + mesh
         out = self.hand.forward_device(images, depth, _record=(None, rec), _tail=lift)
         p2d, mesh, pose3d, raw = out.tail
+        overlay = None
+        if frames is not None:
+            oo = live_overlay_layout(n, v0, *frames.shape[2:])[1]
+            overlay = self._draw(mesh, out.has_hand.view(-1), frames, 1, dev[oo:])
         host.copy_(dev, non_blocking=True)
-        return LiveOutput(out, p2d, mesh, pose3d, host, n, raw)
+        return LiveOutput(out, p2d, mesh, pose3d, host, n, raw, overlay)
 
 
 def live_hands_layout(slots: int, vertices: int):
@@ -182,8 +240,21 @@ def live_hands_layout(slots: int, vertices: int):
     return rows, rb, lifted, mesh, mesh + slots * vertices * 12
 
 
-LiveHandsRead = collections.namedtuple(
-    "LiveHandsRead", "keypoints has_hand crop_box score det_index image_uvd xyz_mm lifted mesh words")
+def live_hands_overlay_layout(slots: int, vertices: int, frames: int, h: int, w: int):
+    """live_hands_layout with the overlay appended: the same five values (every offset where a step without an overlay has
+    it; the fifth is now the overlay's offset) + the total bytes; the overlay is uint8 [frames,h,w,3]."""
+    rows, rb, lifted, mesh, overlay = live_hands_layout(slots, vertices)
+    return rows, rb, lifted, mesh, overlay, overlay + frames * h * w * 3
+
+
+class LiveHandsRead(collections.namedtuple(
+        "LiveHandsRead", "keypoints has_hand crop_box score det_index image_uvd xyz_mm lifted mesh words")):
+    """LiveHandsOutput.read() of a step without an overlay (`.overlay` is None; the fields are the ten it always had)."""
+    __slots__ = ()
+    overlay = None
+
+
+LiveHandsOverlayRead = collections.namedtuple("LiveHandsOverlayRead", LiveHandsRead._fields + ("overlay",))
 
 
 @dataclass
@@ -197,10 +268,11 @@ class LiveHandsOutput:
     n: int = 0
     k: int = 0
     raw_mesh: torch.Tensor = None   # [N*K,V0,3] the lifter's own output on the device
+    overlay: torch.Tensor = None    # [N,H,W,3] uint8 RGB on the device: all lifted meshes of a frame drawn over it (faces=)
 
     def read(self) -> LiveHandsRead:
         """After the stream is synchronised: the step's results per frame and slot as fresh CPU tensors (LiveHandsRead;
-        lifted as bool, words = the step's range words)."""
+        lifted as bool, words = the step's range words; a step with faces=: LiveHandsOverlayRead, + overlay [N,H,W,3] uint8)."""
         n, k, s = self.n, self.k, self.n * self.k
         rows, rb, lo, mo, nbytes = live_hands_layout(s, self.mesh.shape[2])
         rec = self.host[:lo].view(rows, rb)
@@ -209,7 +281,10 @@ class LiveHandsOutput:
         lifted = self.host[lo:mo].view(torch.int32).reshape(n, k) != 0
         mesh = self.host[mo:nbytes].view(torch.float32).reshape(n, k, -1, 3).clone()
         per = lambda t: t.reshape((n, k) + tuple(t.shape[1:]))
-        return LiveHandsRead(per(kp), per(has), per(box), per(score), per(index), per(img), per(xyz), lifted, mesh, words)
+        fields = (per(kp), per(has), per(box), per(score), per(index), per(img), per(xyz), lifted, mesh, words)
+        if self.overlay is None:
+            return LiveHandsRead(*fields)
+        return LiveHandsOverlayRead(*fields, self.host[nbytes:].reshape(self.overlay.shape).clone())
 
 
 class LiveHandsEngine(_LiveStep):
@@ -220,12 +295,16 @@ class LiveHandsEngine(_LiveStep):
     the final mesh (perm_reverse) -> ONE device -> host copy of records + lifted + mesh (live_hands_layout)."""
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, max_hands: int = 2, clamp: bool = True,
-                 perm_reverse=None):
+                 perm_reverse=None, faces=None):
+        """faces: mesh_model.face ([F,3]; needs perm_reverse) -- given, the step ends with the overlay: every lifted mesh of a
+        frame drawn over it with one depth buffer per frame (LiveHandsOutput.overlay, read().overlay), in the same copy."""
         self.max_hands = ops.check_max_hands(max_hands)
-        super().__init__(hand, lifter, paras, clamp, perm_reverse)
+        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces)
 
-    def _nbytes(self, n):
-        return live_hands_layout(n * self.max_hands, self.vertices)[4]
+    def _nbytes(self, n, hw=None):
+        if hw is None:
+            return live_hands_layout(n * self.max_hands, self.vertices)[4]
+        return live_hands_overlay_layout(n * self.max_hands, self.vertices, n, *hw)[5]
 
     @ops.device_guarded
     def forward_device(self, images, depth, _buffers=None) -> LiveHandsOutput:
@@ -233,7 +312,8 @@ class LiveHandsEngine(_LiveStep):
         may run A2J on the filled slots only (HandNetEngine.forward_hands); the lifter always runs on all N*K rows."""
         n, k = len(images), self.max_hands
         s, v = n * k, self.vertices
-        dev, host = _buffers if _buffers is not None else self._out_buffers(n, v)
+        frames = self._frames(images)
+        dev, host = _buffers if _buffers is not None else self._out_buffers(n, v, self._hw(frames))
         rows, rb, lo, mo, nbytes = live_hands_layout(s, v)
         rec = dev[:lo].view(rows, rb)
         lifted = dev[lo:mo].view(torch.int32)
@@ -251,8 +331,11 @@ class LiveHandsEngine(_LiveStep):
         # the step packs its per-slot records, range words, scores and ranks straight into `rec`; ONE copy moves it all
         out = self.hand.forward_hands(images, depth, k, _record=(None, rec), _tail=lift)
         p2d, mesh, pose3d, raw = out.tail
+        overlay = None
+        if frames is not None:
+            overlay = self._draw(mesh, lifted, frames, k, dev[nbytes:])
         host.copy_(dev, non_blocking=True)
-        return LiveHandsOutput(out, p2d, lifted.view(n, k), mesh.view(n, k, v, 3), pose3d, host, n, k, raw)
+        return LiveHandsOutput(out, p2d, lifted.view(n, k), mesh.view(n, k, v, 3), pose3d, host, n, k, raw, overlay)
 
 
 @dataclass

@@ -1668,6 +1668,80 @@ def mesh_finish(mesh, perm, xyz_mm, valid=None, out=None):
     return out
 
 
+def mesh_faces(faces, vertices, device):
+    """The caller's face list (mesh_model.face: numpy / tensor / list, [F,3] vertex indices) checked ON THE HOST against the
+    vertex count and uploaded once: int32 [F,3] on `device`, what mesh_render and the live engines draw with."""
+    f = np.asarray(faces.cpu() if torch.is_tensor(faces) else faces)
+    if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] == 0 or f.dtype.kind not in "iu":
+        raise ValueError(f"faces: expected a non-empty integer [F,3] list, got {f.dtype} {tuple(f.shape)}")
+    if int(f.min()) < 0 or int(f.max()) >= vertices:
+        raise ValueError(f"faces use vertex {int(f.min())}..{int(f.max())} of a mesh with {vertices} vertices")
+    return torch.from_numpy(np.ascontiguousarray(f.astype(np.int32))).to(device)
+
+
+def mesh_render_scratch_bytes(slots, faces):
+    return int(_lib.load().hn_mesh_render_scratch_bytes(slots, faces))
+
+
+def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out=None, scratch=None):
+    """The meshes drawn over their frames (hn_mesh_render_u8; render() of ros_demo.py:86-116 without a graphics pipeline):
+    mesh fp32 [S,V,3] or [N,K,V,3] as mesh_finish writes it, S = N * k slots; faces [F,3]: an int32 GPU tensor (mesh_faces) or
+    a host list (checked index by index and uploaded by THIS call: a caller that renders repeatedly uploads once with mesh_faces
+    and passes the tensor, as the live engines do); paras (fx, fy, cx, cy); frame fp32 [N,3,H,W] in 0..1 or uint8 [N,H,W,3]
+    'bgr8', on the GPU; lifted int32 [S] (0: the slot is not drawn).  Returns the overlay uint8 [N,H,W,3] RGB (`out`);
+    depth_out fp32 [N,H,W], when given, receives the drawn Z (0 where nothing was drawn)."""
+    _req(mesh, name="mesh")
+    if mesh.dim() == 4:
+        mesh = mesh.view(-1, mesh.shape[2], 3)
+    if mesh.dim() != 3 or mesh.shape[2] != 3:
+        raise ValueError(f"mesh: expected [S,V,3], got {tuple(mesh.shape)}")
+    s, v, _ = mesh.shape
+    faces_host = None
+    if not (torch.is_tensor(faces) and faces.is_cuda):
+        faces_host = np.ascontiguousarray(np.asarray(faces.cpu() if torch.is_tensor(faces) else faces).astype(np.int32))
+        if faces_host.ndim != 2 or faces_host.shape[1] != 3:
+            raise ValueError(f"faces: expected [F,3], got {tuple(faces_host.shape)}")
+        faces = torch.from_numpy(faces_host).to(mesh.device)
+    _req(faces, torch.int32, "faces")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces: expected [F,3], got {tuple(faces.shape)}")
+    f = faces.shape[0]
+    if frame.dtype == torch.uint8:
+        _req(frame, torch.uint8, "frame")
+        fmt, (n, h, w) = _lib.FRAME_U8_BGR_HWC, frame.shape[:3]
+        ok = frame.dim() == 4 and frame.shape[3] == 3
+    else:
+        _req(frame, name="frame")
+        fmt, n, (h, w) = _lib.FRAME_F32_CHW, frame.shape[0], frame.shape[2:]
+        ok = frame.dim() == 4 and frame.shape[1] == 3
+    if not ok:
+        raise ValueError(f"frame: expected fp32 [N,3,H,W] or uint8 [N,H,W,3], got {frame.dtype} {tuple(frame.shape)}")
+    if k < 1 or n * k != s:
+        raise ValueError(f"{s} mesh slots for {n} frames with k = {k} slots per frame")
+    if lifted is not None:
+        _req(lifted, torch.int32, "lifted")
+        if lifted.numel() != s:
+            raise ValueError(f"lifted: expected {s} flags, got {lifted.numel()}")
+    if out is None:
+        out = torch.empty((n, h, w, 3), device=mesh.device, dtype=torch.uint8)
+    _req(out, torch.uint8, "out")
+    if out.numel() != n * h * w * 3:
+        raise ValueError(f"out: expected uint8 [{n},{h},{w},3], got {tuple(out.shape)}")
+    if depth_out is not None:
+        _req(depth_out, name="depth_out")
+        if depth_out.numel() != n * h * w:
+            raise ValueError(f"depth_out: expected fp32 [{n},{h},{w}], got {tuple(depth_out.shape)}")
+    need = mesh_render_scratch_bytes(s, f)
+    if scratch is None:
+        scratch = torch.empty((need,), device=mesh.device, dtype=torch.uint8)
+    _req(scratch, torch.uint8, "scratch")
+    p4 = (C.c_float * 4)(*[float(x) for x in paras])
+    check(_lib.load().hn_mesh_render_u8(ptr(mesh), ptr(faces), faces_host.ctypes.data if faces_host is not None else None,
+                                        ptr(lifted), s, v, f, k, p4, ptr(frame), fmt, h, w, ptr(scratch), scratch.numel(),
+                                        ptr(out), ptr(depth_out), _stream()), "hn_mesh_render_u8")
+    return out.view(n, h, w, 3)
+
+
 def pad_split_rows(x, cpad):
     """fp32 [rows, f] -> S32 [rows,1,1,cpad/32,2,32], channels f.. zero (hn_pad_split_rows_f32)."""
     _req(x, name="x")

@@ -33,7 +33,7 @@ extern "C" {
 #define HN_ERR_HIP 2
 
 /* ABI version; bumped whenever a struct below changes (functions added without touching a struct or an existing signature
- * keep it: hn_lifter_input_gated_f32 came under 36). */
+ * keep it: hn_lifter_input_gated_f32 and hn_mesh_render_u8 came under 36). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -675,6 +675,29 @@ int hn_pad_split_rows_f32(const float* x, int64_t rows, int f, int cpad, void* o
  * rounding per operation (bit-identical).  mesh [n][v0][3], xyz_mm [n][joints][3], out [n][v][3]; rows with valid != 1 are zeros. */
 int hn_mesh_finish_f32(const float* mesh, const int64_t* perm, const float* xyz_mm, const int32_t* valid /* or NULL */, int n,
                        int v0, int v, int joints, float* out, void* stream);
+/* The live caller's last call, render(out, paras, h, w, full_image, face) (ros_demo.py:86-116,329-337), without a graphics
+ * pipeline: the meshes of s = n * k hand slots (slot i * k + j = hand j of frame i) rasterised over their frames, one depth
+ * buffer per frame.  mesh [s][v][3] fp32 as hn_mesh_finish_f32 writes it (metres, y and z negated), faces [f][3] int32 vertex
+ * indices (device), lifted [s] int32 or NULL (a slot with lifted == 0 is not drawn), paras = HOST fx, fy, cx, cy of the one
+ * camera.  Vertices are projected with the plain pinhole u = (fx X) / Z + cx, v = (fy Y) / Z + cy, (X, Y, Z) = (x, -y, -z), in
+ * fp32 with one rounding per operation, and snapped to 1/256 pixel; pixel (col, row) is sampled at (col + 0.5, row + 0.5);
+ * coverage is decided by 64-bit integer edge functions with the top-left rule, both windings; the nearest Z wins (the lower
+ * slot, then the lower face on an exact tie); a face with a vertex that is non-finite, nearer than 0.05 m, farther than 100 m
+ * or snapped beyond 2^24, a face of zero area and a face with an index outside [0, v) are not drawn (no clipping).  Covered
+ * pixels get the face's flat colour, floor(255 min(1, 0.3 + 2.4 |n_z| / (|n| pi)) (1, 1, 0.9) + 0.5); every other pixel is
+ * the frame's: frame = fp32 [n][3][h][w] in 0..1 (HN_FRAME_F32_CHW: rint(255 x)) or uint8 [n][h][w][3] 'bgr8'
+ * (HN_FRAME_U8_BGR_HWC).  out_image [n][h][w][3] uint8 RGB; out_depth [n][h][w] fp32 or NULL: Z of the drawn face, 0 where
+ * nothing was drawn.  Two launches on the caller's stream, no allocation, no atomics: the image is a pure function of the
+ * arguments.  scratch: hn_mesh_render_scratch_bytes(s, f) bytes on the device, 16-byte aligned.  faces_host (or NULL): a host
+ * copy of `faces`; when given, an index outside [0, v) is an argument error (nothing is launched).  h, w <= 16384.
+ * Added under ABI 36: new functions only. */
+#define HN_FRAME_F32_CHW 0
+#define HN_FRAME_U8_BGR_HWC 1
+int64_t hn_mesh_render_scratch_bytes(int s, int f);
+int hn_mesh_render_u8(const float* mesh, const int32_t* faces, const int32_t* faces_host /* or NULL */,
+                      const int32_t* lifted /* or NULL */, int s, int v, int f, int k, const float* paras, const void* frame,
+                      int frame_format, int h, int w, void* scratch, int64_t scratch_bytes, uint8_t* out_image,
+                      float* out_depth /* or NULL */, void* stream);
 /* A Linear layer on 1..4 rows as a matrix-vector product on the vector ALU (PoseNet at the live caller's batch, posenet.py:24-41,
  * 78-88: 67 MB of filter bank per 17 M MACs): y[m][:] = act(W (pre(x[m])) + bias (+ residual[m])), pre = relu(x * scale + shift)
  * when scale / shift ([k_real] fp32: the pre-activation BatchNorm) are given.  x fp32 [batch][x_stride] (k_real columns used), w16 =
