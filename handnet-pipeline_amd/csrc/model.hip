@@ -1434,6 +1434,36 @@ extern "C" int hn_fcos_forward_ext(hn_model* m, const float* rgb, int n, int h, 
   return run_planned(m, key, stream, [&](Ctx& cx) -> int { return fcos_graph(cx, rgb, n, h, w, out); });
 }
 
+// The step hn_handnet_forward (max_hands = 0: the top-1 crop, hn_crop_resize) and hn_handnet_forward_hands (max_hands slots per
+// frame, hn_crop_resize_hands; score: [n * max_hands]) share: the detector's outputs in the arena, fcos_graph, the crop stage,
+// a2j_graph on the crops with the slots' has_hand mask.
+static int handnet_graph(Ctx& cx, const float* rgb, const float* depth, int n, int h, int w, int cap, int max_hands,
+                         float* keypoints, int64_t* crop_box, int32_t* has_hand, float* score) {
+  const hn_model* m = cx.m;
+  const int k = max_hands ? n * max_hands : n;
+  FcosOut out;
+  out.cap = cap;
+  out.boxes = (float*)alloc_bytes(cx, (size_t)n * cap * 16);
+  out.scores = (float*)alloc_bytes(cx, (size_t)n * cap * 4);
+  out.labels = (int32_t*)alloc_bytes(cx, (size_t)n * cap * 4);
+  out.sides = (int32_t*)alloc_bytes(cx, (size_t)n * cap * 4);
+  out.level = (int32_t*)alloc_bytes(cx, (size_t)n * cap * 4);
+  out.count = (int32_t*)alloc_bytes(cx, (size_t)n * 4);
+  HN_TRY(fcos_graph(cx, rgb, n, h, w, out));
+  int32_t* det_index = max_hands ? (int32_t*)alloc_bytes(cx, (size_t)k * 4) : nullptr;
+  T crops;
+  crops.n = k; crops.h = kCrop; crops.w = kCrop; crops.c = 4; crops.ps = 4; crops.split = false;
+  crops.p = alloc_bytes(cx, (size_t)k * kCrop * kCrop * 16);
+  const int depth_c = m->cfg.rgbd ? 4 : 1, depth_off = m->cfg.rgbd ? 1 : 0;
+  if (!cx.dry)
+    HN_TRY(max_hands ? hn_crop_resize_hands(out.boxes, out.scores, out.labels, out.count, cap, m->cfg.num_classes - 1, max_hands,
+                                            depth, n, depth_c, depth_off, h, w, kCrop, 4, crop_box, has_hand, score, det_index,
+                                            (float*)crops.p, cx.stream)
+                     : hn_crop_resize(out.boxes, out.labels, out.count, cap, m->cfg.num_classes - 1, depth, n, depth_c, depth_off,
+                                      h, w, kCrop, 4, crop_box, has_hand, (float*)crops.p, cx.stream));
+  return a2j_graph(cx, crops, has_hand, keypoints, has_hand);
+}
+
 extern "C" int hn_handnet_forward(hn_model* m, const float* rgb, const float* depth, int n, int h, int w, float* keypoints,
                                   int64_t* crop_box, int32_t* has_hand, void* stream) {
   HN_CHECK_ARG(m && rgb && depth && keypoints && crop_box && has_hand, "hn_handnet_forward: null pointer");
@@ -1442,22 +1472,7 @@ extern "C" int hn_handnet_forward(hn_model* m, const float* rgb, const float* de
   const int cap = (int)hn_fcos_capacity(m, h, w);
   const std::string key = "handnet:" + std::to_string(n) + "x" + std::to_string(h) + "x" + std::to_string(w);
   return run_planned(m, key, stream, [&](Ctx& cx) -> int {
-    FcosOut out;
-    out.cap = cap;
-    out.boxes = (float*)alloc_bytes(cx, (size_t)n * cap * 16);
-    out.scores = (float*)alloc_bytes(cx, (size_t)n * cap * 4);
-    out.labels = (int32_t*)alloc_bytes(cx, (size_t)n * cap * 4);
-    out.sides = (int32_t*)alloc_bytes(cx, (size_t)n * cap * 4);
-    out.level = (int32_t*)alloc_bytes(cx, (size_t)n * cap * 4);
-    out.count = (int32_t*)alloc_bytes(cx, (size_t)n * 4);
-    HN_TRY(fcos_graph(cx, rgb, n, h, w, out));
-    T crops;
-    crops.n = n; crops.h = kCrop; crops.w = kCrop; crops.c = 4; crops.ps = 4; crops.split = false;
-    crops.p = alloc_bytes(cx, (size_t)n * kCrop * kCrop * 16);
-    if (!cx.dry)
-      HN_TRY(hn_crop_resize(out.boxes, out.labels, out.count, cap, m->cfg.num_classes - 1, depth, n, m->cfg.rgbd ? 4 : 1,
-                            m->cfg.rgbd ? 1 : 0, h, w, kCrop, 4, crop_box, has_hand, (float*)crops.p, cx.stream));
-    return a2j_graph(cx, crops, has_hand, keypoints, has_hand);
+    return handnet_graph(cx, rgb, depth, n, h, w, cap, 0, keypoints, crop_box, has_hand, nullptr);
   });
 }
 
@@ -1468,28 +1483,10 @@ extern "C" int hn_handnet_forward_hands(hn_model* m, const float* rgb, const flo
   HN_CHECK_ARG(n > 0 && h > 0 && w > 0, "bad image batch");
   HN_CHECK_ARG(max_hands >= 1 && max_hands <= 16, "max_hands must be 1..16 (got %d)", max_hands);
   const int cap = (int)hn_fcos_capacity(m, h, w);
-  const int k = n * max_hands;
   const std::string key = "hands:" + std::to_string(n) + "x" + std::to_string(max_hands) + "x" + std::to_string(h) + "x" +
                           std::to_string(w);
   return run_planned(m, key, stream, [&](Ctx& cx) -> int {
-    FcosOut out;
-    out.cap = cap;
-    out.boxes = (float*)alloc_bytes(cx, (size_t)n * cap * 16);
-    out.scores = (float*)alloc_bytes(cx, (size_t)n * cap * 4);
-    out.labels = (int32_t*)alloc_bytes(cx, (size_t)n * cap * 4);
-    out.sides = (int32_t*)alloc_bytes(cx, (size_t)n * cap * 4);
-    out.level = (int32_t*)alloc_bytes(cx, (size_t)n * cap * 4);
-    out.count = (int32_t*)alloc_bytes(cx, (size_t)n * 4);
-    HN_TRY(fcos_graph(cx, rgb, n, h, w, out));
-    int32_t* det_index = (int32_t*)alloc_bytes(cx, (size_t)k * 4);
-    T crops;
-    crops.n = k; crops.h = kCrop; crops.w = kCrop; crops.c = 4; crops.ps = 4; crops.split = false;
-    crops.p = alloc_bytes(cx, (size_t)k * kCrop * kCrop * 16);
-    if (!cx.dry)
-      HN_TRY(hn_crop_resize_hands(out.boxes, out.scores, out.labels, out.count, cap, m->cfg.num_classes - 1, max_hands, depth, n,
-                                  m->cfg.rgbd ? 4 : 1, m->cfg.rgbd ? 1 : 0, h, w, kCrop, 4, crop_box, has_hand, score,
-                                  det_index, (float*)crops.p, cx.stream));
-    return a2j_graph(cx, crops, has_hand, keypoints, has_hand);
+    return handnet_graph(cx, rgb, depth, n, h, w, cap, max_hands, keypoints, crop_box, has_hand, score);
   });
 }
 

@@ -21,6 +21,7 @@ the previous frame's crop (:100-105); here such frames simply count as "no hand"
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -193,14 +194,25 @@ class HandNet(EngineOwner):
             if out is not None:
                 return out
         batch = images if torch.is_tensor(images) else torch.stack([i.float() for i in images])
-        if self._auto_graph(batch.shape, depth_images.shape, batch.is_cuda and depth_images.is_cuda):
+        return self._graph_or_eager(self._auto_graph(batch.shape, depth_images.shape, batch.is_cuda and depth_images.is_cuda),
+                                    lambda: self.forward_device(batch, depth_images, _graph=True, _to_host=True),
+                                    lambda: self.forward_device(batch, depth_images, _graph=False, _to_host=True))
+
+    def _graph_or_eager(self, graph, captured, eager, passing=()):
+        """The one capture ladder of forward(), forward_hands() and forward_raw(): graph -> captured() (capture if need be, and
+        replay), else eager().  A RangeError (and the caller's `passing`: errors of its arguments) always propagates, and so
+        does every failure in the forced mode (enable_graph(True)); in the automatic mode any other failure of captured()
+        ends capturing for good (_capture_failed) and the call runs eagerly."""
+        if graph:
             try:
-                return self.forward_device(batch, depth_images, _graph=True, _to_host=True)
-            except ops.RangeError:
+                return captured()
+            except (ops.RangeError,) + passing:
                 raise
             except Exception as e:  # noqa: BLE001 -- whatever made the capture fail, this call would succeed eagerly
+                if getattr(self, "use_graph", None):
+                    raise
                 self._capture_failed(e)
-        return self.forward_device(batch, depth_images, _graph=False, _to_host=True)
+        return eager()
 
     def _capture_failed(self, e):
         import warnings
@@ -245,48 +257,29 @@ class HandNet(EngineOwner):
         batch, depth = batch.to(dev).float().contiguous(), depth_images.to(dev).float().contiguous()
         mode = getattr(self, "use_graph", None)
         graph = bool(mode) if mode is not None else self._auto_graph(batch.shape, depth.shape, True, hands=k)
-        out = None
-        if graph:
-            try:
-                run, s_img, s_dep, out = eng.graphed_hands(batch, depth, k, to_host=True, limit=self.AUTO_GRAPH_MAX_SHAPES)
-                s_img.copy_(batch)
-                s_dep.copy_(depth)
-                run()
-            except ops.RangeError:
-                raise
-            except Exception as e:  # noqa: BLE001 -- whatever made the capture fail, this call would succeed eagerly
-                if mode:
-                    raise
-                self._capture_failed(e)
-                out = None
-        if out is None:
-            out = eng.forward_hands(batch, depth, k, to_host=True)
+
+        def captured():
+            run, s_img, s_dep, out = eng.graphed_hands(batch, depth, k, to_host=True, limit=self.AUTO_GRAPH_MAX_SHAPES)
+            s_img.copy_(batch)
+            s_dep.copy_(depth)
+            run()
+            return out
+        out = self._graph_or_eager(graph, captured, lambda: eng.forward_hands(batch, depth, k, to_host=True))
         return self._finish_hands(out, n, k, depth)
 
     def _finish_hands(self, out, n, k, depth):
         """forward_hands()'s tuple from the step's one host record (see _finish)."""
-        from hn_amd.pipeline import read_hands_tail, read_host_record
+        from hn_amd.pipeline import read_hands_tail
         rows = n * k
         sel = out.crops_nhwc
         depth_all = (sel.permute(0, 3, 1, 2) if self.RGBD else sel[..., 0].unsqueeze(1)).contiguous()
-        torch.cuda.current_stream(out.keypoints.device).synchronize()
-        joints = out.keypoints.shape[2]
-        if out.image_uvd is not None:
-            kp, has, box, words, more = read_host_record(out.host_record, rows, joints, extras=True)
-            self.last_converted = {"image_uvd": more[0].view(n, k, joints, 3),
-                                   "xyz_mm": more[1].view(n, k, joints, 3) if len(more) > 1 else None}
-        else:
-            kp, has, box, words = read_host_record(out.host_record, rows, joints)
+        kp, box, mask, filled = self._read_step(out, (n, k), "_last_sparse_hands", depth)
         scores, _ = read_hands_tail(out.host_record, rows)
-        mask = has != 0
-        filled = int(mask.sum())
-        self._last_sparse_hands = rows >= 8 and filled * 2 < rows     # (the engine's own threshold for compaction)
-        check_range_contract(kp, words if out.range_flags is not None else None, depth, has_hand=has)
         if filled == rows:
             depth_batch = depth_all
         else:
             depth_batch = depth_all.index_select(0, mask.nonzero().flatten().to(depth_all.device))
-        return kp.view(n, k, joints, 3), depth_batch, box.view(n, k, 4), mask.view(n, k), scores.view(n, k)
+        return kp, depth_batch, box, mask.view(n, k), scores.view(n, k)
 
     def forward_raw(self, bgr_u8, depth_raw, is_3D: bool = False, is_detect: bool = False):
         """The reference caller's ingest AND its network call in one (ros_demo.py:227-231,266-273): bgr_u8 = the cv_bridge
@@ -311,43 +304,39 @@ class HandNet(EngineOwner):
         shapes = ((n, 3, h, w), (n, 4 if self.RGBD else 1, h, w))
         mode = getattr(self, "use_graph", None)
         graph = bool(mode) if mode is not None else self._auto_graph(*shapes)
-        out = None
-        if graph:
-            try:
-                out = eng.forward_raw(bgr, dep, to_host=True, use_graph=True, limit=self.AUTO_GRAPH_MAX_SHAPES)
-            except (ops.RangeError, TypeError, ValueError):
-                raise
-            except Exception as e:  # noqa: BLE001
-                if mode:
-                    raise
-                self._capture_failed(e)
-        if out is None:
-            out = eng.forward_raw(bgr, dep, to_host=True)
+        out = self._graph_or_eager(
+            graph, lambda: eng.forward_raw(bgr, dep, to_host=True, use_graph=True, limit=self.AUTO_GRAPH_MAX_SHAPES),
+            lambda: eng.forward_raw(bgr, dep, to_host=True), passing=(TypeError, ValueError))
         return self._finish(out, n, None, placeholder_shape=shapes[1])
+
+    def _read_step(self, out, lead, sparse_hint, inputs):
+        """What _finish and _finish_hands share: wait for the step, read its host record (rows = the product of `lead`: (N,) or
+        (N, K)), fill last_converted after set_convert(), set the sparse hint `sparse_hint` for the next call and apply the
+        f16x3 range contract to what has just been copied (hn_amd.pipeline.check_range_contract: overflow raises, non-finite
+        depth pixels give NaN rows like the reference).  -> (keypoints lead + [J,3], boxes lead + [4], mask [rows], filled)."""
+        from hn_amd.pipeline import read_host_record
+        torch.cuda.current_stream(out.keypoints.device).synchronize()
+        rows, per = math.prod(lead), lead + tuple(out.keypoints.shape[-2:])
+        kp, has, box, words, more = read_host_record(out.host_record, rows, per[-2], extras=True)
+        if out.image_uvd is not None:
+            self.last_converted = {"image_uvd": more[0].view(per), "xyz_mm": more[1].view(per) if len(more) > 1 else None}
+        mask = has != 0
+        filled = int(mask.sum())
+        setattr(self, sparse_hint, rows >= 8 and filled * 2 < rows)      # (the engine's own threshold for compaction)
+        check_range_contract(kp, words if out.range_flags is not None else None, inputs, has_hand=has)
+        return kp.view(per), box.view(lead + (4,)), mask, filled
 
     def _finish(self, out, n, depth_images, placeholder_shape=None):
         """The reference's return tuple from a step's device results: ONE device -> host copy (and sync) per call -- the
         step's record buffer (keypoints, has-hand flags, crop boxes, range-contract words), which the step has already enqueued
         into pinned memory."""
-        from hn_amd.pipeline import read_host_record
         # the usual case -- every frame has a hand -- needs fresh copies of the crop boxes and the depth crops; they are
         # enqueued BEFORE the sync (hidden behind the step instead of trailing it) and thrown away in the other cases
         # (.contiguous() of the permuted / sliced view is a copy: the caller never holds a view of a captured buffer)
         sel = out.crops_nhwc
         crops_all = out.crop_box.clone()
         depth_all = (sel.permute(0, 3, 1, 2) if self.RGBD else sel[..., 0].unsqueeze(1)).contiguous()
-        torch.cuda.current_stream(out.keypoints.device).synchronize()
-        if out.image_uvd is not None:
-            final_results, has, _box, words, more = read_host_record(out.host_record, n, out.keypoints.shape[1], extras=True)
-            self.last_converted = {"image_uvd": more[0], "xyz_mm": more[1] if len(more) > 1 else None}
-        else:
-            final_results, has, _box, words = read_host_record(out.host_record, n, out.keypoints.shape[1])
-        mask_cpu = has != 0
-        hands = int(mask_cpu.sum())
-        self._last_sparse = n >= 8 and hands * 2 < n      # (the engine's own threshold for compaction)
-        # the f16x3 range contract, decided on what has just been copied (hn_amd.pipeline.check_range_contract): overflow raises,
-        # non-finite depth pixels give NaN rows like the reference
-        check_range_contract(final_results, words if out.range_flags is not None else None, depth_images, has_hand=has)
+        final_results, _box, mask_cpu, hands = self._read_step(out, (n,), "_last_sparse", depth_images)
         if hands == 0:  # handnet_pipeline.py:107-108: the crops placeholder is a CPU float tensor
             zeros = torch.zeros_like(depth_images) if depth_images is not None else torch.zeros(
                 placeholder_shape, device=out.keypoints.device)

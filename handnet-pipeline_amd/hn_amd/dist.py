@@ -336,25 +336,18 @@ class ShardedHandNet:
             s_img, s_dep = torch.empty_like(batch), torch.empty_like(depth)
             s_img.copy_(batch)
             s_dep.copy_(depth)
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with ops.launch_cost_hidden():
-                with torch.cuda.stream(side):
-                    for _ in range(2):     # (a failure HERE is a failure of the eager path: it propagates, like any step's)
-                        self._step(s_img, s_dep, per_rank, bufs, total)
-                torch.cuda.current_stream().wait_stream(side)
-                torch.cuda.current_stream().synchronize()
-                eager = bufs["host"].clone()             # what the last eager step gathered for these inputs
-                why, g, out = None, None, None
-                try:
-                    if os.environ.get("HN_TEST_REFUSE_CAPTURE_RANK") == str(self.rank):     # (tests: a one-rank refusal)
-                        raise RuntimeError("refused on this rank for the test")
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                        out = self._step(s_img, s_dep, per_rank, bufs, total)
-                except Exception as e:  # noqa: BLE001 -- the backend (or a capture-unsafe call elsewhere in the process) refused
-                    torch.cuda.synchronize()
-                    why = f"{type(e).__name__}: {str(e)[:200]}"
+            # (a failure HERE is a failure of the eager path: it propagates, like any step's)
+            ops.warm_up_on_side_stream(lambda: self._step(s_img, s_dep, per_rank, bufs, total))
+            torch.cuda.current_stream().synchronize()
+            eager = bufs["host"].clone()             # what the last eager step gathered for these inputs
+            why, g, out = None, None, None
+            try:
+                if os.environ.get("HN_TEST_REFUSE_CAPTURE_RANK") == str(self.rank):     # (tests: a one-rank refusal)
+                    raise RuntimeError("refused on this rank for the test")
+                g, out = ops.capture(lambda: self._step(s_img, s_dep, per_rank, bufs, total))
+            except Exception as e:  # noqa: BLE001 -- the backend (or a capture-unsafe call elsewhere in the process) refused
+                torch.cuda.synchronize()
+                why = f"{type(e).__name__}: {str(e)[:200]}"
             if not self._agree(why is None):
                 return refused(why or "another rank could not capture it")
             # a captured collective must deliver what the eager one did: one replay on the same inputs, compared byte for

@@ -35,6 +35,17 @@ def _same_device(a, b) -> bool:
     return a.type == b.type and (a.type != "cuda" or index(a) == index(b))
 
 
+def _final_mesh_perm(perm_reverse, lifter, device):
+    """(perm_reverse as int64 on the device -- None stays None --, vertices of the mesh the step hands over): the indices must
+    lie inside the lifter's finest graph."""
+    if perm_reverse is None:
+        return None, lifter.graphs[0].v
+    perm = torch.as_tensor(perm_reverse).to(torch.int64).to(device).contiguous()
+    if int(perm.max()) >= lifter.graphs[0].v or int(perm.min()) < 0:
+        raise ValueError("perm_reverse points outside the lifter's finest graph")
+    return perm, int(perm.shape[0])
+
+
 class LiveRead(collections.namedtuple("LiveRead", "keypoints has_hand crop_box words more mesh")):
     """LiveOutput.read() of a step without an overlay: unpacks as the six results it always had."""
     __slots__ = ()
@@ -71,7 +82,9 @@ class LiveOutput:
         n = self.n
         rec = self.host[: (n + 1) * rb].view(n + 1, rb)
         kp, has, box, words, more = read_host_record(rec, n, extras=True)
-        mo, oo = (n + 1) * rb, (n + 1) * rb + self.mesh[0].numel() * 4 * n
+        # (h = w = 0: a step without an overlay has the records and the mesh at the same offsets, and nothing behind them)
+        h, w = (0, 0) if self.overlay is None else self.overlay.shape[1:3]
+        mo, oo, _ = live_overlay_layout(n, self.mesh.shape[1], h, w)
         mesh = self.host[mo:oo].view(torch.float32).reshape(n, -1, 3).clone()
         if self.overlay is None:
             return LiveRead(kp, has, box, words, more, mesh)
@@ -88,12 +101,7 @@ class _LiveStep:
             raise ValueError(f"HandNet on {hand.device} but the lifter on {lifter.device}")
         self.hand, self.lifter, self.device = hand, lifter, hand.device
         hand.set_convert(paras=paras, clamp=clamp)
-        self.perm = None
-        if perm_reverse is not None:
-            self.perm = torch.as_tensor(perm_reverse).to(torch.int64).to(self.device).contiguous()
-            if int(self.perm.max()) >= lifter.graphs[0].v or int(self.perm.min()) < 0:
-                raise ValueError("perm_reverse points outside the lifter's finest graph")
-        self.vertices = lifter.graphs[0].v if self.perm is None else int(self.perm.shape[0])
+        self.perm, self.vertices = _final_mesh_perm(perm_reverse, lifter, self.device)
         # faces: the mesh's triangles (mesh_model.face) -- given, the step ends with the overlay (ops.mesh_render: the caller's
         # render(), ros_demo.py:86-116) and the image rides behind the mesh in the step's one copy
         self.faces, self.paras = None, tuple(float(p) for p in paras)
@@ -126,14 +134,18 @@ class _LiveStep:
                     (ops.mesh_render_scratch_bytes(s, self.faces.shape[0]),), dtype=torch.uint8, device=self.device)
         return ops.mesh_render(mesh, self.faces, self.paras, frames, lifted=lifted, k=k, out=out, scratch=scratch)
 
+    def _new_buffers(self, n, hw=None):
+        """A fresh (device, pinned host) pair of a step over n frames (hw: with an overlay of that frame size)."""
+        nbytes = self._nbytes(n, hw)
+        return (torch.zeros((nbytes,), dtype=torch.uint8, device=self.device),
+                torch.zeros((nbytes,), dtype=torch.uint8, pin_memory=True))
+
     def _out_buffers(self, n, v0, hw=None):
         key = (n, v0, hw)
         b = self._buffers.get(key)
         if b is None:
-            nbytes = self._nbytes(n, hw)
             with torch.inference_mode(False):
-                b = self._buffers[key] = (torch.zeros((nbytes,), dtype=torch.uint8, device=self.device),
-                                          torch.zeros((nbytes,), dtype=torch.uint8, pin_memory=True))
+                b = self._buffers[key] = self._new_buffers(n, hw)
         return b
 
     @ops.device_guarded
@@ -149,11 +161,7 @@ class _LiveStep:
         if key not in self._graphs:
             rgb, d1, _ = ops.ingest_raw(bgr, dep, device=self.device)
             self.graphed(rgb, d1)
-        g, s_img, s_dep, out = self._graphs[key]
-        ops.ingest_raw(bgr, dep, out_rgb=s_img, out_depth=s_dep)
-        self.hand._staged_done(staged)
-        g.replay()
-        return out
+        return self.hand._ingest_replay(self._graphs[key], bgr, dep, staged)
 
     @ops.device_guarded
     def graphed(self, images: torch.Tensor, depth: torch.Tensor):
@@ -165,19 +173,9 @@ class _LiveStep:
                 s_img, s_dep = torch.empty_like(images), torch.empty_like(depth)
                 s_img.copy_(images)
                 s_dep.copy_(depth)
-                nbytes = self._nbytes(images.shape[0], self._hw(self._frames(images)))
-                bufs = (torch.zeros((nbytes,), dtype=torch.uint8, device=self.device),
-                        torch.zeros((nbytes,), dtype=torch.uint8, pin_memory=True))
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with ops.launch_cost_hidden():
-                    with torch.cuda.stream(side):
-                        for _ in range(2):
-                            self.forward_device(s_img, s_dep, _buffers=bufs)
-                    torch.cuda.current_stream().wait_stream(side)
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                        out = self.forward_device(s_img, s_dep, _buffers=bufs)
+                # the capture's own pair, never the eager cache's (addresses are baked into the graph)
+                bufs = self._new_buffers(images.shape[0], self._hw(self._frames(images)))
+                g, out = ops.capture_step(lambda: self.forward_device(s_img, s_dep, _buffers=bufs))
             hit = self._graphs[key] = (g, s_img, s_dep, out)
         g, s_img, s_dep, out = hit
         return g.replay, s_img, s_dep, out
@@ -371,12 +369,7 @@ class CropMeshEngine:
         if not _same_device(a2j.device, lifter.device):
             raise ValueError(f"A2J on {a2j.device} but the lifter on {lifter.device}")
         self.a2j, self.lifter, self.device, self.clamp = a2j, lifter, a2j.device, bool(clamp)
-        self.perm = None
-        if perm_reverse is not None:
-            self.perm = torch.as_tensor(perm_reverse).to(torch.int64).to(self.device).contiguous()
-            if int(self.perm.max()) >= lifter.graphs[0].v or int(self.perm.min()) < 0:
-                raise ValueError("perm_reverse points outside the lifter's finest graph")
-        self.vertices = lifter.graphs[0].v if self.perm is None else int(self.perm.shape[0])
+        self.perm, self.vertices = _final_mesh_perm(perm_reverse, lifter, self.device)
         self._block = None
         self._graphs = {}
         self._hosts = {}
@@ -399,9 +392,14 @@ class CropMeshEngine:
             _host = self._hosts.get(dev.numel())      # overwrites it (read() hands out copies)
             if _host is None:
                 with torch.inference_mode(False):
-                    _host = self._hosts[dev.numel()] = torch.empty((dev.numel(),), dtype=torch.float32, pin_memory=True)
+                    _host = self._hosts[dev.numel()] = self._new_host(k)
         _host.copy_(dev, non_blocking=True)
         return CropMeshOutput(kp, img, xyz, p2d, mesh, pose3d, raw, _host, k)
+
+    def _new_host(self, k):
+        """The pinned buffer of a step over k crops, as forward_device's torch.cat fills it: three [k,J,3] fields (keypoints,
+        image_uvd, xyz_mm), the mesh [k,V,3], 4 range words."""
+        return torch.zeros((3 * k * self.a2j.joints * 3 + k * self.vertices * 3 + 4,), dtype=torch.float32, pin_memory=True)
 
     @ops.device_guarded
     def graphed(self, crops, box_f32, paras):
@@ -414,18 +412,8 @@ class CropMeshEngine:
                 s = [torch.empty_like(t) for t in (crops, box_f32, paras)]
                 for a, b in zip(s, (crops, box_f32, paras)):
                     a.copy_(b)
-                k = crops.shape[0]
-                host = torch.zeros((3 * k * self.a2j.joints * 3 + k * self.vertices * 3 + 4,), dtype=torch.float32, pin_memory=True)
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with ops.launch_cost_hidden():
-                    with torch.cuda.stream(side):
-                        for _ in range(2):
-                            self.forward_device(*s, _host=host)
-                    torch.cuda.current_stream().wait_stream(side)
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                        out = self.forward_device(*s, _host=host)
+                host = self._new_host(crops.shape[0])
+                g, out = ops.capture_step(lambda: self.forward_device(*s, _host=host))
             hit = self._graphs[key] = (g, s[0], s[1], s[2], out)
         g, s_crops, s_box, s_paras, out = hit
         return g.replay, s_crops, s_box, s_paras, out

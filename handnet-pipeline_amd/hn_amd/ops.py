@@ -250,6 +250,35 @@ class launch_cost_hidden:
     def __exit__(self, *a):
         global SPLITK_EAGER
         SPLITK_EAGER = self._old
+
+
+def warm_up_on_side_stream(step, steps: int = 2):
+    """First half of capture_step: `step()` run eagerly on a side stream, then the streams joined."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with launch_cost_hidden(), torch.cuda.stream(side):
+        for _ in range(steps):  # warm-up (allocator, lazy module load) outside capture
+            step()
+    torch.cuda.current_stream().wait_stream(side)
+
+
+def capture(step):
+    """Second half of capture_step: `step()` captured into a hipGraph -> (graph, what step returned)."""
+    g = torch.cuda.CUDAGraph()
+    # thread_local: GPU work another thread of the host process issues meanwhile (a ROS node's other callbacks)
+    # does not invalidate the capture
+    with launch_cost_hidden(), torch.cuda.graph(g, capture_error_mode="thread_local"):
+        out = step()
+    return g, out
+
+
+def capture_step(step):
+    """The engines' one capture recipe -> (graph, out).  `step` takes no argument and reads static tensors its caller
+    has filled; the caller also holds torch.inference_mode(False) / torch.no_grad() where it allocates them."""
+    warm_up_on_side_stream(step)
+    return capture(step)
+
+
 _WORKSPACES = {}
 
 

@@ -475,24 +475,27 @@ class HandNetEngine:
         n, h, w, _ = bgr.shape
         dshape = (n, 4 if self.a2j.rgbd else 1, h, w)
         hit = self.captured((n, 3, h, w), dshape, to_host)
-        if hit is None and use_graph and not torch.cuda.is_current_stream_capturing():
+        if hit is None:
             rgb, d1, d4 = ops.ingest_raw(bgr, dep, device=self.device, want_rgbd=self.a2j.rgbd, want_depth=not self.a2j.rgbd)
-            self._staged_done(staged)
-            staged = []
-            self.graphed(rgb, d4 if self.a2j.rgbd else d1, to_host=to_host, limit=limit)
+            depth = d4 if self.a2j.rgbd else d1
+            if not use_graph or torch.cuda.is_current_stream_capturing():
+                self._staged_done(staged)
+                return self.forward_device(rgb, depth, to_host=to_host)
+            self.graphed(rgb, depth, to_host=to_host, limit=limit)
             hit = self.captured((n, 3, h, w), dshape, to_host)
-        if hit is not None:
-            g, s_img, s_dep, out = hit
-            if self.a2j.rgbd:     # (the 4-channel tensor only: no separate depth map is written or allocated)
-                ops.ingest_raw(bgr, dep, out_rgb=s_img, out_rgbd=s_dep, want_depth=False)
-            else:
-                ops.ingest_raw(bgr, dep, out_rgb=s_img, out_depth=s_dep)
-            self._staged_done(staged)
-            g.replay()
-            return out
-        rgb, d1, d4 = ops.ingest_raw(bgr, dep, device=self.device, want_rgbd=self.a2j.rgbd, want_depth=not self.a2j.rgbd)
+        return self._ingest_replay(hit, bgr, dep, staged)
+
+    def _ingest_replay(self, hit, bgr, dep, staged):
+        """Ingest into the static inputs of a captured step (this engine's, or a live step's around it) and replay it.  The
+        staging event is recorded ONCE, behind the last ingest_raw of the call that reads the staging buffers."""
+        g, s_img, s_dep, out = hit
+        if self.a2j.rgbd:     # (the 4-channel tensor only: no separate depth map is written or allocated)
+            ops.ingest_raw(bgr, dep, out_rgb=s_img, out_rgbd=s_dep, want_depth=False)
+        else:
+            ops.ingest_raw(bgr, dep, out_rgb=s_img, out_depth=s_dep)
         self._staged_done(staged)
-        return self.forward_device(rgb, d4 if self.a2j.rgbd else d1, to_host=to_host)
+        g.replay()
+        return out
 
     def _capture(self, key, images, depth, to_host=False, hands=None):
         # static buffers are ordinary (non-inference) tensors so that later copy_() works in any mode
@@ -507,17 +510,6 @@ class HandNetEngine:
                 return self.forward_device(s_img, s_dep, _record=record)
             return self.forward_hands(s_img, s_dep, hands, _record=record)
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with ops.launch_cost_hidden():
-            with torch.cuda.stream(side):
-                for _ in range(2):  # warm-up (allocator, lazy module load) outside capture
-                    step()
-            torch.cuda.current_stream().wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            # thread_local: GPU work another thread of the host process issues meanwhile (a ROS node's other callbacks)
-            # does not invalidate the capture
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                out = step()
+        g, out = ops.capture_step(step)
         self._graphs[key] = (g, s_img, s_dep, out)
         return g.replay, s_img, s_dep, out

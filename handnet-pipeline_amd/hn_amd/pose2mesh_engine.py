@@ -239,18 +239,10 @@ class Pose2MeshEngine:
         returns (run, static_input, (mesh, pose3d)); copy new joints into static_input and call run()."""
         key = tuple(pose2d.shape)
         if key not in self._graphs:
-            with torch.inference_mode(False), torch.no_grad(), ops.launch_cost_hidden():
+            with torch.inference_mode(False), torch.no_grad():
                 s_in = torch.empty_like(pose2d, dtype=torch.float32)
                 s_in.copy_(pose2d)
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(2):
-                        self.forward(s_in)
-                torch.cuda.current_stream().wait_stream(side)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    out = self.forward(s_in)
+                g, out = ops.capture_step(lambda: self.forward(s_in))
                 self._graphs[key] = (g, s_in, out)
         g, s_in, out = self._graphs[key]
         return g.replay, s_in, out
