@@ -10,7 +10,9 @@ checkpoints pass their paths in `args` and reload_detector / reload_a2j = True, 
 With --overlay out.png the step also draws the mesh over the frame (the caller's render(), ros_demo.py:86-116,341) and the last
 frame's overlay is written with PIL; --mano FILE reads the face list from a MANO pickle's 'f' entry, else a synthetic face list
 over the 778 vertices is used (a seeded Delaunay triangulation, as tests/golden/make_golden_p2m.py builds one).
-usage (GPU box): python examples/live_demo.py [frames] [--overlay out.png] [--mano MANO_RIGHT.pkl]"""
+With --labels PREFIX the step also draws the loop's other two images (ros_demo.py:310-326): the last frame's box_label (the
+frame with the crop box) and pose_label (the 176 x 176 colour crop with the skeleton) are written as PREFIX_box.npy / PREFIX_pose.npy.
+usage (GPU box): python examples/live_demo.py [frames] [--overlay out.png] [--mano MANO_RIGHT.pkl] [--labels PREFIX]"""
 import sys
 import time
 import types
@@ -43,7 +45,7 @@ def _faces(mano_file):
 def main():
     argv = sys.argv[1:]
     opt = {}
-    for flag in ("--overlay", "--mano"):
+    for flag in ("--overlay", "--mano", "--labels"):
         if flag in argv:
             i = argv.index(flag)
             opt[flag] = argv[i + 1]
@@ -74,7 +76,8 @@ def main():
         print("2. set_convert: joints2d[0] =", conv["image_uvd"][0, 0, :2].tolist(), " joints3d[0] (mm) =", conv["xyz_mm"][0, 0].tolist())
         # 3. the live chain as one captured step
         rev = torch.from_numpy(g["perm_reverse"][:778].astype(np.int64))                  # graph_perm_reverse[:V], ros_demo.py:162
-        live = net.live(model, PARAS, clamp=True, perm_reverse=rev, faces=faces)         # -> the step hands over out['mesh']
+        live = net.live(model, PARAS, clamp=True, perm_reverse=rev, faces=faces,          # -> the step hands over out['mesh']
+                        labels="--labels" in opt)
         run, s_img, s_dep, out = live.graphed(rgb, depth)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -94,6 +97,11 @@ def main():
             Image.fromarray(res.overlay[0].numpy()).save(opt["--overlay"])
             changed = int((res.overlay[0] != (s_img[0] * 255).round().byte().permute(1, 2, 0).cpu()).any(dim=2).sum())
             print(f"4. overlay: {tuple(res.overlay.shape)} uint8 RGB in the same copy, {changed} pixels drawn -> {opt['--overlay']}")
+        if "--labels" in opt:                                                             # ros_demo.py:310-326: box_label, pose_label
+            np.save(opt["--labels"] + "_box.npy", res.box_label[0].numpy())
+            np.save(opt["--labels"] + "_pose.npy", res.pose_label[0].numpy())
+            print(f"5. labels: box_label {tuple(res.box_label.shape)}, pose_label {tuple(res.pose_label.shape)} uint8 RGB in the same "
+                  f"copy -> {opt['--labels']}_box.npy, {opt['--labels']}_pose.npy")
 
 
 if __name__ == "__main__":

@@ -102,32 +102,37 @@ class HandNet(EngineOwner):
         self.last_converted = None
         return self
 
-    def live(self, lifter, paras, clamp: bool = True, perm_reverse=None, faces=None):
+    def live(self, lifter, paras, clamp: bool = True, perm_reverse=None, faces=None, labels: bool = False):
         """The live caller's chain as ONE step (hn_amd.live.LiveHandEngine; ros_demo.py:270-290,329-337): this network, the
         caller's clamp + convert_joints (in the aggregation's epilogue), the lifter's input, Pose2Mesh, one device -> host copy.
         lifter: the drop-in `models.pose2mesh_net.get_model(...)` module (on the GPU) or a Pose2MeshEngine; paras = (fx, fy,
         cx, cy); perm_reverse = graph_perm_reverse[:V]: the step then also does ros_demo.py:162,332-337 and hands over out['mesh'].
         faces = mesh_model.face (needs perm_reverse): the step also draws the mesh over the frame, the caller's render()
         (ros_demo.py:86-116,341): out.overlay on the device, read().overlay on the host.
+        labels: the step also draws the caller's other two images (ros_demo.py:310-326): box_label (the frame with the crop
+        box) and pose_label (the 176 x 176 colour crop with the skeleton), out.box_label / .pose_label, read() likewise.
         The returned engine owns this network's step from then on (forward() of this module keeps working and
         carries the converted joints: set_convert)."""
         from hn_amd.live import LiveHandEngine
         self._convert_cfg = (tuple(paras), bool(clamp))
         return LiveHandEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, clamp, perm_reverse,
-                              faces)
+                              faces, labels)
 
-    def live_hands(self, lifter, paras, max_hands: int = 2, clamp: bool = True, perm_reverse=None, faces=None):
+    def live_hands(self, lifter, paras, max_hands: int = 2, clamp: bool = True, perm_reverse=None, faces=None,
+                   labels: bool = False):
         """live() for up to max_hands (1..16) hands per frame (hn_amd.live.LiveHandsEngine): forward_hands' slots, the
         caller's clamp + convert_joints, the lifter's input with the caller's skip rule per slot (a hand whose 2D box
         process_bbox refuses is not lifted: ros_demo.py:288-300), Pose2Mesh on every slot, one device -> host copy.
         read() of a step's output gives keypoints / boxes / scores per slot, `lifted` [N,K] and the mesh [N,K,V,3].
         faces = mesh_model.face (needs perm_reverse): every lifted mesh of a frame is drawn over it (one depth buffer per frame):
-        out.overlay / read().overlay [N,H,W,3] uint8 RGB."""
+        out.overlay / read().overlay [N,H,W,3] uint8 RGB.
+        labels: as for live(): box_label [N,H,W,3] with the crop box of every lifted slot, pose_label [N,K,176,176,3] (zeros
+        where the slot is not lifted)."""
         from hn_amd.live import LiveHandsEngine
         k = ops.check_max_hands(max_hands)
         self._convert_cfg = (tuple(paras), bool(clamp))
         return LiveHandsEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, k, clamp,
-                               perm_reverse, faces)
+                               perm_reverse, faces, labels)
 
     # forward() switches ITSELF to hipGraph replay once the same input shapes have come in a few times in a row -- the live
     # caller's case (ros_demo.py:270-273: one 640x480 frame per call, ~150 dependent launches whose host cost is 8 % of the

@@ -154,6 +154,7 @@ SIGNATURES = {
                                        C.c_int, VP]),
     "hn_mesh_finish_f32": (C.c_int, [VP, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP]),
     "hn_mesh_render_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "hn_draw_labels_u8": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, VP] + [C.c_int] * 4 + [VP, VP, VP]),
     "hn_mesh_render_u8": (C.c_int, [VP, VP, VP, VP] + [C.c_int] * 4 + [c_f32p, VP, C.c_int, C.c_int, C.c_int, VP, C.c_int64, VP, VP,
                                     VP]),
     "hn_pad_split_rows_f32": (C.c_int, [VP, C.c_int64, C.c_int, C.c_int, VP, VP]),

@@ -46,13 +46,33 @@ def _final_mesh_perm(perm_reverse, lifter, device):
     return perm, int(perm.shape[0])
 
 
-class LiveRead(collections.namedtuple("LiveRead", "keypoints has_hand crop_box words more mesh")):
-    """LiveOutput.read() of a step without an overlay: unpacks as the six results it always had."""
-    __slots__ = ()
-    overlay = None
+def _read_type(name, fields, doc, **absent):
+    """A namedtuple whose absent images (overlay / box_label / pose_label) read as None class attributes."""
+    return type(name, (collections.namedtuple(name, fields),), dict(absent, __slots__=(), __doc__=doc))
 
 
-LiveOverlayRead = collections.namedtuple("LiveOverlayRead", LiveRead._fields + ("overlay",))
+_NO_LABELS = dict(box_label=None, pose_label=None)
+_LABEL_FIELDS = ("box_label", "pose_label")
+LiveRead = _read_type("LiveRead", "keypoints has_hand crop_box words more mesh",
+                      "LiveOutput.read() of a step without images: unpacks as the six results it always had.",
+                      overlay=None, **_NO_LABELS)
+LiveOverlayRead = _read_type("LiveOverlayRead", LiveRead._fields + ("overlay",), "... of a step with faces=.", **_NO_LABELS)
+LiveLabelsRead = _read_type("LiveLabelsRead", LiveRead._fields + _LABEL_FIELDS, "... of a step with labels.", overlay=None)
+LiveOverlayLabelsRead = _read_type("LiveOverlayLabelsRead", LiveRead._fields + ("overlay",) + _LABEL_FIELDS,
+                                   "... of a step with faces= and labels.")
+
+POSE_LABEL = ops.LABEL_CROP                           # side of a pose_label image
+POSE_LABEL_BYTES = POSE_LABEL * POSE_LABEL * 3
+
+
+def _labels_behind(end: int, frames: int, slots: int, h: int, w: int, labels: bool):
+    """(offset of box_label, offset of pose_label, total bytes) of the two label images appended at byte `end` of a step's
+    buffer (each starts on a dword: the kernels store three dwords per four pixels); labels False: (end, end, end)."""
+    if not labels:
+        return end, end, end
+    box = (end + 3) // 4 * 4
+    pose = (box + frames * h * w * 3 + 3) // 4 * 4
+    return box, pose, pose + slots * POSE_LABEL_BYTES
 
 
 def live_overlay_layout(n: int, vertices: int, h: int, w: int):
@@ -61,6 +81,15 @@ def live_overlay_layout(n: int, vertices: int, h: int, w: int):
     mesh = (n + 1) * record_bytes(3)
     overlay = mesh + n * vertices * 12
     return mesh, overlay, overlay + n * h * w * 3
+
+
+def live_labels_layout(n: int, vertices: int, h: int, w: int, overlay: bool = False, labels: bool = True):
+    """Byte layout of the one-hand live step's buffer with the label images: (offset of the mesh, offset of the overlay, offset
+    of box_label (uint8 [n,h,w,3]), offset of pose_label (uint8 [n,176,176,3]), total bytes).  The images are appended behind
+    the mesh, and behind the overlay when there is one: without `labels` the first two offsets and the total are
+    live_overlay_layout's (h = w = 0 there for a step without an overlay)."""
+    mesh, oo, end = live_overlay_layout(n, vertices, h if overlay else 0, w if overlay else 0)
+    return (mesh, oo) + _labels_behind(end, n, n, h, w, labels)
 
 
 @dataclass
@@ -74,21 +103,31 @@ class LiveOutput:
     n: int = 0
     raw_mesh: torch.Tensor = None   # [N,V0,3] the lifter's own output on the device (= mesh without perm_reverse)
     overlay: torch.Tensor = None    # [N,H,W,3] uint8 RGB on the device: the mesh drawn over the frame (engines with faces=)
+    box_label: torch.Tensor = None  # [N,H,W,3] uint8 RGB on the device: the frame with the hand's crop box (engines with labels)
+    pose_label: torch.Tensor = None  # [N,176,176,3] uint8 RGB on the device: the colour crop with the skeleton (zeros: no hand)
 
     def read(self):
         """After the stream is synchronised: (keypoints, has_hand, crop_box, range words, [image_uvd, xyz_mm], mesh) as fresh CPU
-        tensors (LiveRead; `.overlay` is None).  A step with faces= appends the overlay [N,H,W,3] uint8 (LiveOverlayRead)."""
+        tensors (LiveRead; `.overlay`, `.box_label`, `.pose_label` are None).  A step with faces= appends the overlay [N,H,W,3]
+        uint8 (LiveOverlayRead); a step with labels appends box_label [N,H,W,3] and pose_label [N,176,176,3] (LiveLabelsRead,
+        LiveOverlayLabelsRead)."""
         rb = record_bytes(3)
         n = self.n
         rec = self.host[: (n + 1) * rb].view(n + 1, rb)
         kp, has, box, words, more = read_host_record(rec, n, extras=True)
-        # (h = w = 0: a step without an overlay has the records and the mesh at the same offsets, and nothing behind them)
-        h, w = (0, 0) if self.overlay is None else self.overlay.shape[1:3]
-        mo, oo, _ = live_overlay_layout(n, self.mesh.shape[1], h, w)
+        # (h = w = 0: a step without images has the records and the mesh at the same offsets, and nothing behind them)
+        image = self.overlay if self.overlay is not None else self.box_label
+        h, w = (0, 0) if image is None else image.shape[1:3]
+        mo, oo, bo, po, end = live_labels_layout(n, self.mesh.shape[1], h, w, self.overlay is not None, self.box_label is not None)
         mesh = self.host[mo:oo].view(torch.float32).reshape(n, -1, 3).clone()
-        if self.overlay is None:
-            return LiveRead(kp, has, box, words, more, mesh)
-        return LiveOverlayRead(kp, has, box, words, more, mesh, self.host[oo:].reshape(self.overlay.shape).clone())
+        fields = (kp, has, box, words, more, mesh)
+        if self.overlay is not None:
+            fields += (self.host[oo:oo + self.overlay.numel()].reshape(self.overlay.shape).clone(),)
+        if self.box_label is None:
+            return (LiveRead if self.overlay is None else LiveOverlayRead)(*fields)
+        fields += (self.host[bo:bo + self.box_label.numel()].reshape(self.box_label.shape).clone(),
+                   self.host[po:end].reshape(self.pose_label.shape).clone())
+        return (LiveLabelsRead if self.overlay is None else LiveOverlayLabelsRead)(*fields)
 
 
 class _LiveStep:
@@ -96,7 +135,8 @@ class _LiveStep:
     the output buffers of a batch size, the camera feed (forward_raw) and the capture (graphed).  A subclass gives _nbytes(n)
     and forward_device(images, depth, _buffers)."""
 
-    def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None):
+    def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None,
+                 labels: bool = False):
         if not _same_device(hand.device, lifter.device):
             raise ValueError(f"HandNet on {hand.device} but the lifter on {lifter.device}")
         self.hand, self.lifter, self.device = hand, lifter, hand.device
@@ -111,13 +151,16 @@ class _LiveStep:
                                  "vertex order); the lifter's raw output has no camera offset to project")
             with ops.on_device(self.device):
                 self.faces = ops.mesh_faces(faces, self.vertices, self.device)
+        # labels: the step ends with the caller's other two images (ops.draw_labels: ros_demo.py:310-326), behind the overlay
+        self.labels, self.clamp = bool(labels), bool(clamp)
         self._render_scratch = {}
         self._graphs = {}
         self._buffers = {}
 
     def _frames(self, images):
-        """The step's input frames as one fp32 [N,3,H,W] tensor (the overlay's background), or None without faces."""
-        if self.faces is None:
+        """The step's input frames as one fp32 [N,3,H,W] tensor (the background of the overlay and of the label images), or
+        None for a step that draws nothing."""
+        if self.faces is None and not self.labels:
             return None
         frames = images if torch.is_tensor(images) else torch.stack(list(images))
         return frames.contiguous()
@@ -134,8 +177,14 @@ class _LiveStep:
                     (ops.mesh_render_scratch_bytes(s, self.faces.shape[0]),), dtype=torch.uint8, device=self.device)
         return ops.mesh_render(mesh, self.faces, self.paras, frames, lifted=lifted, k=k, out=out, scratch=scratch)
 
+    def _draw_labels(self, kp, crop_box, drawn, frames, k, dev, box_at, pose_at):
+        """The step's two label images, written into its copy buffer `dev` at the layout's offsets."""
+        n, _, h, w = frames.shape
+        return ops.draw_labels(kp, crop_box, frames, drawn=drawn, k=k, clamp=self.clamp,
+                               out_box=dev[box_at:box_at + n * h * w * 3], out_pose=dev[pose_at:pose_at + n * k * POSE_LABEL_BYTES])
+
     def _new_buffers(self, n, hw=None):
-        """A fresh (device, pinned host) pair of a step over n frames (hw: with an overlay of that frame size)."""
+        """A fresh (device, pinned host) pair of a step over n frames (hw: with images of that frame size)."""
         nbytes = self._nbytes(n, hw)
         return (torch.zeros((nbytes,), dtype=torch.uint8, device=self.device),
                 torch.zeros((nbytes,), dtype=torch.uint8, pin_memory=True))
@@ -182,19 +231,22 @@ class _LiveStep:
 
 
 class LiveHandEngine(_LiveStep):
-    def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None):
+    def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None,
+                 labels: bool = False):
         """paras = (fx, fy, cx, cy) of the depth camera (ros_demo.py:191-196); clamp: the caller's clamps before the
         conversion (ros_demo.py:279-283).  perm_reverse: graph_perm_reverse[:V] (int64, V = vertices of the real mesh,
         ros_demo.py:162) -- given, the step also does the caller's last three lines (vertex order, camera offset by the first
         joint, y / z negated: ros_demo.py:332-337) and `mesh` of the outputs IS out['mesh'], [N,V,3]; else the lifter's raw
         [N,V0,3] vertices in coarsening order.  faces: mesh_model.face ([F,3] vertex indices of the real mesh; needs perm_reverse) --
-        given, the step also draws the mesh over the frame (ros_demo.py:86-116 render(): LiveOutput.overlay, read().overlay)."""
-        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces)
+        given, the step also draws the mesh over the frame (ros_demo.py:86-116 render(): LiveOutput.overlay, read().overlay).
+        labels: the step also draws box_label and pose_label (ros_demo.py:310-326: LiveOutput.box_label / .pose_label, read()
+        likewise); a frame without a hand (has_hand != 1) keeps its plain frame and a zero pose_label."""
+        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels)
 
     def _nbytes(self, n, hw=None):
         if hw is None:
             return (n + 1) * record_bytes(3) + n * self.vertices * 12
-        return live_overlay_layout(n, self.vertices, *hw)[2]
+        return live_labels_layout(n, self.vertices, *hw, overlay=self.faces is not None, labels=self.labels)[4]
 
     @ops.device_guarded
     def forward_device(self, images, depth, _buffers=None) -> LiveOutput:
@@ -219,12 +271,16 @@ class LiveHandEngine(_LiveStep):
         # the step packs its wide records and its range words straight into `rec`; ONE copy moves records + mesh
         out = self.hand.forward_device(images, depth, _record=(None, rec), _tail=lift)
         p2d, mesh, pose3d, raw = out.tail
-        overlay = None
+        overlay = box_label = pose_label = None
         if frames is not None:
-            oo = live_overlay_layout(n, v0, *frames.shape[2:])[1]
-            overlay = self._draw(mesh, out.has_hand.view(-1), frames, 1, dev[oo:])
+            h, w = frames.shape[2:]
+            _, oo, bo, po, _ = live_labels_layout(n, v0, h, w, self.faces is not None, self.labels)
+            if self.faces is not None:
+                overlay = self._draw(mesh, out.has_hand.view(-1), frames, 1, dev[oo:oo + n * h * w * 3])
+            if self.labels:
+                box_label, pose_label = self._draw_labels(out.keypoints, out.crop_box, out.has_hand.view(-1), frames, 1, dev, bo, po)
         host.copy_(dev, non_blocking=True)
-        return LiveOutput(out, p2d, mesh, pose3d, host, n, raw, overlay)
+        return LiveOutput(out, p2d, mesh, pose3d, host, n, raw, overlay, box_label, pose_label)
 
 
 def live_hands_layout(slots: int, vertices: int):
@@ -245,14 +301,24 @@ def live_hands_overlay_layout(slots: int, vertices: int, frames: int, h: int, w:
     return rows, rb, lifted, mesh, overlay, overlay + frames * h * w * 3
 
 
-class LiveHandsRead(collections.namedtuple(
-        "LiveHandsRead", "keypoints has_hand crop_box score det_index image_uvd xyz_mm lifted mesh words")):
-    """LiveHandsOutput.read() of a step without an overlay (`.overlay` is None; the fields are the ten it always had)."""
-    __slots__ = ()
-    overlay = None
+def live_hands_labels_layout(slots: int, vertices: int, frames: int, h: int, w: int, overlay: bool = False, labels: bool = True):
+    """live_hands_overlay_layout with the label images appended behind the mesh, and behind the overlay when there is one: its
+    first five values (the overlay's offset: the end of the mesh), then the offset of box_label (uint8 [frames,h,w,3]), the
+    offset of pose_label (uint8 [slots,176,176,3]) and the total bytes.  Without `labels` the total is the one of
+    live_hands_overlay_layout / live_hands_layout."""
+    rows, rb, lifted, mesh, oo, end = live_hands_overlay_layout(slots, vertices, frames, h if overlay else 0, w if overlay else 0)
+    return (rows, rb, lifted, mesh, oo) + _labels_behind(end, frames, slots, h, w, labels)
 
 
-LiveHandsOverlayRead = collections.namedtuple("LiveHandsOverlayRead", LiveHandsRead._fields + ("overlay",))
+LiveHandsRead = _read_type("LiveHandsRead", "keypoints has_hand crop_box score det_index image_uvd xyz_mm lifted mesh words",
+                           "LiveHandsOutput.read() of a step without images (the fields are the ten it always had).",
+                           overlay=None, **_NO_LABELS)
+LiveHandsOverlayRead = _read_type("LiveHandsOverlayRead", LiveHandsRead._fields + ("overlay",), "... of a step with faces=.",
+                                  **_NO_LABELS)
+LiveHandsLabelsRead = _read_type("LiveHandsLabelsRead", LiveHandsRead._fields + _LABEL_FIELDS, "... of a step with labels.",
+                                 overlay=None)
+LiveHandsOverlayLabelsRead = _read_type("LiveHandsOverlayLabelsRead", LiveHandsRead._fields + ("overlay",) + _LABEL_FIELDS,
+                                        "... of a step with faces= and labels.")
 
 
 @dataclass
@@ -267,10 +333,13 @@ class LiveHandsOutput:
     k: int = 0
     raw_mesh: torch.Tensor = None   # [N*K,V0,3] the lifter's own output on the device
     overlay: torch.Tensor = None    # [N,H,W,3] uint8 RGB on the device: all lifted meshes of a frame drawn over it (faces=)
+    box_label: torch.Tensor = None  # [N,H,W,3] uint8 RGB on the device: the frame with the crop box of every lifted slot (labels)
+    pose_label: torch.Tensor = None  # [N*K,176,176,3] uint8 RGB on the device: per slot, the colour crop with the skeleton
 
     def read(self) -> LiveHandsRead:
         """After the stream is synchronised: the step's results per frame and slot as fresh CPU tensors (LiveHandsRead;
-        lifted as bool, words = the step's range words; a step with faces=: LiveHandsOverlayRead, + overlay [N,H,W,3] uint8)."""
+        lifted as bool, words = the step's range words; a step with faces=: LiveHandsOverlayRead, + overlay [N,H,W,3] uint8; a
+        step with labels: + box_label [N,H,W,3], pose_label [N,K,176,176,3] -- LiveHandsLabelsRead, LiveHandsOverlayLabelsRead)."""
         n, k, s = self.n, self.k, self.n * self.k
         rows, rb, lo, mo, nbytes = live_hands_layout(s, self.mesh.shape[2])
         rec = self.host[:lo].view(rows, rb)
@@ -280,9 +349,15 @@ class LiveHandsOutput:
         mesh = self.host[mo:nbytes].view(torch.float32).reshape(n, k, -1, 3).clone()
         per = lambda t: t.reshape((n, k) + tuple(t.shape[1:]))
         fields = (per(kp), per(has), per(box), per(score), per(index), per(img), per(xyz), lifted, mesh, words)
-        if self.overlay is None:
-            return LiveHandsRead(*fields)
-        return LiveHandsOverlayRead(*fields, self.host[nbytes:].reshape(self.overlay.shape).clone())
+        if self.overlay is not None:
+            fields += (self.host[nbytes:nbytes + self.overlay.numel()].reshape(self.overlay.shape).clone(),)
+        if self.box_label is None:
+            return (LiveHandsRead if self.overlay is None else LiveHandsOverlayRead)(*fields)
+        h, w = self.box_label.shape[1:3]
+        bo, po, end = live_hands_labels_layout(s, self.mesh.shape[2], n, h, w, self.overlay is not None)[5:]
+        fields += (self.host[bo:bo + self.box_label.numel()].reshape(self.box_label.shape).clone(),
+                   self.host[po:end].reshape(n, k, POSE_LABEL, POSE_LABEL, 3).clone())
+        return (LiveHandsLabelsRead if self.overlay is None else LiveHandsOverlayLabelsRead)(*fields)
 
 
 class LiveHandsEngine(_LiveStep):
@@ -293,16 +368,19 @@ class LiveHandsEngine(_LiveStep):
     the final mesh (perm_reverse) -> ONE device -> host copy of records + lifted + mesh (live_hands_layout)."""
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, max_hands: int = 2, clamp: bool = True,
-                 perm_reverse=None, faces=None):
+                 perm_reverse=None, faces=None, labels: bool = False):
         """faces: mesh_model.face ([F,3]; needs perm_reverse) -- given, the step ends with the overlay: every lifted mesh of a
-        frame drawn over it with one depth buffer per frame (LiveHandsOutput.overlay, read().overlay), in the same copy."""
+        frame drawn over it with one depth buffer per frame (LiveHandsOutput.overlay, read().overlay), in the same copy.
+        labels: the step ends with box_label (the crop box of every lifted slot on its frame) and one pose_label per slot
+        (zeros where the slot is not lifted: the reference's condition, ros_demo.py:294), in the same copy."""
         self.max_hands = ops.check_max_hands(max_hands)
-        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces)
+        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels)
 
     def _nbytes(self, n, hw=None):
         if hw is None:
             return live_hands_layout(n * self.max_hands, self.vertices)[4]
-        return live_hands_overlay_layout(n * self.max_hands, self.vertices, n, *hw)[5]
+        return live_hands_labels_layout(n * self.max_hands, self.vertices, n, *hw, overlay=self.faces is not None,
+                                        labels=self.labels)[7]
 
     @ops.device_guarded
     def forward_device(self, images, depth, _buffers=None) -> LiveHandsOutput:
@@ -329,11 +407,17 @@ class LiveHandsEngine(_LiveStep):
         # the step packs its per-slot records, range words, scores and ranks straight into `rec`; ONE copy moves it all
         out = self.hand.forward_hands(images, depth, k, _record=(None, rec), _tail=lift)
         p2d, mesh, pose3d, raw = out.tail
-        overlay = None
+        overlay = box_label = pose_label = None
         if frames is not None:
-            overlay = self._draw(mesh, lifted, frames, k, dev[nbytes:])
+            h, w = frames.shape[2:]
+            bo, po, _ = live_hands_labels_layout(s, v, n, h, w, self.faces is not None, self.labels)[5:]
+            if self.faces is not None:
+                overlay = self._draw(mesh, lifted, frames, k, dev[nbytes:nbytes + n * h * w * 3])
+            if self.labels:
+                box_label, pose_label = self._draw_labels(out.keypoints, out.crop_box, lifted, frames, k, dev, bo, po)
         host.copy_(dev, non_blocking=True)
-        return LiveHandsOutput(out, p2d, lifted.view(n, k), mesh.view(n, k, v, 3), pose3d, host, n, k, raw, overlay)
+        return LiveHandsOutput(out, p2d, lifted.view(n, k), mesh.view(n, k, v, 3), pose3d, host, n, k, raw, overlay, box_label,
+                               pose_label)
 
 
 @dataclass

@@ -1771,6 +1771,56 @@ def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out
     return out.view(n, h, w, 3)
 
 
+LABEL_CROP = 176      # side of a pose_label image
+
+
+def draw_labels(keypoints, crop_box, frame, drawn=None, k=1, clamp=True, out_box=None, out_pose=None, box=True, pose=True):
+    """The live loop's box and pose images (hn_draw_labels_u8; ros_demo.py:310-326 without OpenCV): keypoints fp32 [S,21,3] (or
+    [N,K,21,3]) crop-space (u,v,d), crop_box int64 [S,4] (x1,y1,x2,y2), S = N * k slots; frame fp32 [N,3,H,W] in 0..1 or uint8
+    [N,H,W,3] 'bgr8', on the GPU; drawn int32 [S] (a slot is drawn when its flag is 1; None: every slot); clamp: the caller's
+    clamps first (box to the frame as written at ros_demo.py:280-281, keypoints to [0,176]).  Returns (box_label uint8
+    [N,H,W,3] RGB: the frame with the drawn slots' crop rectangles; pose_label uint8 [S,176,176,3] RGB: each drawn slot's colour
+    crop resized to 176 x 176 with its skeleton, zeros for the others); box=False / pose=False leaves that image out (None)."""
+    _req(keypoints, name="keypoints"); _req(crop_box, torch.int64, "crop_box")
+    keypoints, crop_box = keypoints.view(-1, 21, 3), crop_box.view(-1, 4)
+    s = keypoints.shape[0]
+    if crop_box.shape[0] != s:
+        raise ValueError(f"{s} keypoint rows but {crop_box.shape[0]} crop boxes")
+    if frame.dtype == torch.uint8:
+        _req(frame, torch.uint8, "frame")
+        fmt, (n, h, w) = _lib.FRAME_U8_BGR_HWC, frame.shape[:3]
+        ok = frame.dim() == 4 and frame.shape[3] == 3
+    else:
+        _req(frame, name="frame")
+        fmt, n, (h, w) = _lib.FRAME_F32_CHW, frame.shape[0], frame.shape[2:]
+        ok = frame.dim() == 4 and frame.shape[1] == 3
+    if not ok:
+        raise ValueError(f"frame: expected fp32 [N,3,H,W] or uint8 [N,H,W,3], got {frame.dtype} {tuple(frame.shape)}")
+    if k < 1 or n * k != s:
+        raise ValueError(f"{s} slots for {n} frames with k = {k} slots per frame")
+    if drawn is not None:
+        _req(drawn, torch.int32, "drawn")
+        if drawn.numel() != s:
+            raise ValueError(f"drawn: expected {s} flags, got {drawn.numel()}")
+    if not (box or pose):
+        raise ValueError("neither image asked for")
+    if box and out_box is None:
+        out_box = torch.empty((n, h, w, 3), device=keypoints.device, dtype=torch.uint8)
+    if pose and out_pose is None:
+        out_pose = torch.empty((s, LABEL_CROP, LABEL_CROP, 3), device=keypoints.device, dtype=torch.uint8)
+    for t, want, nm in ((out_box if box else None, n * h * w * 3, "out_box"),
+                        (out_pose if pose else None, s * LABEL_CROP * LABEL_CROP * 3, "out_pose")):
+        if t is not None:
+            _req(t, torch.uint8, nm)
+            if t.numel() != want:
+                raise ValueError(f"{nm}: expected {want} bytes, got {tuple(t.shape)}")
+    check(_lib.load().hn_draw_labels_u8(ptr(keypoints), ptr(crop_box), ptr(drawn), s, k, ptr(frame), fmt, h, w, 1 if clamp else 0,
+                                        ptr(out_box) if box else None, ptr(out_pose) if pose else None, _stream()),
+          "hn_draw_labels_u8")
+    return (out_box.view(n, h, w, 3) if box else None,
+            out_pose.view(s, LABEL_CROP, LABEL_CROP, 3) if pose else None)
+
+
 def pad_split_rows(x, cpad):
     """fp32 [rows, f] -> S32 [rows,1,1,cpad/32,2,32], channels f.. zero (hn_pad_split_rows_f32)."""
     _req(x, name="x")

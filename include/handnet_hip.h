@@ -698,6 +698,20 @@ int hn_mesh_render_u8(const float* mesh, const int32_t* faces, const int32_t* fa
                       const int32_t* lifted /* or NULL */, int s, int v, int f, int k, const float* paras, const void* frame,
                       int frame_format, int h, int w, void* scratch, int64_t scratch_bytes, uint8_t* out_image,
                       float* out_depth /* or NULL */, void* stream);
+/* The live caller's two other images (ros_demo.py:310-326) for s = n * k hand slots: out_box [n][h][w][3] uint8 RGB = the frame
+ * with the crop rectangle of every drawn slot of the frame in (0,255,0), thickness 1, inclusive corners (cv2.rectangle);
+ * out_pose [s][176][176][3] uint8 RGB = frame[y1:y2, x1:x2] (clipped to the frame, exclusive ends) resized to 176 x 176 with
+ * OpenCV's 8-bit fixed-point bilinear rule, the 21 joints (discs of radius 2) and 20 bones (8-connected lines) of
+ * VisualUtil('dexycb').plot drawn over it at (int(u), int(v)); all zeros for a slot that is not drawn.  keypoints [s][21][3] fp32
+ * crop-space (u, v, d), crop_box [s][4] int64 (x1, y1, x2, y2), drawn [s] int32 or NULL: a slot is drawn when drawn == 1 (NULL:
+ * every slot) and its clipped crop is not empty.  clamp != 0: the caller's clamps first (x1, y1 to [0, h]; x2, y2 to [0, w], as
+ * written at ros_demo.py:280-281; every keypoint coordinate to [0, 176]).  frame as for hn_mesh_render_u8.  Either output may
+ * be NULL (not both).  At most two launches on the caller's stream; no allocation, no synchronisation, no atomics: every pixel
+ * is written once and the images are a pure function of the arguments (DESIGN.md section 9c states the rule).  h, w <= 16384,
+ * s <= 65535.  Added under ABI 36: a new function only. */
+int hn_draw_labels_u8(const float* keypoints, const int64_t* crop_box, const int32_t* drawn /* or NULL */, int s, int k,
+                      const void* frame, int frame_format, int h, int w, int clamp, uint8_t* out_box /* or NULL */,
+                      uint8_t* out_pose /* or NULL */, void* stream);
 /* A Linear layer on 1..4 rows as a matrix-vector product on the vector ALU (PoseNet at the live caller's batch, posenet.py:24-41,
  * 78-88: 67 MB of filter bank per 17 M MACs): y[m][:] = act(W (pre(x[m])) + bias (+ residual[m])), pre = relu(x * scale + shift)
  * when scale / shift ([k_real] fp32: the pre-activation BatchNorm) are given.  x fp32 [batch][x_stride] (k_real columns used), w16 =

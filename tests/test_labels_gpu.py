@@ -1,0 +1,327 @@
+"""box_label / pose_label on the GPU (csrc/label_draw.hip, ops.draw_labels, the live engines' labels=) against the numpy
+statement of the rule (tests/draw_ref.py): byte for byte, no tolerance."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import draw_ref as dr
+
+pytestmark = pytest.mark.gpu
+
+LIVE_PARAS = (617.343, 617.343, 312.42, 241.42)
+H, W = 480, 640
+
+
+def _noise(n, h, w, seed):
+    return np.random.default_rng(seed).integers(0, 256, size=(n, h, w, 3), dtype=np.uint8)       # RGB
+
+
+def _kp(s, seed, lo=8.0, hi=168.0):
+    kp = np.random.default_rng(seed).uniform(lo, hi, size=(s, 21, 3)).astype(np.float32)
+    return kp
+
+
+def _scenes():
+    """name -> (rgb uint8 [N,H,W,3], k, boxes [S,4], keypoints [S,21,3], drawn [S] or None, clamp)"""
+    sc = {}
+    sc["inside"] = (_noise(2, 96, 128, 1), 1, [[20, 10, 90, 80], [5, 5, 60, 60]], _kp(2, 11), [1, 0], True)
+    # a box touching each frame edge; x2 == W and y2 == H
+    sc["edges"] = (_noise(1, 96, 128, 2), 5, [[0, 20, 40, 60], [30, 0, 70, 40], [88, 20, 128, 60], [30, 56, 70, 96], [10, 10, 50, 50]],
+                   _kp(5, 12), [1, 1, 1, 1, 0], True)
+    # ros_demo.py:280: x1 is clamped to H (96), not to W
+    sc["clamp_quirk"] = (_noise(1, 96, 128, 3), 2, [[110, 10, 128, 50], [110, 10, 128, 50]], _kp(2, 13), [1, 0], True)
+    sc["no_clamp"] = (_noise(1, 96, 128, 4), 3, [[110, 10, 128, 50], [-20, -7, 40, 300], [3, 3, 9, 9]],
+                      _kp(3, 14, -30.0, 230.0), [1, 1, 0], False)
+    sc["thin"] = (_noise(1, 96, 128, 5), 3, [[50, 10, 51, 60], [10, 50, 60, 51], [1, 1, 9, 9]], _kp(3, 15), [1, 1, 0], True)
+    # sw, sh below, at and above 176, including 352
+    sc["sizes"] = (_noise(1, 400, 420, 6), 5, [[10, 20, 110, 372], [200, 100, 376, 276], [30, 40, 382, 160], [100, 3, 400, 178],
+                                               [0, 0, 50, 50]], _kp(5, 16), [1, 1, 1, 1, 0], True)
+    special = _kp(2, 17)
+    special[0, 0, :2] = (0.0, 176.0)
+    special[0, 1, :2] = (176.0, 0.0)
+    special[0, 2, :2] = (57.99999, 58.0)
+    special[0, 3, :2] = (np.nextafter(np.float32(100), np.float32(0)), 99.5)
+    special[0, 4, :2] = (200.0, -5.0)                   # clamped to (176, 0)
+    special[0, 5, :2] = (0.999, 175.99)
+    sc["joints_special"] = (_noise(2, 96, 128, 7), 1, [[20, 10, 90, 80], [5, 5, 60, 60]], special, [1, 0], True)
+    one = _kp(2, 18)
+    one[0, :, :2] = (88.7, 31.2)
+    sc["one_pixel"] = (_noise(1, 96, 128, 8), 2, [[20, 10, 90, 80], [5, 5, 60, 60]], one, [1, 0], True)
+    sc["overlap_k2"] = (_noise(2, 96, 128, 9), 2, [[20, 10, 90, 80], [50, 40, 120, 90], [20, 10, 90, 80], [50, 40, 120, 90]],
+                        _kp(4, 19), [1, 1, 0, 0], True)
+    # drawn = NULL: every slot is drawn, except the one whose crop is empty
+    sc["zero_area_null"] = (_noise(1, 96, 128, 10), 3, [[20, 10, 90, 80], [40, 20, 40, 70], [128, 5, 128, 60]], _kp(3, 20), None, True)
+    # rows that are no multiple of four pixels, frames that start off a dword
+    sc["odd_frame"] = (_noise(2, 37, 53, 11), 1, [[3, 2, 50, 36], [5, 5, 30, 30]], _kp(2, 21), [1, 0], True)
+    sc["flag_two"] = (_noise(1, 96, 128, 12), 2, [[20, 10, 90, 80], [5, 5, 60, 60]], _kp(2, 22), [1, 2], True)
+    return sc
+
+
+SCENES = _scenes()
+
+
+def _frames(rgb, fmt):
+    if fmt == "bgr8":
+        return np.ascontiguousarray(rgb[..., ::-1])
+    return np.ascontiguousarray(rgb.transpose(0, 3, 1, 2)).astype(np.float32) / np.float32(255.0)
+
+
+def _gpu(kp, boxes, drawn, k, frames, clamp, **kw):
+    from hn_amd import ops
+    d = None if drawn is None else torch.tensor(drawn, dtype=torch.int32).cuda()
+    box, pose = ops.draw_labels(torch.from_numpy(np.asarray(kp, np.float32)).cuda(), torch.tensor(boxes, dtype=torch.int64).cuda(),
+                                torch.from_numpy(frames).cuda(), drawn=d, k=k, clamp=clamp, **kw)
+    torch.cuda.synchronize()
+    return (None if box is None else box.cpu().numpy()), (None if pose is None else pose.cpu().numpy())
+
+
+def _assert_skeleton_visible(name, slot, pose, bare, kp, clamp):
+    """On a drawn slot at least one disc pixel and one line pixel differ from the bare resized crop."""
+    seen = {"disc": 0, "line": 0}
+    for kind, pts, colour in dr.skeleton_layers(kp, clamp):
+        for x, y in pts:
+            if 0 <= x < 176 and 0 <= y < 176 and tuple(pose[y, x]) == colour and tuple(bare[y, x]) != colour:
+                seen[kind] += 1
+    assert seen["disc"] > 0 and seen["line"] > 0, (name, slot, seen)
+
+
+@pytest.mark.parametrize("fmt", ["f32", "bgr8"])
+@pytest.mark.parametrize("name", list(SCENES))
+def test_op_matches_the_rule(name, fmt):
+    rgb, k, boxes, kp, drawn, clamp = SCENES[name]
+    frames = _frames(rgb, fmt)
+    want_box, want_pose, bare = dr.draw_labels(kp, boxes, drawn, k, frames, clamp, with_bare=True)
+    assert np.array_equal(np.stack([dr.frame_to_rgb(f) for f in frames]), rgb)       # both formats carry the same pixels
+    h, w = rgb.shape[1:3]
+    states = [dr.slot_box(b, None if drawn is None else drawn[i], h, w, clamp)[3] for i, b in enumerate(boxes)]
+    assert any(states) and not all(states), f"{name}: a scene needs a drawn and a not-drawn slot"
+    got_box, got_pose = _gpu(kp, boxes, drawn, k, frames, clamp)
+    diff_box, diff_pose = int((got_box != want_box).sum()), int((got_pose != want_pose).sum())
+    print(f"{name} {fmt}: box_label bytes off {diff_box}, pose_label bytes off {diff_pose}, green pixels "
+          f"{int(((want_box == (0, 255, 0)).all(axis=3) & (rgb != (0, 255, 0)).any(axis=3)).sum())}")
+    assert diff_box == 0 and diff_pose == 0
+    for slot, on in enumerate(states):
+        if on:
+            _assert_skeleton_visible(name, slot, want_pose[slot], bare[slot], kp[slot], clamp)
+            assert (want_box[slot // k] != rgb[slot // k]).any()
+        else:
+            assert not got_pose[slot].any()
+    # a frame all of whose slots are not drawn is the frame
+    for i in range(rgb.shape[0]):
+        if not any(states[i * k:(i + 1) * k]):
+            assert np.array_equal(got_box[i], rgb[i])
+    # two runs are bit-identical; each output alone is the same image and leaves the other buffer alone
+    again_box, again_pose = _gpu(kp, boxes, drawn, k, frames, clamp)
+    assert np.array_equal(again_box, got_box) and np.array_equal(again_pose, got_pose)
+
+
+def test_each_output_alone():
+    from hn_amd import _lib, ops
+    rgb, k, boxes, kp, drawn, clamp = SCENES["overlap_k2"]
+    frames = _frames(rgb, "f32")
+    both_box, both_pose = _gpu(kp, boxes, drawn, k, frames, clamp)
+    only_box, none_pose = _gpu(kp, boxes, drawn, k, frames, clamp, pose=False)
+    none_box, only_pose = _gpu(kp, boxes, drawn, k, frames, clamp, box=False)
+    assert none_pose is None and none_box is None
+    assert np.array_equal(only_box, both_box) and np.array_equal(only_pose, both_pose)
+    # through the C ABI on raw pointers: a NULL output is not written, the other buffer keeps its bytes
+    n, h, w = rgb.shape[:3]
+    t_kp, t_box = torch.from_numpy(kp).cuda(), torch.tensor(boxes, dtype=torch.int64).cuda()
+    t_dr, t_fr = torch.tensor(drawn, dtype=torch.int32).cuda(), torch.from_numpy(frames).cuda()
+    out_box = torch.full((n, h, w, 3), 7, dtype=torch.uint8, device="cuda")
+    out_pose = torch.full((n * k, 176, 176, 3), 9, dtype=torch.uint8, device="cuda")
+    lib = _lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+
+    def call(ob, op_):
+        rc = lib.hn_draw_labels_u8(t_kp.data_ptr(), t_box.data_ptr(), t_dr.data_ptr(), n * k, k, t_fr.data_ptr(), _lib.FRAME_F32_CHW,
+                                   h, w, 1, ob, op_, st)
+        torch.cuda.synchronize()
+        return rc
+    assert call(out_box.data_ptr(), None) == 0
+    assert np.array_equal(out_box.cpu().numpy(), both_box) and bool((out_pose == 9).all())
+    out_box.fill_(7)
+    assert call(None, out_pose.data_ptr()) == 0
+    assert np.array_equal(out_pose.cpu().numpy(), both_pose) and bool((out_box == 7).all())
+    assert call(None, None) == 1 and b"both NULL" in lib.hn_last_error()
+    # an output that does not start on a dword gets the same bytes
+    raw = torch.zeros((n * h * w * 3 + 8,), dtype=torch.uint8, device="cuda")
+    off_box, _ = ops.draw_labels(t_kp, t_box, t_fr, drawn=t_dr, k=k, clamp=True, out_box=raw[1:1 + n * h * w * 3], pose=False)
+    raw_pose = torch.zeros((n * k * 92928 + 8,), dtype=torch.uint8, device="cuda")
+    _, off_pose = ops.draw_labels(t_kp, t_box, t_fr, drawn=t_dr, k=k, clamp=True, out_pose=raw_pose[3:3 + n * k * 92928], box=False)
+    torch.cuda.synchronize()
+    assert np.array_equal(off_box.cpu().numpy(), both_box) and np.array_equal(off_pose.cpu().numpy(), both_pose)
+    assert int(raw[0]) == 0 and not bool(raw[1 + n * h * w * 3:].any()) and not bool(raw_pose[:3].any())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the live engines
+# ---------------------------------------------------------------------------------------------------------------------
+def _synthetic_faces(seed=7, nv=778):
+    from scipy.spatial import Delaunay
+    pts = np.random.default_rng(seed).random((nv, 2))
+    return Delaunay(pts).simplices.astype(np.int64)
+
+
+@pytest.fixture(scope="module")
+def parts(golden_dir, fcos_sd, a2j_sd):
+    from hn_amd import synth
+    from hn_amd.a2j_engine import A2JEngine
+    from hn_amd.fcos_engine import FCOSEngine
+    from hn_amd.pipeline import HandNetEngine
+    from hn_amd.pose2mesh_engine import Pose2MeshEngine
+    from oracle import pose2mesh_ref
+    g = np.load(golden_dir / "pose2mesh_forward.npz")
+    graphs = pose2mesh_ref.load_graphs(g)
+    p2m_sd = synth.make_pose2mesh_state_dict(seed=int(g["weight_seed"]), graph_sizes=[m.shape[0] for m in graphs])
+    hand = HandNetEngine(FCOSEngine(fcos_sd, 3, device="cuda"), A2JEngine(a2j_sd, device="cuda"), 3)
+    lifter = Pose2MeshEngine(p2m_sd, graphs, device="cuda")
+    return hand, lifter, g["perm_reverse"][:778], _synthetic_faces()
+
+
+def _camera(seed):
+    rng = np.random.default_rng(seed)
+    bgr = rng.integers(0, 256, size=(1, H, W, 3), dtype=np.uint8)
+    mm = rng.integers(300, 1500, size=(1, H, W)).astype(np.uint16)
+    rgb = torch.from_numpy(np.ascontiguousarray(bgr[..., ::-1].transpose(0, 3, 1, 2)).astype(np.float32) / 255.0).cuda()
+    dep = torch.from_numpy(mm.astype(np.float32) / 1000.0).unsqueeze(1).cuda()
+    return bgr, mm, rgb, dep
+
+
+def _run(eng, rgb, depth, graphed=False):
+    if graphed:
+        run, s_img, s_dep, out = eng.graphed(rgb, depth)
+        s_img.copy_(rgb)
+        s_dep.copy_(depth)
+        run()
+    else:
+        out = eng.forward_device(rgb, depth)
+    torch.cuda.synchronize()
+    return out, out.read()
+
+
+def _same(a, b, tag):
+    assert a._fields == b._fields
+    for f in a._fields:
+        x, y = getattr(a, f), getattr(b, f)
+        if torch.is_tensor(x):
+            assert torch.equal(x, y), (tag, f)
+        elif isinstance(x, list) and x and torch.is_tensor(x[0]):
+            assert all(torch.equal(p, q) for p, q in zip(x, y)), (tag, f)
+        else:
+            assert x == y, (tag, f)
+
+
+def _check_against_rule(tag, r, drawn, k, rgb):
+    """read().box_label / .pose_label against the rule applied to the same step's own host record and the frame."""
+    n = rgb.shape[0]
+    want_box, want_pose = dr.draw_labels(r.keypoints.numpy().reshape(-1, 21, 3), r.crop_box.numpy().reshape(-1, 4),
+                                         drawn.reshape(-1).astype(np.int32), k, rgb.cpu().numpy(), clamp=True)
+    got_pose = r.pose_label.numpy().reshape(-1, 176, 176, 3)
+    print(f"{tag}: drawn {drawn.reshape(-1).tolist()}, boxes {r.crop_box.reshape(-1, 4).tolist()}, box_label bytes off "
+          f"{int((r.box_label.numpy() != want_box).sum())}, pose_label bytes off {int((got_pose != want_pose).sum())}")
+    assert tuple(r.box_label.shape) == (n, H, W, 3) and r.box_label.dtype == torch.uint8
+    assert np.array_equal(r.box_label.numpy(), want_box) and np.array_equal(got_pose, want_pose)
+    states = [dr.slot_box(b, drawn.reshape(-1)[i], H, W, True)[3] for i, b in enumerate(r.crop_box.numpy().reshape(-1, 4))]
+    assert any(states), f"{tag}: the fixture draws no slot"
+    for slot, on in enumerate(states):
+        assert bool(got_pose[slot].any()) == on
+
+
+@pytest.mark.parametrize("hands", [None, 2])
+def test_engines_eager_replay_and_raw_frames(parts, hands):
+    from hn_amd.live import LiveHandEngine, LiveHandsEngine
+    hand, lifter, perm, _faces = parts
+    if hands is None:
+        eng, k = LiveHandEngine(hand, lifter, LIVE_PARAS, True, perm, labels=True), 1
+    else:
+        eng, k = LiveHandsEngine(hand, lifter, LIVE_PARAS, hands, True, perm, labels=True), hands
+    seen = []
+    for i in range(2):
+        bgr, mm, rgb, dep = _camera(40 + i)
+        out, e = _run(eng, rgb, dep)
+        assert torch.equal(out.box_label.cpu(), e.box_label)
+        assert torch.equal(out.pose_label.cpu().reshape(e.pose_label.shape), e.pose_label)
+        assert tuple(e.pose_label.shape) == ((1, 176, 176, 3) if hands is None else (1, k, 176, 176, 3))
+        assert e.overlay is None and len(e) == len(type(e)._fields)
+        _o, e2 = _run(eng, rgb, dep)
+        _o, g = _run(eng, rgb, dep, graphed=True)
+        raw = eng.forward_raw(torch.from_numpy(bgr), torch.from_numpy(mm))
+        torch.cuda.synchronize()
+        _same(e, e2, "eager twice")
+        _same(e, g, "replay")
+        _same(e, raw.read(), "raw frames")
+        drawn = (e.has_hand.numpy() == 1) if hands is None else e.lifted.numpy()
+        _check_against_rule(f"engine K={hands} frame {i}", e, drawn, k, rgb)
+        seen.append(e.pose_label.clone())
+    assert not torch.equal(seen[0], seen[1])
+
+
+def test_labels_and_faces_together(parts):
+    from hn_amd.live import LiveHandsEngine
+    hand, lifter, perm, faces = parts
+    _bgr, _mm, rgb, dep = _camera(50)
+    _o, both = _run(LiveHandsEngine(hand, lifter, LIVE_PARAS, 2, True, perm, faces=faces, labels=True), rgb, dep)
+    _o, only_faces = _run(LiveHandsEngine(hand, lifter, LIVE_PARAS, 2, True, perm, faces=faces), rgb, dep)
+    _o, only_labels = _run(LiveHandsEngine(hand, lifter, LIVE_PARAS, 2, True, perm, labels=True), rgb, dep)
+    assert only_faces.box_label is None and only_faces.pose_label is None and only_labels.overlay is None
+    assert both._fields == only_faces._fields + ("box_label", "pose_label")
+    for f in only_faces._fields:
+        x, y = getattr(both, f), getattr(only_faces, f)
+        assert torch.equal(x, y) if torch.is_tensor(x) else x == y, f
+    assert torch.equal(both.box_label, only_labels.box_label) and torch.equal(both.pose_label, only_labels.pose_label)
+    assert bool(both.lifted.any()) and bool(both.pose_label.any())
+
+
+def _kernel_launches(fn):
+    """Kernel launches of one call (device activity of torch.profiler, as tools/bench_live_hands.py counts them), or None
+    when the profiler records no device work."""
+    from torch.profiler import ProfilerActivity, profile
+    fn()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    kernels = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
+               and "memcpy" not in e.name.lower() and "memset" not in e.name.lower()]
+    return len(kernels) or None
+
+
+@pytest.mark.parametrize("hands", [None, 2])
+def test_default_is_unchanged(parts, hands, monkeypatch):
+    """An engine built without labels: the parent's buffer size and layout, no call of the new op, the same launches; with
+    labels the step grows by the two images and at most two launches, and everything in front of them keeps its bytes."""
+    from hn_amd import live, ops
+    from hn_amd.pipeline import record_bytes
+    hand, lifter, perm, _faces = parts
+    calls = []
+    real = ops.draw_labels
+    monkeypatch.setattr(ops, "draw_labels", lambda *a, **kw: (calls.append(1), real(*a, **kw))[1])
+    _bgr, _mm, rgb, dep = _camera(60)
+
+    def build(**kw):
+        if hands is None:
+            return live.LiveHandEngine(hand, lifter, LIVE_PARAS, True, perm, **kw)
+        return live.LiveHandsEngine(hand, lifter, LIVE_PARAS, hands, True, perm, **kw)
+    k = hands or 1
+    plain, explicit, labelled = build(), build(labels=False), build(labels=True)
+    parent = ((1 + 1) * record_bytes(3) + 778 * 12) if hands is None else live.live_hands_layout(k, 778)[4]
+    assert plain._nbytes(1) == plain._nbytes(1, None) == explicit._nbytes(1) == parent
+    assert labelled._nbytes(1, (H, W)) == parent + H * W * 3 + k * 92928
+    out_p, r_p = _run(plain, rgb, dep)
+    assert not calls and out_p.host.numel() == parent and out_p.box_label is None and r_p.box_label is None and r_p.pose_label is None
+    out_l, r_l = _run(labelled, rgb, dep)
+    assert len(calls) == 1
+    assert torch.equal(out_l.host[:parent], out_p.host)           # records, flags and mesh where the parent has them
+    assert out_l.host.numel() == parent + H * W * 3 + k * 92928
+    for f in r_p._fields:
+        x, y = getattr(r_p, f), getattr(r_l, f)
+        if torch.is_tensor(x):
+            assert torch.equal(x, y), f
+    counts = [_kernel_launches(lambda e=e: e.forward_device(rgb, dep)) for e in (plain, explicit, labelled)]
+    print(f"K={hands}: kernel launches of an eager step: default {counts[0]}, labels=False {counts[1]}, labels=True {counts[2]}")
+    assert counts[0] == counts[1]
+    if counts[0] is not None:
+        assert counts[2] - counts[0] == 2
