@@ -12,7 +12,12 @@ frame's overlay is written with PIL; --mano FILE reads the face list from a MANO
 over the 778 vertices is used (a seeded Delaunay triangulation, as tests/golden/make_golden_p2m.py builds one).
 With --labels PREFIX the step also draws the loop's other two images (ros_demo.py:310-326): the last frame's box_label (the
 frame with the crop box) and pose_label (the 176 x 176 colour crop with the skeleton) are written as PREFIX_box.npy / PREFIX_pose.npy.
-usage (GPU box): python examples/live_demo.py [frames] [--overlay out.png] [--mano MANO_RIGHT.pkl] [--labels PREFIX]"""
+With --left the step runs in the caller's mirror mode for a left-handed subject (ImageListener(left=True), ros_demo.py:259-262):
+frame and depth map are mirrored before anything else and every result is in the mirrored frame.  With --handed the last frame
+also goes through the K = 2 step with per-slot handedness: the detector's side of each slot, and which slots ran mirrored
+through the right-handed pose network and lifter (side == left_side; 0 is an assumption about the checkpoint's convention).
+usage (GPU box): python examples/live_demo.py [frames] [--overlay out.png] [--mano MANO_RIGHT.pkl] [--labels PREFIX] [--left]
+                 [--handed]"""
 import sys
 import time
 import types
@@ -50,6 +55,8 @@ def main():
             i = argv.index(flag)
             opt[flag] = argv[i + 1]
             del argv[i:i + 2]
+    left, handed = "--left" in argv, "--handed" in argv
+    argv = [a for a in argv if a not in ("--left", "--handed")]
     frames = int(argv[0]) if argv else 20
     faces = _faces(opt.get("--mano")) if "--overlay" in opt else None
     args = types.SimpleNamespace(pretrained_fcos="-", pretrained_a2j="-")
@@ -77,7 +84,7 @@ def main():
         # 3. the live chain as one captured step
         rev = torch.from_numpy(g["perm_reverse"][:778].astype(np.int64))                  # graph_perm_reverse[:V], ros_demo.py:162
         live = net.live(model, PARAS, clamp=True, perm_reverse=rev, faces=faces,          # -> the step hands over out['mesh']
-                        labels="--labels" in opt)
+                        labels="--labels" in opt, left=left)
         run, s_img, s_dep, out = live.graphed(rgb, depth)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -95,13 +102,21 @@ def main():
         if faces is not None:                                                             # ros_demo.py:341: the mesh_label image
             from PIL import Image
             Image.fromarray(res.overlay[0].numpy()).save(opt["--overlay"])
-            changed = int((res.overlay[0] != (s_img[0] * 255).round().byte().permute(1, 2, 0).cpu()).any(dim=2).sum())
+            shown = s_img[0].flip(-1) if left else s_img[0]                                # (--left: the mirrored frame is drawn on)
+            changed = int((res.overlay[0] != (shown * 255).round().byte().permute(1, 2, 0).cpu()).any(dim=2).sum())
             print(f"4. overlay: {tuple(res.overlay.shape)} uint8 RGB in the same copy, {changed} pixels drawn -> {opt['--overlay']}")
         if "--labels" in opt:                                                             # ros_demo.py:310-326: box_label, pose_label
             np.save(opt["--labels"] + "_box.npy", res.box_label[0].numpy())
             np.save(opt["--labels"] + "_pose.npy", res.pose_label[0].numpy())
             print(f"5. labels: box_label {tuple(res.box_label.shape)}, pose_label {tuple(res.pose_label.shape)} uint8 RGB in the same "
                   f"copy -> {opt['--labels']}_box.npy, {opt['--labels']}_pose.npy")
+        if handed:                                                                        # a left and a right hand in one frame
+            two = net.live_hands(model, PARAS, max_hands=2, clamp=True, perm_reverse=rev, handed=True, left_side=0)
+            o2 = two.forward_device(s_img, s_dep)
+            torch.cuda.current_stream().synchronize()
+            r2 = o2.read()
+            print(f"6. handed: side per slot {r2.side.tolist()} (-1: empty), mirrored {o2.mirror.tolist()}, lifted {r2.lifted.tolist()}; "
+                  f"mesh {tuple(r2.mesh.shape)} in the frame's own coordinates")
 
 
 if __name__ == "__main__":

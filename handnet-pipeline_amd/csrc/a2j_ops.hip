@@ -71,6 +71,8 @@ struct ConvertSpec {
   int clamp_h, clamp_w;   // > 0: clamp box x1,y1 to [0, clamp_h] and x2,y2 to [0, clamp_w] first (ros_demo.py:279-280, as written there)
   float* image_uvd;       // [n,J,3] or nullptr
   float* xyz_mm;          // [n,J,3] or nullptr
+  const int* mirror;      // [n] or nullptr: rows with mirror != 0 come from a crop mirrored along its width (a left hand on its
+                          // way through the right-handed network): the aggregation un-mirrors u = crop_w - u first of all
 };
 
 __device__ __forceinline__ void convert_one(const ConvertSpec& cs, int img, long joint_row, float ku, float kv, float kd) {
@@ -229,7 +231,9 @@ __global__ __launch_bounds__(1024) void a2j_aggregate_kernel(const float* __rest
       td += lds[3 * AW + aa * Jw + jj];
     }
     float* o = out + ((long)k * J + j0 + jj) * 3;
-    const float ku = t0 / t, kv = t1 / t, kd = td / t;
+    float ku = t0 / t;
+    const float kv = t1 / t, kd = td / t;
+    if (cs.mirror && cs.mirror[k]) ku = cs.crop_w - ku;   // (one fp32 subtraction, before anything else sees the value)
     o[0] = ku;
     o[1] = kv;
     o[2] = kd;
@@ -349,10 +353,10 @@ extern "C" int hn_a2j_aggregate_f32(const float* cls, const float* reg, const fl
   return launch_aggregate(cls, reg, dep, valid, k, fh, fw, joints, stride, out, ConvertSpec{}, stream);
 }
 
-extern "C" int hn_a2j_aggregate_convert_f32(const float* cls, const float* reg, const float* dep, const int32_t* valid, int k,
-                                            int fh, int fw, int joints, int stride, const int64_t* crop_box, float crop_w,
-                                            float crop_h, const float* paras, const hn_convert_opts* opts, float* out_uvd,
-                                            float* out_image_uvd, float* out_xyz_mm, void* stream) {
+static int aggregate_convert_run(const float* cls, const float* reg, const float* dep, const int32_t* valid, int k, int fh, int fw,
+                                 int joints, int stride, const int64_t* crop_box, float crop_w, float crop_h, const float* paras,
+                                 const hn_convert_opts* opts, const int32_t* mirror, float* out_uvd, float* out_image_uvd,
+                                 float* out_xyz_mm, void* stream) {
   HN_CHECK_ARG(cls && reg && dep && out_uvd, "hn_a2j_aggregate_convert_f32: null pointer");
   HN_CHECK_ARG(crop_box || (opts && opts->sample_box), "hn_a2j_aggregate_convert_f32: no boxes (crop_box or opts->sample_box)");
   HN_CHECK_ARG(out_image_uvd || out_xyz_mm, "hn_a2j_aggregate_convert_f32: no converted output requested");
@@ -378,7 +382,26 @@ extern "C" int hn_a2j_aggregate_convert_f32(const float* cls, const float* reg, 
   HN_CHECK_ARG((cs.clamp_h > 0) == (cs.clamp_w > 0), "clamp_box_h and clamp_box_w are given together");
   cs.image_uvd = out_image_uvd;
   cs.xyz_mm = out_xyz_mm;
+  cs.mirror = mirror;
   return launch_aggregate(cls, reg, dep, valid, k, fh, fw, joints, stride, out_uvd, cs, stream);
+}
+
+extern "C" int hn_a2j_aggregate_convert_f32(const float* cls, const float* reg, const float* dep, const int32_t* valid, int k,
+                                            int fh, int fw, int joints, int stride, const int64_t* crop_box, float crop_w,
+                                            float crop_h, const float* paras, const hn_convert_opts* opts, float* out_uvd,
+                                            float* out_image_uvd, float* out_xyz_mm, void* stream) {
+  return aggregate_convert_run(cls, reg, dep, valid, k, fh, fw, joints, stride, crop_box, crop_w, crop_h, paras, opts, nullptr,
+                               out_uvd, out_image_uvd, out_xyz_mm, stream);
+}
+
+extern "C" int hn_a2j_aggregate_convert_mirror_f32(const float* cls, const float* reg, const float* dep, const int32_t* valid,
+                                                   const int32_t* mirror, int k, int fh, int fw, int joints, int stride,
+                                                   const int64_t* crop_box, float crop_w, float crop_h, const float* paras,
+                                                   const hn_convert_opts* opts, float* out_uvd, float* out_image_uvd,
+                                                   float* out_xyz_mm, void* stream) {
+  HN_CHECK_ARG(mirror, "hn_a2j_aggregate_convert_mirror_f32: null pointer");
+  return aggregate_convert_run(cls, reg, dep, valid, k, fh, fw, joints, stride, crop_box, crop_w, crop_h, paras, opts, mirror,
+                               out_uvd, out_image_uvd, out_xyz_mm, stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -459,8 +482,11 @@ __device__ __forceinline__ bool bbox_kept(float x, float y, float w, float h) {
   return w * h > 0.f && x2 >= x && y2 >= y;
 }
 
+// mirror (or nullptr): a lifted row with mirror != 0 gets column 0 negated -- exactly the standardisation of the joints
+// mirrored in x (the mean negates, the std stays); the gate itself is evaluated on the plain joints
 __global__ __launch_bounds__(64) void lifter_input_gated_kernel(const float* __restrict__ uvd, const int* __restrict__ valid,
-                                                                int J, float* __restrict__ out, int* __restrict__ lifted) {
+                                                                int J, float* __restrict__ out, int* __restrict__ lifted,
+                                                                const int* __restrict__ mirror) {
   const int img = blockIdx.x, lane = threadIdx.x;
   float* o = out + (long)img * J * 2;
   const float* p = uvd + (long)img * J * 3;
@@ -504,8 +530,10 @@ __global__ __launch_bounds__(64) void lifter_input_gated_kernel(const float* __r
     v1 += b * b;
   }
   const double s0 = sqrt(v0 / J), s1 = sqrt(v1 / J);
+  const bool flip = mirror && mirror[img];
   for (int j = lane; j < J; j += 64) {
-    o[j * 2 + 0] = (float)(((double)p[j * 3 + 0] - m0) / s0);
+    const float x = (float)(((double)p[j * 3 + 0] - m0) / s0);
+    o[j * 2 + 0] = flip ? -x : x;
     o[j * 2 + 1] = (float)(((double)p[j * 3 + 1] - m1) / s1);
   }
 }
@@ -517,7 +545,18 @@ extern "C" int hn_lifter_input_gated_f32(const float* image_uvd, const int32_t* 
   HN_CHECK_ARG(n >= 0 && joints > 1, "bad dims");
   if (n == 0) return HN_OK;
   hipLaunchKernelGGL(lifter_input_gated_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, image_uvd, valid, joints, out,
-                     lifted);
+                     lifted, (const int*)nullptr);
+  HN_CHECK_LAUNCH("lifter_input_gated_kernel");
+  return HN_OK;
+}
+
+extern "C" int hn_lifter_input_gated_mirror_f32(const float* image_uvd, const int32_t* valid, const int32_t* mirror, int n,
+                                                int joints, float* out, int32_t* lifted, void* stream) {
+  HN_CHECK_ARG(image_uvd && mirror && out && lifted, "hn_lifter_input_gated_mirror_f32: null pointer");
+  HN_CHECK_ARG(n >= 0 && joints > 1, "bad dims");
+  if (n == 0) return HN_OK;
+  hipLaunchKernelGGL(lifter_input_gated_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, image_uvd, valid, joints, out,
+                     lifted, (const int*)mirror);
   HN_CHECK_LAUNCH("lifter_input_gated_kernel");
   return HN_OK;
 }

@@ -975,13 +975,17 @@ __device__ __forceinline__ void write_slot(long slot, const long long b[4], int 
 // One wave64 per frame.  The survivor list is walked 64 entries at a time: a ballot of the hand-label lanes, and a
 // lane's rank among the frame's hand detections is the popcount of the matching lanes below it plus those of earlier
 // chunks.  The walk ends as soon as max_hands are found (real frames: the first chunk); slots left over are zeroed.
+// SIDED: the slot's handedness in the same launch -- side = det_sides of the slot's detection (-1: empty slot), mirror = 1
+// for a filled slot whose side is left_side (such a slot goes through the right-handed pose network and lifter mirrored)
+template <bool SIDED>
 __global__ __launch_bounds__(64) void hand_slots_kernel(const float* __restrict__ det_boxes,
                                                         const float* __restrict__ det_scores,
                                                         const int* __restrict__ det_labels,
                                                         const int* __restrict__ det_count, int cap, int hand_label,
                                                         int max_hands, int h, int w, long long* __restrict__ crop_box,
                                                         int* __restrict__ has_hand, float* __restrict__ score,
-                                                        int* __restrict__ det_index) {
+                                                        int* __restrict__ det_index, const int* __restrict__ det_sides,
+                                                        int left_side, int* __restrict__ side, int* __restrict__ mirror) {
   const int img = blockIdx.x, lane = threadIdx.x;
   const int cnt = min(det_count[img], cap);
   const long row = (long)img * cap;
@@ -995,27 +999,40 @@ __global__ __launch_bounds__(64) void hand_slots_kernel(const float* __restrict_
       long long b[4];
       const int ok = pad_hand_box(det_boxes + (row + i) * 4, h, w, b);
       write_slot((long)img * max_hands + rank, b, ok, det_scores[row + i], i, crop_box, has_hand, score, det_index);
+      if (SIDED) {
+        const int sd = ok ? det_sides[row + i] : -1;
+        side[(long)img * max_hands + rank] = sd;
+        mirror[(long)img * max_hands + rank] = (ok && sd == left_side) ? 1 : 0;
+      }
     }
     found += __popcll(mask);
   }
   if (lane >= found && lane < max_hands) {
     const long long z[4] = {0, 0, 0, 0};
     write_slot((long)img * max_hands + lane, z, 0, 0.f, -1, crop_box, has_hand, score, det_index);
+    if (SIDED) {
+      side[(long)img * max_hands + lane] = -1;
+      mirror[(long)img * max_hands + lane] = 0;
+    }
   }
 }
 
 // crop_gather_kernel over n * max_hands crops: crop `slot` reads frame slot / max_hands
+// SIDED: a slot with mirror != 0 is cut mirrored -- its pixel (oy, ox) is the plain crop's pixel (oy, out - 1 - ox): the
+// source-column rule below, evaluated at out - 1 - ox
+template <bool SIDED>
 __global__ __launch_bounds__(256) void hand_crop_gather_kernel(const float* __restrict__ depth,
                                                                const long long* __restrict__ crop_box,
                                                                const int* __restrict__ has_hand, int n, int max_hands,
                                                                int h, int w, int in_ch, int reorder, int out, int c4,
-                                                               float* __restrict__ crops) {
+                                                               float* __restrict__ crops, const int* __restrict__ mirror) {
   const long total = (long)n * max_hands * out * out;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int ox = (int)(i % out);
+    int ox = (int)(i % out);
     const long t = i / out;
     const int oy = (int)(t % out);
     const long slot = t / out;
+    if (SIDED && mirror[slot]) ox = out - 1 - ox;
     const long img = slot / max_hands;
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
     if (has_hand[slot]) {
@@ -1305,23 +1322,57 @@ extern "C" int hn_crop_resize(const float* det_boxes, const int32_t* det_labels,
   return HN_OK;
 }
 
-extern "C" int hn_crop_resize_hands(const float* det_boxes, const float* det_scores, const int32_t* det_labels,
-                                    const int32_t* det_count, int cap, int hand_label, int max_hands, const float* depth,
-                                    int n, int in_ch, int reorder_bgr, int h, int w, int out, int cpad, int64_t* crop_box,
-                                    int32_t* has_hand, float* score, int32_t* det_index, float* crops, void* stream) {
+static int crop_resize_hands_run(const char* who, const float* det_boxes, const float* det_scores, const int32_t* det_labels,
+                                 const int32_t* det_sides, const int32_t* det_count, int cap, int hand_label, int left_side,
+                                 int max_hands, const float* depth, int n, int in_ch, int reorder_bgr, int h, int w, int out,
+                                 int cpad, int64_t* crop_box, int32_t* has_hand, float* score, int32_t* det_index,
+                                 int32_t* side, int32_t* mirror, float* crops, void* stream) {
   HN_CHECK_ARG(det_boxes && det_scores && det_labels && det_count && depth && crop_box && has_hand && score && det_index && crops,
-               "hn_crop_resize_hands: null pointer");
+               "%s: null pointer", who);
   HN_CHECK_ARG(max_hands >= 1 && max_hands <= kMaxHands, "max_hands must be 1..%d (got %d)", kMaxHands, max_hands);
   HN_CHECK_ARG(n > 0 && h > 0 && w > 0 && out > 0 && cap > 0 && cpad >= 4 && cpad % 4 == 0, "bad dims");
   HN_CHECK_ARG(in_ch >= 1 && in_ch <= 4, "depth image must have 1..4 channels (got %d)", in_ch);
   HN_CHECK_ARG((uintptr_t)crop_box % 16 == 0 && (uintptr_t)crops % 16 == 0, "crop_box / crops must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(hand_slots_kernel, dim3(n), dim3(64), 0, st, det_boxes, det_scores, det_labels, det_count, cap,
-                     hand_label, max_hands, h, w, (long long*)crop_box, has_hand, score, det_index);
-  HN_CHECK_LAUNCH("hand_slots_kernel");
   const long total = (long)n * max_hands * out * out;
-  hipLaunchKernelGGL(hand_crop_gather_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, depth,
-                     (const long long*)crop_box, has_hand, n, max_hands, h, w, in_ch, reorder_bgr, out, cpad / 4, crops);
+  if (det_sides) {
+    hipLaunchKernelGGL(hand_slots_kernel<true>, dim3(n), dim3(64), 0, st, det_boxes, det_scores, det_labels, det_count, cap,
+                       hand_label, max_hands, h, w, (long long*)crop_box, has_hand, score, det_index, det_sides, left_side, side,
+                       mirror);
+    HN_CHECK_LAUNCH("hand_slots_kernel");
+    hipLaunchKernelGGL(hand_crop_gather_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, st, depth,
+                       (const long long*)crop_box, has_hand, n, max_hands, h, w, in_ch, reorder_bgr, out, cpad / 4, crops,
+                       (const int*)mirror);
+    HN_CHECK_LAUNCH("hand_crop_gather_kernel");
+    return HN_OK;
+  }
+  hipLaunchKernelGGL(hand_slots_kernel<false>, dim3(n), dim3(64), 0, st, det_boxes, det_scores, det_labels, det_count, cap,
+                     hand_label, max_hands, h, w, (long long*)crop_box, has_hand, score, det_index, (const int*)nullptr, 0,
+                     (int*)nullptr, (int*)nullptr);
+  HN_CHECK_LAUNCH("hand_slots_kernel");
+  hipLaunchKernelGGL(hand_crop_gather_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, st, depth,
+                     (const long long*)crop_box, has_hand, n, max_hands, h, w, in_ch, reorder_bgr, out, cpad / 4, crops,
+                     (const int*)nullptr);
   HN_CHECK_LAUNCH("hand_crop_gather_kernel");
   return HN_OK;
+}
+
+extern "C" int hn_crop_resize_hands(const float* det_boxes, const float* det_scores, const int32_t* det_labels,
+                                    const int32_t* det_count, int cap, int hand_label, int max_hands, const float* depth,
+                                    int n, int in_ch, int reorder_bgr, int h, int w, int out, int cpad, int64_t* crop_box,
+                                    int32_t* has_hand, float* score, int32_t* det_index, float* crops, void* stream) {
+  return crop_resize_hands_run("hn_crop_resize_hands", det_boxes, det_scores, det_labels, nullptr, det_count, cap, hand_label, 0,
+                               max_hands, depth, n, in_ch, reorder_bgr, h, w, out, cpad, crop_box, has_hand, score, det_index,
+                               nullptr, nullptr, crops, stream);
+}
+
+extern "C" int hn_crop_resize_hands_sided(const float* det_boxes, const float* det_scores, const int32_t* det_labels,
+                                          const int32_t* det_sides, const int32_t* det_count, int cap, int hand_label,
+                                          int left_side, int max_hands, const float* depth, int n, int in_ch, int reorder_bgr,
+                                          int h, int w, int out, int cpad, int64_t* crop_box, int32_t* has_hand, float* score,
+                                          int32_t* det_index, int32_t* side, int32_t* mirror, float* crops, void* stream) {
+  HN_CHECK_ARG(det_sides && side && mirror, "hn_crop_resize_hands_sided: null pointer");
+  return crop_resize_hands_run("hn_crop_resize_hands_sided", det_boxes, det_scores, det_labels, det_sides, det_count, cap,
+                               hand_label, left_side, max_hands, depth, n, in_ch, reorder_bgr, h, w, out, cpad, crop_box,
+                               has_hand, score, det_index, side, mirror, crops, stream);
 }

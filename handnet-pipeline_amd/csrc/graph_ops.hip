@@ -542,9 +542,13 @@ namespace {
 // out['mesh'] of ros_demo.py:162,332-337: the vertices of the real mesh in original order (pred_mesh[:, graph_perm_reverse[:V]]),
 // moved to the camera frame of the depth sensor -- (mesh * 1000 + joints3d[0]) / 1000 -- with y and z negated; numpy float32
 // arithmetic, one rounding per operation (contraction is switched off inside the kernel)
+// mirror (or nullptr): a row with mirror != 0 is the lifter's mesh of a MIRRORED hand -- the x of its raw vertices is negated
+// before the arithmetic; perm == nullptr (mirror form only): no permutation and no camera offset, the raw vertices (x negated
+// where mirrored), zero rows where not valid
 __global__ __launch_bounds__(256) void mesh_finish_kernel(const float* __restrict__ mesh, const long long* __restrict__ perm,
                                                           const float* __restrict__ xyz_mm, const int* __restrict__ valid,
-                                                          float* __restrict__ out, int n, int v0, int v, int joints) {
+                                                          float* __restrict__ out, int n, int v0, int v, int joints,
+                                                          const int* __restrict__ mirror) {
 #pragma clang fp contract(off)   // (HIP's __fmul_rn / __fadd_rn are plain operators: without this the pair becomes one fma)
   const long total = (long)n * v * 3;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -553,12 +557,17 @@ __global__ __launch_bounds__(256) void mesh_finish_kernel(const float* __restric
     const int vv = (int)(r % v), img = (int)(r / v);
     float val = 0.f;
     if (!valid || valid[img] == 1) {
-      const float m = mesh[((long)img * v0 + perm[vv]) * 3 + c];
-      const float root = xyz_mm[(long)img * joints * 3 + c];               // joints3d[0]: the first joint
-      const float scaled = m * 1000.f;
-      const float moved = scaled + root;
-      val = moved / 1000.f;
-      if (c) val = -val;
+      float m = mesh[((long)img * v0 + (perm ? perm[vv] : vv)) * 3 + c];
+      if (mirror && c == 0 && mirror[img]) m = -m;
+      if (perm) {
+        const float root = xyz_mm[(long)img * joints * 3 + c];               // joints3d[0]: the first joint
+        const float scaled = m * 1000.f;
+        const float moved = scaled + root;
+        val = moved / 1000.f;
+        if (c) val = -val;
+      } else {
+        val = m;
+      }
     }
     out[i] = val;
   }
@@ -570,7 +579,17 @@ extern "C" int hn_mesh_finish_f32(const float* mesh, const int64_t* perm, const 
   HN_CHECK_ARG(mesh && perm && xyz_mm && out, "hn_mesh_finish_f32: null pointer");
   HN_CHECK_ARG(n > 0 && v0 > 0 && v > 0 && joints > 0, "bad dims");
   hipLaunchKernelGGL(mesh_finish_kernel, dim3(grid_for((long)n * v * 3)), dim3(256), 0, (hipStream_t)stream, mesh,
-                     (const long long*)perm, xyz_mm, valid, out, n, v0, v, joints);
+                     (const long long*)perm, xyz_mm, valid, out, n, v0, v, joints, (const int*)nullptr);
+  HN_CHECK_LAUNCH("mesh_finish_kernel");
+  return HN_OK;
+}
+
+extern "C" int hn_mesh_finish_mirror_f32(const float* mesh, const int64_t* perm, const float* xyz_mm, const int32_t* valid,
+                                         const int32_t* mirror, int n, int v0, int v, int joints, float* out, void* stream) {
+  HN_CHECK_ARG(mesh && mirror && out && (perm == nullptr) == (xyz_mm == nullptr), "hn_mesh_finish_mirror_f32: null pointer");
+  HN_CHECK_ARG(n > 0 && v0 > 0 && v > 0 && joints > 0 && (perm || v == v0), "bad dims");
+  hipLaunchKernelGGL(mesh_finish_kernel, dim3(grid_for((long)n * v * 3)), dim3(256), 0, (hipStream_t)stream, mesh,
+                     (const long long*)perm, xyz_mm, valid, out, n, v0, v, joints, (const int*)mirror);
   HN_CHECK_LAUNCH("mesh_finish_kernel");
   return HN_OK;
 }

@@ -102,7 +102,7 @@ class HandNet(EngineOwner):
         self.last_converted = None
         return self
 
-    def live(self, lifter, paras, clamp: bool = True, perm_reverse=None, faces=None, labels: bool = False):
+    def live(self, lifter, paras, clamp: bool = True, perm_reverse=None, faces=None, labels: bool = False, left: bool = False):
         """The live caller's chain as ONE step (hn_amd.live.LiveHandEngine; ros_demo.py:270-290,329-337): this network, the
         caller's clamp + convert_joints (in the aggregation's epilogue), the lifter's input, Pose2Mesh, one device -> host copy.
         lifter: the drop-in `models.pose2mesh_net.get_model(...)` module (on the GPU) or a Pose2MeshEngine; paras = (fx, fy,
@@ -111,15 +111,17 @@ class HandNet(EngineOwner):
         (ros_demo.py:86-116,341): out.overlay on the device, read().overlay on the host.
         labels: the step also draws the caller's other two images (ros_demo.py:310-326): box_label (the frame with the crop
         box) and pose_label (the 176 x 176 colour crop with the skeleton), out.box_label / .pose_label, read() likewise.
+        left: the caller's ImageListener(left=True) (ros_demo.py:259-262): frame and depth map are mirrored along the width
+        before anything else runs -- inside the ingest kernel for forward_raw -- and every result is in the mirrored frame.
         The returned engine owns this network's step from then on (forward() of this module keeps working and
         carries the converted joints: set_convert)."""
         from hn_amd.live import LiveHandEngine
         self._convert_cfg = (tuple(paras), bool(clamp))
         return LiveHandEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, clamp, perm_reverse,
-                              faces, labels)
+                              faces, labels, left)
 
     def live_hands(self, lifter, paras, max_hands: int = 2, clamp: bool = True, perm_reverse=None, faces=None,
-                   labels: bool = False):
+                   labels: bool = False, left: bool = False, handed: bool = False, left_side: int = 0):
         """live() for up to max_hands (1..16) hands per frame (hn_amd.live.LiveHandsEngine): forward_hands' slots, the
         caller's clamp + convert_joints, the lifter's input with the caller's skip rule per slot (a hand whose 2D box
         process_bbox refuses is not lifted: ros_demo.py:288-300), Pose2Mesh on every slot, one device -> host copy.
@@ -127,12 +129,18 @@ class HandNet(EngineOwner):
         faces = mesh_model.face (needs perm_reverse): every lifted mesh of a frame is drawn over it (one depth buffer per frame):
         out.overlay / read().overlay [N,H,W,3] uint8 RGB.
         labels: as for live(): box_label [N,H,W,3] with the crop box of every lifted slot, pose_label [N,K,176,176,3] (zeros
-        where the slot is not lifted)."""
+        where the slot is not lifted).
+        left: as for live().  handed: per-slot handedness instead -- read().side is the detector's side of every slot and a
+        slot whose side equals left_side goes mirrored through the right-handed A2J and Pose2Mesh and comes back un-mirrored, so
+        a left hand's mesh has its thumb on the right side; no launch is added.  left_side = 0 assumes the 100DOH
+        convention of the detector's training targets, which the reference does not state.  left with handed: ValueError."""
         from hn_amd.live import LiveHandsEngine
         k = ops.check_max_hands(max_hands)
+        if left and handed:
+            raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
         self._convert_cfg = (tuple(paras), bool(clamp))
         return LiveHandsEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, k, clamp,
-                               perm_reverse, faces, labels)
+                               perm_reverse, faces, labels, left, handed, left_side)
 
     # forward() switches ITSELF to hipGraph replay once the same input shapes have come in a few times in a row -- the live
     # caller's case (ros_demo.py:270-273: one 640x480 frame per call, ~150 dependent launches whose host cost is 8 % of the
@@ -160,7 +168,7 @@ class HandNet(EngineOwner):
             self._auto_graph_allowed = True
         return self
 
-    def _auto_graph(self, image_shape, depth_shape, on_gpu=True, hands=None) -> bool:
+    def _auto_graph(self, image_shape, depth_shape, on_gpu=True, hands=None, handed=(False, 0)) -> bool:
         """Whether this call of forward() (hands = K: of forward_hands()) should run as a graph replay (capturing first if
         need be)."""
         eng = self.engine()
@@ -168,9 +176,9 @@ class HandNet(EngineOwner):
         if not self._auto_graph_allowed or eng.check_range or sparse or not on_gpu:
             return False
         if (eng.has_graph(image_shape, depth_shape, to_host=True) if hands is None
-                else eng.has_graph_hands(image_shape, depth_shape, hands, to_host=True)):
+                else eng.has_graph_hands(image_shape, depth_shape, hands, to_host=True, handed=handed[0], left_side=handed[1])):
             return True
-        key = (tuple(image_shape), tuple(depth_shape)) + (() if hands is None else (hands,))
+        key = (tuple(image_shape), tuple(depth_shape)) + (() if hands is None else (hands,)) + (handed if handed[0] else ())
         if key == getattr(self, "_streak_key", None):
             self._streak += 1
         else:
@@ -239,7 +247,8 @@ class HandNet(EngineOwner):
             out = self.forward_device(images, depth_images, _to_host=True)
         return self._finish(out, n, depth_images)
 
-    def forward_hands(self, images, depth_images, max_hands: int = 2, is_3D: bool = False, is_detect: bool = False):
+    def forward_hands(self, images, depth_images, max_hands: int = 2, is_3D: bool = False, is_detect: bool = False,
+                      handed: bool = False, left_side: int = 0):
         """forward() for up to max_hands (1..16) hands per frame.  Slot k of frame i is the k-th hand-class detection of
         frame i in the detector's score order (the reference keeps slot 0 only, handnet_pipeline.py:84-85), padded and
         cropped as forward() crops it.  images / depth_images as forward() takes them.  Returns
@@ -249,42 +258,50 @@ class HandNet(EngineOwner):
           boxes       [N,K,4] int64 on the CPU (padded, clamped x1,y1,x2,y2; zeros for empty slots)
           hand_mask   [N,K] bool on the CPU
           scores      [N,K] fp32 on the CPU (the detections' scores; 0 for empty slots)
-        One device -> host copy and one sync per call; repeated shapes switch to graph replay as forward() does."""
+        One device -> host copy and one sync per call; repeated shapes switch to graph replay as forward() does.
+        handed: a sixth result, sides [N,K] int32 on the CPU (the detector's side of the slot's detection, -1 for empty slots),
+        and a slot whose side equals left_side goes through the right-handed A2J mirrored (its crop in depth_batch is flipped
+        along the width) and its keypoints come back un-mirrored (u = 176 - u).  left_side = 0 assumes the 100DOH convention
+        of the detector's training targets, which the reference does not state."""
         if is_detect or is_3D:
             return None
         if depth_images is None:
             raise ValueError("depth_images is required for the ensemble inference branch")
         k = ops.check_max_hands(max_hands)
+        handed, left_side = bool(handed), int(left_side)
         eng = self.engine()
         n = len(images)
         dev = eng.device
         batch = images if torch.is_tensor(images) else torch.stack([i.float() for i in images])
         batch, depth = batch.to(dev).float().contiguous(), depth_images.to(dev).float().contiguous()
         mode = getattr(self, "use_graph", None)
-        graph = bool(mode) if mode is not None else self._auto_graph(batch.shape, depth.shape, True, hands=k)
+        graph = bool(mode) if mode is not None else self._auto_graph(batch.shape, depth.shape, True, hands=k,
+                                                                     handed=(handed, left_side))
 
         def captured():
-            run, s_img, s_dep, out = eng.graphed_hands(batch, depth, k, to_host=True, limit=self.AUTO_GRAPH_MAX_SHAPES)
+            run, s_img, s_dep, out = eng.graphed_hands(batch, depth, k, to_host=True, limit=self.AUTO_GRAPH_MAX_SHAPES,
+                                                       handed=handed, left_side=left_side)
             s_img.copy_(batch)
             s_dep.copy_(depth)
             run()
             return out
-        out = self._graph_or_eager(graph, captured, lambda: eng.forward_hands(batch, depth, k, to_host=True))
-        return self._finish_hands(out, n, k, depth)
+        out = self._graph_or_eager(graph, captured, lambda: eng.forward_hands(batch, depth, k, to_host=True, handed=handed,
+                                                                              left_side=left_side))
+        return self._finish_hands(out, n, k, depth, handed)
 
-    def _finish_hands(self, out, n, k, depth):
+    def _finish_hands(self, out, n, k, depth, handed=False):
         """forward_hands()'s tuple from the step's one host record (see _finish)."""
         from hn_amd.pipeline import read_hands_tail
         rows = n * k
         sel = out.crops_nhwc
         depth_all = (sel.permute(0, 3, 1, 2) if self.RGBD else sel[..., 0].unsqueeze(1)).contiguous()
         kp, box, mask, filled = self._read_step(out, (n, k), "_last_sparse_hands", depth)
-        scores, _ = read_hands_tail(out.host_record, rows)
+        scores, _, *sides = read_hands_tail(out.host_record, rows, handed)
         if filled == rows:
             depth_batch = depth_all
         else:
             depth_batch = depth_all.index_select(0, mask.nonzero().flatten().to(depth_all.device))
-        return kp, depth_batch, box, mask.view(n, k), scores.view(n, k)
+        return (kp, depth_batch, box, mask.view(n, k), scores.view(n, k)) + tuple(sd.view(n, k) for sd in sides)
 
     def forward_raw(self, bgr_u8, depth_raw, is_3D: bool = False, is_detect: bool = False):
         """The reference caller's ingest AND its network call in one (ros_demo.py:227-231,266-273): bgr_u8 = the cv_bridge

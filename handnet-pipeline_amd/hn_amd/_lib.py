@@ -216,6 +216,14 @@ SIGNATURES = {
     "hn_lifter_input_gated_f32": (C.c_int, [VP, VP, C.c_int, C.c_int, VP, VP, VP]),
     "hn_handnet_forward_xyz": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_int, c_f32p, C.POINTER(ConvertOpts),
                                          VP, VP, VP, VP, VP, VP]),
+    # mirror mode / per-slot handedness (new functions under ABI 36)
+    "hn_ingest_u8bgr_u16mm_flip": (C.c_int, [VP, VP, C.c_int, VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP]),
+    "hn_flip_w_f32": (C.c_int, [VP, VP, C.c_int64, VP, VP, C.c_int64, C.c_int, VP]),
+    "hn_crop_resize_hands_sided": (C.c_int, [VP] * 5 + [C.c_int] * 4 + [VP] + [C.c_int] * 7 + [VP] * 8),
+    "hn_a2j_aggregate_convert_mirror_f32": (C.c_int, [VP] * 5 + [C.c_int] * 5 + [VP, C.c_float, C.c_float, c_f32p,
+                                                      C.POINTER(ConvertOpts), VP, VP, VP, VP]),
+    "hn_lifter_input_gated_mirror_f32": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, VP, VP, VP]),
+    "hn_mesh_finish_mirror_f32": (C.c_int, [VP] * 5 + [C.c_int] * 4 + [VP, VP]),
 }
 
 _lock = threading.Lock()

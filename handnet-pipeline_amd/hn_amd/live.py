@@ -136,7 +136,7 @@ class _LiveStep:
     and forward_device(images, depth, _buffers)."""
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None,
-                 labels: bool = False):
+                 labels: bool = False, left: bool = False):
         if not _same_device(hand.device, lifter.device):
             raise ValueError(f"HandNet on {hand.device} but the lifter on {lifter.device}")
         self.hand, self.lifter, self.device = hand, lifter, hand.device
@@ -153,6 +153,10 @@ class _LiveStep:
                 self.faces = ops.mesh_faces(faces, self.vertices, self.device)
         # labels: the step ends with the caller's other two images (ops.draw_labels: ros_demo.py:310-326), behind the overlay
         self.labels, self.clamp = bool(labels), bool(clamp)
+        # left: the caller's mirror mode (ImageListener(left=True), ros_demo.py:259-262): the step runs on the frame and the
+        # depth map flipped along the width, and every result is in that mirrored frame, as the reference publishes it
+        self.left = bool(left)
+        self._mirrored = {}
         self._render_scratch = {}
         self._graphs = {}
         self._buffers = {}
@@ -167,6 +171,19 @@ class _LiveStep:
 
     def _hw(self, frames):
         return None if frames is None else (int(frames.shape[2]), int(frames.shape[3]))
+
+    def _mirror_inputs(self, images, depth, owned=None):
+        """The `left` step's inputs: frames and depth map mirrored along the width into buffers of the engine (`owned`: of a
+        capture) by ONE launch (ops.flip_w)."""
+        images = (images if torch.is_tensor(images) else torch.stack(list(images))).float().contiguous()
+        depth = depth.float().contiguous()
+        if owned is None:
+            key = (tuple(images.shape), tuple(depth.shape))
+            owned = self._mirrored.get(key)
+            if owned is None:
+                with torch.inference_mode(False):
+                    owned = self._mirrored[key] = (torch.empty_like(images), torch.empty_like(depth))
+        return ops.flip_w(images, depth, out=owned[0], out_other=owned[1])
 
     def _draw(self, mesh, lifted, frames, k, out):
         s = mesh.shape[0]
@@ -206,16 +223,19 @@ class _LiveStep:
         staged = []
         bgr, dep = self.hand._device_readable(bgr_u8, staged), self.hand._device_readable(depth_raw, staged)
         n, h, w, _ = bgr.shape
-        key = ((n, 3, h, w), (n, 1, h, w))
+        # (a `left` step: the ingest kernel mirrors while it converts, so this capture -- keyed apart from graphed()'s -- takes
+        # its inputs as already mirrored and holds no mirror launch)
+        key = ((n, 3, h, w), (n, 1, h, w)) + (("mirrored",) if self.left else ())
         if key not in self._graphs:
-            rgb, d1, _ = ops.ingest_raw(bgr, dep, device=self.device)
-            self.graphed(rgb, d1)
-        return self.hand._ingest_replay(self._graphs[key], bgr, dep, staged)
+            rgb, d1, _ = ops.ingest_raw(bgr, dep, device=self.device, flip_w=self.left)
+            self.graphed(rgb, d1, _mirrored=self.left)
+        return self.hand._ingest_replay(self._graphs[key], bgr, dep, staged, flip_w=self.left)
 
     @ops.device_guarded
-    def graphed(self, images: torch.Tensor, depth: torch.Tensor):
-        """(run, static images, static depth, static LiveOutput): copy new frames into the static inputs and call run()."""
-        key = (tuple(images.shape), tuple(depth.shape))
+    def graphed(self, images: torch.Tensor, depth: torch.Tensor, _mirrored: bool = False):
+        """(run, static images, static depth, static LiveOutput): copy new frames into the static inputs and call run().
+        (A `left` step: the captured step mirrors the static inputs itself, one launch.)"""
+        key = (tuple(images.shape), tuple(depth.shape)) + (("mirrored",) if _mirrored else ())
         hit = self._graphs.get(key)
         if hit is None:
             with torch.inference_mode(False), torch.no_grad():
@@ -224,7 +244,13 @@ class _LiveStep:
                 s_dep.copy_(depth)
                 # the capture's own pair, never the eager cache's (addresses are baked into the graph)
                 bufs = self._new_buffers(images.shape[0], self._hw(self._frames(images)))
-                g, out = ops.capture_step(lambda: self.forward_device(s_img, s_dep, _buffers=bufs))
+                flipped = None
+                if self.left and not _mirrored:
+                    # the capture's mirrored inputs: owned by the engine for as long as the capture lives (their addresses are
+                    # baked into the graph, and nothing the step hands out refers to them)
+                    flipped = self._mirrored[("capture",) + key] = (torch.empty_like(s_img), torch.empty_like(s_dep))
+                g, out = ops.capture_step(lambda: self.forward_device(s_img, s_dep, _buffers=bufs,
+                                                                      _mirror=False if _mirrored else flipped))
             hit = self._graphs[key] = (g, s_img, s_dep, out)
         g, s_img, s_dep, out = hit
         return g.replay, s_img, s_dep, out
@@ -232,7 +258,7 @@ class _LiveStep:
 
 class LiveHandEngine(_LiveStep):
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None,
-                 labels: bool = False):
+                 labels: bool = False, left: bool = False):
         """paras = (fx, fy, cx, cy) of the depth camera (ros_demo.py:191-196); clamp: the caller's clamps before the
         conversion (ros_demo.py:279-283).  perm_reverse: graph_perm_reverse[:V] (int64, V = vertices of the real mesh,
         ros_demo.py:162) -- given, the step also does the caller's last three lines (vertex order, camera offset by the first
@@ -240,8 +266,12 @@ class LiveHandEngine(_LiveStep):
         [N,V0,3] vertices in coarsening order.  faces: mesh_model.face ([F,3] vertex indices of the real mesh; needs perm_reverse) --
         given, the step also draws the mesh over the frame (ros_demo.py:86-116 render(): LiveOutput.overlay, read().overlay).
         labels: the step also draws box_label and pose_label (ros_demo.py:310-326: LiveOutput.box_label / .pose_label, read()
-        likewise); a frame without a hand (has_hand != 1) keeps its plain frame and a zero pose_label."""
-        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels)
+        likewise); a frame without a hand (has_hand != 1) keeps its plain frame and a zero pose_label.
+        left: the reference's mirror mode for a left-handed subject (ImageListener(left=True), ros_demo.py:259-262) -- every
+        output equals the one of this engine without `left` on frames and depth flipped along the width, bit for bit (boxes,
+        keypoints, mesh and images are in the mirrored frame, as the reference publishes them).  forward_raw mirrors inside the
+        ingest kernel (no launch added); fp32 feeds (forward_device / graphed) cost one launch."""
+        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left)
 
     def _nbytes(self, n, hw=None):
         if hw is None:
@@ -249,9 +279,12 @@ class LiveHandEngine(_LiveStep):
         return live_labels_layout(n, self.vertices, *hw, overlay=self.faces is not None, labels=self.labels)[4]
 
     @ops.device_guarded
-    def forward_device(self, images, depth, _buffers=None) -> LiveOutput:
-        """images [N,3,H,W] 0..1 (or a list), depth [N,1,H,W] metres on the GPU -> LiveOutput (no sync)."""
+    def forward_device(self, images, depth, _buffers=None, _mirror=None) -> LiveOutput:
+        """images [N,3,H,W] 0..1 (or a list), depth [N,1,H,W] metres on the GPU -> LiveOutput (no sync).
+        (_mirror: a `left` capture's own mirrored-input buffers; False: the inputs are mirrored already.)"""
         n = len(images)
+        if self.left and _mirror is not False:
+            images, depth = self._mirror_inputs(images, depth, _mirror)
         v0 = self.vertices
         frames = self._frames(images)
         dev, host = _buffers if _buffers is not None else self._out_buffers(n, v0, self._hw(frames))
@@ -283,30 +316,34 @@ class LiveHandEngine(_LiveStep):
         return LiveOutput(out, p2d, mesh, pose3d, host, n, raw, overlay, box_label, pose_label)
 
 
-def live_hands_layout(slots: int, vertices: int):
+def live_hands_layout(slots: int, vertices: int, handed: bool = False):
     """Byte layout of the K-hand live step's one buffer for `slots` = N*K hand slots: (record rows, record bytes, offset of
     `lifted` (int32 [slots]), offset of the mesh (fp32 [slots,V,3]), total bytes).  The record is forward_hands' wide record
-    unchanged (one row per slot, the range-word row, the scores and detection ranks: hands_record_rows)."""
+    unchanged (one row per slot, the range-word row, the scores and detection ranks: hands_record_rows).  handed: the
+    slots' sides (int32 [slots]) sit behind the score and rank rows, at `rows * record bytes` -- `lifted` and everything behind
+    it move up by 4 * slots bytes, nothing else changes."""
     rb = record_bytes(3)
     rows = hands_record_rows(slots, rb)
-    lifted = rows * rb
+    lifted = rows * rb + (4 * slots if handed else 0)
     mesh = lifted + 4 * slots
     return rows, rb, lifted, mesh, mesh + slots * vertices * 12
 
 
-def live_hands_overlay_layout(slots: int, vertices: int, frames: int, h: int, w: int):
+def live_hands_overlay_layout(slots: int, vertices: int, frames: int, h: int, w: int, handed: bool = False):
     """live_hands_layout with the overlay appended: the same five values (every offset where a step without an overlay has
     it; the fifth is now the overlay's offset) + the total bytes; the overlay is uint8 [frames,h,w,3]."""
-    rows, rb, lifted, mesh, overlay = live_hands_layout(slots, vertices)
+    rows, rb, lifted, mesh, overlay = live_hands_layout(slots, vertices, handed)
     return rows, rb, lifted, mesh, overlay, overlay + frames * h * w * 3
 
 
-def live_hands_labels_layout(slots: int, vertices: int, frames: int, h: int, w: int, overlay: bool = False, labels: bool = True):
+def live_hands_labels_layout(slots: int, vertices: int, frames: int, h: int, w: int, overlay: bool = False, labels: bool = True,
+                             handed: bool = False):
     """live_hands_overlay_layout with the label images appended behind the mesh, and behind the overlay when there is one: its
     first five values (the overlay's offset: the end of the mesh), then the offset of box_label (uint8 [frames,h,w,3]), the
     offset of pose_label (uint8 [slots,176,176,3]) and the total bytes.  Without `labels` the total is the one of
     live_hands_overlay_layout / live_hands_layout."""
-    rows, rb, lifted, mesh, oo, end = live_hands_overlay_layout(slots, vertices, frames, h if overlay else 0, w if overlay else 0)
+    rows, rb, lifted, mesh, oo, end = live_hands_overlay_layout(slots, vertices, frames, h if overlay else 0, w if overlay else 0,
+                                                                handed)
     return (rows, rb, lifted, mesh, oo) + _labels_behind(end, frames, slots, h, w, labels)
 
 
@@ -319,6 +356,10 @@ LiveHandsLabelsRead = _read_type("LiveHandsLabelsRead", LiveHandsRead._fields + 
                                  overlay=None)
 LiveHandsOverlayLabelsRead = _read_type("LiveHandsOverlayLabelsRead", LiveHandsRead._fields + ("overlay",) + _LABEL_FIELDS,
                                         "... of a step with faces= and labels.")
+# ... and of a handed step: the same fields + `side` [N,K] int32 (the detector's side of the slot's detection, -1: empty slot)
+_SIDED_READS = {t: _read_type(t.__name__.replace("Read", "SidedRead"), t._fields + ("side",), t.__doc__ + "  Handed: + side.",
+                              **{f: None for f in ("overlay",) + _LABEL_FIELDS if f not in t._fields})
+                for t in (LiveHandsRead, LiveHandsOverlayRead, LiveHandsLabelsRead, LiveHandsOverlayLabelsRead)}
 
 
 @dataclass
@@ -335,14 +376,23 @@ class LiveHandsOutput:
     overlay: torch.Tensor = None    # [N,H,W,3] uint8 RGB on the device: all lifted meshes of a frame drawn over it (faces=)
     box_label: torch.Tensor = None  # [N,H,W,3] uint8 RGB on the device: the frame with the crop box of every lifted slot (labels)
     pose_label: torch.Tensor = None  # [N*K,176,176,3] uint8 RGB on the device: per slot, the colour crop with the skeleton
+    side: torch.Tensor = None        # handed steps: [N,K] int32 on the device, the detector's side per slot (-1: empty slot)
+    mirror: torch.Tensor = None      # handed steps: [N,K] int32 on the device, 1 where the slot ran mirrored (a left hand)
 
     def read(self) -> LiveHandsRead:
         """After the stream is synchronised: the step's results per frame and slot as fresh CPU tensors (LiveHandsRead;
         lifted as bool, words = the step's range words; a step with faces=: LiveHandsOverlayRead, + overlay [N,H,W,3] uint8; a
-        step with labels: + box_label [N,H,W,3], pose_label [N,K,176,176,3] -- LiveHandsLabelsRead, LiveHandsOverlayLabelsRead)."""
+        step with labels: + box_label [N,H,W,3], pose_label [N,K,176,176,3] -- LiveHandsLabelsRead, LiveHandsOverlayLabelsRead;
+        a handed step: the same with `side` [N,K] int32 as the last field)."""
         n, k, s = self.n, self.k, self.n * self.k
-        rows, rb, lo, mo, nbytes = live_hands_layout(s, self.mesh.shape[2])
-        rec = self.host[:lo].view(rows, rb)
+        handed = self.side is not None
+        rows, rb, lo, mo, nbytes = live_hands_layout(s, self.mesh.shape[2], handed)
+
+        def sided(kind, values):
+            if not handed:
+                return kind(*values)
+            return _SIDED_READS[kind](*values, self.host[rows * rb:lo].view(torch.int32).reshape(n, k).clone())
+        rec = self.host[:rows * rb].view(rows, rb)
         kp, has, box, words, (img, xyz) = read_host_record(rec, s, extras=True)
         score, index = read_hands_tail(rec, s)
         lifted = self.host[lo:mo].view(torch.int32).reshape(n, k) != 0
@@ -352,12 +402,12 @@ class LiveHandsOutput:
         if self.overlay is not None:
             fields += (self.host[nbytes:nbytes + self.overlay.numel()].reshape(self.overlay.shape).clone(),)
         if self.box_label is None:
-            return (LiveHandsRead if self.overlay is None else LiveHandsOverlayRead)(*fields)
+            return sided(LiveHandsRead if self.overlay is None else LiveHandsOverlayRead, fields)
         h, w = self.box_label.shape[1:3]
-        bo, po, end = live_hands_labels_layout(s, self.mesh.shape[2], n, h, w, self.overlay is not None)[5:]
+        bo, po, end = live_hands_labels_layout(s, self.mesh.shape[2], n, h, w, self.overlay is not None, handed=handed)[5:]
         fields += (self.host[bo:bo + self.box_label.numel()].reshape(self.box_label.shape).clone(),
                    self.host[po:end].reshape(n, k, POSE_LABEL, POSE_LABEL, 3).clone())
-        return (LiveHandsLabelsRead if self.overlay is None else LiveHandsOverlayLabelsRead)(*fields)
+        return sided(LiveHandsLabelsRead if self.overlay is None else LiveHandsOverlayLabelsRead, fields)
 
 
 class LiveHandsEngine(_LiveStep):
@@ -368,56 +418,78 @@ class LiveHandsEngine(_LiveStep):
     the final mesh (perm_reverse) -> ONE device -> host copy of records + lifted + mesh (live_hands_layout)."""
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, max_hands: int = 2, clamp: bool = True,
-                 perm_reverse=None, faces=None, labels: bool = False):
+                 perm_reverse=None, faces=None, labels: bool = False, left: bool = False, handed: bool = False,
+                 left_side: int = 0):
         """faces: mesh_model.face ([F,3]; needs perm_reverse) -- given, the step ends with the overlay: every lifted mesh of a
         frame drawn over it with one depth buffer per frame (LiveHandsOutput.overlay, read().overlay), in the same copy.
         labels: the step ends with box_label (the crop box of every lifted slot on its frame) and one pose_label per slot
-        (zeros where the slot is not lifted: the reference's condition, ros_demo.py:294), in the same copy."""
+        (zeros where the slot is not lifted: the reference's condition, ros_demo.py:294), in the same copy.
+        left: the reference's whole-frame mirror mode, as LiveHandEngine's.
+        handed: the per-slot form of that mirror, for frames that hold a left AND a right hand.  The detector's side of every
+        slot is handed over (LiveHandsOutput.side, read().side; -1: empty slot) and a filled slot whose side equals left_side
+        goes MIRRORED through the right-handed pose network and lifter and comes back un-mirrored: its crop is flipped along
+        the width, the aggregation writes u = 176 - u, the lifter's input has column 0 negated and the x of the lifter's raw
+        vertices is negated before the final mesh's arithmetic -- all flags on launches the step makes anyway.  Keypoints,
+        mesh and images are in the frame's own coordinates; slots that are not mirrored are the plain step's, bit for bit.
+        left_side = 0 is an ASSUMPTION: the detector's side targets are box_info[:, 1] of its training set, whose convention
+        (100DOH: 0 = left) the reference does not state -- it never reads `sides`.  Check it on your checkpoint.
+        left and handed together: ValueError (a mirrored frame swaps the sides)."""
         self.max_hands = ops.check_max_hands(max_hands)
-        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels)
+        if left and handed:
+            raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
+        self.handed, self.left_side = bool(handed), int(left_side)
+        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left)
 
     def _nbytes(self, n, hw=None):
         if hw is None:
-            return live_hands_layout(n * self.max_hands, self.vertices)[4]
+            return live_hands_layout(n * self.max_hands, self.vertices, self.handed)[4]
         return live_hands_labels_layout(n * self.max_hands, self.vertices, n, *hw, overlay=self.faces is not None,
-                                        labels=self.labels)[7]
+                                        labels=self.labels, handed=self.handed)[7]
 
     @ops.device_guarded
-    def forward_device(self, images, depth, _buffers=None) -> LiveHandsOutput:
+    def forward_device(self, images, depth, _buffers=None, _mirror=None) -> LiveHandsOutput:
         """images [N,3,H,W] 0..1 (or a list), depth [N,1,H,W] metres on the GPU -> LiveHandsOutput (no sync).  Eager steps
-        may run A2J on the filled slots only (HandNetEngine.forward_hands); the lifter always runs on all N*K rows."""
+        may run A2J on the filled slots only (HandNetEngine.forward_hands); the lifter always runs on all N*K rows.
+        (_mirror: as LiveHandEngine.forward_device's.)"""
         n, k = len(images), self.max_hands
+        if self.left and _mirror is not False:
+            images, depth = self._mirror_inputs(images, depth, _mirror)
         s, v = n * k, self.vertices
         frames = self._frames(images)
         dev, host = _buffers if _buffers is not None else self._out_buffers(n, v, self._hw(frames))
-        rows, rb, lo, mo, nbytes = live_hands_layout(s, v)
-        rec = dev[:lo].view(rows, rb)
+        rows, rb, lo, mo, nbytes = live_hands_layout(s, v, self.handed)
+        rec = dev[:rows * rb].view(rows, rb)
+        side = dev[rows * rb:lo].view(torch.int32) if self.handed else None
         lifted = dev[lo:mo].view(torch.int32)
         mesh_buf = dev[mo:nbytes].view(torch.float32).view(s, v, 3)
 
-        def lift(_kp, image_uvd, xyz, has_hand):
-            # (inside the step's range scope, as LiveHandEngine's lifter)
-            p2d, _ = ops.lifter_input_gated(image_uvd, valid=has_hand, lifted=lifted)
+        def lift(_kp, image_uvd, xyz, has_hand, mirror=None):
+            # (inside the step's range scope, as LiveHandEngine's lifter; mirror: the handed step's per-slot flags)
+            p2d, _ = ops.lifter_input_gated(image_uvd, valid=has_hand, lifted=lifted, mirror=mirror)
             raw, pose3d = self.lifter.forward(p2d)
-            if self.perm is None:
+            if mirror is not None:      # (also without perm_reverse: the raw vertices, x negated where mirrored)
+                mesh = ops.mesh_finish(raw, self.perm, xyz if self.perm is not None else None, valid=lifted, out=mesh_buf,
+                                       mirror=mirror)
+            elif self.perm is None:
                 mesh = torch.mul(raw, lifted.view(s, 1, 1), out=mesh_buf)       # (x * 1 is x: rows not lifted -> zeros)
             else:
                 mesh = ops.mesh_finish(raw, self.perm, xyz, valid=lifted, out=mesh_buf)
             return p2d, mesh, pose3d, raw
         # the step packs its per-slot records, range words, scores and ranks straight into `rec`; ONE copy moves it all
-        out = self.hand.forward_hands(images, depth, k, _record=(None, rec), _tail=lift)
+        out = self.hand.forward_hands(images, depth, k, _record=(None, rec), _tail=lift, handed=self.handed,
+                                      left_side=self.left_side, _side=side)
         p2d, mesh, pose3d, raw = out.tail
         overlay = box_label = pose_label = None
         if frames is not None:
             h, w = frames.shape[2:]
-            bo, po, _ = live_hands_labels_layout(s, v, n, h, w, self.faces is not None, self.labels)[5:]
+            bo, po, _ = live_hands_labels_layout(s, v, n, h, w, self.faces is not None, self.labels, self.handed)[5:]
             if self.faces is not None:
                 overlay = self._draw(mesh, lifted, frames, k, dev[nbytes:nbytes + n * h * w * 3])
             if self.labels:
                 box_label, pose_label = self._draw_labels(out.keypoints, out.crop_box, lifted, frames, k, dev, bo, po)
         host.copy_(dev, non_blocking=True)
         return LiveHandsOutput(out, p2d, lifted.view(n, k), mesh.view(n, k, v, 3), pose3d, host, n, k, raw, overlay, box_label,
-                               pose_label)
+                               pose_label, out.side, out.mirror)
 
 
 @dataclass

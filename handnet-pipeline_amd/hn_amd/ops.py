@@ -880,12 +880,15 @@ def _device_readable(t: torch.Tensor, name: str):
     return t
 
 
-def ingest_raw(bgr_u8, depth=None, device=None, out_rgb=None, out_depth=None, out_rgbd=None, want_rgbd=False, want_depth=True):
+def ingest_raw(bgr_u8, depth=None, device=None, out_rgb=None, out_depth=None, out_rgbd=None, want_rgbd=False, want_depth=True,
+               flip_w=False):
     """The reference caller's host-side conversions as ONE kernel (hn_ingest_u8bgr_u16mm; ros_demo.py:227-231,266-269):
     bgr_u8 uint8 [N,H,W,3] (cv_bridge 'bgr8' frames), depth [N,H,W] uint16 / int16 millimetres (16UC1) or float32 metres
     (32FC1), each on the GPU or in PINNED host memory -> (rgb fp32 [N,3,H,W] in 0..1, depth fp32 [N,1,H,W] metres or None,
     rgbd fp32 [N,4,H,W] or None) on the GPU; bit-identical to `astype(float32) / 255.0` and `/ 1000.0`.
-    want_depth=False (with an RGB-D output): the separate depth map is neither allocated nor written."""
+    want_depth=False (with an RGB-D output): the separate depth map is neither allocated nor written.
+    flip_w: the caller's `left` mode (cv2.flip(., 1) of frame and depth, ros_demo.py:259-262) in the same launch
+    (hn_ingest_u8bgr_u16mm_flip): every output is the one of the arrays flipped along the width axis, bit for bit."""
     if bgr_u8.dtype != torch.uint8 or bgr_u8.dim() != 4 or bgr_u8.shape[3] != 3:
         raise TypeError(f"bgr_u8: expected uint8 [N,H,W,3], got {bgr_u8.dtype} {tuple(bgr_u8.shape)}")
     _device_readable(bgr_u8, "bgr_u8")
@@ -914,11 +917,41 @@ def ingest_raw(bgr_u8, depth=None, device=None, out_rgb=None, out_depth=None, ou
     for t, nm in ((out_rgb, "out_rgb"), (out_depth, "out_depth"), (out_rgbd, "out_rgbd")):
         if t is not None:
             _req(t, name=nm)
-    check(_lib.load().hn_ingest_u8bgr_u16mm(bgr_u8.data_ptr(), depth.data_ptr() if kind else None, kind, ptr(out_rgb),
-                                            ptr(out_depth) if (kind and out_depth is not None) else None, ptr(out_rgbd),
-                                            n, h, w, _stream()),
-          "hn_ingest_u8bgr_u16mm")
+    args = (bgr_u8.data_ptr(), depth.data_ptr() if kind else None, kind, ptr(out_rgb),
+            ptr(out_depth) if (kind and out_depth is not None) else None, ptr(out_rgbd), n, h, w)
+    if flip_w:
+        check(_lib.load().hn_ingest_u8bgr_u16mm_flip(*args, 1, _stream()), "hn_ingest_u8bgr_u16mm_flip")
+    else:
+        check(_lib.load().hn_ingest_u8bgr_u16mm(*args, _stream()), "hn_ingest_u8bgr_u16mm")
     return out_rgb, (out_depth if kind else None), out_rgbd
+
+
+def flip_w(x, other=None, out=None, out_other=None):
+    """x [..., W] fp32 mirrored along its last axis (x.flip(-1), bit for bit) in ONE launch (hn_flip_w_f32) -- and `other`
+    (same W) with it in the same launch: the frames and the depth map of a `left` live step fed with fp32 tensors.  Returns
+    out, or (out, out_other) when `other` is given.  Not in place."""
+    _req(x, name="x")
+    w = x.shape[-1]
+    if out is None:
+        out = torch.empty_like(x)
+    _req(out, name="out")
+    if out.shape != x.shape or out.data_ptr() == x.data_ptr():
+        raise ValueError("out must have x's shape and its own memory")
+    rows_b = 0
+    if other is not None:
+        _req(other, name="other")
+        if other.shape[-1] != w:
+            raise ValueError("other must have x's width")
+        if out_other is None:
+            out_other = torch.empty_like(other)
+        _req(out_other, name="out_other")
+        if out_other.shape != other.shape or out_other.data_ptr() == other.data_ptr():
+            raise ValueError("out_other must have other's shape and its own memory")
+        rows_b = other.numel() // w
+    if x.numel():
+        check(_lib.load().hn_flip_w_f32(ptr(x), ptr(out), x.numel() // w, ptr(other) if rows_b else None,
+                                        ptr(out_other) if rows_b else None, rows_b, w, _stream()), "hn_flip_w_f32")
+    return out if other is None else (out, out_other)
 
 
 def fcos_preprocess(images, oh, ow, ph, pw, mean, std, out=None):
@@ -1239,11 +1272,15 @@ def check_max_hands(max_hands) -> int:
 
 
 def crop_resize_hands(det: Detections, hand_label, depth, max_hands, out_size=176, cpad=4, crop_box=None, has_hand=None,
-                      score=None, det_index=None, crops=None, reorder_bgr=False):
+                      score=None, det_index=None, crops=None, reorder_bgr=False, handed=False, left_side=0, side=None,
+                      mirror=None):
     """crop_resize for the first max_hands hand detections of each frame: slot k of frame i is the k-th detection with label
     hand_label in frame i's score-ordered list, padded and cut as crop_resize cuts the first.  -> (crop_box [N,K,4] int64,
     has_hand [N,K] int32, score [N,K] fp32, det_index [N,K] int32 (-1: empty slot), crops [N*K,out,out,cpad] NHWC).
-    An empty slot (no such detection, or an empty padded slice) has zeros everywhere and still uses up its rank."""
+    An empty slot (no such detection, or an empty padded slice) has zeros everywhere and still uses up its rank.
+    handed: the slots' handedness in the same two launches (hn_crop_resize_hands_sided) -- two more results, side [N,K] int32
+    (det.sides of the slot's detection, -1 for an empty slot) and mirror [N,K] int32 (1 for a filled slot whose side is
+    left_side); the crop of a mirror slot is the plain crop flipped along its width, everything else is unchanged."""
     k = check_max_hands(max_hands)
     _req(depth, name="depth")
     n, c, h, w = depth.shape
@@ -1261,6 +1298,20 @@ def crop_resize_hands(det: Detections, hand_label, depth, max_hands, out_size=17
         det_index = torch.empty((n, k), device=dev, dtype=torch.int32)
     if crops is None:
         crops = torch.empty((n * k, out_size, out_size, cpad), device=dev, dtype=torch.float32)
+    if handed:
+        if side is None:
+            side = torch.empty((n, k), device=dev, dtype=torch.int32)
+        if mirror is None:
+            mirror = torch.empty((n, k), device=dev, dtype=torch.int32)
+        _req(side, torch.int32, "side"); _req(mirror, torch.int32, "mirror"); _req(det.sides, torch.int32, "det.sides")
+        if side.numel() != n * k or mirror.numel() != n * k:
+            raise ValueError("side and mirror must hold one value per slot")
+        check(_lib.load().hn_crop_resize_hands_sided(ptr(det.boxes), ptr(det.scores), ptr(det.labels), ptr(det.sides),
+                                                     ptr(det.count), cap, int(hand_label), int(left_side), k, ptr(depth), n, c,
+                                                     1 if reorder_bgr else 0, h, w, out_size, cpad, ptr(crop_box), ptr(has_hand),
+                                                     ptr(score), ptr(det_index), ptr(side), ptr(mirror), ptr(crops), _stream()),
+              "hn_crop_resize_hands_sided")
+        return crop_box, has_hand, score, det_index, crops, side, mirror
     check(_lib.load().hn_crop_resize_hands(ptr(det.boxes), ptr(det.scores), ptr(det.labels), ptr(det.count), cap,
                                            int(hand_label), k, ptr(depth), n, c, 1 if reorder_bgr else 0, h, w, out_size, cpad,
                                            ptr(crop_box), ptr(has_hand), ptr(score), ptr(det_index), ptr(crops), _stream()),
@@ -1303,7 +1354,9 @@ def a2j_aggregate(cls, reg, dep, joints=21, stride=16, valid=None, out=None, con
     convert: optional dict -- convert_joints + uvd2xyz in the SAME launch (hn_a2j_aggregate_convert_f32):
       crop_box [K,4] int64 (the boxes the crops were cut with), paras = (fx, fy, cx, cy) or None, crop = 176,
       clamp_keypoints / clamp_box = (H, W): the live caller's clamps (ros_demo.py:279-283),
-      image_uvd / xyz_mm: preallocated outputs (optional).
+      image_uvd / xyz_mm: preallocated outputs (optional),
+      mirror [K] int32: rows whose crop was cut mirrored (crop_resize_hands(handed=True)) -- u = crop - u before anything
+      else sees the value (hn_a2j_aggregate_convert_mirror_f32).
     Then returns (crop_uvd, image_uvd [K,J,3], xyz_mm [K,J,3] or None), bit-identical to convert_joints() on crop_uvd."""
     lib = _lib.load()
     _req(cls, name="cls"); _req(reg, name="reg"); _req(dep, name="dep")
@@ -1341,6 +1394,15 @@ def a2j_aggregate(cls, reg, dep, joints=21, stride=16, valid=None, out=None, con
             opts = _lib.ConvertOpts(1 if convert.get("clamp_keypoints") else 0, int(cb[0]) if cb else 0, int(cb[1]) if cb else 0, 0,
                                     ptr(sbox), ptr(sparas))
         crop = float(convert.get("crop", 176))
+        mirror = convert.get("mirror")
+        if mirror is not None:
+            if _req(mirror, torch.int32, "mirror").numel() != k:
+                raise ValueError("mirror must hold one flag per crop")
+            check(lib.hn_a2j_aggregate_convert_mirror_f32(ptr(cls), ptr(reg), ptr(dep), ptr(valid), ptr(mirror), k, fh, fw, joints,
+                                                          stride, ptr(box), crop, crop, pp,
+                                                          C.byref(opts) if opts is not None else None, ptr(out), ptr(img),
+                                                          ptr(xyz), _stream()), "hn_a2j_aggregate_convert_mirror_f32")
+            return out, img, xyz
         check(lib.hn_a2j_aggregate_convert_f32(ptr(cls), ptr(reg), ptr(dep), ptr(valid), k, fh, fw, joints, stride, ptr(box),
                                                crop, crop, pp, C.byref(opts) if opts is not None else None, ptr(out), ptr(img),
                                                ptr(xyz), _stream()), "hn_a2j_aggregate_convert_f32")
@@ -1365,11 +1427,13 @@ def joints2d_standardize(image_uvd, valid=None, out=None):
     return out
 
 
-def lifter_input_gated(image_uvd, valid=None, out=None, lifted=None):
+def lifter_input_gated(image_uvd, valid=None, out=None, lifted=None, mirror=None):
     """joints2d_standardize with the live caller's skip rule (ros_demo.py:288-300): image (u,v,d) [N,J,3] -> (the lifter's
     input [N,J,2], lifted [N] int32).  A row is lifted (1, and joints2d_standardize's row bit for bit) iff valid is None or 1
     there, its (u,v) are finite and process_bbox(get_bbox(uv)) is not None (coord_utils.py:21-49, fp32 as numpy evaluates
-    it); every other row is zeros with lifted 0 -- so a degenerate hand never reaches the lifter as inf / NaN."""
+    it); every other row is zeros with lifted 0 -- so a degenerate hand never reaches the lifter as inf / NaN.
+    mirror [N] int32: a lifted row with mirror != 0 has column 0 negated (hn_lifter_input_gated_mirror_f32) -- the
+    standardisation of the joints mirrored in x; the gate sees the plain joints."""
     _req(image_uvd, name="image_uvd")
     n, j, _ = image_uvd.shape
     if out is None:
@@ -1383,6 +1447,12 @@ def lifter_input_gated(image_uvd, valid=None, out=None, lifted=None):
         _req(valid, torch.int32, "valid")
         if valid.numel() != n:
             raise ValueError("valid must hold one flag per row")
+    if mirror is not None:
+        if _req(mirror, torch.int32, "mirror").numel() != n:
+            raise ValueError("mirror must hold one flag per row")
+        check(_lib.load().hn_lifter_input_gated_mirror_f32(ptr(image_uvd), ptr(valid), ptr(mirror), n, j, ptr(out), ptr(lifted),
+                                                           _stream()), "hn_lifter_input_gated_mirror_f32")
+        return out, lifted
     check(_lib.load().hn_lifter_input_gated_f32(ptr(image_uvd), ptr(valid), n, j, ptr(out), ptr(lifted), _stream()),
           "hn_lifter_input_gated_f32")
     return out, lifted
@@ -1682,16 +1752,29 @@ def linear_rows(x, cw, scale=None, shift=None, residual=None, relu=False, n_out=
     return y
 
 
-def mesh_finish(mesh, perm, xyz_mm, valid=None, out=None):
+def mesh_finish(mesh, perm, xyz_mm, valid=None, out=None, mirror=None):
     """mesh [N,V0,3], perm int64 [V] (graph_perm_reverse[:V]), xyz_mm [N,J,3] -> [N,V,3] = ((mesh[:, perm] * 1000 + xyz_mm[:, 0])
-    / 1000) * (1, -1, -1): out['mesh'] of ros_demo.py:162,332-337, bit-identical to the numpy float32 arithmetic."""
-    _req(mesh, name="mesh"); _req(perm, torch.int64, "perm"); _req(xyz_mm, name="xyz_mm")
+    / 1000) * (1, -1, -1): out['mesh'] of ros_demo.py:162,332-337, bit-identical to the numpy float32 arithmetic.
+    mirror [N] int32 (hn_mesh_finish_mirror_f32): rows with mirror != 0 are meshes of mirrored hands -- the x of their raw
+    vertices is negated before the arithmetic; then perm and xyz_mm may both be None: the raw vertices, x negated where
+    mirrored, zero rows where valid != 1."""
+    _req(mesh, name="mesh")
     n, v0, _ = mesh.shape
-    v = perm.shape[0]
+    if mirror is not None and perm is None and xyz_mm is None:
+        v, joints = v0, 1
+    else:
+        _req(perm, torch.int64, "perm"); _req(xyz_mm, name="xyz_mm")
+        v, joints = perm.shape[0], xyz_mm.shape[1]
     if out is None:
         out = torch.empty((n, v, 3), device=mesh.device, dtype=torch.float32)
     if valid is not None:
         _req(valid, torch.int32, "valid")
+    if mirror is not None:
+        if _req(mirror, torch.int32, "mirror").numel() != n:
+            raise ValueError("mirror must hold one flag per row")
+        check(_lib.load().hn_mesh_finish_mirror_f32(ptr(mesh), ptr(perm), ptr(xyz_mm), ptr(valid), ptr(mirror), n, v0, v, joints,
+                                                    ptr(out), _stream()), "hn_mesh_finish_mirror_f32")
+        return out
     check(_lib.load().hn_mesh_finish_f32(ptr(mesh), ptr(perm), ptr(xyz_mm), ptr(valid), n, v0, v, xyz_mm.shape[1], ptr(out), _stream()),
           "hn_mesh_finish_f32")
     return out

@@ -58,6 +58,8 @@ class HandsOutput:
     host_record: torch.Tensor = None   # to_host steps: pinned uint8; rows 0..N*K-1 = one record per slot, row N*K = the range
     #                                    words, then score [N*K] fp32 and det_index [N*K] int32 (read_hands_tail)
     tail: object = None                # what forward_hands' `_tail` callable returned (the multi-hand live step, hn_amd/live.py)
+    side: torch.Tensor = None          # handed steps: [N,K] int32 device, detections.sides of the slot's detection (-1 when empty)
+    mirror: torch.Tensor = None        # handed steps: [N,K] int32 device, 1 where the slot went through A2J mirrored (a left hand)
 
 
 RECORD_BYTES = 296      # hn_amd.dist's per-frame record (box 32 + flags 8 + 21 x 3 fp32 keypoints, padded to 8)
@@ -91,22 +93,27 @@ def read_host_record(rec: torch.Tensor, n: int, joints: int = 21, extras: bool =
     return kp, has, box, words, more
 
 
-def hands_record_rows(slots: int, rec_bytes: int) -> int:
-    """Rows of a forward_hands record: one per slot, the range-word row, then the slots' scores and detection ranks."""
-    return slots + 1 + (8 * slots + rec_bytes - 1) // rec_bytes
+def hands_record_rows(slots: int, rec_bytes: int, handed: bool = False) -> int:
+    """Rows of a forward_hands record: one per slot, the range-word row, then the slots' scores and detection ranks -- and,
+    for a handed step, their sides behind those."""
+    return slots + 1 + ((12 if handed else 8) * slots + rec_bytes - 1) // rec_bytes
 
 
-def _hands_tail(rec: torch.Tensor, slots: int):
-    """(score [slots] fp32, det_index [slots] int32) views of a forward_hands record (device or host)."""
+def _hands_tail(rec: torch.Tensor, slots: int, handed: bool = False):
+    """(score [slots] fp32, det_index [slots] int32) views of a forward_hands record (device or host); handed: + side [slots]
+    int32, behind them."""
     flat = rec.view(-1)
     base = (slots + 1) * rec.shape[1]
-    return (flat[base:base + 4 * slots].view(torch.float32), flat[base + 4 * slots:base + 8 * slots].view(torch.int32))
+    tail = (flat[base:base + 4 * slots].view(torch.float32), flat[base + 4 * slots:base + 8 * slots].view(torch.int32))
+    if handed:
+        tail += (flat[base + 8 * slots:base + 12 * slots].view(torch.int32),)
+    return tail
 
 
-def read_hands_tail(rec: torch.Tensor, slots: int):
-    """A synchronised forward_hands host_record -> (score [slots] fp32, det_index [slots] int32), fresh CPU tensors."""
-    score, index = _hands_tail(rec, slots)
-    return score.clone(), index.clone()
+def read_hands_tail(rec: torch.Tensor, slots: int, handed: bool = False):
+    """A synchronised forward_hands host_record -> (score [slots] fp32, det_index [slots] int32), fresh CPU tensors; handed
+    (the record of a handed step): + side [slots] int32."""
+    return tuple(t.clone() for t in _hands_tail(rec, slots, handed))
 
 
 def range_message(bits: int) -> str:
@@ -230,18 +237,27 @@ class HandNetEngine:
 
     @ops.device_guarded
     def forward_hands(self, images, depth: torch.Tensor, max_hands: int = 2, to_host: bool = False, _record=None,
-                      _tail=None) -> HandsOutput:
+                      _tail=None, handed: bool = False, left_side: int = 0, _side=None) -> HandsOutput:
         """forward_device for up to max_hands (1..16) hands per frame: slot k of frame i is the k-th hand-label detection of
         frame i in the detector's score order, cropped as forward_device crops the first (max_hands = 1 IS forward_device's
         crop); A2J runs on the N * max_hands crops with the slots' has_hand mask (capturable), or -- eager, when the previous
         step filled fewer than half of its slots -- on the filled slots only.  to_host: one record row per slot, the range
         words, then the scores and detection ranks, in ONE device -> host copy (HandsOutput.host_record; read_host_record /
         read_hands_tail after a sync).  _tail(keypoints, image_uvd, xyz_mm, has_hand), all per slot ([N*K,...]): as for
-        forward_device; its return value is HandsOutput.tail."""
-        return self._step(images, depth, ops.check_max_hands(max_hands), to_host, _record, _tail)
+        forward_device; its return value is HandsOutput.tail.
+        handed: per-slot handedness.  HandsOutput.side = detections.sides of the slot's detection (-1: empty slot); a filled
+        slot whose side equals left_side (HandsOutput.mirror) goes through the right-handed pose network MIRRORED -- its crop
+        is flipped along the width and the aggregation writes u = 176 - u -- so keypoints, image_uvd and xyz_mm are in the
+        frame's own coordinates; every other slot is the step without `handed`, bit for bit, and no launch is added.
+        left_side = 0 is an ASSUMPTION (the detector's side targets are box_info[:, 1] of its training set; the 100DOH
+        convention 0 = left is not stated by the reference, which never reads `sides`): check it on your checkpoint.  to_host
+        records carry the sides behind the scores and ranks (read_hands_tail(..., handed=True))."""
+        return self._step(images, depth, ops.check_max_hands(max_hands), to_host, _record, _tail,
+                          (int(left_side), _side) if handed else None)
 
-    def _step(self, images, depth, hands, to_host, _record, _tail):
-        """The body of forward_device (hands None: the top-1 crop, HandNetOutput) and forward_hands (hands = K)."""
+    def _step(self, images, depth, hands, to_host, _record, _tail, handed=None):
+        """The body of forward_device (hands None: the top-1 crop, HandNetOutput) and forward_hands (hands = K; handed =
+        (left_side, where the sides go or None): the handed step)."""
         want_c = 4 if self.a2j.rgbd else 1
         if depth.dim() != 4 or depth.shape[1] != want_c or depth.shape[0] != len(images):
             raise ValueError(f"depth_images must be [N,{want_c},H,W] matching images"
@@ -254,7 +270,7 @@ class HandNetEngine:
         record = None
         if hands is not None and (to_host or _record is not None):
             # (fetched first: the crop stage writes the scores and ranks straight into the record)
-            record = _record if _record is not None else self._host_record_buffers(n, hands)
+            record = _record if _record is not None else self._host_record_buffers(n, hands, handed is not None)
         # (the scope is this host thread's: another engine on another thread keeps its own switch and block)
         with ops.range_scope(self._range_block, on=noting):
             det, cand = self.fcos.detect(images)
@@ -263,19 +279,43 @@ class HandNetEngine:
                                                             reorder_bgr=self.a2j.rgbd)
                 box_rows, has_rows = crop_box, has_hand
             else:
-                score, det_index = _hands_tail(record[1], rows) if record is not None else (None, None)
-                crop_box, has_hand, score, det_index, crops = ops.crop_resize_hands(
-                    det, self.num_classes - 1, depth.float().contiguous(), hands, CROP, 4, score=score, det_index=det_index,
-                    reorder_bgr=self.a2j.rgbd)
+                side = mirror = None
+                if handed is None:
+                    score, det_index = _hands_tail(record[1], rows) if record is not None else (None, None)
+                    crop_box, has_hand, score, det_index, crops = ops.crop_resize_hands(
+                        det, self.num_classes - 1, depth.float().contiguous(), hands, CROP, 4, score=score, det_index=det_index,
+                        reorder_bgr=self.a2j.rgbd)
+                else:
+                    # (the sides go where the caller wants them -- the live step's buffer -- else behind the scores and ranks
+                    # of this step's own record)
+                    score, det_index, side = None, None, handed[1]
+                    if record is not None:
+                        views = _hands_tail(record[1], rows, handed=side is None)
+                        score, det_index = views[:2]
+                        side = views[2] if side is None else side
+                    crop_box, has_hand, score, det_index, crops, side, mirror = ops.crop_resize_hands(
+                        det, self.num_classes - 1, depth.float().contiguous(), hands, CROP, 4, score=score, det_index=det_index,
+                        reorder_bgr=self.a2j.rgbd, handed=True, left_side=handed[0], side=side)
+                    side, mirror = side.view(n, hands), mirror.view(n, hands)
                 box_rows, has_rows = crop_box.view(rows, 4), has_hand.view(rows)
             conv = self._convert_spec(box_rows, tuple(depth.shape[-2:]))
+            unconverted = hands is not None and mirror is not None and conv is None
+            if unconverted:     # (the un-mirror is part of the converting aggregation: its image (u,v,d) is not handed out)
+                conv = {"crop_box": box_rows, "paras": None, "crop": CROP}
+            if hands is not None and mirror is not None:
+                conv["mirror"] = mirror.view(rows)
             kp = self._a2j_sparse(crops, has_rows, conv) if self._use_compaction(rows) else None
             if kp is None:
                 kp = self.a2j.forward_nhwc(crops, valid=has_rows, convert=conv)
             img_uvd = xyz = None
             if conv is not None:
                 kp, img_uvd, xyz = kp
-            tail = _tail(kp, img_uvd, xyz, has_rows) if _tail is not None else None
+                if unconverted:
+                    img_uvd = None
+            if _tail is None:
+                tail = None
+            else:
+                tail = _tail(kp, img_uvd, xyz, has_rows) if handed is None else _tail(kp, img_uvd, xyz, has_rows, mirror.view(rows))
             host_rec = None
             if to_host or _record is not None:
                 host_rec, dev_rec = record if record is not None else (
@@ -297,7 +337,7 @@ class HandNetEngine:
         per_slot = (n, hands) + tuple(kp.shape[1:])
         return HandsOutput(kp.view(per_slot), crops, crop_box, has_hand, score, det_index, det, cand, flags,
                            None if img_uvd is None else img_uvd.view(per_slot), None if xyz is None else xyz.view(per_slot),
-                           host_rec, tail)
+                           host_rec, tail, side, mirror)
 
     # -------------------------------------------------------------------------------
     # sparse streams: A2J on the frames with a hand only
@@ -335,6 +375,8 @@ class HandNetEngine:
         if k:
             v = has_hand[idx].contiguous()
             sub = None if conv is None else dict(conv, crop_box=conv["crop_box"][idx].contiguous())
+            if sub is not None and sub.get("mirror") is not None:
+                sub["mirror"] = sub["mirror"][idx].contiguous()
             res = self.a2j.forward_nhwc(crops[idx].contiguous(), valid=v, convert=sub)
             for o, r in zip(outs, res if conv is not None else (res,)):
                 o[idx] = r
@@ -346,19 +388,20 @@ class HandNetEngine:
     # -------------------------------------------------------------------------------
     # hipGraph replay for a fixed batch shape (launch-bound at small batch)
     # -------------------------------------------------------------------------------
-    def _new_record(self, n, hands=None):
-        """(pinned host, device) record buffers of a step over n frames (hands: forward_hands with that many slots per frame)."""
+    def _new_record(self, n, hands=None, handed=False):
+        """(pinned host, device) record buffers of a step over n frames (hands: forward_hands with that many slots per frame;
+        handed: with the slots' sides)."""
         rb = record_bytes(self._fields())
-        rows = n + 1 if hands is None else hands_record_rows(n * hands, rb)
+        rows = n + 1 if hands is None else hands_record_rows(n * hands, rb, handed)
         return (torch.zeros((rows, rb), dtype=torch.uint8, pin_memory=True),
                 torch.zeros((rows, rb), dtype=torch.uint8, device=self.device))
 
-    def _host_record_buffers(self, n, hands=None):
-        key = n if hands is None else ("hands", n, hands)
+    def _host_record_buffers(self, n, hands=None, handed=False):
+        key = n if hands is None else ("hands", n, hands) + (("handed",) if handed else ())
         buf = self._host_records.get(key)
         if buf is None:
             with torch.inference_mode(False):   # ordinary tensors: written in place by later calls in any mode
-                buf = self._host_records[key] = self._new_record(n, hands)
+                buf = self._host_records[key] = self._new_record(n, hands, handed)
         return buf
 
     @ops.device_guarded
@@ -372,25 +415,30 @@ class HandNetEngine:
 
     @ops.device_guarded
     def graphed_hands(self, images: torch.Tensor, depth: torch.Tensor, max_hands: int = 2, to_host: bool = False,
-                      limit: int | None = None):
-        """graphed() for forward_hands(images, depth, max_hands, to_host): (run, static_images, static_depth, static
-        HandsOutput).  Its captures are keyed apart from graphed()'s and share their eviction order (limit)."""
+                      limit: int | None = None, handed: bool = False, left_side: int = 0):
+        """graphed() for forward_hands(images, depth, max_hands, to_host, handed=, left_side=): (run, static_images,
+        static_depth, static HandsOutput).  Its captures are keyed apart from graphed()'s (a handed step apart from a plain one)
+        and share their eviction order (limit)."""
         k = ops.check_max_hands(max_hands)
-        return self._graphed(self._hands_key(images.shape, depth.shape, k, to_host), images, depth, to_host, limit, k)
+        handed = (int(left_side), None) if handed else None
+        return self._graphed(self._hands_key(images.shape, depth.shape, k, to_host, handed), images, depth, to_host, limit, k,
+                             handed)
 
     @staticmethod
-    def _hands_key(image_shape, depth_shape, max_hands, to_host):
-        return ("hands", tuple(image_shape), tuple(depth_shape), int(max_hands), bool(to_host))
+    def _hands_key(image_shape, depth_shape, max_hands, to_host, handed=None):
+        key = ("hands", tuple(image_shape), tuple(depth_shape), int(max_hands), bool(to_host))
+        return key if handed is None else key + ("handed", handed[0])
 
-    def has_graph_hands(self, image_shape, depth_shape, max_hands, to_host: bool = False) -> bool:
-        return self._hands_key(image_shape, depth_shape, max_hands, to_host) in self._graphs
+    def has_graph_hands(self, image_shape, depth_shape, max_hands, to_host: bool = False, handed: bool = False,
+                        left_side: int = 0) -> bool:
+        return self._hands_key(image_shape, depth_shape, max_hands, to_host, (int(left_side), None) if handed else None) in self._graphs
 
-    def _graphed(self, key, images, depth, to_host, limit, hands):
+    def _graphed(self, key, images, depth, to_host, limit, hands, handed=None):
         if key not in self._graphs:
             while limit is not None and len(self._graphs) >= max(1, limit):
                 self._graphs.popitem(last=False)
             with torch.inference_mode(False), torch.no_grad():
-                return self._capture(key, images, depth, to_host, hands)
+                return self._capture(key, images, depth, to_host, hands, handed)
         self._graphs.move_to_end(key)
         g, s_img, s_dep, out = self._graphs[key]
         return g.replay, s_img, s_dep, out
@@ -485,30 +533,32 @@ class HandNetEngine:
             hit = self.captured((n, 3, h, w), dshape, to_host)
         return self._ingest_replay(hit, bgr, dep, staged)
 
-    def _ingest_replay(self, hit, bgr, dep, staged):
+    def _ingest_replay(self, hit, bgr, dep, staged, flip_w=False):
         """Ingest into the static inputs of a captured step (this engine's, or a live step's around it) and replay it.  The
-        staging event is recorded ONCE, behind the last ingest_raw of the call that reads the staging buffers."""
+        staging event is recorded ONCE, behind the last ingest_raw of the call that reads the staging buffers.  flip_w: the
+        live step's `left` mode, done by the ingest kernel."""
         g, s_img, s_dep, out = hit
         if self.a2j.rgbd:     # (the 4-channel tensor only: no separate depth map is written or allocated)
-            ops.ingest_raw(bgr, dep, out_rgb=s_img, out_rgbd=s_dep, want_depth=False)
+            ops.ingest_raw(bgr, dep, out_rgb=s_img, out_rgbd=s_dep, want_depth=False, flip_w=flip_w)
         else:
-            ops.ingest_raw(bgr, dep, out_rgb=s_img, out_depth=s_dep)
+            ops.ingest_raw(bgr, dep, out_rgb=s_img, out_depth=s_dep, flip_w=flip_w)
         self._staged_done(staged)
         g.replay()
         return out
 
-    def _capture(self, key, images, depth, to_host=False, hands=None):
+    def _capture(self, key, images, depth, to_host=False, hands=None, handed=None):
         # static buffers are ordinary (non-inference) tensors so that later copy_() works in any mode
         s_img, s_dep = torch.empty_like(images), torch.empty_like(depth)
         s_img.copy_(images)
         s_dep.copy_(depth)
         # the capture's own record buffers (addresses are baked into the graph)
-        record = self._new_record(images.shape[0], hands) if to_host else None
+        record = self._new_record(images.shape[0], hands, handed is not None) if to_host else None
 
         def step():
             if hands is None:
                 return self.forward_device(s_img, s_dep, _record=record)
-            return self.forward_hands(s_img, s_dep, hands, _record=record)
+            return self.forward_hands(s_img, s_dep, hands, _record=record, handed=handed is not None,
+                                      left_side=0 if handed is None else handed[0])
 
         g, out = ops.capture_step(step)
         self._graphs[key] = (g, s_img, s_dep, out)

@@ -33,7 +33,9 @@ extern "C" {
 #define HN_ERR_HIP 2
 
 /* ABI version; bumped whenever a struct below changes (functions added without touching a struct or an existing signature
- * keep it: hn_lifter_input_gated_f32 and hn_mesh_render_u8 came under 36). */
+ * keep it: hn_lifter_input_gated_f32 and hn_mesh_render_u8 came under 36, and so did the mirror / handedness entries
+ * hn_ingest_u8bgr_u16mm_flip, hn_flip_w_f32, hn_crop_resize_hands_sided, hn_a2j_aggregate_convert_mirror_f32,
+ * hn_lifter_input_gated_mirror_f32 and hn_mesh_finish_mirror_f32). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -383,6 +385,17 @@ int hn_conv3x3_thin_affine_f16x3_levels(const hn_thin_levels* lv, const hn_thin_
  * ------------------------------------------------------------------------------------ */
 int hn_ingest_u8bgr_u16mm(const uint8_t* bgr, const void* depth, int depth_kind, float* rgb, float* depth_m,
                           float* rgbd, int n, int h, int w, void* stream);
+/* The same with the caller's `left` mode (ros_demo.py:259-262: cv2.flip(., 1) of the colour frame and of the depth map before
+ * anything else): flip_w != 0 -- output column x is source column w - 1 - x in every output, in the same one launch (a lane
+ * reads the mirrored twelve bytes and swaps its four pixels in registers; w % 4 != 0 takes the per-pixel path).  flip_w == 0
+ * is hn_ingest_u8bgr_u16mm.  Added under ABI 36: a new function only. */
+int hn_ingest_u8bgr_u16mm_flip(const uint8_t* bgr, const void* depth, int depth_kind, float* rgb, float* depth_m,
+                               float* rgbd, int n, int h, int w, int flip_w, void* stream);
+/* The mirror for fp32 feeds, ONE launch over two tensors of rows of w floats: a_out[r][x] = a[r][w - 1 - x] for rows_a rows,
+ * and the same for b -> b_out (rows_b rows; b = b_out = NULL and rows_b = 0: one tensor).  Not in place.  16-byte loads and
+ * stores, reversed in registers, when w % 4 == 0 and the pointers are 16-byte aligned.  Added under ABI 36. */
+int hn_flip_w_f32(const float* a, float* a_out, int64_t rows_a, const float* b, float* b_out, int64_t rows_b, int w,
+                  void* stream);
 
 /* ------------------------------------------------------------------------------------
  * FCOS pre-processing: normalize + bilinear resize (align_corners=False, scale =
@@ -520,6 +533,18 @@ int hn_crop_resize_hands(const float* det_boxes, const float* det_scores, const 
                          const int32_t* det_count, int cap, int hand_label, int max_hands, const float* depth, int n,
                          int in_ch, int reorder_bgr, int h, int w, int out, int cpad, int64_t* crop_box, int32_t* has_hand,
                          float* score, int32_t* det_index, float* crops, void* stream);
+/* hn_crop_resize_hands with the slots' handedness, in the same two launches (added under ABI 36: a new function only).
+ * det_sides [n][cap] int32 as hn_fcos_nms writes it (the detector's hand_lr head); left_side = the value that means "left".
+ *   side   [n][max_hands] int32: det_sides of the slot's detection, -1 for an empty slot
+ *   mirror [n][max_hands] int32: 1 for a filled slot with side == left_side, else 0
+ * The crop of a slot with mirror == 1 is cut mirrored along its width: its pixel (oy, ox) is the plain crop's pixel
+ * (oy, out - 1 - ox) on every channel (a left hand on its way through a right-handed pose network); every other slot, and
+ * every other output, is hn_crop_resize_hands' bit for bit. */
+int hn_crop_resize_hands_sided(const float* det_boxes, const float* det_scores, const int32_t* det_labels,
+                               const int32_t* det_sides, const int32_t* det_count, int cap, int hand_label, int left_side,
+                               int max_hands, const float* depth, int n, int in_ch, int reorder_bgr, int h, int w, int out,
+                               int cpad, int64_t* crop_box, int32_t* has_hand, float* score, int32_t* det_index, int32_t* side,
+                               int32_t* mirror, float* crops, void* stream);
 
 /* fp32 NHWC(4) image [n][h][w][4] -> the stem image of hn_conv_stem_f16x3 / hn_conv_stem_pool_f16x3 (two fp16 planes hi, lo of
  * [n][h + 2*border][w + 2*border][4], zero border): the A2J crops on their way to the split-precision stem
@@ -593,6 +618,15 @@ int hn_a2j_aggregate_convert_f32(const float* cls, const float* reg, const float
                                  int fw, int joints, int stride, const int64_t* crop_box, float crop_w, float crop_h,
                                  const float* paras /* host, 4 floats, or NULL */, const hn_convert_opts* opts /* host or NULL */,
                                  float* out_uvd, float* out_image_uvd, float* out_xyz_mm, void* stream);
+/* The same for crops of which some were cut mirrored (hn_crop_resize_hands_sided): mirror [k] int32 on the device; for a row
+ * with mirror != 0 the thread that holds a joint replaces u by crop_w - u (one fp32 subtraction) before it writes out_uvd, so
+ * out_uvd, the clamps and both conversions are in plain-crop coordinates.  Rows with mirror == 0: hn_a2j_aggregate_convert_f32
+ * bit for bit.  Added under ABI 36: hn_convert_opts is unchanged. */
+int hn_a2j_aggregate_convert_mirror_f32(const float* cls, const float* reg, const float* dep, const int32_t* valid,
+                                        const int32_t* mirror, int k, int fh, int fw, int joints, int stride,
+                                        const int64_t* crop_box, float crop_w, float crop_h, const float* paras,
+                                        const hn_convert_opts* opts, float* out_uvd, float* out_image_uvd, float* out_xyz_mm,
+                                        void* stream);
 
 /* The lifter's input from a step's image-(u,v) joints (the live caller's glue between the path and Pose2Mesh,
  * ros_demo.py:148-157: get_bbox -> process_bbox -> j2d_processing (rot 0, no flip) -> / input_shape -> (x - mean) / std):
@@ -608,6 +642,11 @@ int hn_joints2d_standardize_f32(const float* image_uvd, const int32_t* valid /* 
  * hn_amd.live.LiveHandsEngine).  Added under ABI 36: a new function only, no struct or existing signature changed. */
 int hn_lifter_input_gated_f32(const float* image_uvd /* [n][joints][3] */, const int32_t* valid /* or NULL */, int n,
                               int joints, float* out /* [n][joints][2] */, int32_t* lifted /* [n] */, void* stream);
+/* The same for hands that went through the pose network mirrored: the gate is evaluated on image_uvd as it stands (plain
+ * image joints); a LIFTED row with mirror[i] != 0 (device int32 [n]) has column 0 of its standardised row negated -- exactly
+ * the standardisation of the joints mirrored in x (the mean negates, the std does not change).  Added under ABI 36. */
+int hn_lifter_input_gated_mirror_f32(const float* image_uvd, const int32_t* valid /* or NULL */, const int32_t* mirror, int n,
+                                     int joints, float* out, int32_t* lifted, void* stream);
 
 /* Per-frame result records for the N > 1 all-gather (ONE collective of fixed-size records per step).
  * Record layout (rec_bytes >= 40 + 12*joints, multiple of 8): bytes 0..31 crop box 4 x int64, 32..35 has_hand,
@@ -675,6 +714,13 @@ int hn_pad_split_rows_f32(const float* x, int64_t rows, int f, int cpad, void* o
  * rounding per operation (bit-identical).  mesh [n][v0][3], xyz_mm [n][joints][3], out [n][v][3]; rows with valid != 1 are zeros. */
 int hn_mesh_finish_f32(const float* mesh, const int64_t* perm, const float* xyz_mm, const int32_t* valid /* or NULL */, int n,
                        int v0, int v, int joints, float* out, void* stream);
+/* The same for meshes the lifter made of mirrored hands: for rows with mirror[i] != 0 (device int32 [n]) the x of the raw
+ * vertex is negated before the arithmetic, ((-x) * 1000 + root_x) / 1000.  perm and xyz_mm may both be NULL (then v == v0):
+ * no permutation and no camera offset -- out = the raw vertices, x negated where mirrored, zero rows where valid != 1.
+ * Added under ABI 36. */
+int hn_mesh_finish_mirror_f32(const float* mesh, const int64_t* perm /* or NULL */, const float* xyz_mm /* or NULL */,
+                              const int32_t* valid /* or NULL */, const int32_t* mirror, int n, int v0, int v, int joints,
+                              float* out, void* stream);
 /* The live caller's last call, render(out, paras, h, w, full_image, face) (ros_demo.py:86-116,329-337), without a graphics
  * pipeline: the meshes of s = n * k hand slots (slot i * k + j = hand j of frame i) rasterised over their frames, one depth
  * buffer per frame.  mesh [s][v][3] fp32 as hn_mesh_finish_f32 writes it (metres, y and z negated), faces [f][3] int32 vertex
