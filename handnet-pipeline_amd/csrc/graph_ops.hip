@@ -360,7 +360,7 @@ extern "C" int hn_graph_conv_cheby3_f16x3(const hn_graph_csr* L, const hn_graph_
   HN_CHECK_ARG(fin >= 4 && fin % 4 == 0 && fin <= 256, "Fin must be a multiple of 4 in [4, 256]");
   HN_CHECK_ARG(fout >= 1 && fout <= 16 * kGcWaves, "Fout must be in [1, 256]");
   HN_CHECK_ARG(up >= 1 && up <= 4 && (!xin || fi > 0), "bad residual / up-sampling arguments");
-  HN_CHECK_ARG(!out_split || fout % 32 == 0, "the S32 output needs Fout % 32 == 0");
+  HN_CHECK_ARG(!out_split || fout % 32 == 0, "the S32 output needs Fout %% 32 == 0");
   HN_CHECK_ARG((uintptr_t)x % 16 == 0 && (uintptr_t)w16 % 16 == 0, "unaligned operands");
   GraphConvParams p;
   p.l_ptr = L->indptr; p.l_idx = L->indices; p.l_val = L->values;
