@@ -18,7 +18,9 @@ crops + the dataset's float32 boxes + per-sample intrinsics -> A2J -> clip + con
 from __future__ import annotations
 
 import collections
-from dataclasses import dataclass
+import functools
+import math
+from dataclasses import dataclass, field
 
 import torch
 
@@ -46,50 +48,101 @@ def _final_mesh_perm(perm_reverse, lifter, device):
     return perm, int(perm.shape[0])
 
 
-def _read_type(name, fields, doc, **absent):
-    """A namedtuple whose absent images (overlay / box_label / pose_label) read as None class attributes."""
+POSE_LABEL = ops.LABEL_CROP                           # side of a pose_label image
+
+LiveViews = collections.namedtuple("LiveViews", "records side lifted mesh overlay box_label pose_label")
+
+
+@dataclass(frozen=True)
+class LiveLayout:
+    """Byte layout of a live step's one copy buffer, in this order: the records (one-hand step: a wide record per frame + the
+    range-word row; K-hand step: forward_hands' wide record unchanged -- a row per slot, the range-word row, the scores and
+    detection ranks: hands_record_rows), `side` int32 [slots] (handed steps: the detector's side per slot), `lifted` int32
+    [slots] (K-hand steps), the mesh fp32 [slots,V,3], the overlay uint8 [frames,h,w,3], box_label uint8 [frames,h,w,3] and
+    pose_label uint8 [slots,176,176,3] (each label image starts on a dword: the kernels store three dwords per four pixels).
+    slots = frames for the one-hand step (hands None), frames * hands for the K-hand step.  A part the step does not have takes
+    no bytes and its offset is None; every part in front of it stays where a step without the option has it."""
+    frames: int
+    hands: int                   # None: the one-hand step, else K
+    vertices: int
+    hw: tuple = None             # (h, w) of the frames; None: a step that draws nothing
+    overlay: bool = False
+    labels: bool = False
+    handed: bool = False
+    record_rows: int = field(init=False)
+    record_bytes: int = field(init=False)
+    side_at: int = field(init=False)
+    lifted_at: int = field(init=False)
+    mesh_at: int = field(init=False)
+    overlay_at: int = field(init=False)
+    box_label_at: int = field(init=False)
+    pose_label_at: int = field(init=False)
+    nbytes: int = field(init=False)
+
+    def __post_init__(self):
+        if ((self.overlay or self.labels) and self.hw is None) or (self.handed and self.hands is None):
+            raise ValueError("an overlay or label images need the frames' (h, w), and handed is a K-hand step's option")
+        s, rb = self.slots, record_bytes(3)
+        rows = self.frames + 1 if self.hands is None else hands_record_rows(s, rb)
+        image = None if self.hw is None else (self.frames, *self.hw, 3)
+        put = lambda name, value: object.__setattr__(self, name, value)
+        end, spans = 0, {}
+        for name, present, dtype, shape, align in (("records", True, torch.uint8, (rows, rb), 1),
+                                                   ("side", self.handed, torch.int32, (s,), 1),
+                                                   ("lifted", self.hands is not None, torch.int32, (s,), 1),
+                                                   ("mesh", True, torch.float32, (s, self.vertices, 3), 1),
+                                                   ("overlay", self.overlay, torch.uint8, image, 1),
+                                                   ("box_label", self.labels, torch.uint8, image, 4),
+                                                   ("pose_label", self.labels, torch.uint8, (s, POSE_LABEL, POSE_LABEL, 3), 4)):
+            start = None
+            if present:
+                start = (end + align - 1) // align * align
+                end = start + math.prod(shape) * dtype.itemsize
+                spans[name] = (start, end, dtype, shape)
+            if name != "records":
+                put(name + "_at", start)
+        put("record_rows", rows)
+        put("record_bytes", rb)
+        put("nbytes", end)
+        put("_spans", spans)         # (no field: what views() cuts, worked out once)
+
+    @property
+    def slots(self) -> int:
+        return self.frames * (self.hands or 1)
+
+    def views(self, buf) -> LiveViews:
+        """The parts of a step's flat uint8 buffer (the device buffer or its pinned copy), typed and shaped; None: not there."""
+        cut = {name: buf[a:b].view(dtype).view(shape) for name, (a, b, dtype, shape) in self._spans.items()}
+        return LiveViews(*(cut.get(name) for name in LiveViews._fields))
+
+
+@functools.lru_cache(maxsize=None)
+def _read_type(step: str, base: tuple, overlay: bool, labels: bool, side: bool):
+    """The namedtuple a step's read() returns: the base fields, then overlay, box_label + pose_label and side, each only when the
+    step has it; an absent image (overlay / box_label / pose_label) reads as a None class attribute.  (One class per
+    combination: call it with positional arguments only, the cache keys on them.)"""
+    has = dict(overlay=overlay, box_label=labels, pose_label=labels, side=side)
+    fields = base + tuple(f for f, on in has.items() if on)
+    name = step + "Overlay" * overlay + "Labels" * labels + "Sided" * side + "Read"
+    absent = {f: None for f, on in has.items() if not on and f != "side"}
+    doc = f"{step}Output.read(): {' '.join(base)}" + "".join(f" + {f}" for f in fields[len(base):]) + "."
     return type(name, (collections.namedtuple(name, fields),), dict(absent, __slots__=(), __doc__=doc))
 
 
-_NO_LABELS = dict(box_label=None, pose_label=None)
-_LABEL_FIELDS = ("box_label", "pose_label")
-LiveRead = _read_type("LiveRead", "keypoints has_hand crop_box words more mesh",
-                      "LiveOutput.read() of a step without images: unpacks as the six results it always had.",
-                      overlay=None, **_NO_LABELS)
-LiveOverlayRead = _read_type("LiveOverlayRead", LiveRead._fields + ("overlay",), "... of a step with faces=.", **_NO_LABELS)
-LiveLabelsRead = _read_type("LiveLabelsRead", LiveRead._fields + _LABEL_FIELDS, "... of a step with labels.", overlay=None)
-LiveOverlayLabelsRead = _read_type("LiveOverlayLabelsRead", LiveRead._fields + ("overlay",) + _LABEL_FIELDS,
-                                   "... of a step with faces= and labels.")
-
-POSE_LABEL = ops.LABEL_CROP                           # side of a pose_label image
-POSE_LABEL_BYTES = POSE_LABEL * POSE_LABEL * 3
+def _read(step, base, values, layout, v, per_slot=lambda t: t):
+    """read()'s result: `values` + fresh copies of the images and the sides the step has, as the step's read type."""
+    if layout.overlay:
+        values += (v.overlay.clone(),)
+    if layout.labels:
+        values += (v.box_label.clone(), per_slot(v.pose_label).clone())
+    if layout.handed:
+        values += (per_slot(v.side).clone(),)
+    return _read_type(step, base, layout.overlay, layout.labels, layout.handed)(*values)
 
 
-def _labels_behind(end: int, frames: int, slots: int, h: int, w: int, labels: bool):
-    """(offset of box_label, offset of pose_label, total bytes) of the two label images appended at byte `end` of a step's
-    buffer (each starts on a dword: the kernels store three dwords per four pixels); labels False: (end, end, end)."""
-    if not labels:
-        return end, end, end
-    box = (end + 3) // 4 * 4
-    pose = (box + frames * h * w * 3 + 3) // 4 * 4
-    return box, pose, pose + slots * POSE_LABEL_BYTES
-
-
-def live_overlay_layout(n: int, vertices: int, h: int, w: int):
-    """Byte layout of the one-hand live step's buffer with an overlay: (offset of the mesh, offset of the overlay (uint8
-    [n,h,w,3], appended: the records and the mesh stay where a step without one has them), total bytes)."""
-    mesh = (n + 1) * record_bytes(3)
-    overlay = mesh + n * vertices * 12
-    return mesh, overlay, overlay + n * h * w * 3
-
-
-def live_labels_layout(n: int, vertices: int, h: int, w: int, overlay: bool = False, labels: bool = True):
-    """Byte layout of the one-hand live step's buffer with the label images: (offset of the mesh, offset of the overlay, offset
-    of box_label (uint8 [n,h,w,3]), offset of pose_label (uint8 [n,176,176,3]), total bytes).  The images are appended behind
-    the mesh, and behind the overlay when there is one: without `labels` the first two offsets and the total are
-    live_overlay_layout's (h = w = 0 there for a step without an overlay)."""
-    mesh, oo, end = live_overlay_layout(n, vertices, h if overlay else 0, w if overlay else 0)
-    return (mesh, oo) + _labels_behind(end, n, n, h, w, labels)
+_LIVE_FIELDS = ("keypoints", "has_hand", "crop_box", "words", "more", "mesh")      # the six a plain step always had
+LiveRead, LiveOverlayRead, LiveLabelsRead, LiveOverlayLabelsRead = (
+    _read_type("Live", _LIVE_FIELDS, overlay, labels, False) for labels in (False, True) for overlay in (False, True))
 
 
 @dataclass
@@ -99,41 +152,32 @@ class LiveOutput:
     mesh: torch.Tensor           # [N,V0,3] Pose2Mesh vertices (finest level of the graph hierarchy, coarsening order), or --
     #                              with perm_reverse -- [N,V,3] = out['mesh'] of ros_demo.py:337 (camera frame, original order)
     pose3d: torch.Tensor         # [N,21,3] PoseNet's lifted joints (millimetre scale of the lifter's training set)
-    host: torch.Tensor           # pinned uint8: (N + 1) wide records, then the mesh as fp32 -- ONE copy, enqueued by the step
+    host: torch.Tensor           # pinned uint8 (`layout`): (N + 1) wide records, the mesh as fp32, the images -- ONE copy,
+    #                              enqueued by the step
     n: int = 0
     raw_mesh: torch.Tensor = None   # [N,V0,3] the lifter's own output on the device (= mesh without perm_reverse)
     overlay: torch.Tensor = None    # [N,H,W,3] uint8 RGB on the device: the mesh drawn over the frame (engines with faces=)
     box_label: torch.Tensor = None  # [N,H,W,3] uint8 RGB on the device: the frame with the hand's crop box (engines with labels)
     pose_label: torch.Tensor = None  # [N,176,176,3] uint8 RGB on the device: the colour crop with the skeleton (zeros: no hand)
+    layout: LiveLayout = None        # where everything lies in `host`
 
     def read(self):
         """After the stream is synchronised: (keypoints, has_hand, crop_box, range words, [image_uvd, xyz_mm], mesh) as fresh CPU
         tensors (LiveRead; `.overlay`, `.box_label`, `.pose_label` are None).  A step with faces= appends the overlay [N,H,W,3]
         uint8 (LiveOverlayRead); a step with labels appends box_label [N,H,W,3] and pose_label [N,176,176,3] (LiveLabelsRead,
         LiveOverlayLabelsRead)."""
-        rb = record_bytes(3)
-        n = self.n
-        rec = self.host[: (n + 1) * rb].view(n + 1, rb)
-        kp, has, box, words, more = read_host_record(rec, n, extras=True)
-        # (h = w = 0: a step without images has the records and the mesh at the same offsets, and nothing behind them)
-        image = self.overlay if self.overlay is not None else self.box_label
-        h, w = (0, 0) if image is None else image.shape[1:3]
-        mo, oo, bo, po, end = live_labels_layout(n, self.mesh.shape[1], h, w, self.overlay is not None, self.box_label is not None)
-        mesh = self.host[mo:oo].view(torch.float32).reshape(n, -1, 3).clone()
-        fields = (kp, has, box, words, more, mesh)
-        if self.overlay is not None:
-            fields += (self.host[oo:oo + self.overlay.numel()].reshape(self.overlay.shape).clone(),)
-        if self.box_label is None:
-            return (LiveRead if self.overlay is None else LiveOverlayRead)(*fields)
-        fields += (self.host[bo:bo + self.box_label.numel()].reshape(self.box_label.shape).clone(),
-                   self.host[po:end].reshape(self.pose_label.shape).clone())
-        return (LiveLabelsRead if self.overlay is None else LiveOverlayLabelsRead)(*fields)
+        v = self.layout.views(self.host)
+        kp, has, box, words, more = read_host_record(v.records, self.layout.frames, extras=True)
+        return _read("Live", _LIVE_FIELDS, (kp, has, box, words, more, v.mesh.clone()), self.layout, v)
 
 
 class _LiveStep:
-    """What the one-hand and the K-hand live steps share: the engines, the caller's conversion, the final-mesh permutation,
-    the output buffers of a batch size, the camera feed (forward_raw) and the capture (graphed).  A subclass gives _nbytes(n)
-    and forward_device(images, depth, _buffers)."""
+    """The live step, for one hand per frame or K: the engines, the caller's conversion, the final-mesh permutation, the layout
+    and the output buffers of a batch size, the step itself (forward_device), the camera feed (forward_raw) and the capture
+    (graphed).  A subclass says which step of the hand engine runs (_hand_step), how the lifter's input is gated
+    (_lifter_input), how the mesh is finished (_mesh) and what the step hands out (_output)."""
+    hands = None                 # K of the K-hand step
+    handed = False
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None,
                  labels: bool = False, left: bool = False):
@@ -194,25 +238,54 @@ class _LiveStep:
                     (ops.mesh_render_scratch_bytes(s, self.faces.shape[0]),), dtype=torch.uint8, device=self.device)
         return ops.mesh_render(mesh, self.faces, self.paras, frames, lifted=lifted, k=k, out=out, scratch=scratch)
 
-    def _draw_labels(self, kp, crop_box, drawn, frames, k, dev, box_at, pose_at):
-        """The step's two label images, written into its copy buffer `dev` at the layout's offsets."""
-        n, _, h, w = frames.shape
-        return ops.draw_labels(kp, crop_box, frames, drawn=drawn, k=k, clamp=self.clamp,
-                               out_box=dev[box_at:box_at + n * h * w * 3], out_pose=dev[pose_at:pose_at + n * k * POSE_LABEL_BYTES])
+    def _layout(self, n, hw=None) -> LiveLayout:
+        """The buffer of a step over n frames (hw: of a step that draws, the frames' size)."""
+        return LiveLayout(n, self.hands, self.vertices, hw, hw is not None and self.faces is not None,
+                          hw is not None and self.labels, self.handed)
 
     def _new_buffers(self, n, hw=None):
-        """A fresh (device, pinned host) pair of a step over n frames (hw: with images of that frame size)."""
-        nbytes = self._nbytes(n, hw)
-        return (torch.zeros((nbytes,), dtype=torch.uint8, device=self.device),
-                torch.zeros((nbytes,), dtype=torch.uint8, pin_memory=True))
+        """A fresh (layout, device buffer, pinned host buffer) of a step over n frames."""
+        layout = self._layout(n, hw)
+        return (layout, torch.zeros((layout.nbytes,), dtype=torch.uint8, device=self.device),
+                torch.zeros((layout.nbytes,), dtype=torch.uint8, pin_memory=True))
 
-    def _out_buffers(self, n, v0, hw=None):
-        key = (n, v0, hw)
-        b = self._buffers.get(key)
+    def _out_buffers(self, n, hw=None):
+        b = self._buffers.get((n, hw))
         if b is None:
             with torch.inference_mode(False):
-                b = self._buffers[key] = self._new_buffers(n, hw)
+                b = self._buffers[(n, hw)] = self._new_buffers(n, hw)
         return b
+
+    @ops.device_guarded
+    def forward_device(self, images, depth, _buffers=None, _mirror=None):
+        """images [N,3,H,W] 0..1 (or a list), depth [N,1,H,W] metres on the GPU -> the step's output (no sync).
+        (_mirror: a `left` capture's own mirrored-input buffers; False: the inputs are mirrored already.)"""
+        n = len(images)
+        if self.left and _mirror is not False:
+            images, depth = self._mirror_inputs(images, depth, _mirror)
+        frames = self._frames(images)
+        layout, dev, host = _buffers if _buffers is not None else self._out_buffers(n, self._hw(frames))
+        at = layout.views(dev)
+
+        def lift(_kp, image_uvd, xyz, has_hand, mirror=None):
+            # (inside the step's range scope: the lifter's split producers note into the step's flag words, which the step's one
+            # collect launch hands over -- an overflowing activation of the lifter raises like one of the pose network;
+            # mirror: the handed step's per-slot flags)
+            p2d = self._lifter_input(image_uvd, has_hand, at.lifted, mirror)
+            return (p2d,) + self._mesh(p2d, xyz, has_hand, at, mirror)
+        # the step packs its wide records and its range words straight into the buffer; ONE copy moves records, mesh and images
+        out = self._hand_step(images, depth, at, lift)
+        p2d, mesh, pose3d, raw = out.tail
+        drawn, k = out.has_hand.view(-1) if self.hands is None else at.lifted, self.hands or 1
+        overlay = box_label = pose_label = None
+        if layout.overlay:
+            overlay = self._draw(mesh, drawn, frames, k, at.overlay)
+        if layout.labels:
+            box_label, pose_label = ops.draw_labels(out.keypoints, out.crop_box, frames, drawn=drawn, k=k, clamp=self.clamp,
+                                                    out_box=at.box_label, out_pose=at.pose_label)
+        host.copy_(dev, non_blocking=True)
+        return self._output(out, at, layout, host, dict(pose2d=p2d, mesh=mesh, pose3d=pose3d, raw_mesh=raw, overlay=overlay,
+                                                        box_label=box_label, pose_label=pose_label))
 
     @ops.device_guarded
     def forward_raw(self, bgr_u8, depth_raw) -> LiveOutput:
@@ -242,7 +315,7 @@ class _LiveStep:
                 s_img, s_dep = torch.empty_like(images), torch.empty_like(depth)
                 s_img.copy_(images)
                 s_dep.copy_(depth)
-                # the capture's own pair, never the eager cache's (addresses are baked into the graph)
+                # the capture's own buffers, never the eager cache's (addresses are baked into the graph)
                 bufs = self._new_buffers(images.shape[0], self._hw(self._frames(images)))
                 flipped = None
                 if self.left and not _mirrored:
@@ -257,109 +330,40 @@ class _LiveStep:
 
 
 class LiveHandEngine(_LiveStep):
-    def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None,
-                 labels: bool = False, left: bool = False):
-        """paras = (fx, fy, cx, cy) of the depth camera (ros_demo.py:191-196); clamp: the caller's clamps before the
-        conversion (ros_demo.py:279-283).  perm_reverse: graph_perm_reverse[:V] (int64, V = vertices of the real mesh,
-        ros_demo.py:162) -- given, the step also does the caller's last three lines (vertex order, camera offset by the first
-        joint, y / z negated: ros_demo.py:332-337) and `mesh` of the outputs IS out['mesh'], [N,V,3]; else the lifter's raw
-        [N,V0,3] vertices in coarsening order.  faces: mesh_model.face ([F,3] vertex indices of the real mesh; needs perm_reverse) --
-        given, the step also draws the mesh over the frame (ros_demo.py:86-116 render(): LiveOutput.overlay, read().overlay).
-        labels: the step also draws box_label and pose_label (ros_demo.py:310-326: LiveOutput.box_label / .pose_label, read()
-        likewise); a frame without a hand (has_hand != 1) keeps its plain frame and a zero pose_label.
-        left: the reference's mirror mode for a left-handed subject (ImageListener(left=True), ros_demo.py:259-262) -- every
-        output equals the one of this engine without `left` on frames and depth flipped along the width, bit for bit (boxes,
-        keypoints, mesh and images are in the mirrored frame, as the reference publishes them).  forward_raw mirrors inside the
-        ingest kernel (no launch added); fp32 feeds (forward_device / graphed) cost one launch."""
-        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left)
+    """paras = (fx, fy, cx, cy) of the depth camera (ros_demo.py:191-196); clamp: the caller's clamps before the
+    conversion (ros_demo.py:279-283).  perm_reverse: graph_perm_reverse[:V] (int64, V = vertices of the real mesh,
+    ros_demo.py:162) -- given, the step also does the caller's last three lines (vertex order, camera offset by the first
+    joint, y / z negated: ros_demo.py:332-337) and `mesh` of the outputs IS out['mesh'], [N,V,3]; else the lifter's raw
+    [N,V0,3] vertices in coarsening order.  faces: mesh_model.face ([F,3] vertex indices of the real mesh; needs perm_reverse) --
+    given, the step also draws the mesh over the frame (ros_demo.py:86-116 render(): LiveOutput.overlay, read().overlay).
+    labels: the step also draws box_label and pose_label (ros_demo.py:310-326: LiveOutput.box_label / .pose_label, read()
+    likewise); a frame without a hand (has_hand != 1) keeps its plain frame and a zero pose_label.
+    left: the reference's mirror mode for a left-handed subject (ImageListener(left=True), ros_demo.py:259-262) -- every
+    output equals the one of this engine without `left` on frames and depth flipped along the width, bit for bit (boxes,
+    keypoints, mesh and images are in the mirrored frame, as the reference publishes them).  forward_raw mirrors inside the
+    ingest kernel (no launch added); fp32 feeds (forward_device / graphed) cost one launch."""
 
-    def _nbytes(self, n, hw=None):
-        if hw is None:
-            return (n + 1) * record_bytes(3) + n * self.vertices * 12
-        return live_labels_layout(n, self.vertices, *hw, overlay=self.faces is not None, labels=self.labels)[4]
+    def _hand_step(self, images, depth, at, lift):
+        return self.hand.forward_device(images, depth, _record=(None, at.records), _tail=lift)
 
-    @ops.device_guarded
-    def forward_device(self, images, depth, _buffers=None, _mirror=None) -> LiveOutput:
-        """images [N,3,H,W] 0..1 (or a list), depth [N,1,H,W] metres on the GPU -> LiveOutput (no sync).
-        (_mirror: a `left` capture's own mirrored-input buffers; False: the inputs are mirrored already.)"""
-        n = len(images)
-        if self.left and _mirror is not False:
-            images, depth = self._mirror_inputs(images, depth, _mirror)
-        v0 = self.vertices
-        frames = self._frames(images)
-        dev, host = _buffers if _buffers is not None else self._out_buffers(n, v0, self._hw(frames))
-        rb = record_bytes(3)
-        rec = dev[: (n + 1) * rb].view(n + 1, rb)
-        mesh_buf = dev[(n + 1) * rb:(n + 1) * rb + n * v0 * 12].view(torch.float32).view(n, v0, 3)
+    def _lifter_input(self, image_uvd, has_hand, _lifted, _mirror):
+        return ops.joints2d_standardize(image_uvd, valid=has_hand)
 
-        def lift(_kp, image_uvd, xyz, has_hand):
-            # (inside the step's range scope: the lifter's split producers note into the step's flag words, which the step's one
-            # collect launch hands over -- an overflowing activation of the lifter raises like one of the pose network)
-            p2d = ops.joints2d_standardize(image_uvd, valid=has_hand)
-            if self.perm is None:
-                mesh, pose3d = self.lifter.forward(p2d, mesh_out=mesh_buf)          # the last layer writes into the copy buffer
-                return p2d, mesh, pose3d, mesh
-            raw, pose3d = self.lifter.forward(p2d)
-            return p2d, ops.mesh_finish(raw, self.perm, xyz, valid=has_hand, out=mesh_buf), pose3d, raw
-        # the step packs its wide records and its range words straight into `rec`; ONE copy moves records + mesh
-        out = self.hand.forward_device(images, depth, _record=(None, rec), _tail=lift)
-        p2d, mesh, pose3d, raw = out.tail
-        overlay = box_label = pose_label = None
-        if frames is not None:
-            h, w = frames.shape[2:]
-            _, oo, bo, po, _ = live_labels_layout(n, v0, h, w, self.faces is not None, self.labels)
-            if self.faces is not None:
-                overlay = self._draw(mesh, out.has_hand.view(-1), frames, 1, dev[oo:oo + n * h * w * 3])
-            if self.labels:
-                box_label, pose_label = self._draw_labels(out.keypoints, out.crop_box, out.has_hand.view(-1), frames, 1, dev, bo, po)
-        host.copy_(dev, non_blocking=True)
-        return LiveOutput(out, p2d, mesh, pose3d, host, n, raw, overlay, box_label, pose_label)
+    def _mesh(self, p2d, xyz, has_hand, at, _mirror):
+        if self.perm is None:
+            mesh, pose3d = self.lifter.forward(p2d, mesh_out=at.mesh)               # the last layer writes into the copy buffer
+            return mesh, pose3d, mesh
+        raw, pose3d = self.lifter.forward(p2d)
+        return ops.mesh_finish(raw, self.perm, xyz, valid=has_hand, out=at.mesh), pose3d, raw
+
+    def _output(self, out, at, layout, host, parts) -> LiveOutput:
+        return LiveOutput(hand=out, host=host, n=layout.frames, layout=layout, **parts)
 
 
-def live_hands_layout(slots: int, vertices: int, handed: bool = False):
-    """Byte layout of the K-hand live step's one buffer for `slots` = N*K hand slots: (record rows, record bytes, offset of
-    `lifted` (int32 [slots]), offset of the mesh (fp32 [slots,V,3]), total bytes).  The record is forward_hands' wide record
-    unchanged (one row per slot, the range-word row, the scores and detection ranks: hands_record_rows).  handed: the
-    slots' sides (int32 [slots]) sit behind the score and rank rows, at `rows * record bytes` -- `lifted` and everything behind
-    it move up by 4 * slots bytes, nothing else changes."""
-    rb = record_bytes(3)
-    rows = hands_record_rows(slots, rb)
-    lifted = rows * rb + (4 * slots if handed else 0)
-    mesh = lifted + 4 * slots
-    return rows, rb, lifted, mesh, mesh + slots * vertices * 12
-
-
-def live_hands_overlay_layout(slots: int, vertices: int, frames: int, h: int, w: int, handed: bool = False):
-    """live_hands_layout with the overlay appended: the same five values (every offset where a step without an overlay has
-    it; the fifth is now the overlay's offset) + the total bytes; the overlay is uint8 [frames,h,w,3]."""
-    rows, rb, lifted, mesh, overlay = live_hands_layout(slots, vertices, handed)
-    return rows, rb, lifted, mesh, overlay, overlay + frames * h * w * 3
-
-
-def live_hands_labels_layout(slots: int, vertices: int, frames: int, h: int, w: int, overlay: bool = False, labels: bool = True,
-                             handed: bool = False):
-    """live_hands_overlay_layout with the label images appended behind the mesh, and behind the overlay when there is one: its
-    first five values (the overlay's offset: the end of the mesh), then the offset of box_label (uint8 [frames,h,w,3]), the
-    offset of pose_label (uint8 [slots,176,176,3]) and the total bytes.  Without `labels` the total is the one of
-    live_hands_overlay_layout / live_hands_layout."""
-    rows, rb, lifted, mesh, oo, end = live_hands_overlay_layout(slots, vertices, frames, h if overlay else 0, w if overlay else 0,
-                                                                handed)
-    return (rows, rb, lifted, mesh, oo) + _labels_behind(end, frames, slots, h, w, labels)
-
-
-LiveHandsRead = _read_type("LiveHandsRead", "keypoints has_hand crop_box score det_index image_uvd xyz_mm lifted mesh words",
-                           "LiveHandsOutput.read() of a step without images (the fields are the ten it always had).",
-                           overlay=None, **_NO_LABELS)
-LiveHandsOverlayRead = _read_type("LiveHandsOverlayRead", LiveHandsRead._fields + ("overlay",), "... of a step with faces=.",
-                                  **_NO_LABELS)
-LiveHandsLabelsRead = _read_type("LiveHandsLabelsRead", LiveHandsRead._fields + _LABEL_FIELDS, "... of a step with labels.",
-                                 overlay=None)
-LiveHandsOverlayLabelsRead = _read_type("LiveHandsOverlayLabelsRead", LiveHandsRead._fields + ("overlay",) + _LABEL_FIELDS,
-                                        "... of a step with faces= and labels.")
+_HANDS_FIELDS = ("keypoints", "has_hand", "crop_box", "score", "det_index", "image_uvd", "xyz_mm", "lifted", "mesh", "words")
+LiveHandsRead, LiveHandsOverlayRead, LiveHandsLabelsRead, LiveHandsOverlayLabelsRead = (       # (plain: the ten it always had)
+    _read_type("LiveHands", _HANDS_FIELDS, overlay, labels, False) for labels in (False, True) for overlay in (False, True))
 # ... and of a handed step: the same fields + `side` [N,K] int32 (the detector's side of the slot's detection, -1: empty slot)
-_SIDED_READS = {t: _read_type(t.__name__.replace("Read", "SidedRead"), t._fields + ("side",), t.__doc__ + "  Handed: + side.",
-                              **{f: None for f in ("overlay",) + _LABEL_FIELDS if f not in t._fields})
-                for t in (LiveHandsRead, LiveHandsOverlayRead, LiveHandsLabelsRead, LiveHandsOverlayLabelsRead)}
 
 
 @dataclass
@@ -369,7 +373,7 @@ class LiveHandsOutput:
     lifted: torch.Tensor         # [N,K] int32: 1 where the slot's hand went through the lifter (the caller's skip rule)
     mesh: torch.Tensor           # [N,K,V,3] as LiveOutput.mesh, per slot; zero rows where not lifted
     pose3d: torch.Tensor         # [N*K,21,3] PoseNet's lifted joints (every row: rows not lifted are the lifter on zeros)
-    host: torch.Tensor           # pinned uint8 (live_hands_layout): records, lifted, mesh -- ONE copy, enqueued by the step
+    host: torch.Tensor           # pinned uint8 (`layout`): records, side, lifted, mesh, images -- ONE copy, enqueued by the step
     n: int = 0
     k: int = 0
     raw_mesh: torch.Tensor = None   # [N*K,V0,3] the lifter's own output on the device
@@ -378,36 +382,20 @@ class LiveHandsOutput:
     pose_label: torch.Tensor = None  # [N*K,176,176,3] uint8 RGB on the device: per slot, the colour crop with the skeleton
     side: torch.Tensor = None        # handed steps: [N,K] int32 on the device, the detector's side per slot (-1: empty slot)
     mirror: torch.Tensor = None      # handed steps: [N,K] int32 on the device, 1 where the slot ran mirrored (a left hand)
+    layout: LiveLayout = None        # where everything lies in `host`
 
     def read(self) -> LiveHandsRead:
         """After the stream is synchronised: the step's results per frame and slot as fresh CPU tensors (LiveHandsRead;
         lifted as bool, words = the step's range words; a step with faces=: LiveHandsOverlayRead, + overlay [N,H,W,3] uint8; a
         step with labels: + box_label [N,H,W,3], pose_label [N,K,176,176,3] -- LiveHandsLabelsRead, LiveHandsOverlayLabelsRead;
         a handed step: the same with `side` [N,K] int32 as the last field)."""
-        n, k, s = self.n, self.k, self.n * self.k
-        handed = self.side is not None
-        rows, rb, lo, mo, nbytes = live_hands_layout(s, self.mesh.shape[2], handed)
-
-        def sided(kind, values):
-            if not handed:
-                return kind(*values)
-            return _SIDED_READS[kind](*values, self.host[rows * rb:lo].view(torch.int32).reshape(n, k).clone())
-        rec = self.host[:rows * rb].view(rows, rb)
-        kp, has, box, words, (img, xyz) = read_host_record(rec, s, extras=True)
-        score, index = read_hands_tail(rec, s)
-        lifted = self.host[lo:mo].view(torch.int32).reshape(n, k) != 0
-        mesh = self.host[mo:nbytes].view(torch.float32).reshape(n, k, -1, 3).clone()
-        per = lambda t: t.reshape((n, k) + tuple(t.shape[1:]))
-        fields = (per(kp), per(has), per(box), per(score), per(index), per(img), per(xyz), lifted, mesh, words)
-        if self.overlay is not None:
-            fields += (self.host[nbytes:nbytes + self.overlay.numel()].reshape(self.overlay.shape).clone(),)
-        if self.box_label is None:
-            return sided(LiveHandsRead if self.overlay is None else LiveHandsOverlayRead, fields)
-        h, w = self.box_label.shape[1:3]
-        bo, po, end = live_hands_labels_layout(s, self.mesh.shape[2], n, h, w, self.overlay is not None, handed=handed)[5:]
-        fields += (self.host[bo:bo + self.box_label.numel()].reshape(self.box_label.shape).clone(),
-                   self.host[po:end].reshape(n, k, POSE_LABEL, POSE_LABEL, 3).clone())
-        return sided(LiveHandsLabelsRead if self.overlay is None else LiveHandsOverlayLabelsRead, fields)
+        v, s = self.layout.views(self.host), self.layout.slots
+        per = lambda t: t.reshape((self.layout.frames, self.layout.hands) + tuple(t.shape[1:]))
+        kp, has, box, words, (img, xyz) = read_host_record(v.records, s, extras=True)
+        score, index = read_hands_tail(v.records, s)
+        values = (per(kp), per(has), per(box), per(score), per(index), per(img), per(xyz), per(v.lifted) != 0, per(v.mesh).clone(),
+                  words)
+        return _read("LiveHands", _HANDS_FIELDS, values, self.layout, v, per)
 
 
 class LiveHandsEngine(_LiveStep):
@@ -415,7 +403,8 @@ class LiveHandsEngine(_LiveStep):
     hand detection) -> clamp + convert in the aggregation's epilogue -> the lifter's input WITH the caller's skip rule per
     slot (ros_demo.py:288-300: a hand whose 2D box process_bbox refuses is not lifted; hn_lifter_input_gated_f32) ->
     Pose2Mesh on all N*K rows (dense: rejected rows are zeros, so the step stays capturable and its activations finite) ->
-    the final mesh (perm_reverse) -> ONE device -> host copy of records + lifted + mesh (live_hands_layout)."""
+    the final mesh (perm_reverse) -> ONE device -> host copy of records + lifted + mesh (LiveLayout).  Eager steps may run A2J
+    on the filled slots only (HandNetEngine.forward_hands); the lifter always runs on all N*K rows."""
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, max_hands: int = 2, clamp: bool = True,
                  perm_reverse=None, faces=None, labels: bool = False, left: bool = False, handed: bool = False,
@@ -434,62 +423,36 @@ class LiveHandsEngine(_LiveStep):
         left_side = 0 is an ASSUMPTION: the detector's side targets are box_info[:, 1] of its training set, whose convention
         (100DOH: 0 = left) the reference does not state -- it never reads `sides`.  Check it on your checkpoint.
         left and handed together: ValueError (a mirrored frame swaps the sides)."""
-        self.max_hands = ops.check_max_hands(max_hands)
+        self.hands = self.max_hands = ops.check_max_hands(max_hands)
         if left and handed:
             raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
         self.handed, self.left_side = bool(handed), int(left_side)
         super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left)
 
-    def _nbytes(self, n, hw=None):
-        if hw is None:
-            return live_hands_layout(n * self.max_hands, self.vertices, self.handed)[4]
-        return live_hands_labels_layout(n * self.max_hands, self.vertices, n, *hw, overlay=self.faces is not None,
-                                        labels=self.labels, handed=self.handed)[7]
+    def _hand_step(self, images, depth, at, lift):
+        # (the per-slot records, range words, scores and ranks go straight into the buffer, the handed step's sides behind them)
+        return self.hand.forward_hands(images, depth, self.hands, _record=(None, at.records), _tail=lift, handed=self.handed,
+                                       left_side=self.left_side, _side=at.side)
 
-    @ops.device_guarded
-    def forward_device(self, images, depth, _buffers=None, _mirror=None) -> LiveHandsOutput:
-        """images [N,3,H,W] 0..1 (or a list), depth [N,1,H,W] metres on the GPU -> LiveHandsOutput (no sync).  Eager steps
-        may run A2J on the filled slots only (HandNetEngine.forward_hands); the lifter always runs on all N*K rows.
-        (_mirror: as LiveHandEngine.forward_device's.)"""
-        n, k = len(images), self.max_hands
-        if self.left and _mirror is not False:
-            images, depth = self._mirror_inputs(images, depth, _mirror)
-        s, v = n * k, self.vertices
-        frames = self._frames(images)
-        dev, host = _buffers if _buffers is not None else self._out_buffers(n, v, self._hw(frames))
-        rows, rb, lo, mo, nbytes = live_hands_layout(s, v, self.handed)
-        rec = dev[:rows * rb].view(rows, rb)
-        side = dev[rows * rb:lo].view(torch.int32) if self.handed else None
-        lifted = dev[lo:mo].view(torch.int32)
-        mesh_buf = dev[mo:nbytes].view(torch.float32).view(s, v, 3)
+    def _lifter_input(self, image_uvd, has_hand, lifted, mirror):
+        return ops.lifter_input_gated(image_uvd, valid=has_hand, lifted=lifted, mirror=mirror)[0]
 
-        def lift(_kp, image_uvd, xyz, has_hand, mirror=None):
-            # (inside the step's range scope, as LiveHandEngine's lifter; mirror: the handed step's per-slot flags)
-            p2d, _ = ops.lifter_input_gated(image_uvd, valid=has_hand, lifted=lifted, mirror=mirror)
-            raw, pose3d = self.lifter.forward(p2d)
-            if mirror is not None:      # (also without perm_reverse: the raw vertices, x negated where mirrored)
-                mesh = ops.mesh_finish(raw, self.perm, xyz if self.perm is not None else None, valid=lifted, out=mesh_buf,
-                                       mirror=mirror)
-            elif self.perm is None:
-                mesh = torch.mul(raw, lifted.view(s, 1, 1), out=mesh_buf)       # (x * 1 is x: rows not lifted -> zeros)
-            else:
-                mesh = ops.mesh_finish(raw, self.perm, xyz, valid=lifted, out=mesh_buf)
-            return p2d, mesh, pose3d, raw
-        # the step packs its per-slot records, range words, scores and ranks straight into `rec`; ONE copy moves it all
-        out = self.hand.forward_hands(images, depth, k, _record=(None, rec), _tail=lift, handed=self.handed,
-                                      left_side=self.left_side, _side=side)
-        p2d, mesh, pose3d, raw = out.tail
-        overlay = box_label = pose_label = None
-        if frames is not None:
-            h, w = frames.shape[2:]
-            bo, po, _ = live_hands_labels_layout(s, v, n, h, w, self.faces is not None, self.labels, self.handed)[5:]
-            if self.faces is not None:
-                overlay = self._draw(mesh, lifted, frames, k, dev[nbytes:nbytes + n * h * w * 3])
-            if self.labels:
-                box_label, pose_label = self._draw_labels(out.keypoints, out.crop_box, lifted, frames, k, dev, bo, po)
-        host.copy_(dev, non_blocking=True)
-        return LiveHandsOutput(out, p2d, lifted.view(n, k), mesh.view(n, k, v, 3), pose3d, host, n, k, raw, overlay, box_label,
-                               pose_label, out.side, out.mirror)
+    def _mesh(self, p2d, xyz, _has_hand, at, mirror):
+        raw, pose3d = self.lifter.forward(p2d)
+        if mirror is not None:      # (also without perm_reverse: the raw vertices, x negated where mirrored)
+            mesh = ops.mesh_finish(raw, self.perm, xyz if self.perm is not None else None, valid=at.lifted, out=at.mesh,
+                                   mirror=mirror)
+        elif self.perm is None:
+            mesh = torch.mul(raw, at.lifted.view(-1, 1, 1), out=at.mesh)       # (x * 1 is x: rows not lifted -> zeros)
+        else:
+            mesh = ops.mesh_finish(raw, self.perm, xyz, valid=at.lifted, out=at.mesh)
+        return mesh, pose3d, raw
+
+    def _output(self, out, at, layout, host, parts) -> LiveHandsOutput:
+        n, k = layout.frames, layout.hands
+        parts["mesh"] = parts["mesh"].view(n, k, self.vertices, 3)
+        return LiveHandsOutput(hands=out, lifted=at.lifted.view(n, k), host=host, n=n, k=k, side=out.side, mirror=out.mirror,
+                               layout=layout, **parts)
 
 
 @dataclass

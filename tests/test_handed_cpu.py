@@ -57,7 +57,7 @@ def test_left_with_handed_is_refused():
 def test_layouts(slots, frames):
     """handed=False: today's numbers (restated here from the record format); handed=True: exactly 4 bytes per slot more, the
     sides behind the score and rank rows and everything behind them moved up by as much."""
-    from hn_amd import live
+    from hn_amd.live import LiveLayout
     from hn_amd.pipeline import hands_record_rows, record_bytes
     v, h, w = 778, 480, 640
     rb = record_bytes(3)
@@ -65,18 +65,24 @@ def test_layouts(slots, frames):
     rows = slots + 1 + (8 * slots + rb - 1) // rb
     assert hands_record_rows(slots, rb) == hands_record_rows(slots, rb, False) == rows
     today = (rows, rb, rows * rb, rows * rb + 4 * slots, rows * rb + 4 * slots + slots * v * 12)
-    assert live.live_hands_layout(slots, v) == live.live_hands_layout(slots, v, False) == today
-    got = live.live_hands_layout(slots, v, True)
-    assert got[:2] == today[:2] and tuple(g - t for g, t in zip(got[2:], today[2:])) == (4 * slots,) * 3
+    k = slots // frames
+    named = lambda a: (a.record_rows, a.record_bytes, a.lifted_at, a.mesh_at, a.nbytes)
+    behind = ("lifted_at", "mesh_at", "overlay_at", "box_label_at", "pose_label_at", "nbytes")
+    plain = LiveLayout(frames, k, v)
+    assert named(plain) == named(LiveLayout(frames, k, v, handed=False)) == today and plain.side_at is None
+    got = LiveLayout(frames, k, v, handed=True)
+    assert named(got)[:2] == today[:2] and tuple(g - t for g, t in zip(named(got)[2:], today[2:])) == (4 * slots,) * 3
+    assert got.side_at == rows * rb
     for overlay in (False, True):
         for labels in (False, True):
-            a = live.live_hands_labels_layout(slots, v, frames, h, w, overlay, labels)
-            assert a == live.live_hands_labels_layout(slots, v, frames, h, w, overlay, labels, False)
-            b = live.live_hands_labels_layout(slots, v, frames, h, w, overlay, labels, True)
-            assert b[7] - a[7] == 4 * slots and b[:2] == a[:2]
-            assert all(y - x == 4 * slots for x, y in zip(a[2:5], b[2:5]))
-    a, b = live.live_hands_overlay_layout(slots, v, frames, h, w), live.live_hands_overlay_layout(slots, v, frames, h, w, True)
-    assert a == live.live_hands_overlay_layout(slots, v, frames, h, w, False) and b[5] - a[5] == 4 * slots
+            a = LiveLayout(frames, k, v, (h, w), overlay, labels)
+            assert a == LiveLayout(frames, k, v, (h, w), overlay, labels, False) and a.side_at is None
+            b = LiveLayout(frames, k, v, (h, w), overlay, labels, True)
+            assert b.side_at == rows * rb and (b.record_rows, b.record_bytes) == (a.record_rows, a.record_bytes)
+            for f in behind:            # `lifted` and everything behind it: 4 bytes per slot further, or not there in both
+                x, y = getattr(a, f), getattr(b, f)
+                assert (x is None and y is None) or y - x == 4 * slots, f
+            assert (a.overlay_at is not None) == overlay and (a.box_label_at is not None) == labels == (a.pose_label_at is not None)
     # the engine's own to_host record: whole rows, the sides behind the scores and ranks
     assert hands_record_rows(slots, rb, True) == slots + 1 + (12 * slots + rb - 1) // rb
 

@@ -174,8 +174,8 @@ def test_handed_false_is_todays_step_and_handed_adds_no_launch(parts, labels):
     default, explicit, handed = _engine(parts, 2, labels=labels), _engine(parts, 2, labels=labels, handed=False), \
         _engine(parts, 2, labels=labels, handed=True)
     hw = (H, W) if labels else None
-    assert default._nbytes(1, hw) == explicit._nbytes(1, hw) == handed._nbytes(1, hw) - 4 * 2
-    assert default._nbytes(1) == live.live_hands_layout(2, 778)[4]
+    assert default._layout(1, hw).nbytes == explicit._layout(1, hw).nbytes == handed._layout(1, hw).nbytes - 4 * 2
+    assert default._layout(1).nbytes == live.LiveLayout(1, 2, 778).nbytes == 21880
     for graphed in (False, True):
         a, oa = _host(default, rgb, dep, graphed)
         b, ob = _host(explicit, rgb, dep, graphed)

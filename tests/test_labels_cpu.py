@@ -131,26 +131,29 @@ def test_rectangle_and_box_rule():
 
 
 def test_layouts_without_labels_are_the_parents():
-    from hn_amd import live
+    from hn_amd.live import LiveLayout
+    front = lambda a: (a.record_rows, a.record_bytes, a.side_at, a.lifted_at, a.mesh_at)       # what every step has
     for n, v, h, w in ((1, 778, 480, 640), (3, 778, 37, 53), (32, 1538, 480, 640)):
-        mesh, oo, end = live.live_overlay_layout(n, v, h, w)
-        assert live.live_labels_layout(n, v, h, w, overlay=True, labels=False) == (mesh, oo, end, end, end)
-        plain = live.live_overlay_layout(n, v, 0, 0)
-        assert live.live_labels_layout(n, v, h, w, overlay=False, labels=False) == plain[:2] + (plain[2],) * 3
-        m2, o2, bo, po, total = live.live_labels_layout(n, v, h, w, overlay=True, labels=True)
-        assert (m2, o2) == (mesh, oo) and end <= bo < end + 4 and bo % 4 == 0 and po % 4 == 0
-        assert bo + n * h * w * 3 <= po < bo + n * h * w * 3 + 4 and total == po + n * 92928
-        for k in (1, 2):
-            s = n * k
-            parent = live.live_hands_overlay_layout(s, v, n, h, w)
-            assert live.live_hands_labels_layout(s, v, n, h, w, overlay=True, labels=False) == parent[:5] + (parent[5],) * 3
-            bare = live.live_hands_layout(s, v)
-            assert live.live_hands_labels_layout(s, v, n, h, w, overlay=False, labels=False) == bare + (bare[4],) * 3
-            got = live.live_hands_labels_layout(s, v, n, h, w, overlay=False, labels=True)
-            assert got[:5] == bare and got[5] % 4 == 0 and got[6] % 4 == 0 and got[7] == got[6] + s * 92928
+        for k in (None, 1, 2):
+            s = n * (k or 1)
+            # labels off: the step with an overlay and the bare step as they were, and no offset for what is not there
+            bare, shown = LiveLayout(n, k, v), LiveLayout(n, k, v, (h, w), overlay=True)
+            assert LiveLayout(n, k, v, (h, w), overlay=True, labels=False) == shown
+            assert LiveLayout(n, k, v, (h, w), overlay=False, labels=False).nbytes == bare.nbytes
+            assert front(LiveLayout(n, k, v, (h, w))) == front(bare) == front(shown)
+            assert bare.overlay_at is None and shown.overlay_at == bare.nbytes and shown.nbytes == bare.nbytes + n * h * w * 3
+            for a in (bare, shown):
+                assert a.box_label_at is None and a.pose_label_at is None
+            # labels on: both images behind what the parent step has, each on a dword, nothing in front of them moved
+            for parent in (bare, shown):
+                got = LiveLayout(n, k, v, (h, w), overlay=parent.overlay, labels=True)
+                end, bo, po = parent.nbytes, got.box_label_at, got.pose_label_at
+                assert front(got) == front(parent) and got.overlay_at == parent.overlay_at
+                assert end <= bo < end + 4 and bo % 4 == 0 and po % 4 == 0
+                assert bo + n * h * w * 3 <= po < bo + n * h * w * 3 + 4 and got.nbytes == po + s * 92928
     # the camera's frame needs no padding: the growth is exactly N H W 3 + N K 92928
-    a = live.live_hands_labels_layout(64, 778, 32, 480, 640, overlay=True, labels=False)[7]
-    b = live.live_hands_labels_layout(64, 778, 32, 480, 640, overlay=True, labels=True)[7]
+    a = LiveLayout(32, 2, 778, (480, 640), overlay=True, labels=False).nbytes
+    b = LiveLayout(32, 2, 778, (480, 640), overlay=True, labels=True).nbytes
     assert b - a == 32 * 480 * 640 * 3 + 64 * 92928
 
 

@@ -307,9 +307,9 @@ def test_default_is_unchanged(parts, hands, monkeypatch):
         return live.LiveHandsEngine(hand, lifter, LIVE_PARAS, hands, True, perm, **kw)
     k = hands or 1
     plain, explicit, labelled = build(), build(labels=False), build(labels=True)
-    parent = ((1 + 1) * record_bytes(3) + 778 * 12) if hands is None else live.live_hands_layout(k, 778)[4]
-    assert plain._nbytes(1) == plain._nbytes(1, None) == explicit._nbytes(1) == parent
-    assert labelled._nbytes(1, (H, W)) == parent + H * W * 3 + k * 92928
+    parent = ((1 + 1) * record_bytes(3) + 778 * 12) if hands is None else live.LiveLayout(1, k, 778).nbytes
+    assert plain._layout(1).nbytes == plain._layout(1, None).nbytes == explicit._layout(1).nbytes == parent
+    assert labelled._layout(1, (H, W)).nbytes == parent + H * W * 3 + k * 92928
     out_p, r_p = _run(plain, rgb, dep)
     assert not calls and out_p.host.numel() == parent and out_p.box_label is None and r_p.box_label is None and r_p.pose_label is None
     out_l, r_l = _run(labelled, rgb, dep)
@@ -325,3 +325,38 @@ def test_default_is_unchanged(parts, hands, monkeypatch):
     assert counts[0] == counts[1]
     if counts[0] is not None:
         assert counts[2] - counts[0] == 2
+
+
+@pytest.mark.parametrize("hands", [None, 2])
+def test_host_buffer_is_the_layouts_views_of_the_device_results(parts, hands):
+    """Every part of the step's one buffer at once (faces= and labels, K = 2 also handed): the output's layout cuts the pinned
+    copy into the device tensors the output hands out, bit for bit, read() returns those views' contents, the buffer is
+    layout.nbytes long, and the eager and the captured step copy the same bytes.  (480 x 640 frames: N H W 3 is a multiple of
+    4, so neither label image is padded here; tests/test_live_layout_cpu.py has the padded layouts.)"""
+    from hn_amd.live import LiveHandEngine, LiveHandsEngine
+    hand, lifter, perm, faces = parts
+    if hands is None:
+        eng = LiveHandEngine(hand, lifter, LIVE_PARAS, True, perm, faces=faces, labels=True)
+    else:
+        eng = LiveHandsEngine(hand, lifter, LIVE_PARAS, hands, True, perm, faces=faces, labels=True, handed=True)
+    _bgr, _mm, rgb, dep = _camera(40 if hands is None else 50)      # (frames on which the other tests here draw)
+    hosts = []
+    for graphed in (False, True):
+        out, r = _run(eng, rgb, dep, graphed)
+        lay = out.layout
+        assert out.host.numel() == lay.nbytes and lay.box_label_at == lay.overlay_at + H * W * 3       # (no padding)
+        assert (lay.frames, lay.hands, lay.hw, lay.overlay, lay.labels, lay.handed) == (1, hands, (H, W), True, True, hands is not None)
+        v = lay.views(out.host)
+        per = (lambda t: t) if hands is None else (lambda t: t.reshape((1, hands) + tuple(t.shape[1:])))
+        device = dict(mesh=out.mesh, overlay=out.overlay, box_label=out.box_label, pose_label=per(out.pose_label))
+        if hands is not None:
+            device.update(lifted=out.lifted, side=out.side)
+        for name, t in device.items():
+            got = per(getattr(v, name)) if name in ("mesh", "lifted", "side") else getattr(v, name).reshape(t.shape)
+            assert got.dtype == t.dtype and torch.equal(got, t.cpu()), (graphed, name)
+            field = getattr(r, name)
+            assert torch.equal(field, got != 0 if name == "lifted" else got), (graphed, name)
+            assert field.data_ptr() != got.data_ptr()                    # read() hands out copies
+        assert bool(v.mesh.any()) and bool(v.pose_label.any()) and bool((v.overlay != v.box_label).any())
+        hosts.append(out.host.clone())
+    assert torch.equal(hosts[0], hosts[1])

@@ -97,9 +97,11 @@ def test_host_buffer_layout_and_read(n, k, v):
     """The buffer's offsets follow from hands_record_rows, and LiveHandsOutput.read() takes every field from its place."""
     import torch
     from hn_amd import pipeline
-    from hn_amd.live import LiveHandsOutput, live_hands_layout
+    from hn_amd.live import LiveHandsOutput, LiveLayout
     s = n * k
-    rows, rb, lo, mo, nbytes = live_hands_layout(s, v)
+    layout = LiveLayout(n, k, v)
+    rows, rb, lo, mo, nbytes = layout.record_rows, layout.record_bytes, layout.lifted_at, layout.mesh_at, layout.nbytes
+    assert layout.side_at is None and layout.overlay_at is None and layout.box_label_at is None and layout.pose_label_at is None
     assert rb == pipeline.record_bytes(3) and rows == pipeline.hands_record_rows(s, rb)
     assert lo == rows * rb and mo == lo + 4 * s and nbytes == mo + s * v * 12 and lo % 8 == 0 and mo % 4 == 0
     g = torch.Generator().manual_seed(s)
@@ -121,7 +123,7 @@ def test_host_buffer_layout_and_read(n, k, v):
     ix.copy_(index)
     host[lo:mo] = lifted.view(torch.uint8)
     host[mo:] = mesh.view(-1).view(torch.uint8)
-    r = LiveHandsOutput(None, None, None, torch.empty((n, k, v, 3)), None, host, n, k).read()
+    r = LiveHandsOutput(None, None, None, torch.empty((n, k, v, 3)), None, host, n, k, layout=layout).read()
     per = lambda t: t.reshape((n, k) + tuple(t.shape[1:]))
     assert torch.equal(r.keypoints, per(kp)) and torch.equal(r.image_uvd, per(img)) and torch.equal(r.xyz_mm, per(xyz))
     assert torch.equal(r.crop_box, per(box)) and torch.equal(r.has_hand, per(has))

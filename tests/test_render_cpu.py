@@ -113,35 +113,40 @@ def test_pyrender_intrinsics_camera_reduces_to_the_pinhole():
 
 @pytest.mark.parametrize("n,k,v", [(1, 1, 778), (1, 2, 778), (32, 2, 778)])
 def test_overlay_layout_keeps_every_offset(n, k, v):
-    from hn_amd.live import (LiveHandsOutput, LiveHandsRead, LiveOutput, live_hands_layout, live_hands_overlay_layout,
-                             live_overlay_layout)
+    from hn_amd.live import LiveHandsOutput, LiveHandsRead, LiveLayout, LiveOutput
     from hn_amd.pipeline import record_bytes
     h, w, s = 48, 64, n * k
-    plain = live_hands_layout(s, v)
-    ext = live_hands_overlay_layout(s, v, n, h, w)
-    assert ext[:5] == plain and ext[5] == plain[4] + n * h * w * 3
-    mo, oo, total = live_overlay_layout(n, v, h, w)
+    plain, ext = LiveLayout(n, k, v), LiveLayout(n, k, v, (h, w), overlay=True)
+    front = lambda a: (a.record_rows, a.record_bytes, a.side_at, a.lifted_at, a.mesh_at)
+    assert front(ext) == front(plain) and plain.overlay_at is None and ext.overlay_at == plain.nbytes
+    assert ext.nbytes == plain.nbytes + n * h * w * 3
+    one_plain, one_ext = LiveLayout(n, None, v), LiveLayout(n, None, v, (h, w), overlay=True)
+    mo, oo, total = one_ext.mesh_at, one_ext.overlay_at, one_ext.nbytes
     assert mo == (n + 1) * record_bytes(3) and oo == mo + n * v * 12 and total == oo + n * h * w * 3
+    assert front(one_plain) == front(one_ext) and one_plain.nbytes == oo and one_plain.overlay_at is None
     # a step without faces: read().overlay is None and the read has the fields it always had
-    host = torch.zeros((plain[4],), dtype=torch.uint8)
-    out = LiveHandsOutput(None, None, None, torch.empty((n, k, v, 3)), None, host, n, k)
+    host = torch.zeros((plain.nbytes,), dtype=torch.uint8)
+    out = LiveHandsOutput(None, None, None, torch.empty((n, k, v, 3)), None, host, n, k, layout=plain)
     r = out.read()
     assert out.overlay is None and r.overlay is None and isinstance(r, LiveHandsRead) and "overlay" not in r._fields
     assert len(r) == 10
-    one = LiveOutput(None, None, torch.empty((n, v, 3)), None, torch.zeros((mo + n * v * 12,), dtype=torch.uint8), n)
+    one = LiveOutput(None, None, torch.empty((n, v, 3)), None, torch.zeros((mo + n * v * 12,), dtype=torch.uint8), n,
+                     layout=one_plain)
     r1 = one.read()
     assert one.overlay is None and r1.overlay is None and len(r1) == 6
     # a step with faces: the overlay is read from behind the mesh, everything else from where it was
     g = torch.Generator().manual_seed(n * k)
-    host = torch.randint(0, 256, (ext[5],), generator=g, dtype=torch.uint8)
-    host[:plain[3]] = 0
+    host = torch.randint(0, 256, (ext.nbytes,), generator=g, dtype=torch.uint8)
+    host[:plain.mesh_at] = 0
     shown = LiveHandsOutput(None, None, None, torch.empty((n, k, v, 3)), None, host, n, k, None,
-                            torch.empty((n, h, w, 3), dtype=torch.uint8)).read()
-    assert torch.equal(shown.overlay, host[plain[4]:].view(n, h, w, 3)) and shown.overlay.dtype == torch.uint8
-    assert torch.equal(shown.mesh.view(torch.uint8).view(-1), host[plain[3]:plain[4]]) and tuple(shown.mesh.shape) == (n, k, v, 3)
+                            torch.empty((n, h, w, 3), dtype=torch.uint8), layout=ext).read()
+    assert torch.equal(shown.overlay, host[plain.nbytes:].view(n, h, w, 3)) and shown.overlay.dtype == torch.uint8
+    assert torch.equal(shown.mesh.view(torch.uint8).view(-1), host[plain.mesh_at:plain.nbytes])
+    assert tuple(shown.mesh.shape) == (n, k, v, 3)
     host1 = torch.randint(0, 256, (total,), generator=g, dtype=torch.uint8)
     host1[:mo] = 0
-    r1 = LiveOutput(None, None, torch.empty((n, v, 3)), None, host1, n, None, torch.empty((n, h, w, 3), dtype=torch.uint8)).read()
+    r1 = LiveOutput(None, None, torch.empty((n, v, 3)), None, host1, n, None, torch.empty((n, h, w, 3), dtype=torch.uint8),
+                    layout=one_ext).read()
     assert len(r1) == 7 and torch.equal(r1.overlay, host1[oo:].view(n, h, w, 3)) and tuple(r1.mesh.shape) == (n, v, 3)
 
 
