@@ -16,8 +16,10 @@ With --left the step runs in the caller's mirror mode for a left-handed subject 
 frame and depth map are mirrored before anything else and every result is in the mirrored frame.  With --handed the last frame
 also goes through the K = 2 step with per-slot handedness: the detector's side of each slot, and which slots ran mirrored
 through the right-handed pose network and lifter (side == left_side; 0 is an assumption about the checkpoint's convention).
+With --track a few frames go through the K = 2 step with tracked slots (live_hands(track=True)): the track id and age of every
+slot are printed per frame -- a hand keeps its slot and id whatever its score rank, a slot whose hand is missing is held.
 usage (GPU box): python examples/live_demo.py [frames] [--overlay out.png] [--mano MANO_RIGHT.pkl] [--labels PREFIX] [--left]
-                 [--handed]"""
+                 [--handed] [--track]"""
 import sys
 import time
 import types
@@ -55,8 +57,8 @@ def main():
             i = argv.index(flag)
             opt[flag] = argv[i + 1]
             del argv[i:i + 2]
-    left, handed = "--left" in argv, "--handed" in argv
-    argv = [a for a in argv if a not in ("--left", "--handed")]
+    left, handed, track = "--left" in argv, "--handed" in argv, "--track" in argv
+    argv = [a for a in argv if a not in ("--left", "--handed", "--track")]
     frames = int(argv[0]) if argv else 20
     faces = _faces(opt.get("--mano")) if "--overlay" in opt else None
     args = types.SimpleNamespace(pretrained_fcos="-", pretrained_a2j="-")
@@ -117,6 +119,19 @@ def main():
             r2 = o2.read()
             print(f"6. handed: side per slot {r2.side.tolist()} (-1: empty), mirrored {o2.mirror.tolist()}, lifted {r2.lifted.tolist()}; "
                   f"mesh {tuple(r2.mesh.shape)} in the frame's own coordinates")
+        if track:                                                                         # stable slots and ids across frames
+            tracked = net.live_hands(model, PARAS, max_hands=2, clamp=True, perm_reverse=rev, track=True, track_iou=0.3,
+                                     track_hold=5)
+            tracked.track_reset()
+            run, t_img, t_dep, o3 = tracked.graphed(rgb, depth)
+            for i in range(min(frames, 6)):
+                t_img.copy_(synth.make_rgb(1, seed=1000 + i // 2).cuda())                  # (every frame twice: ages count up)
+                t_dep.copy_(synth.make_depth(1, seed=2000 + i // 2).cuda())
+                run()
+                torch.cuda.current_stream().synchronize()
+                r3 = o3.read()
+                print(f"7. track, frame {i}: id per slot {r3.track_id[0].tolist()} (0: free), age {r3.track_age[0].tolist()}, "
+                      f"filled {(r3.has_hand[0] != 0).tolist()}, detection {r3.det_index[0].tolist()}")
 
 
 if __name__ == "__main__":

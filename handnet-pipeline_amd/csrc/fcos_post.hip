@@ -1017,6 +1017,186 @@ __global__ __launch_bounds__(64) void hand_slots_kernel(const float* __restrict_
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// tracked hands: the slots carry over from one step to the next
+// ---------------------------------------------------------------------------------------
+constexpr int kTrackWords = 12;     // int32 words of a state row: box (4 x int64) | id | age | missed | 0
+
+// position of the n-th (0-based) set bit of m, -1 when m has no more than n (n <= 15)
+__device__ __forceinline__ int nth_set_bit(unsigned long long m, int n) {
+  for (int j = 0; j < kMaxHands - 1; ++j)
+    if (j < n) m &= m - 1ull;
+  return m ? __ffsll((long long)m) - 1 : -1;
+}
+
+// (I, U, key) of one slot x candidate pair; key = slot * 16 + cand, the lower key wins an exact tie.  I == 0: not eligible.
+struct TrackPair {
+  unsigned i, u, key;
+};
+
+// a beats b: larger I / U (cross-multiplied, 32 x 32 -> 64 bits: I, U < 2^31 for frames up to 32767 a side), then lower key
+__device__ __forceinline__ bool pair_beats(const TrackPair& a, const TrackPair& b) {
+  const unsigned long long l = (unsigned long long)a.i * b.u, r = (unsigned long long)b.i * a.u;
+  return l > r || (l == r && a.key < b.key);
+}
+
+// hand_slots_kernel with the association of DESIGN.md 9e, one wave64 per frame: the first 16 hand detections of the frame's
+// list are the candidates (candidate c in the registers of lane c), lane s < K holds track slot s of the frame's state row (read
+// whole before anything is written; updated in place), the K x 16 pairs lie four to a lane (lane = 16 * (slot % 4) + cand, its
+// j-th pair is slot lane / 16 + 4 j) and every greedy round is one wave-wide arg-max.  Integer arithmetic on the padded boxes
+// only: h, w <= 32767 keeps a coordinate in 15 bits, an area in 30 and I * U in 61.
+template <bool SIDED>
+__global__ __launch_bounds__(64) void hand_slots_tracked_kernel(
+    const float* __restrict__ det_boxes, const float* __restrict__ det_scores, const int* __restrict__ det_labels,
+    const int* __restrict__ det_count, int cap, int hand_label, int max_hands, int h, int w, long long* __restrict__ crop_box,
+    int* __restrict__ has_hand, float* __restrict__ score, int* __restrict__ det_index, const int* __restrict__ det_sides,
+    int left_side, int* __restrict__ side, int* __restrict__ mirror, int* __restrict__ state, int thr_milli, int hold,
+    int* __restrict__ track_id, int* __restrict__ track_age) {
+  typedef int i32x4 __attribute__((ext_vector_type(4)));
+  typedef long long i64x2 __attribute__((ext_vector_type(2)));
+  const int img = blockIdx.x, lane = threadIdx.x;
+  const int cnt = min(det_count[img], cap);
+  const long row = (long)img * cap;
+
+  // the frame's state row, before anything is written
+  int* st_row = state + (long)img * (1 + max_hands) * kTrackWords;
+  const int header = st_row[0];
+  int sx1 = 0, sy1 = 0, sx2 = 0, sy2 = 0, sid = 0, sage = 0, smiss = 0;
+  if (lane < max_hands) {
+    const int* p = st_row + (1 + lane) * kTrackWords;
+    const i64x2 lo = *reinterpret_cast<const i64x2*>(p), hi = *reinterpret_cast<const i64x2*>(p + 4);
+    const i32x4 t = *reinterpret_cast<const i32x4*>(p + 8);
+    sx1 = (int)lo[0]; sy1 = (int)lo[1]; sx2 = (int)hi[0]; sy2 = (int)hi[1];
+    sid = t[0]; sage = t[1]; smiss = t[2];
+  }
+
+  // 1. candidates: the first 16 hand detections, candidate c on lane c
+  int ncand = 0;
+  int cx1 = 0, cy1 = 0, cx2 = 0, cy2 = 0, cok = 0, cidx = -1, csd = -1;
+  float csc = 0.f;
+  for (int base = 0; base < cnt && ncand < kMaxHands; base += 64) {
+    const int i = base + lane;
+    const bool hand = i < cnt && det_labels[row + i] == hand_label;
+    const unsigned long long mask = __ballot(hand);
+    long long b[4] = {0, 0, 0, 0};
+    int ok = 0, sd = -1;
+    float sc = 0.f;
+    if (hand) {
+      ok = pad_hand_box(det_boxes + (row + i) * 4, h, w, b);
+      sc = det_scores[row + i];
+      if (SIDED) sd = det_sides[row + i];
+    }
+    const int want = lane - ncand;
+    const bool take = lane < kMaxHands && want >= 0 && want < __popcll(mask);
+    const int src = take ? nth_set_bit(mask, want) : lane;
+    const int gx1 = __shfl((int)b[0], src), gy1 = __shfl((int)b[1], src), gx2 = __shfl((int)b[2], src),
+              gy2 = __shfl((int)b[3], src), gok = __shfl(ok, src), gsd = __shfl(sd, src);
+    const float gsc = __shfl(sc, src);
+    if (take) {
+      cx1 = gx1; cy1 = gy1; cx2 = gx2; cy2 = gy2; cok = gok; csd = gsd; csc = gsc; cidx = base + src;
+    }
+    ncand = min(kMaxHands, ncand + __popcll(mask));
+  }
+  const bool cvalid = lane < ncand && cok;
+
+  // 2. pairs: this lane's candidate against its (up to) four slots
+  const int pc = lane & 15, ps = lane >> 4;
+  const int qx1 = __shfl(cx1, pc), qy1 = __shfl(cy1, pc), qx2 = __shfl(cx2, pc), qy2 = __shfl(cy2, pc);
+  const int qvalid = __shfl((int)cvalid, pc);
+  const unsigned carea = (unsigned)((qx2 - qx1) * (qy2 - qy1));
+  TrackPair pr[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int s = ps + 4 * j;
+    const int tx1 = __shfl(sx1, s), ty1 = __shfl(sy1, s), tx2 = __shfl(sx2, s), ty2 = __shfl(sy2, s), tid = __shfl(sid, s);
+    const int iw = max(0, min(tx2, qx2) - max(tx1, qx1)), ih = max(0, min(ty2, qy2) - max(ty1, qy1));
+    const unsigned inter = (unsigned)(iw * ih);
+    const unsigned uni = (unsigned)((tx2 - tx1) * (ty2 - ty1)) + carea - inter;
+    const bool eligible = tid != 0 && qvalid && inter > 0 &&
+                          1000ull * inter >= (unsigned long long)thr_milli * uni;
+    pr[j].i = eligible ? inter : 0u;
+    pr[j].u = eligible ? uni : 1u;
+    pr[j].key = (unsigned)(s * 16 + pc);
+  }
+
+  // 3. greedy match: the best pair left, wave-wide, until none is eligible
+  unsigned slot_done = 0, cand_done = 0;      // bit sets, the same on every lane
+  int mycand = -1;                            // lane s < K: the candidate its slot took
+  const int rounds = min(max_hands, kMaxHands);
+  for (int r = 0; r < rounds; ++r) {
+    TrackPair best = {0u, 1u, 0xffffu};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      TrackPair p = pr[j];
+      if ((slot_done >> (ps + 4 * j)) & 1u || (cand_done >> pc) & 1u) { p.i = 0u; p.u = 1u; }
+      if (pair_beats(p, best)) best = p;
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+      TrackPair o;
+      o.i = __shfl_xor(best.i, m); o.u = __shfl_xor(best.u, m); o.key = __shfl_xor(best.key, m);
+      if (pair_beats(o, best)) best = o;
+    }
+    if (best.i == 0u) break;                  // (the same on every lane: the arg-max is a total order)
+    const int ms = (int)(best.key >> 4), mc = (int)(best.key & 15u);
+    slot_done |= 1u << ms;
+    cand_done |= 1u << mc;
+    if (lane == ms) mycand = mc;
+  }
+
+  // 4. unmatched live slots: held, or freed once missed for more than `hold` steps
+  const bool live = lane < max_hands && sid != 0;
+  if (live && mycand < 0) {
+    smiss += 1;
+    if (smiss > hold) { sx1 = sy1 = sx2 = sy2 = 0; sid = sage = smiss = 0; }
+  } else if (live) {
+    sage += 1;
+    smiss = 0;
+  }
+
+  // 5. unmatched candidates, in score order, into the free slots, lowest first
+  const unsigned free_mask = (unsigned)__ballot(lane < max_hands && sid == 0);
+  const unsigned new_mask = (unsigned)__ballot(cvalid && !((cand_done >> lane) & 1u));
+  const int admitted = min(__popc(free_mask), __popc(new_mask));
+  if (lane < max_hands && sid == 0) {
+    const int q = __popc(free_mask & ((1u << lane) - 1u));
+    if (q < admitted) {
+      mycand = nth_set_bit(new_mask, q);
+      sid = header + q + 1;
+      sage = 0; smiss = 0;
+    }
+  }
+
+  // 6. the slots' outputs and the new state (every lane takes part in the gather of its candidate's registers)
+  const int from = mycand >= 0 ? mycand : lane;
+  const int nx1 = __shfl(cx1, from), ny1 = __shfl(cy1, from), nx2 = __shfl(cx2, from), ny2 = __shfl(cy2, from),
+            nidx = __shfl(cidx, from), nsd = __shfl(csd, from);
+  const float nsc = __shfl(csc, from);
+  if (lane < max_hands) {
+    const long slot = (long)img * max_hands + lane;
+    const bool filled = mycand >= 0;
+    if (filled) { sx1 = nx1; sy1 = ny1; sx2 = nx2; sy2 = ny2; }
+    const long long ob[4] = {filled ? sx1 : 0, filled ? sy1 : 0, filled ? sx2 : 0, filled ? sy2 : 0};
+    write_slot(slot, ob, filled ? 1 : 0, nsc, nidx, crop_box, has_hand, score, det_index);
+    if (SIDED) {
+      side[slot] = filled ? nsd : -1;
+      mirror[slot] = (filled && nsd == left_side) ? 1 : 0;
+    }
+    track_id[slot] = sid;
+    track_age[slot] = sage;
+    int* p = st_row + (1 + lane) * kTrackWords;
+    *reinterpret_cast<i64x2*>(p) = i64x2{sx1, sy1};
+    *reinterpret_cast<i64x2*>(p + 4) = i64x2{sx2, sy2};
+    *reinterpret_cast<i32x4*>(p + 8) = i32x4{sid, sage, smiss, 0};
+  }
+  if (lane == 0) {
+    const i32x4 z = {0, 0, 0, 0};
+    *reinterpret_cast<i32x4*>(st_row) = i32x4{header + admitted, 0, 0, 0};
+    *reinterpret_cast<i32x4*>(st_row + 4) = z;
+    *reinterpret_cast<i32x4*>(st_row + 8) = z;
+  }
+}
+
 // crop_gather_kernel over n * max_hands crops: crop `slot` reads frame slot / max_hands
 // SIDED: a slot with mirror != 0 is cut mirrored -- its pixel (oy, ox) is the plain crop's pixel (oy, out - 1 - ox): the
 // source-column rule below, evaluated at out - 1 - ox
@@ -1375,4 +1555,52 @@ extern "C" int hn_crop_resize_hands_sided(const float* det_boxes, const float* d
   return crop_resize_hands_run("hn_crop_resize_hands_sided", det_boxes, det_scores, det_labels, det_sides, det_count, cap,
                                hand_label, left_side, max_hands, depth, n, in_ch, reorder_bgr, h, w, out, cpad, crop_box,
                                has_hand, score, det_index, side, mirror, crops, stream);
+}
+
+extern "C" int64_t hn_track_state_bytes(int n, int max_hands) {
+  if (n <= 0 || max_hands < 1 || max_hands > kMaxHands) return 0;
+  return (int64_t)n * (1 + max_hands) * kTrackWords * 4;
+}
+
+extern "C" int hn_crop_resize_hands_tracked(const float* det_boxes, const float* det_scores, const int32_t* det_labels,
+                                            const int32_t* det_sides, const int32_t* det_count, int cap, int hand_label,
+                                            int left_side, int max_hands, const float* depth, int n, int in_ch, int reorder_bgr,
+                                            int h, int w, int out, int cpad, int64_t* crop_box, int32_t* has_hand, float* score,
+                                            int32_t* det_index, int32_t* side, int32_t* mirror, float* crops, int32_t* state,
+                                            int thr_milli, int hold, int32_t* track_id, int32_t* track_age, void* stream) {
+  HN_CHECK_ARG(det_boxes && det_scores && det_labels && det_count && depth && crop_box && has_hand && score && det_index && crops &&
+                   state && track_id && track_age,
+               "hn_crop_resize_hands_tracked: null pointer");
+  HN_CHECK_ARG((det_sides && side && mirror) || (!det_sides && !side && !mirror),
+               "hn_crop_resize_hands_tracked: det_sides, side and mirror go together (all given, or all NULL)");
+  HN_CHECK_ARG(max_hands >= 1 && max_hands <= kMaxHands, "max_hands must be 1..%d (got %d)", kMaxHands, max_hands);
+  HN_CHECK_ARG(n > 0 && h > 0 && w > 0 && out > 0 && cap > 0 && cpad >= 4 && cpad % 4 == 0, "bad dims");
+  HN_CHECK_ARG(h <= 32767 && w <= 32767, "tracked hands: frames of at most 32767 x 32767 pixels (got %d x %d)", h, w);
+  HN_CHECK_ARG(in_ch >= 1 && in_ch <= 4, "depth image must have 1..4 channels (got %d)", in_ch);
+  HN_CHECK_ARG(thr_milli >= 1 && thr_milli <= 1000, "thr_milli must be 1..1000 (got %d)", thr_milli);
+  HN_CHECK_ARG(hold >= 0 && hold <= 1000000, "hold must be 0..1000000 (got %d)", hold);
+  HN_CHECK_ARG((uintptr_t)crop_box % 16 == 0 && (uintptr_t)crops % 16 == 0, "crop_box / crops must be 16-byte aligned");
+  HN_CHECK_ARG((uintptr_t)state % 16 == 0, "state must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const long total = (long)n * max_hands * out * out;
+  if (det_sides) {
+    hipLaunchKernelGGL(hand_slots_tracked_kernel<true>, dim3(n), dim3(64), 0, st, det_boxes, det_scores, det_labels, det_count,
+                       cap, hand_label, max_hands, h, w, (long long*)crop_box, has_hand, score, det_index, det_sides, left_side,
+                       side, mirror, state, thr_milli, hold, track_id, track_age);
+    HN_CHECK_LAUNCH("hand_slots_tracked_kernel");
+    hipLaunchKernelGGL(hand_crop_gather_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, st, depth,
+                       (const long long*)crop_box, has_hand, n, max_hands, h, w, in_ch, reorder_bgr, out, cpad / 4, crops,
+                       (const int*)mirror);
+    HN_CHECK_LAUNCH("hand_crop_gather_kernel");
+    return HN_OK;
+  }
+  hipLaunchKernelGGL(hand_slots_tracked_kernel<false>, dim3(n), dim3(64), 0, st, det_boxes, det_scores, det_labels, det_count,
+                     cap, hand_label, max_hands, h, w, (long long*)crop_box, has_hand, score, det_index, (const int*)nullptr, 0,
+                     (int*)nullptr, (int*)nullptr, state, thr_milli, hold, track_id, track_age);
+  HN_CHECK_LAUNCH("hand_slots_tracked_kernel");
+  hipLaunchKernelGGL(hand_crop_gather_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, st, depth,
+                     (const long long*)crop_box, has_hand, n, max_hands, h, w, in_ch, reorder_bgr, out, cpad / 4, crops,
+                     (const int*)nullptr);
+  HN_CHECK_LAUNCH("hand_crop_gather_kernel");
+  return HN_OK;
 }

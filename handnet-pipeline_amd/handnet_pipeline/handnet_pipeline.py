@@ -121,7 +121,8 @@ class HandNet(EngineOwner):
                               faces, labels, left)
 
     def live_hands(self, lifter, paras, max_hands: int = 2, clamp: bool = True, perm_reverse=None, faces=None,
-                   labels: bool = False, left: bool = False, handed: bool = False, left_side: int = 0):
+                   labels: bool = False, left: bool = False, handed: bool = False, left_side: int = 0, track: bool = False,
+                   track_iou: float = 0.3, track_hold: int = 5):
         """live() for up to max_hands (1..16) hands per frame (hn_amd.live.LiveHandsEngine): forward_hands' slots, the
         caller's clamp + convert_joints, the lifter's input with the caller's skip rule per slot (a hand whose 2D box
         process_bbox refuses is not lifted: ros_demo.py:288-300), Pose2Mesh on every slot, one device -> host copy.
@@ -133,14 +134,18 @@ class HandNet(EngineOwner):
         left: as for live().  handed: per-slot handedness instead -- read().side is the detector's side of every slot and a
         slot whose side equals left_side goes mirrored through the right-handed A2J and Pose2Mesh and comes back un-mirrored, so
         a left hand's mesh has its thumb on the right side; no launch is added.  left_side = 0 assumes the 100DOH
-        convention of the detector's training targets, which the reference does not state.  left with handed: ValueError."""
+        convention of the detector's training targets, which the reference does not state.  left with handed: ValueError.
+        track: the slots are tracked from step to step (batch row i = one camera stream): a hand keeps its slot and its
+        read().track_id while its padded box overlaps the slot's last one with IoU >= track_iou, a slot whose hand is missing is
+        held empty for track_hold steps, and max_hands=1 sticks to its hand instead of jumping to the top score
+        (engine.track_reset() starts over)."""
         from hn_amd.live import LiveHandsEngine
         k = ops.check_max_hands(max_hands)
         if left and handed:
             raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
         self._convert_cfg = (tuple(paras), bool(clamp))
         return LiveHandsEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, k, clamp,
-                               perm_reverse, faces, labels, left, handed, left_side)
+                               perm_reverse, faces, labels, left, handed, left_side, track, track_iou, track_hold)
 
     # forward() switches ITSELF to hipGraph replay once the same input shapes have come in a few times in a row -- the live
     # caller's case (ros_demo.py:270-273: one 640x480 frame per call, ~150 dependent launches whose host cost is 8 % of the
@@ -168,7 +173,7 @@ class HandNet(EngineOwner):
             self._auto_graph_allowed = True
         return self
 
-    def _auto_graph(self, image_shape, depth_shape, on_gpu=True, hands=None, handed=(False, 0)) -> bool:
+    def _auto_graph(self, image_shape, depth_shape, on_gpu=True, hands=None, handed=(False, 0), tracked=None) -> bool:
         """Whether this call of forward() (hands = K: of forward_hands()) should run as a graph replay (capturing first if
         need be)."""
         eng = self.engine()
@@ -176,9 +181,11 @@ class HandNet(EngineOwner):
         if not self._auto_graph_allowed or eng.check_range or sparse or not on_gpu:
             return False
         if (eng.has_graph(image_shape, depth_shape, to_host=True) if hands is None
-                else eng.has_graph_hands(image_shape, depth_shape, hands, to_host=True, handed=handed[0], left_side=handed[1])):
+                else eng.has_graph_hands(image_shape, depth_shape, hands, to_host=True, handed=handed[0], left_side=handed[1],
+                                         **(tracked or {}))):
             return True
         key = (tuple(image_shape), tuple(depth_shape)) + (() if hands is None else (hands,)) + (handed if handed[0] else ())
+        key += tuple(sorted((tracked or {}).items()))
         if key == getattr(self, "_streak_key", None):
             self._streak += 1
         else:
@@ -248,7 +255,8 @@ class HandNet(EngineOwner):
         return self._finish(out, n, depth_images)
 
     def forward_hands(self, images, depth_images, max_hands: int = 2, is_3D: bool = False, is_detect: bool = False,
-                      handed: bool = False, left_side: int = 0):
+                      handed: bool = False, left_side: int = 0, track: bool = False, track_iou: float = 0.3,
+                      track_hold: int = 5):
         """forward() for up to max_hands (1..16) hands per frame.  Slot k of frame i is the k-th hand-class detection of
         frame i in the detector's score order (the reference keeps slot 0 only, handnet_pipeline.py:84-85), padded and
         cropped as forward() crops it.  images / depth_images as forward() takes them.  Returns
@@ -262,13 +270,18 @@ class HandNet(EngineOwner):
         handed: a sixth result, sides [N,K] int32 on the CPU (the detector's side of the slot's detection, -1 for empty slots),
         and a slot whose side equals left_side goes through the right-handed A2J mirrored (its crop in depth_batch is flipped
         along the width) and its keypoints come back un-mirrored (u = 176 - u).  left_side = 0 assumes the 100DOH convention
-        of the detector's training targets, which the reference does not state."""
+        of the detector's training targets, which the reference does not state.
+        track: the slots are tracked from call to call (engine().forward_hands(track=True); engine().track_reset() starts
+        over) and two more results end the tuple: track_id and track_age [N,K] int32 on the CPU."""
         if is_detect or is_3D:
             return None
         if depth_images is None:
             raise ValueError("depth_images is required for the ensemble inference branch")
         k = ops.check_max_hands(max_hands)
         handed, left_side = bool(handed), int(left_side)
+        tracked = dict(track=True, track_iou=track_iou, track_hold=track_hold) if track else {}
+        if track:
+            ops.check_track_options(track_iou, track_hold)
         eng = self.engine()
         n = len(images)
         dev = eng.device
@@ -276,27 +289,27 @@ class HandNet(EngineOwner):
         batch, depth = batch.to(dev).float().contiguous(), depth_images.to(dev).float().contiguous()
         mode = getattr(self, "use_graph", None)
         graph = bool(mode) if mode is not None else self._auto_graph(batch.shape, depth.shape, True, hands=k,
-                                                                     handed=(handed, left_side))
+                                                                     handed=(handed, left_side), tracked=tracked)
 
         def captured():
             run, s_img, s_dep, out = eng.graphed_hands(batch, depth, k, to_host=True, limit=self.AUTO_GRAPH_MAX_SHAPES,
-                                                       handed=handed, left_side=left_side)
+                                                       handed=handed, left_side=left_side, **tracked)
             s_img.copy_(batch)
             s_dep.copy_(depth)
             run()
             return out
         out = self._graph_or_eager(graph, captured, lambda: eng.forward_hands(batch, depth, k, to_host=True, handed=handed,
-                                                                              left_side=left_side))
-        return self._finish_hands(out, n, k, depth, handed)
+                                                                              left_side=left_side, **tracked))
+        return self._finish_hands(out, n, k, depth, handed, bool(track))
 
-    def _finish_hands(self, out, n, k, depth, handed=False):
+    def _finish_hands(self, out, n, k, depth, handed=False, tracked=False):
         """forward_hands()'s tuple from the step's one host record (see _finish)."""
         from hn_amd.pipeline import read_hands_tail
         rows = n * k
         sel = out.crops_nhwc
         depth_all = (sel.permute(0, 3, 1, 2) if self.RGBD else sel[..., 0].unsqueeze(1)).contiguous()
         kp, box, mask, filled = self._read_step(out, (n, k), "_last_sparse_hands", depth)
-        scores, _, *sides = read_hands_tail(out.host_record, rows, handed)
+        scores, _, *sides = read_hands_tail(out.host_record, rows, handed, tracked)      # (sides: + the track ids and ages)
         if filled == rows:
             depth_batch = depth_all
         else:

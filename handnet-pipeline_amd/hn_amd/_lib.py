@@ -224,6 +224,10 @@ SIGNATURES = {
                                                       C.POINTER(ConvertOpts), VP, VP, VP, VP]),
     "hn_lifter_input_gated_mirror_f32": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, VP, VP, VP]),
     "hn_mesh_finish_mirror_f32": (C.c_int, [VP] * 5 + [C.c_int] * 4 + [VP, VP]),
+    # tracked hand slots (new functions under ABI 36)
+    "hn_crop_resize_hands_tracked": (C.c_int, [VP] * 5 + [C.c_int] * 4 + [VP] + [C.c_int] * 7 + [VP] * 8
+                                     + [C.c_int, C.c_int, VP, VP, VP]),
+    "hn_track_state_bytes": (C.c_int64, [C.c_int, C.c_int]),
 }
 
 _lock = threading.Lock()

@@ -51,14 +51,16 @@ def _final_mesh_perm(perm_reverse, lifter, device):
 POSE_LABEL = ops.LABEL_CROP                           # side of a pose_label image
 
 LiveViews = collections.namedtuple("LiveViews", "records side lifted mesh overlay box_label pose_label")
+# ... and of a tracked step: the same fields, then the two rows of the tracker
+LiveTrackedViews = collections.namedtuple("LiveTrackedViews", LiveViews._fields + ("track_id", "track_age"))
 
 
 @dataclass(frozen=True)
 class LiveLayout:
     """Byte layout of a live step's one copy buffer, in this order: the records (one-hand step: a wide record per frame + the
     range-word row; K-hand step: forward_hands' wide record unchanged -- a row per slot, the range-word row, the scores and
-    detection ranks: hands_record_rows), `side` int32 [slots] (handed steps: the detector's side per slot), `lifted` int32
-    [slots] (K-hand steps), the mesh fp32 [slots,V,3], the overlay uint8 [frames,h,w,3], box_label uint8 [frames,h,w,3] and
+    detection ranks: hands_record_rows), `side` int32 [slots] (handed steps: the detector's side per slot), `track_id` and
+    `track_age` int32 [slots] each (tracked steps), `lifted` int32 [slots] (K-hand steps), the mesh fp32 [slots,V,3], the overlay uint8 [frames,h,w,3], box_label uint8 [frames,h,w,3] and
     pose_label uint8 [slots,176,176,3] (each label image starts on a dword: the kernels store three dwords per four pixels).
     slots = frames for the one-hand step (hands None), frames * hands for the K-hand step.  A part the step does not have takes
     no bytes and its offset is None; every part in front of it stays where a step without the option has it."""
@@ -69,9 +71,12 @@ class LiveLayout:
     overlay: bool = False
     labels: bool = False
     handed: bool = False
+    tracked: bool = False
     record_rows: int = field(init=False)
     record_bytes: int = field(init=False)
     side_at: int = field(init=False)
+    track_id_at: int = field(init=False)
+    track_age_at: int = field(init=False)
     lifted_at: int = field(init=False)
     mesh_at: int = field(init=False)
     overlay_at: int = field(init=False)
@@ -80,8 +85,8 @@ class LiveLayout:
     nbytes: int = field(init=False)
 
     def __post_init__(self):
-        if ((self.overlay or self.labels) and self.hw is None) or (self.handed and self.hands is None):
-            raise ValueError("an overlay or label images need the frames' (h, w), and handed is a K-hand step's option")
+        if ((self.overlay or self.labels) and self.hw is None) or ((self.handed or self.tracked) and self.hands is None):
+            raise ValueError("an overlay or label images need the frames' (h, w), and handed / tracked are a K-hand step's options")
         s, rb = self.slots, record_bytes(3)
         rows = self.frames + 1 if self.hands is None else hands_record_rows(s, rb)
         image = None if self.hw is None else (self.frames, *self.hw, 3)
@@ -89,6 +94,8 @@ class LiveLayout:
         end, spans = 0, {}
         for name, present, dtype, shape, align in (("records", True, torch.uint8, (rows, rb), 1),
                                                    ("side", self.handed, torch.int32, (s,), 1),
+                                                   ("track_id", self.tracked, torch.int32, (s,), 1),
+                                                   ("track_age", self.tracked, torch.int32, (s,), 1),
                                                    ("lifted", self.hands is not None, torch.int32, (s,), 1),
                                                    ("mesh", True, torch.float32, (s, self.vertices, 3), 1),
                                                    ("overlay", self.overlay, torch.uint8, image, 1),
@@ -113,18 +120,19 @@ class LiveLayout:
     def views(self, buf) -> LiveViews:
         """The parts of a step's flat uint8 buffer (the device buffer or its pinned copy), typed and shaped; None: not there."""
         cut = {name: buf[a:b].view(dtype).view(shape) for name, (a, b, dtype, shape) in self._spans.items()}
-        return LiveViews(*(cut.get(name) for name in LiveViews._fields))
+        kind = LiveTrackedViews if self.tracked else LiveViews
+        return kind(*(cut.get(name) for name in kind._fields))
 
 
 @functools.lru_cache(maxsize=None)
-def _read_type(step: str, base: tuple, overlay: bool, labels: bool, side: bool):
-    """The namedtuple a step's read() returns: the base fields, then overlay, box_label + pose_label and side, each only when the
-    step has it; an absent image (overlay / box_label / pose_label) reads as a None class attribute.  (One class per
-    combination: call it with positional arguments only, the cache keys on them.)"""
-    has = dict(overlay=overlay, box_label=labels, pose_label=labels, side=side)
+def _read_type(step: str, base: tuple, overlay: bool, labels: bool, side: bool, tracked: bool = False):
+    """The namedtuple a step's read() returns: the base fields, then overlay, box_label + pose_label, side and track_id +
+    track_age, each only when the step has it; an absent image (overlay / box_label / pose_label) reads as a None class
+    attribute.  (One class per combination: call it with positional arguments only, the cache keys on them.)"""
+    has = dict(overlay=overlay, box_label=labels, pose_label=labels, side=side, track_age=tracked, track_id=tracked)
     fields = base + tuple(f for f, on in has.items() if on)
-    name = step + "Overlay" * overlay + "Labels" * labels + "Sided" * side + "Read"
-    absent = {f: None for f, on in has.items() if not on and f != "side"}
+    name = step + "Overlay" * overlay + "Labels" * labels + "Sided" * side + "Tracked" * tracked + "Read"
+    absent = {f: None for f, on in has.items() if not on and f not in ("side", "track_id", "track_age")}
     doc = f"{step}Output.read(): {' '.join(base)}" + "".join(f" + {f}" for f in fields[len(base):]) + "."
     return type(name, (collections.namedtuple(name, fields),), dict(absent, __slots__=(), __doc__=doc))
 
@@ -137,6 +145,9 @@ def _read(step, base, values, layout, v, per_slot=lambda t: t):
         values += (v.box_label.clone(), per_slot(v.pose_label).clone())
     if layout.handed:
         values += (per_slot(v.side).clone(),)
+    if layout.tracked:
+        values += (per_slot(v.track_age).clone(), per_slot(v.track_id).clone())
+        return _read_type(step, base, layout.overlay, layout.labels, layout.handed, True)(*values)
     return _read_type(step, base, layout.overlay, layout.labels, layout.handed)(*values)
 
 
@@ -178,6 +189,7 @@ class _LiveStep:
     (_lifter_input), how the mesh is finished (_mesh) and what the step hands out (_output)."""
     hands = None                 # K of the K-hand step
     handed = False
+    track = None                 # the tracked K-hand step: (track_iou, track_hold)
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None,
                  labels: bool = False, left: bool = False):
@@ -241,7 +253,7 @@ class _LiveStep:
     def _layout(self, n, hw=None) -> LiveLayout:
         """The buffer of a step over n frames (hw: of a step that draws, the frames' size)."""
         return LiveLayout(n, self.hands, self.vertices, hw, hw is not None and self.faces is not None,
-                          hw is not None and self.labels, self.handed)
+                          hw is not None and self.labels, self.handed, self.track is not None)
 
     def _new_buffers(self, n, hw=None):
         """A fresh (layout, device buffer, pinned host buffer) of a step over n frames."""
@@ -322,8 +334,12 @@ class _LiveStep:
                     # the capture's mirrored inputs: owned by the engine for as long as the capture lives (their addresses are
                     # baked into the graph, and nothing the step hands out refers to them)
                     flipped = self._mirrored[("capture",) + key] = (torch.empty_like(s_img), torch.empty_like(s_dep))
-                g, out = ops.capture_step(lambda: self.forward_device(s_img, s_dep, _buffers=bufs,
-                                                                      _mirror=False if _mirrored else flipped))
+                step = lambda: self.forward_device(s_img, s_dep, _buffers=bufs, _mirror=False if _mirrored else flipped)
+                if self.track is not None:      # (the warm-up steps of a capture must not advance the tracker)
+                    with self.hand._track_untouched(images.shape[0], self.hands):
+                        g, out = ops.capture_step(step)
+                else:
+                    g, out = ops.capture_step(step)
             hit = self._graphs[key] = (g, s_img, s_dep, out)
         g, s_img, s_dep, out = hit
         return g.replay, s_img, s_dep, out
@@ -383,12 +399,15 @@ class LiveHandsOutput:
     side: torch.Tensor = None        # handed steps: [N,K] int32 on the device, the detector's side per slot (-1: empty slot)
     mirror: torch.Tensor = None      # handed steps: [N,K] int32 on the device, 1 where the slot ran mirrored (a left hand)
     layout: LiveLayout = None        # where everything lies in `host`
+    track_id: torch.Tensor = None    # tracked steps: [N,K] int32 on the device, the slot's track id (held slots included; 0: free)
+    track_age: torch.Tensor = None   # tracked steps: [N,K] int32 on the device, the steps on which the slot's track was seen again
 
     def read(self) -> LiveHandsRead:
         """After the stream is synchronised: the step's results per frame and slot as fresh CPU tensors (LiveHandsRead;
         lifted as bool, words = the step's range words; a step with faces=: LiveHandsOverlayRead, + overlay [N,H,W,3] uint8; a
         step with labels: + box_label [N,H,W,3], pose_label [N,K,176,176,3] -- LiveHandsLabelsRead, LiveHandsOverlayLabelsRead;
-        a handed step: the same with `side` [N,K] int32 as the last field)."""
+        a handed step: the same with `side` [N,K] int32 behind them; a tracked step: track_age and then track_id [N,K] int32
+        as the last fields)."""
         v, s = self.layout.views(self.host), self.layout.slots
         per = lambda t: t.reshape((self.layout.frames, self.layout.hands) + tuple(t.shape[1:]))
         kp, has, box, words, (img, xyz) = read_host_record(v.records, s, extras=True)
@@ -408,7 +427,7 @@ class LiveHandsEngine(_LiveStep):
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, max_hands: int = 2, clamp: bool = True,
                  perm_reverse=None, faces=None, labels: bool = False, left: bool = False, handed: bool = False,
-                 left_side: int = 0):
+                 left_side: int = 0, track: bool = False, track_iou: float = 0.3, track_hold: int = 5):
         """faces: mesh_model.face ([F,3]; needs perm_reverse) -- given, the step ends with the overlay: every lifted mesh of a
         frame drawn over it with one depth buffer per frame (LiveHandsOutput.overlay, read().overlay), in the same copy.
         labels: the step ends with box_label (the crop box of every lifted slot on its frame) and one pose_label per slot
@@ -422,17 +441,32 @@ class LiveHandsEngine(_LiveStep):
         mesh and images are in the frame's own coordinates; slots that are not mirrored are the plain step's, bit for bit.
         left_side = 0 is an ASSUMPTION: the detector's side targets are box_info[:, 1] of its training set, whose convention
         (100DOH: 0 = left) the reference does not state -- it never reads `sides`.  Check it on your checkpoint.
-        left and handed together: ValueError (a mirrored frame swaps the sides)."""
+        left and handed together: ValueError (a mirrored frame swaps the sides).
+        track: the slots are tracked from step to step (HandNetEngine.forward_hands(track=True)): batch row i is
+        one camera stream, a hand keeps its slot and its id (LiveHandsOutput.track_id, read().track_id) whatever its score
+        rank, and a slot whose hand is missing is held for track_hold steps -- has_hand 0, so not lifted, a zero mesh, nothing
+        drawn and a zero pose_label, the path of every empty slot.  max_hands = 1 is the sticky top-1.  The state lives in the
+        hand engine, one per (N, K), shared by forward_device, graphed and forward_raw; track_reset() empties it."""
         self.hands = self.max_hands = ops.check_max_hands(max_hands)
         if left and handed:
             raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
         self.handed, self.left_side = bool(handed), int(left_side)
+        self.track = (float(track_iou), track_hold) if track else None
+        if track:
+            ops.check_track_options(track_iou, track_hold)
         super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left)
 
     def _hand_step(self, images, depth, at, lift):
         # (the per-slot records, range words, scores and ranks go straight into the buffer, the handed step's sides behind them)
+        more = {} if self.track is None else dict(track=True, track_iou=self.track[0], track_hold=self.track[1],
+                                                  _track_out=(at.track_id, at.track_age))      # (at: LiveTrackedViews)
         return self.hand.forward_hands(images, depth, self.hands, _record=(None, at.records), _tail=lift, handed=self.handed,
-                                       left_side=self.left_side, _side=at.side)
+                                       left_side=self.left_side, _side=at.side, **more)
+
+    def track_reset(self):
+        """Empty the hand engine's trackers (HandNetEngine.track_reset; also between replays of a captured step)."""
+        self.hand.track_reset()
+        return self
 
     def _lifter_input(self, image_uvd, has_hand, lifted, mirror):
         return ops.lifter_input_gated(image_uvd, valid=has_hand, lifted=lifted, mirror=mirror)[0]
@@ -452,7 +486,7 @@ class LiveHandsEngine(_LiveStep):
         n, k = layout.frames, layout.hands
         parts["mesh"] = parts["mesh"].view(n, k, self.vertices, 3)
         return LiveHandsOutput(hands=out, lifted=at.lifted.view(n, k), host=host, n=n, k=k, side=out.side, mirror=out.mirror,
-                               layout=layout, **parts)
+                               layout=layout, track_id=out.track_id, track_age=out.track_age, **parts)
 
 
 @dataclass

@@ -1271,17 +1271,50 @@ def check_max_hands(max_hands) -> int:
     return k
 
 
+TRACK_WORDS = 12           # int32 words of a row of the tracker's state (48 bytes)
+TRACK_MAX_SIDE = 32767     # frames the tracked step takes: the rule's products then fit in int64
+
+
+def check_track_options(track_iou, track_hold):
+    """(thr_milli, hold) of the tracked step's C entry: int(round(1000 * track_iou)) in 1..1000 and track_hold as an int in
+    0..1000000, else ValueError."""
+    thr_milli = int(round(1000 * float(track_iou)))
+    if not 1 <= thr_milli <= 1000:
+        raise ValueError(f"track_iou must round to 0.001..1 (got {track_iou!r})")
+    try:
+        hold = int(track_hold)
+    except (TypeError, ValueError):
+        hold = None
+    if hold is None or hold != track_hold or not 0 <= hold <= 1000000:
+        raise ValueError(f"track_hold must be an integer in 0..1000000 (got {track_hold!r})")
+    return thr_milli, hold
+
+
+def track_state(n, k, device):
+    """The empty tracker of n frames with k slots each: zeroed int32 [n, 1 + k, 12] (reset: state.zero_())."""
+    return torch.zeros((int(n), 1 + check_max_hands(k), TRACK_WORDS), device=device, dtype=torch.int32)
+
+
 def crop_resize_hands(det: Detections, hand_label, depth, max_hands, out_size=176, cpad=4, crop_box=None, has_hand=None,
                       score=None, det_index=None, crops=None, reorder_bgr=False, handed=False, left_side=0, side=None,
-                      mirror=None):
+                      mirror=None, track=None, track_iou=0.3, track_hold=5, track_id=None, track_age=None):
     """crop_resize for the first max_hands hand detections of each frame: slot k of frame i is the k-th detection with label
     hand_label in frame i's score-ordered list, padded and cut as crop_resize cuts the first.  -> (crop_box [N,K,4] int64,
     has_hand [N,K] int32, score [N,K] fp32, det_index [N,K] int32 (-1: empty slot), crops [N*K,out,out,cpad] NHWC).
     An empty slot (no such detection, or an empty padded slice) has zeros everywhere and still uses up its rank.
     handed: the slots' handedness in the same two launches (hn_crop_resize_hands_sided) -- two more results, side [N,K] int32
     (det.sides of the slot's detection, -1 for an empty slot) and mirror [N,K] int32 (1 for a filled slot whose side is
-    left_side); the crop of a mirror slot is the plain crop flipped along its width, everything else is unchanged."""
+    left_side); the crop of a mirror slot is the plain crop flipped along its width, everything else is unchanged.
+    track: a state tensor of track_state(N, K) -- the slots are TRACKED from call to call (hn_crop_resize_hands_tracked, DESIGN.md
+    9e: a hand keeps its slot and its id while its padded box overlaps the slot's last one with IoU >= track_iou; a slot whose
+    hand is missing is held, empty, for track_hold steps), the state is updated in place, and two more results end the tuple:
+    track_id, track_age [N,K] int32.  Frames of at most 32767 x 32767 pixels."""
     k = check_max_hands(max_hands)
+    if track is not None:       # (the options and the frame-size limit first: refused before anything touches a device)
+        thr_milli, hold = check_track_options(track_iou, track_hold)
+        if max(depth.shape[-2:]) > TRACK_MAX_SIDE:
+            raise ValueError(f"tracked hands: frames of at most {TRACK_MAX_SIDE} x {TRACK_MAX_SIDE} pixels "
+                             f"(got {depth.shape[-2]} x {depth.shape[-1]})")
     _req(depth, name="depth")
     n, c, h, w = depth.shape
     if c not in (1, 4):
@@ -1298,6 +1331,32 @@ def crop_resize_hands(det: Detections, hand_label, depth, max_hands, out_size=17
         det_index = torch.empty((n, k), device=dev, dtype=torch.int32)
     if crops is None:
         crops = torch.empty((n * k, out_size, out_size, cpad), device=dev, dtype=torch.float32)
+    if track is not None:
+        _req(track, torch.int32, "track")
+        if track.numel() != n * (1 + k) * TRACK_WORDS:
+            raise ValueError(f"track must be track_state({n}, {k}): int32 [{n},{1 + k},{TRACK_WORDS}]")
+        if handed:
+            if side is None:
+                side = torch.empty((n, k), device=dev, dtype=torch.int32)
+            if mirror is None:
+                mirror = torch.empty((n, k), device=dev, dtype=torch.int32)
+            _req(side, torch.int32, "side"); _req(mirror, torch.int32, "mirror"); _req(det.sides, torch.int32, "det.sides")
+            if side.numel() != n * k or mirror.numel() != n * k:
+                raise ValueError("side and mirror must hold one value per slot")
+        if track_id is None:
+            track_id = torch.empty((n, k), device=dev, dtype=torch.int32)
+        if track_age is None:
+            track_age = torch.empty((n, k), device=dev, dtype=torch.int32)
+        _req(track_id, torch.int32, "track_id"); _req(track_age, torch.int32, "track_age")
+        if track_id.numel() != n * k or track_age.numel() != n * k:
+            raise ValueError("track_id and track_age must hold one value per slot")
+        check(_lib.load().hn_crop_resize_hands_tracked(
+            ptr(det.boxes), ptr(det.scores), ptr(det.labels), ptr(det.sides) if handed else None, ptr(det.count), cap,
+            int(hand_label), int(left_side), k, ptr(depth), n, c, 1 if reorder_bgr else 0, h, w, out_size, cpad, ptr(crop_box),
+            ptr(has_hand), ptr(score), ptr(det_index), ptr(side) if handed else None, ptr(mirror) if handed else None, ptr(crops),
+            ptr(track), thr_milli, hold, ptr(track_id), ptr(track_age), _stream()), "hn_crop_resize_hands_tracked")
+        head = (crop_box, has_hand, score, det_index, crops) + ((side, mirror) if handed else ())
+        return head + (track_id, track_age)
     if handed:
         if side is None:
             side = torch.empty((n, k), device=dev, dtype=torch.int32)

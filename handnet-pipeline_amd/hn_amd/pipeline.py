@@ -60,6 +60,8 @@ class HandsOutput:
     tail: object = None                # what forward_hands' `_tail` callable returned (the multi-hand live step, hn_amd/live.py)
     side: torch.Tensor = None          # handed steps: [N,K] int32 device, detections.sides of the slot's detection (-1 when empty)
     mirror: torch.Tensor = None        # handed steps: [N,K] int32 device, 1 where the slot went through A2J mirrored (a left hand)
+    track_id: torch.Tensor = None      # tracked steps: [N,K] int32 device, the slot's track id (held slots included; 0: free)
+    track_age: torch.Tensor = None     # tracked steps: [N,K] int32 device, the steps on which the slot's track was seen again
 
 
 RECORD_BYTES = 296      # hn_amd.dist's per-frame record (box 32 + flags 8 + 21 x 3 fp32 keypoints, padded to 8)
@@ -93,27 +95,29 @@ def read_host_record(rec: torch.Tensor, n: int, joints: int = 21, extras: bool =
     return kp, has, box, words, more
 
 
-def hands_record_rows(slots: int, rec_bytes: int, handed: bool = False) -> int:
+def hands_record_rows(slots: int, rec_bytes: int, handed: bool = False, tracked: bool = False) -> int:
     """Rows of a forward_hands record: one per slot, the range-word row, then the slots' scores and detection ranks -- and,
-    for a handed step, their sides behind those."""
-    return slots + 1 + ((12 if handed else 8) * slots + rec_bytes - 1) // rec_bytes
+    for a handed step, their sides behind those; for a tracked step, the track ids and ages behind all of them."""
+    return slots + 1 + ((8 + 4 * bool(handed) + 8 * bool(tracked)) * slots + rec_bytes - 1) // rec_bytes
 
 
-def _hands_tail(rec: torch.Tensor, slots: int, handed: bool = False):
+def _hands_tail(rec: torch.Tensor, slots: int, handed: bool = False, tracked: bool = False):
     """(score [slots] fp32, det_index [slots] int32) views of a forward_hands record (device or host); handed: + side [slots]
-    int32, behind them."""
+    int32, behind them; tracked: + track_id, track_age [slots] int32, last."""
     flat = rec.view(-1)
     base = (slots + 1) * rec.shape[1]
     tail = (flat[base:base + 4 * slots].view(torch.float32), flat[base + 4 * slots:base + 8 * slots].view(torch.int32))
-    if handed:
-        tail += (flat[base + 8 * slots:base + 12 * slots].view(torch.int32),)
+    end = base + 8 * slots
+    for _ in range(bool(handed) + 2 * bool(tracked)):
+        tail += (flat[end:end + 4 * slots].view(torch.int32),)
+        end += 4 * slots
     return tail
 
 
-def read_hands_tail(rec: torch.Tensor, slots: int, handed: bool = False):
+def read_hands_tail(rec: torch.Tensor, slots: int, handed: bool = False, tracked: bool = False):
     """A synchronised forward_hands host_record -> (score [slots] fp32, det_index [slots] int32), fresh CPU tensors; handed
-    (the record of a handed step): + side [slots] int32."""
-    return tuple(t.clone() for t in _hands_tail(rec, slots, handed))
+    (the record of a handed step): + side [slots] int32; tracked: + track_id, track_age [slots] int32."""
+    return tuple(t.clone() for t in _hands_tail(rec, slots, handed, tracked))
 
 
 def range_message(bits: int) -> str:
@@ -199,6 +203,7 @@ class HandNetEngine:
         self._hand_stat = None      # (event, pinned count tensor, frames) of the last eager step
         self._sparse_hint = False
         self._convert = None        # set_convert(): the aggregation's epilogue also writes image (u,v,d) / camera xyz
+        self._track_states = {}     # tracked steps: (N, K) -> the tracker's state (ops.track_state), shared by eager steps and captures
 
     def set_convert(self, paras=None, clamp: bool = False, on: bool = True):
         """convert_joints + uvd2xyz as part of the step (a2j/a2j.py:17-43, what ros_demo.py:289,329-330 does with
@@ -237,7 +242,8 @@ class HandNetEngine:
 
     @ops.device_guarded
     def forward_hands(self, images, depth: torch.Tensor, max_hands: int = 2, to_host: bool = False, _record=None,
-                      _tail=None, handed: bool = False, left_side: int = 0, _side=None) -> HandsOutput:
+                      _tail=None, handed: bool = False, left_side: int = 0, _side=None, track: bool = False,
+                      track_iou: float = 0.3, track_hold: int = 5, _track_out=None) -> HandsOutput:
         """forward_device for up to max_hands (1..16) hands per frame: slot k of frame i is the k-th hand-label detection of
         frame i in the detector's score order, cropped as forward_device crops the first (max_hands = 1 IS forward_device's
         crop); A2J runs on the N * max_hands crops with the slots' has_hand mask (capturable), or -- eager, when the previous
@@ -251,13 +257,35 @@ class HandNetEngine:
         frame's own coordinates; every other slot is the step without `handed`, bit for bit, and no launch is added.
         left_side = 0 is an ASSUMPTION (the detector's side targets are box_info[:, 1] of its training set; the 100DOH
         convention 0 = left is not stated by the reference, which never reads `sides`): check it on your checkpoint.  to_host
-        records carry the sides behind the scores and ranks (read_hands_tail(..., handed=True))."""
+        records carry the sides behind the scores and ranks (read_hands_tail(..., handed=True)).
+        track: the slots are tracked from step to step -- batch row i is one camera stream; a hand keeps its
+        slot and its HandsOutput.track_id while its padded crop box overlaps the slot's last one with IoU >= track_iou, whatever
+        its score rank; a slot whose hand is missing is held EMPTY (has_hand 0) for track_hold steps, then freed; new hands
+        take the free slots, lowest first, in score order.  The engine owns one state per (N, K), shared by eager steps and
+        captures of that shape (track_reset() empties it).  to_host records carry track_id and track_age last
+        (read_hands_tail(..., tracked=True)).  Frames of at most 32767 x 32767 pixels."""
         return self._step(images, depth, ops.check_max_hands(max_hands), to_host, _record, _tail,
-                          (int(left_side), _side) if handed else None)
+                          (int(left_side), _side) if handed else None,
+                          ops.check_track_options(track_iou, track_hold) + (_track_out,) if track else None)
 
-    def _step(self, images, depth, hands, to_host, _record, _tail, handed=None):
+    def _track_state(self, n, hands):
+        st = self._track_states.get((n, hands))
+        if st is None:
+            with torch.inference_mode(False):
+                st = self._track_states[(n, hands)] = ops.track_state(n, hands, self.device)
+        return st
+
+    @ops.device_guarded
+    def track_reset(self):
+        """Empty every tracker of this engine (a memset on the current stream; also between replays of a captured step)."""
+        for st in self._track_states.values():
+            st.zero_()
+        return self
+
+    def _step(self, images, depth, hands, to_host, _record, _tail, handed=None, track=None):
         """The body of forward_device (hands None: the top-1 crop, HandNetOutput) and forward_hands (hands = K; handed =
-        (left_side, where the sides go or None): the handed step)."""
+        (left_side, where the sides go or None): the handed step; track = (thr_milli, hold, (where the ids go, the ages) or
+        None): the tracked step)."""
         want_c = 4 if self.a2j.rgbd else 1
         if depth.dim() != 4 or depth.shape[1] != want_c or depth.shape[0] != len(images):
             raise ValueError(f"depth_images must be [N,{want_c},H,W] matching images"
@@ -270,7 +298,8 @@ class HandNetEngine:
         record = None
         if hands is not None and (to_host or _record is not None):
             # (fetched first: the crop stage writes the scores and ranks straight into the record)
-            record = _record if _record is not None else self._host_record_buffers(n, hands, handed is not None)
+            record = _record if _record is not None else self._host_record_buffers(n, hands, handed is not None,
+                                                                                   track is not None)
         # (the scope is this host thread's: another engine on another thread keeps its own switch and block)
         with ops.range_scope(self._range_block, on=noting):
             det, cand = self.fcos.detect(images)
@@ -279,8 +308,31 @@ class HandNetEngine:
                                                             reorder_bgr=self.a2j.rgbd)
                 box_rows, has_rows = crop_box, has_hand
             else:
-                side = mirror = None
-                if handed is None:
+                side = mirror = track_id = track_age = None
+                if track is not None:
+                    # (sides, ids and ages go where the caller wants them -- the live step's buffer -- else behind the scores
+                    # and ranks of this step's own record)
+                    score = det_index = None
+                    side = None if handed is None else handed[1]
+                    track_id, track_age = track[2] if track[2] is not None else (None, None)
+                    if record is not None:
+                        own_side, own_track = handed is not None and side is None, track[2] is None
+                        views = list(_hands_tail(record[1], rows, handed=own_side, tracked=own_track))
+                        score, det_index = views[:2]
+                        if own_side:
+                            side = views[2]
+                        if own_track:
+                            track_id, track_age = views[-2:]
+                    res = ops.crop_resize_hands(
+                        det, self.num_classes - 1, depth.float().contiguous(), hands, CROP, 4, score=score, det_index=det_index,
+                        reorder_bgr=self.a2j.rgbd, handed=handed is not None, left_side=0 if handed is None else handed[0],
+                        side=side, track=self._track_state(n, hands), track_iou=track[0] / 1000.0, track_hold=track[1],
+                        track_id=track_id, track_age=track_age)
+                    crop_box, has_hand, score, det_index, crops = res[:5]
+                    if handed is not None:
+                        side, mirror = res[5].view(n, hands), res[6].view(n, hands)
+                    track_id, track_age = res[-2].view(n, hands), res[-1].view(n, hands)
+                elif handed is None:
                     score, det_index = _hands_tail(record[1], rows) if record is not None else (None, None)
                     crop_box, has_hand, score, det_index, crops = ops.crop_resize_hands(
                         det, self.num_classes - 1, depth.float().contiguous(), hands, CROP, 4, score=score, det_index=det_index,
@@ -337,7 +389,7 @@ class HandNetEngine:
         per_slot = (n, hands) + tuple(kp.shape[1:])
         return HandsOutput(kp.view(per_slot), crops, crop_box, has_hand, score, det_index, det, cand, flags,
                            None if img_uvd is None else img_uvd.view(per_slot), None if xyz is None else xyz.view(per_slot),
-                           host_rec, tail, side, mirror)
+                           host_rec, tail, side, mirror, track_id, track_age)
 
     # -------------------------------------------------------------------------------
     # sparse streams: A2J on the frames with a hand only
@@ -388,20 +440,20 @@ class HandNetEngine:
     # -------------------------------------------------------------------------------
     # hipGraph replay for a fixed batch shape (launch-bound at small batch)
     # -------------------------------------------------------------------------------
-    def _new_record(self, n, hands=None, handed=False):
+    def _new_record(self, n, hands=None, handed=False, tracked=False):
         """(pinned host, device) record buffers of a step over n frames (hands: forward_hands with that many slots per frame;
-        handed: with the slots' sides)."""
+        handed: with the slots' sides; tracked: with their track ids and ages)."""
         rb = record_bytes(self._fields())
-        rows = n + 1 if hands is None else hands_record_rows(n * hands, rb, handed)
+        rows = n + 1 if hands is None else hands_record_rows(n * hands, rb, handed, tracked)
         return (torch.zeros((rows, rb), dtype=torch.uint8, pin_memory=True),
                 torch.zeros((rows, rb), dtype=torch.uint8, device=self.device))
 
-    def _host_record_buffers(self, n, hands=None, handed=False):
-        key = n if hands is None else ("hands", n, hands) + (("handed",) if handed else ())
+    def _host_record_buffers(self, n, hands=None, handed=False, tracked=False):
+        key = n if hands is None else ("hands", n, hands) + (("handed",) if handed else ()) + (("tracked",) if tracked else ())
         buf = self._host_records.get(key)
         if buf is None:
             with torch.inference_mode(False):   # ordinary tensors: written in place by later calls in any mode
-                buf = self._host_records[key] = self._new_record(n, hands, handed)
+                buf = self._host_records[key] = self._new_record(n, hands, handed, tracked)
         return buf
 
     @ops.device_guarded
@@ -415,30 +467,51 @@ class HandNetEngine:
 
     @ops.device_guarded
     def graphed_hands(self, images: torch.Tensor, depth: torch.Tensor, max_hands: int = 2, to_host: bool = False,
-                      limit: int | None = None, handed: bool = False, left_side: int = 0):
-        """graphed() for forward_hands(images, depth, max_hands, to_host, handed=, left_side=): (run, static_images,
-        static_depth, static HandsOutput).  Its captures are keyed apart from graphed()'s (a handed step apart from a plain one)
-        and share their eviction order (limit)."""
+                      limit: int | None = None, handed: bool = False, left_side: int = 0, track: bool = False,
+                      track_iou: float = 0.3, track_hold: int = 5):
+        """graphed() for forward_hands(images, depth, max_hands, to_host, handed=, left_side=, track=, ...): (run,
+        static_images, static_depth, static HandsOutput).  Its captures are keyed apart from graphed()'s (a handed step apart
+        from a plain one, a tracked step apart from both) and share their eviction order (limit).  A tracked capture bakes in
+        the engine's state of its (N, K) -- the one eager tracked steps of that shape use -- and capturing leaves that state as
+        it found it."""
         k = ops.check_max_hands(max_hands)
         handed = (int(left_side), None) if handed else None
-        return self._graphed(self._hands_key(images.shape, depth.shape, k, to_host, handed), images, depth, to_host, limit, k,
-                             handed)
+        track = ops.check_track_options(track_iou, track_hold) + (None,) if track else None
+        return self._graphed(self._hands_key(images.shape, depth.shape, k, to_host, handed, track), images, depth, to_host, limit,
+                             k, handed, track)
 
     @staticmethod
-    def _hands_key(image_shape, depth_shape, max_hands, to_host, handed=None):
+    def _hands_key(image_shape, depth_shape, max_hands, to_host, handed=None, track=None):
         key = ("hands", tuple(image_shape), tuple(depth_shape), int(max_hands), bool(to_host))
-        return key if handed is None else key + ("handed", handed[0])
+        key = key if handed is None else key + ("handed", handed[0])
+        return key if track is None else key + ("tracked", track[0], track[1])
 
     def has_graph_hands(self, image_shape, depth_shape, max_hands, to_host: bool = False, handed: bool = False,
-                        left_side: int = 0) -> bool:
-        return self._hands_key(image_shape, depth_shape, max_hands, to_host, (int(left_side), None) if handed else None) in self._graphs
+                        left_side: int = 0, track: bool = False, track_iou: float = 0.3, track_hold: int = 5) -> bool:
+        return self._hands_key(image_shape, depth_shape, max_hands, to_host, (int(left_side), None) if handed else None,
+                               ops.check_track_options(track_iou, track_hold) if track else None) in self._graphs
 
-    def _graphed(self, key, images, depth, to_host, limit, hands, handed=None):
+    def _track_untouched(self, n, hands):
+        """Context manager around the capture of a tracked step over (n, hands): the capture's eager warm-up steps advance the
+        tracker, so the state is put back as it was when the capture is done."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def keep():
+            state = self._track_state(n, hands)
+            saved = state.clone()
+            try:
+                yield state
+            finally:
+                state.copy_(saved)
+        return keep()
+
+    def _graphed(self, key, images, depth, to_host, limit, hands, handed=None, track=None):
         if key not in self._graphs:
             while limit is not None and len(self._graphs) >= max(1, limit):
                 self._graphs.popitem(last=False)
             with torch.inference_mode(False), torch.no_grad():
-                return self._capture(key, images, depth, to_host, hands, handed)
+                return self._capture(key, images, depth, to_host, hands, handed, track)
         self._graphs.move_to_end(key)
         g, s_img, s_dep, out = self._graphs[key]
         return g.replay, s_img, s_dep, out
@@ -546,20 +619,26 @@ class HandNetEngine:
         g.replay()
         return out
 
-    def _capture(self, key, images, depth, to_host=False, hands=None, handed=None):
+    def _capture(self, key, images, depth, to_host=False, hands=None, handed=None, track=None):
         # static buffers are ordinary (non-inference) tensors so that later copy_() works in any mode
         s_img, s_dep = torch.empty_like(images), torch.empty_like(depth)
         s_img.copy_(images)
         s_dep.copy_(depth)
         # the capture's own record buffers (addresses are baked into the graph)
-        record = self._new_record(images.shape[0], hands, handed is not None) if to_host else None
+        record = self._new_record(images.shape[0], hands, handed is not None, track is not None) if to_host else None
 
         def step():
             if hands is None:
                 return self.forward_device(s_img, s_dep, _record=record)
             return self.forward_hands(s_img, s_dep, hands, _record=record, handed=handed is not None,
-                                      left_side=0 if handed is None else handed[0])
+                                      left_side=0 if handed is None else handed[0], track=track is not None,
+                                      track_iou=0.3 if track is None else track[0] / 1000.0,
+                                      track_hold=5 if track is None else track[1])
 
-        g, out = ops.capture_step(step)
+        if track is not None:
+            with self._track_untouched(images.shape[0], hands):
+                g, out = ops.capture_step(step)
+        else:
+            g, out = ops.capture_step(step)
         self._graphs[key] = (g, s_img, s_dep, out)
         return g.replay, s_img, s_dep, out

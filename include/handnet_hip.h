@@ -35,7 +35,8 @@ extern "C" {
 /* ABI version; bumped whenever a struct below changes (functions added without touching a struct or an existing signature
  * keep it: hn_lifter_input_gated_f32 and hn_mesh_render_u8 came under 36, and so did the mirror / handedness entries
  * hn_ingest_u8bgr_u16mm_flip, hn_flip_w_f32, hn_crop_resize_hands_sided, hn_a2j_aggregate_convert_mirror_f32,
- * hn_lifter_input_gated_mirror_f32 and hn_mesh_finish_mirror_f32). */
+ * hn_lifter_input_gated_mirror_f32 and hn_mesh_finish_mirror_f32, and the tracked slots' hn_crop_resize_hands_tracked and
+ * hn_track_state_bytes). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -545,6 +546,27 @@ int hn_crop_resize_hands_sided(const float* det_boxes, const float* det_scores, 
                                int max_hands, const float* depth, int n, int in_ch, int reorder_bgr, int h, int w, int out,
                                int cpad, int64_t* crop_box, int32_t* has_hand, float* score, int32_t* det_index, int32_t* side,
                                int32_t* mirror, float* crops, void* stream);
+/* hn_crop_resize_hands_sided with the slots TRACKED from one call to the next (added under ABI 36: new functions only).
+ * state: int32 [n][1 + max_hands][12] on the device, 16-byte aligned, hn_track_state_bytes(n, max_hands) bytes, updated in
+ * place; all zeros = the empty tracker (reset: a memset).  Row 0 of a frame: word 0 = the last track id issued, the rest 0.
+ * Row 1 + s = slot s: words 0..7 the padded box as four int64, word 8 id (0: free), word 9 age (steps since the track was
+ * created on which it was seen), word 10 missed (consecutive steps without a match), word 11 zero.
+ * Per frame: the candidates are the first 16 hand-label detections of the score-ordered list whose padded slice is not
+ * empty; a live slot and a candidate are a pair when their padded boxes overlap (I > 0) with 1000 * I >= thr_milli * U
+ * (thr_milli 1..1000); pairs are matched greedily by IoU (cross-multiplied in int64; ties: lower slot, then lower candidate); a
+ * live slot without a match is held (empty outputs, no other hand may take it) for up to `hold` (0..1000000) steps and freed
+ * after that; the candidates left over take the free slots, lowest first, in score order, each with a new id.
+ * A matched or new slot is written as hn_crop_resize_hands[_sided] writes the slot of its detection; a held or free slot is an
+ * empty slot.  track_id / track_age [n][max_hands] int32: the slot's id (0: free) and age, held slots included.
+ * det_sides, side and mirror may be NULL together: the unsided step.  h, w <= 32767 (else HN_ERR_ARG). */
+int hn_crop_resize_hands_tracked(const float* det_boxes, const float* det_scores, const int32_t* det_labels,
+                                 const int32_t* det_sides, const int32_t* det_count, int cap, int hand_label, int left_side,
+                                 int max_hands, const float* depth, int n, int in_ch, int reorder_bgr, int h, int w, int out,
+                                 int cpad, int64_t* crop_box, int32_t* has_hand, float* score, int32_t* det_index, int32_t* side,
+                                 int32_t* mirror, float* crops, int32_t* state, int thr_milli, int hold, int32_t* track_id,
+                                 int32_t* track_age, void* stream);
+/* bytes of the state of n frames with max_hands slots each (0 for arguments out of range) */
+int64_t hn_track_state_bytes(int n, int max_hands);
 
 /* fp32 NHWC(4) image [n][h][w][4] -> the stem image of hn_conv_stem_f16x3 / hn_conv_stem_pool_f16x3 (two fp16 planes hi, lo of
  * [n][h + 2*border][w + 2*border][4], zero border): the A2J crops on their way to the split-precision stem
