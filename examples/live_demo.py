@@ -18,8 +18,11 @@ also goes through the K = 2 step with per-slot handedness: the detector's side o
 through the right-handed pose network and lifter (side == left_side; 0 is an assumption about the checkpoint's convention).
 With --track a few frames go through the K = 2 step with tracked slots (live_hands(track=True)): the track id and age of every
 slot are printed per frame -- a hand keeps its slot and id whatever its score rank, a slot whose hand is missing is held.
+With --smooth the same frames go through the tracked K = 2 step with the filter on (live_hands(track=True, smooth=True)): per
+frame, how far the filtered mesh and joints lie from the raw ones (0 on a slot's first frame and on a repeated frame); the
+filter's parameters are the paper's starting values, not tuned on this model.
 usage (GPU box): python examples/live_demo.py [frames] [--overlay out.png] [--mano MANO_RIGHT.pkl] [--labels PREFIX] [--left]
-                 [--handed] [--track]"""
+                 [--handed] [--track] [--smooth]"""
 import sys
 import time
 import types
@@ -57,8 +60,8 @@ def main():
             i = argv.index(flag)
             opt[flag] = argv[i + 1]
             del argv[i:i + 2]
-    left, handed, track = "--left" in argv, "--handed" in argv, "--track" in argv
-    argv = [a for a in argv if a not in ("--left", "--handed", "--track")]
+    left, handed, track, smooth = "--left" in argv, "--handed" in argv, "--track" in argv, "--smooth" in argv
+    argv = [a for a in argv if a not in ("--left", "--handed", "--track", "--smooth")]
     frames = int(argv[0]) if argv else 20
     faces = _faces(opt.get("--mano")) if "--overlay" in opt else None
     args = types.SimpleNamespace(pretrained_fcos="-", pretrained_a2j="-")
@@ -132,6 +135,21 @@ def main():
                 r3 = o3.read()
                 print(f"7. track, frame {i}: id per slot {r3.track_id[0].tolist()} (0: free), age {r3.track_age[0].tolist()}, "
                       f"filled {(r3.has_hand[0] != 0).tolist()}, detection {r3.det_index[0].tolist()}")
+        if smooth:                                                                        # ... and their signals filtered over time
+            smoothed = net.live_hands(model, PARAS, max_hands=2, clamp=True, perm_reverse=rev, track=True, smooth=True,
+                                      smooth_min_cutoff=1.0, smooth_beta=0.007, smooth_d_cutoff=1.0, smooth_rate=30.0)
+            smoothed.track_reset()                                                        # (empties the filters too)
+            run, t_img, t_dep, o4 = smoothed.graphed(rgb, depth)
+            for i in range(min(frames, 6)):
+                t_img.copy_(synth.make_rgb(1, seed=1000 + i // 2).cuda())
+                t_dep.copy_(synth.make_depth(1, seed=2000 + i // 2).cuda())
+                smoothed.smooth_dt(1 / 30)                                                 # (a camera would give its frame time)
+                run()
+                torch.cuda.current_stream().synchronize()
+                r4 = o4.read()
+                print(f"8. smooth, frame {i}: id per slot {r4.track_id[0].tolist()}, |smooth_mesh - mesh| max "
+                      f"{1e3 * float((r4.smooth_mesh - r4.mesh).abs().max()):.3f} mm, |smooth_xyz - xyz_mm| max "
+                      f"{float((r4.smooth_xyz - r4.xyz_mm).abs().max()):.3f} mm")
 
 
 if __name__ == "__main__":

@@ -572,7 +572,121 @@ __global__ __launch_bounds__(256) void mesh_finish_kernel(const float* __restric
     out[i] = val;
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The smoothed live step's last launch: mesh_finish_kernel's value for every mesh element (the same expressions), written
+// to `out`, and a One Euro filter (Casiez et al. 2012) per coordinate over two signals of every slot -- the final mesh
+// (metres, gate: lifted == 1) into smooth_mesh and, by further threads of the same grid, xyz_mm (camera millimetres, gate:
+// has_hand == 1) into smooth_xyz.  State: one 16-byte record {xh, dxh, id, 0} per element, [slots][joints + v][3]; a thread
+// reads and writes its own record only (one dwordx4 load, one dwordx4 store: lane i at record i of its slot, 1 KiB per wave
+// instruction).  tests/smooth_ref.py restates the rule in numpy float32, operation for operation.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ bool finite_bits(unsigned int b) { return (b & 0x7f800000u) != 0x7f800000u; }
+
+// one element: x (the unfiltered value; 0 where the gate is off), its slot's track id t -> the filtered value; *rec updated
+__device__ __forceinline__ float one_euro(float x, bool gate, int t, u32x4* rec, float dt, float min_cutoff, float beta,
+                                          float d_cutoff) {
+#pragma clang fp contract(off)
+  const u32x4 s = *rec;
+  u32x4 next = {0u, 0u, 0u, 0u};
+  float y = 0.f;
+  if (gate) {                                                             // (rule 1: gate off -> 0, the record zeroed)
+    y = x;
+    if (finite_bits(__float_as_uint(x))) {                                // (rule 2: x not finite -> x, the record zeroed)
+      const int id = (int)s[2];
+      if (id == 0 || id != t || t == 0 || !finite_bits(s[0]) || !finite_bits(s[1])) {      // rule 3: initialise
+        next[0] = __float_as_uint(x);
+        next[2] = (unsigned int)t;
+      } else {                                                            // rule 4: filter
+        const float xp = __uint_as_float(s[0]), dxp = __uint_as_float(s[1]);
+        const float two_pi = 6.2831855f;
+        const float rd = (two_pi * d_cutoff) * dt;
+        const float ad = rd / (rd + 1.f);
+        const float dx = (x - xp) / dt;
+        const float edx = dxp + ad * (dx - dxp);
+        const float fc = min_cutoff + beta * fabsf(edx);
+        const float r = (two_pi * fc) * dt;
+        const float a = r / (r + 1.f);
+        y = xp + a * (x - xp);
+        next[0] = __float_as_uint(y);
+        next[1] = __float_as_uint(edx);
+        next[2] = (unsigned int)t;
+      }
+    }
+  }
+  *rec = next;
+  return y;
+}
+
+__global__ __launch_bounds__(256) void mesh_finish_smooth_kernel(
+    const float* __restrict__ mesh, const long long* __restrict__ perm, const float* __restrict__ xyz_mm,
+    const int* __restrict__ lifted, const int* __restrict__ has_hand, const int* __restrict__ mirror,
+    const int* __restrict__ track_id, const float* __restrict__ dt_word, u32x4* __restrict__ state, int n, int v0, int v,
+    int joints, float min_cutoff, float beta_xyz, float beta_mesh, float d_cutoff, float* __restrict__ out,
+    float* __restrict__ smooth_xyz, float* __restrict__ smooth_mesh) {
+#pragma clang fp contract(off)
+  const long mesh_total = (long)n * v * 3, total = mesh_total + (long)n * joints * 3;
+  const long per_slot = (long)(joints + v) * 3;                           // records of a slot: its joints, then its vertices
+  const float dt = *dt_word;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    if (i < mesh_total) {
+      const int c = (int)(i % 3);
+      const long r = i / 3;
+      const int vv = (int)(r % v), img = (int)(r / v);
+      const bool gate = lifted[img] == 1;
+      float val = 0.f;
+      if (gate) {                                                         // (mesh_finish_kernel's arithmetic, as it stands)
+        float m = mesh[((long)img * v0 + perm[vv]) * 3 + c];
+        if (mirror && c == 0 && mirror[img]) m = -m;
+        const float root = xyz_mm[(long)img * joints * 3 + c];
+        const float scaled = m * 1000.f;
+        const float moved = scaled + root;
+        val = moved / 1000.f;
+        if (c) val = -val;
+      }
+      out[i] = val;
+      u32x4* rec = state + (long)img * per_slot + (long)(joints + vv) * 3 + c;
+      smooth_mesh[i] = one_euro(val, gate, track_id[img], rec, dt, min_cutoff, beta_mesh, d_cutoff);
+    } else {
+      const long j = i - mesh_total;
+      const int img = (int)(j / ((long)joints * 3));
+      const long e = j - (long)img * joints * 3;                          // (joint, coordinate) of the slot
+      const bool gate = has_hand[img] == 1;
+      const float x = gate ? xyz_mm[j] : 0.f;
+      smooth_xyz[j] = one_euro(x, gate, track_id[img], state + (long)img * per_slot + e, dt, min_cutoff, beta_xyz, d_cutoff);
+    }
+  }
+}
 }  // namespace
+
+extern "C" int64_t hn_smooth_state_bytes(int slots, int joints, int v) {
+  if (slots <= 0 || joints <= 0 || v <= 0) return 0;
+  return (int64_t)slots * (joints + v) * 3 * 16;
+}
+
+extern "C" int hn_mesh_finish_smooth_f32(const float* mesh, const int64_t* perm, const float* xyz_mm, const int32_t* lifted,
+                                         const int32_t* has_hand, const int32_t* mirror, const int32_t* track_id,
+                                         const float* dt, void* state, int n, int v0, int v, int joints, float min_cutoff,
+                                         float beta_xyz, float beta_mesh, float d_cutoff, float* out, float* smooth_xyz,
+                                         float* smooth_mesh, void* stream) {
+  HN_CHECK_ARG(mesh && perm && xyz_mm && lifted && has_hand && track_id && dt && state && out && smooth_xyz && smooth_mesh,
+               "hn_mesh_finish_smooth_f32: null pointer");
+  HN_CHECK_ARG((uintptr_t)state % 16 == 0, "hn_mesh_finish_smooth_f32: state must be 16-byte aligned");
+  HN_CHECK_ARG(n > 0 && v0 > 0 && v > 0 && joints > 0, "hn_mesh_finish_smooth_f32: bad dims");
+  const auto positive = [](float x) { return x > 0.f && x <= 3.402823466e38f; };
+  const auto not_negative = [](float x) { return x >= 0.f && x <= 3.402823466e38f; };
+  HN_CHECK_ARG(positive(min_cutoff) && positive(d_cutoff),
+               "hn_mesh_finish_smooth_f32: min_cutoff and d_cutoff must be finite and > 0 (got %g, %g)", (double)min_cutoff,
+               (double)d_cutoff);
+  HN_CHECK_ARG(not_negative(beta_xyz) && not_negative(beta_mesh),
+               "hn_mesh_finish_smooth_f32: beta must be finite and >= 0 (got %g, %g)", (double)beta_xyz, (double)beta_mesh);
+  hipLaunchKernelGGL(mesh_finish_smooth_kernel, dim3(grid_for((long)n * (v + joints) * 3)), dim3(256), 0, (hipStream_t)stream,
+                     mesh, (const long long*)perm, xyz_mm, lifted, has_hand, (const int*)mirror, track_id, dt, (u32x4*)state, n,
+                     v0, v, joints, min_cutoff, beta_xyz, beta_mesh, d_cutoff, out, smooth_xyz, smooth_mesh);
+  HN_CHECK_LAUNCH("mesh_finish_smooth_kernel");
+  return HN_OK;
+}
 
 extern "C" int hn_mesh_finish_f32(const float* mesh, const int64_t* perm, const float* xyz_mm, const int32_t* valid, int n, int v0,
                                   int v, int joints, float* out, void* stream) {

@@ -122,7 +122,8 @@ class HandNet(EngineOwner):
 
     def live_hands(self, lifter, paras, max_hands: int = 2, clamp: bool = True, perm_reverse=None, faces=None,
                    labels: bool = False, left: bool = False, handed: bool = False, left_side: int = 0, track: bool = False,
-                   track_iou: float = 0.3, track_hold: int = 5):
+                   track_iou: float = 0.3, track_hold: int = 5, smooth: bool = False, smooth_min_cutoff: float = 1.0,
+                   smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0, smooth_rate: float = 30.0):
         """live() for up to max_hands (1..16) hands per frame (hn_amd.live.LiveHandsEngine): forward_hands' slots, the
         caller's clamp + convert_joints, the lifter's input with the caller's skip rule per slot (a hand whose 2D box
         process_bbox refuses is not lifted: ros_demo.py:288-300), Pose2Mesh on every slot, one device -> host copy.
@@ -138,14 +139,21 @@ class HandNet(EngineOwner):
         track: the slots are tracked from step to step (batch row i = one camera stream): a hand keeps its slot and its
         read().track_id while its padded box overlaps the slot's last one with IoU >= track_iou, a slot whose hand is missing is
         held empty for track_hold steps, and max_hands=1 sticks to its hand instead of jumping to the top score
-        (engine.track_reset() starts over)."""
+        (engine.track_reset() starts over).
+        smooth (needs track and perm_reverse): the tracked slots' xyz_mm and final mesh are also filtered over time on the
+        device (a One Euro filter per coordinate, inside the step's last mesh launch): read().smooth_xyz [N,K,21,3] and
+        read().smooth_mesh [N,K,V,3] behind track_id, and the overlay is drawn from smooth_mesh; everything else stays
+        unfiltered.  smooth_min_cutoff, smooth_beta (per mm/s), smooth_d_cutoff and smooth_rate (steps per second) are the
+        paper's starting values, NOT tuned on this model; engine.smooth_dt(seconds) follows the camera's real frame time and
+        engine.smooth_reset() restarts the filters.  max_hands=1, track=True, smooth=True is the smoothed sticky top-1."""
         from hn_amd.live import LiveHandsEngine
         k = ops.check_max_hands(max_hands)
         if left and handed:
             raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
         self._convert_cfg = (tuple(paras), bool(clamp))
         return LiveHandsEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, k, clamp,
-                               perm_reverse, faces, labels, left, handed, left_side, track, track_iou, track_hold)
+                               perm_reverse, faces, labels, left, handed, left_side, track, track_iou, track_hold, smooth,
+                               smooth_min_cutoff, smooth_beta, smooth_d_cutoff, smooth_rate)
 
     # forward() switches ITSELF to hipGraph replay once the same input shapes have come in a few times in a row -- the live
     # caller's case (ros_demo.py:270-273: one 640x480 frame per call, ~150 dependent launches whose host cost is 8 % of the

@@ -228,6 +228,9 @@ SIGNATURES = {
     "hn_crop_resize_hands_tracked": (C.c_int, [VP] * 5 + [C.c_int] * 4 + [VP] + [C.c_int] * 7 + [VP] * 8
                                      + [C.c_int, C.c_int, VP, VP, VP]),
     "hn_track_state_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    # the smoothed live step (new functions under ABI 36)
+    "hn_mesh_finish_smooth_f32": (C.c_int, [VP] * 9 + [C.c_int] * 4 + [C.c_float] * 4 + [VP] * 4),
+    "hn_smooth_state_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
 }
 
 _lock = threading.Lock()

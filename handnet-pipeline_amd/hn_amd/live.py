@@ -18,10 +18,12 @@ crops + the dataset's float32 boxes + per-sample intrinsics -> A2J -> clip + con
 from __future__ import annotations
 
 import collections
+import contextlib
 import functools
 import math
 from dataclasses import dataclass, field
 
+import numpy as np
 import torch
 
 from . import ops
@@ -53,6 +55,9 @@ POSE_LABEL = ops.LABEL_CROP                           # side of a pose_label ima
 LiveViews = collections.namedtuple("LiveViews", "records side lifted mesh overlay box_label pose_label")
 # ... and of a tracked step: the same fields, then the two rows of the tracker
 LiveTrackedViews = collections.namedtuple("LiveTrackedViews", LiveViews._fields + ("track_id", "track_age"))
+# ... and of a smoothed step: those, then the two filtered signals
+LiveSmoothedViews = collections.namedtuple("LiveSmoothedViews", LiveTrackedViews._fields + ("smooth_xyz", "smooth_mesh"))
+SMOOTH_JOINTS = ops.SMOOTH_JOINTS
 
 
 @dataclass(frozen=True)
@@ -61,7 +66,8 @@ class LiveLayout:
     range-word row; K-hand step: forward_hands' wide record unchanged -- a row per slot, the range-word row, the scores and
     detection ranks: hands_record_rows), `side` int32 [slots] (handed steps: the detector's side per slot), `track_id` and
     `track_age` int32 [slots] each (tracked steps), `lifted` int32 [slots] (K-hand steps), the mesh fp32 [slots,V,3], the overlay uint8 [frames,h,w,3], box_label uint8 [frames,h,w,3] and
-    pose_label uint8 [slots,176,176,3] (each label image starts on a dword: the kernels store three dwords per four pixels).
+    pose_label uint8 [slots,176,176,3] (each label image starts on a dword: the kernels store three dwords per four pixels),
+    and -- smoothed steps -- `smooth_xyz` fp32 [slots,21,3] and `smooth_mesh` fp32 [slots,V,3], each on a dword, as the last parts.
     slots = frames for the one-hand step (hands None), frames * hands for the K-hand step.  A part the step does not have takes
     no bytes and its offset is None; every part in front of it stays where a step without the option has it."""
     frames: int
@@ -72,6 +78,7 @@ class LiveLayout:
     labels: bool = False
     handed: bool = False
     tracked: bool = False
+    smoothed: bool = False
     record_rows: int = field(init=False)
     record_bytes: int = field(init=False)
     side_at: int = field(init=False)
@@ -82,11 +89,15 @@ class LiveLayout:
     overlay_at: int = field(init=False)
     box_label_at: int = field(init=False)
     pose_label_at: int = field(init=False)
+    smooth_xyz_at: int = field(init=False)
+    smooth_mesh_at: int = field(init=False)
     nbytes: int = field(init=False)
 
     def __post_init__(self):
         if ((self.overlay or self.labels) and self.hw is None) or ((self.handed or self.tracked) and self.hands is None):
             raise ValueError("an overlay or label images need the frames' (h, w), and handed / tracked are a K-hand step's options")
+        if self.smoothed and not self.tracked:
+            raise ValueError("a smoothed step is a tracked step: the filters follow the track ids")
         s, rb = self.slots, record_bytes(3)
         rows = self.frames + 1 if self.hands is None else hands_record_rows(s, rb)
         image = None if self.hw is None else (self.frames, *self.hw, 3)
@@ -100,7 +111,9 @@ class LiveLayout:
                                                    ("mesh", True, torch.float32, (s, self.vertices, 3), 1),
                                                    ("overlay", self.overlay, torch.uint8, image, 1),
                                                    ("box_label", self.labels, torch.uint8, image, 4),
-                                                   ("pose_label", self.labels, torch.uint8, (s, POSE_LABEL, POSE_LABEL, 3), 4)):
+                                                   ("pose_label", self.labels, torch.uint8, (s, POSE_LABEL, POSE_LABEL, 3), 4),
+                                                   ("smooth_xyz", self.smoothed, torch.float32, (s, SMOOTH_JOINTS, 3), 4),
+                                                   ("smooth_mesh", self.smoothed, torch.float32, (s, self.vertices, 3), 4)):
             start = None
             if present:
                 start = (end + align - 1) // align * align
@@ -120,19 +133,21 @@ class LiveLayout:
     def views(self, buf) -> LiveViews:
         """The parts of a step's flat uint8 buffer (the device buffer or its pinned copy), typed and shaped; None: not there."""
         cut = {name: buf[a:b].view(dtype).view(shape) for name, (a, b, dtype, shape) in self._spans.items()}
-        kind = LiveTrackedViews if self.tracked else LiveViews
+        kind = LiveSmoothedViews if self.smoothed else LiveTrackedViews if self.tracked else LiveViews
         return kind(*(cut.get(name) for name in kind._fields))
 
 
 @functools.lru_cache(maxsize=None)
-def _read_type(step: str, base: tuple, overlay: bool, labels: bool, side: bool, tracked: bool = False):
-    """The namedtuple a step's read() returns: the base fields, then overlay, box_label + pose_label, side and track_id +
-    track_age, each only when the step has it; an absent image (overlay / box_label / pose_label) reads as a None class
-    attribute.  (One class per combination: call it with positional arguments only, the cache keys on them.)"""
-    has = dict(overlay=overlay, box_label=labels, pose_label=labels, side=side, track_age=tracked, track_id=tracked)
+def _read_type(step: str, base: tuple, overlay: bool, labels: bool, side: bool, tracked: bool = False, smoothed: bool = False):
+    """The namedtuple a step's read() returns: the base fields, then overlay, box_label + pose_label, side, track_age +
+    track_id and smooth_xyz + smooth_mesh, each only when the step has it; an absent image (overlay / box_label / pose_label)
+    reads as a None class attribute.  (One class per combination: call it with positional arguments only, the cache keys on
+    them.)"""
+    has = dict(overlay=overlay, box_label=labels, pose_label=labels, side=side, track_age=tracked, track_id=tracked,
+               smooth_xyz=smoothed, smooth_mesh=smoothed)
     fields = base + tuple(f for f, on in has.items() if on)
-    name = step + "Overlay" * overlay + "Labels" * labels + "Sided" * side + "Tracked" * tracked + "Read"
-    absent = {f: None for f, on in has.items() if not on and f not in ("side", "track_id", "track_age")}
+    name = step + "Overlay" * overlay + "Labels" * labels + "Sided" * side + "Tracked" * tracked + "Smoothed" * smoothed + "Read"
+    absent = {f: None for f, on in has.items() if not on and f in ("overlay", "box_label", "pose_label")}
     doc = f"{step}Output.read(): {' '.join(base)}" + "".join(f" + {f}" for f in fields[len(base):]) + "."
     return type(name, (collections.namedtuple(name, fields),), dict(absent, __slots__=(), __doc__=doc))
 
@@ -147,6 +162,9 @@ def _read(step, base, values, layout, v, per_slot=lambda t: t):
         values += (per_slot(v.side).clone(),)
     if layout.tracked:
         values += (per_slot(v.track_age).clone(), per_slot(v.track_id).clone())
+        if layout.smoothed:
+            values += (per_slot(v.smooth_xyz).clone(), per_slot(v.smooth_mesh).clone())
+            return _read_type(step, base, layout.overlay, layout.labels, layout.handed, True, True)(*values)
         return _read_type(step, base, layout.overlay, layout.labels, layout.handed, True)(*values)
     return _read_type(step, base, layout.overlay, layout.labels, layout.handed)(*values)
 
@@ -190,6 +208,7 @@ class _LiveStep:
     hands = None                 # K of the K-hand step
     handed = False
     track = None                 # the tracked K-hand step: (track_iou, track_hold)
+    smooth = None                # the smoothed K-hand step: (min_cutoff, beta, d_cutoff)
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None,
                  labels: bool = False, left: bool = False):
@@ -253,7 +272,7 @@ class _LiveStep:
     def _layout(self, n, hw=None) -> LiveLayout:
         """The buffer of a step over n frames (hw: of a step that draws, the frames' size)."""
         return LiveLayout(n, self.hands, self.vertices, hw, hw is not None and self.faces is not None,
-                          hw is not None and self.labels, self.handed, self.track is not None)
+                          hw is not None and self.labels, self.handed, self.track is not None, self.smooth is not None)
 
     def _new_buffers(self, n, hw=None):
         """A fresh (layout, device buffer, pinned host buffer) of a step over n frames."""
@@ -290,14 +309,21 @@ class _LiveStep:
         p2d, mesh, pose3d, raw = out.tail
         drawn, k = out.has_hand.view(-1) if self.hands is None else at.lifted, self.hands or 1
         overlay = box_label = pose_label = None
-        if layout.overlay:
-            overlay = self._draw(mesh, drawn, frames, k, at.overlay)
+        if layout.overlay:      # (a smoothed step draws what it smoothed)
+            overlay = self._draw(at.smooth_mesh if layout.smoothed else mesh, drawn, frames, k, at.overlay)
         if layout.labels:
             box_label, pose_label = ops.draw_labels(out.keypoints, out.crop_box, frames, drawn=drawn, k=k, clamp=self.clamp,
                                                     out_box=at.box_label, out_pose=at.pose_label)
         host.copy_(dev, non_blocking=True)
         return self._output(out, at, layout, host, dict(pose2d=p2d, mesh=mesh, pose3d=pose3d, raw_mesh=raw, overlay=overlay,
                                                         box_label=box_label, pose_label=pose_label))
+
+    def _key_options(self) -> tuple:
+        """What a capture's key carries behind the shapes (the smoothed step: its filter's parameters, kernel arguments)."""
+        return ()
+
+    def _smooth_untouched(self, n):
+        return contextlib.nullcontext()
 
     @ops.device_guarded
     def forward_raw(self, bgr_u8, depth_raw) -> LiveOutput:
@@ -310,7 +336,7 @@ class _LiveStep:
         n, h, w, _ = bgr.shape
         # (a `left` step: the ingest kernel mirrors while it converts, so this capture -- keyed apart from graphed()'s -- takes
         # its inputs as already mirrored and holds no mirror launch)
-        key = ((n, 3, h, w), (n, 1, h, w)) + (("mirrored",) if self.left else ())
+        key = ((n, 3, h, w), (n, 1, h, w)) + (("mirrored",) if self.left else ()) + self._key_options()
         if key not in self._graphs:
             rgb, d1, _ = ops.ingest_raw(bgr, dep, device=self.device, flip_w=self.left)
             self.graphed(rgb, d1, _mirrored=self.left)
@@ -320,7 +346,7 @@ class _LiveStep:
     def graphed(self, images: torch.Tensor, depth: torch.Tensor, _mirrored: bool = False):
         """(run, static images, static depth, static LiveOutput): copy new frames into the static inputs and call run().
         (A `left` step: the captured step mirrors the static inputs itself, one launch.)"""
-        key = (tuple(images.shape), tuple(depth.shape)) + (("mirrored",) if _mirrored else ())
+        key = (tuple(images.shape), tuple(depth.shape)) + (("mirrored",) if _mirrored else ()) + self._key_options()
         hit = self._graphs.get(key)
         if hit is None:
             with torch.inference_mode(False), torch.no_grad():
@@ -335,8 +361,8 @@ class _LiveStep:
                     # baked into the graph, and nothing the step hands out refers to them)
                     flipped = self._mirrored[("capture",) + key] = (torch.empty_like(s_img), torch.empty_like(s_dep))
                 step = lambda: self.forward_device(s_img, s_dep, _buffers=bufs, _mirror=False if _mirrored else flipped)
-                if self.track is not None:      # (the warm-up steps of a capture must not advance the tracker)
-                    with self.hand._track_untouched(images.shape[0], self.hands):
+                if self.track is not None:      # (the warm-up steps of a capture must not advance the tracker, nor the filters)
+                    with self.hand._track_untouched(images.shape[0], self.hands), self._smooth_untouched(images.shape[0]):
                         g, out = ops.capture_step(step)
                 else:
                     g, out = ops.capture_step(step)
@@ -401,13 +427,15 @@ class LiveHandsOutput:
     layout: LiveLayout = None        # where everything lies in `host`
     track_id: torch.Tensor = None    # tracked steps: [N,K] int32 on the device, the slot's track id (held slots included; 0: free)
     track_age: torch.Tensor = None   # tracked steps: [N,K] int32 on the device, the steps on which the slot's track was seen again
+    smooth_xyz: torch.Tensor = None  # smoothed steps: [N,K,21,3] on the device, xyz_mm filtered over time (zeros: has_hand != 1)
+    smooth_mesh: torch.Tensor = None  # smoothed steps: [N,K,V,3] on the device, `mesh` filtered over time (zeros: not lifted)
 
     def read(self) -> LiveHandsRead:
         """After the stream is synchronised: the step's results per frame and slot as fresh CPU tensors (LiveHandsRead;
         lifted as bool, words = the step's range words; a step with faces=: LiveHandsOverlayRead, + overlay [N,H,W,3] uint8; a
         step with labels: + box_label [N,H,W,3], pose_label [N,K,176,176,3] -- LiveHandsLabelsRead, LiveHandsOverlayLabelsRead;
         a handed step: the same with `side` [N,K] int32 behind them; a tracked step: track_age and then track_id [N,K] int32
-        as the last fields)."""
+        as the last fields; a smoothed step: behind those, smooth_xyz [N,K,21,3] and smooth_mesh [N,K,V,3])."""
         v, s = self.layout.views(self.host), self.layout.slots
         per = lambda t: t.reshape((self.layout.frames, self.layout.hands) + tuple(t.shape[1:]))
         kp, has, box, words, (img, xyz) = read_host_record(v.records, s, extras=True)
@@ -427,7 +455,9 @@ class LiveHandsEngine(_LiveStep):
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, max_hands: int = 2, clamp: bool = True,
                  perm_reverse=None, faces=None, labels: bool = False, left: bool = False, handed: bool = False,
-                 left_side: int = 0, track: bool = False, track_iou: float = 0.3, track_hold: int = 5):
+                 left_side: int = 0, track: bool = False, track_iou: float = 0.3, track_hold: int = 5, smooth: bool = False,
+                 smooth_min_cutoff: float = 1.0, smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0,
+                 smooth_rate: float = 30.0):
         """faces: mesh_model.face ([F,3]; needs perm_reverse) -- given, the step ends with the overlay: every lifted mesh of a
         frame drawn over it with one depth buffer per frame (LiveHandsOutput.overlay, read().overlay), in the same copy.
         labels: the step ends with box_label (the crop box of every lifted slot on its frame) and one pose_label per slot
@@ -446,7 +476,16 @@ class LiveHandsEngine(_LiveStep):
         one camera stream, a hand keeps its slot and its id (LiveHandsOutput.track_id, read().track_id) whatever its score
         rank, and a slot whose hand is missing is held for track_hold steps -- has_hand 0, so not lifted, a zero mesh, nothing
         drawn and a zero pose_label, the path of every empty slot.  max_hands = 1 is the sticky top-1.  The state lives in the
-        hand engine, one per (N, K), shared by forward_device, graphed and forward_raw; track_reset() empties it."""
+        hand engine, one per (N, K), shared by forward_device, graphed and forward_raw; track_reset() empties it.
+        smooth (needs track and perm_reverse): a One Euro filter over time on every coordinate of the slots'
+        xyz_mm and final mesh, inside the launch that finishes the mesh -- LiveHandsOutput.smooth_xyz / .smooth_mesh,
+        read().smooth_xyz / .smooth_mesh behind track_id; mesh, records and label images stay unfiltered, the overlay (faces=)
+        is drawn from smooth_mesh.  A slot's filter restarts when the slot was empty or held, or its track id changed.
+        smooth_min_cutoff / smooth_d_cutoff in Hz, smooth_beta per mm/s (the vertices, in metres, use 1000 * smooth_beta),
+        smooth_rate = steps per second (dt = 1 / rate; smooth_dt(seconds) sets another dt, also between replays).  The
+        defaults are the paper's starting values and have NOT been tuned on this model.  This engine owns one filter state and
+        one dt word per (N, K), shared by forward_device, graphed and forward_raw; smooth_reset() -- and track_reset() --
+        empties the state."""
         self.hands = self.max_hands = ops.check_max_hands(max_hands)
         if left and handed:
             raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
@@ -454,6 +493,13 @@ class LiveHandsEngine(_LiveStep):
         self.track = (float(track_iou), track_hold) if track else None
         if track:
             ops.check_track_options(track_iou, track_hold)
+        if smooth:
+            if not track:
+                raise ValueError("smooth=True needs track=True: the filters follow the slots' track ids")
+            if perm_reverse is None:
+                raise ValueError("smooth=True needs perm_reverse=: the filter runs in the launch that finishes the mesh")
+            mc, beta, dc, rate = ops.check_smooth_options(smooth_min_cutoff, smooth_beta, smooth_d_cutoff, smooth_rate)
+            self.smooth, self._dt, self._smooth_states = (mc, beta, dc), 1.0 / rate, {}
         super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left)
 
     def _hand_step(self, images, depth, at, lift):
@@ -464,16 +510,75 @@ class LiveHandsEngine(_LiveStep):
                                        left_side=self.left_side, _side=at.side, **more)
 
     def track_reset(self):
-        """Empty the hand engine's trackers (HandNetEngine.track_reset; also between replays of a captured step)."""
+        """Empty the hand engine's trackers (HandNetEngine.track_reset; also between replays of a captured step) and, on a
+        smoothed engine, the filters."""
         self.hand.track_reset()
+        return self.smooth_reset() if self.smooth is not None else self
+
+    def _need_smooth(self):
+        if self.smooth is None:
+            raise ValueError("this engine does not smooth: build it with smooth=True")
+
+    def _smooth_state(self, n):
+        """(filter state, dt word) of the step over n frames: made empty, with the engine's dt, on first use."""
+        st = self._smooth_states.get(n)
+        if st is None:
+            with torch.inference_mode(False):
+                st = self._smooth_states[n] = (ops.smooth_state(n * self.hands, SMOOTH_JOINTS, self.vertices, self.device),
+                                               torch.full((1,), self._dt, dtype=torch.float32, device=self.device))
+        return st
+
+    @ops.device_guarded
+    def smooth_reset(self):
+        """Empty every filter of this engine: each slot's next value passes unfiltered (a memset on the current stream; also
+        between replays of a captured step)."""
+        self._need_smooth()
+        for state, _dt in self._smooth_states.values():
+            state.zero_()
         return self
+
+    @ops.device_guarded
+    def smooth_dt(self, seconds):
+        """The time between two steps from now on, 0 < seconds < inf (checked here, on the host; the kernel reads the word
+        from device memory): filled on the current stream, so a captured step takes it at its next replay."""
+        self._need_smooth()
+        dt = float(seconds)
+        if not (0.0 < dt < math.inf) or not (0.0 < float(np.float32(dt)) < math.inf):
+            raise ValueError(f"smooth_dt: 0 < seconds < inf as fp32 (got {seconds!r})")
+        self._dt = dt
+        for _state, word in self._smooth_states.values():
+            word.fill_(dt)
+        return self
+
+    def _key_options(self) -> tuple:
+        return () if self.smooth is None else ("smoothed",) + self.smooth
+
+    def _smooth_untouched(self, n):
+        """Context manager around the capture of a smoothed step over n frames: the warm-up steps run the filters, so the
+        state is put back as it was when the capture is done (HandNetEngine._track_untouched)."""
+        if self.smooth is None:
+            return contextlib.nullcontext()
+
+        @contextlib.contextmanager
+        def keep():
+            state = self._smooth_state(n)[0]
+            saved = state.clone()
+            try:
+                yield state
+            finally:
+                state.copy_(saved)
+        return keep()
 
     def _lifter_input(self, image_uvd, has_hand, lifted, mirror):
         return ops.lifter_input_gated(image_uvd, valid=has_hand, lifted=lifted, mirror=mirror)[0]
 
-    def _mesh(self, p2d, xyz, _has_hand, at, mirror):
+    def _mesh(self, p2d, xyz, has_hand, at, mirror):
         raw, pose3d = self.lifter.forward(p2d)
-        if mirror is not None:      # (also without perm_reverse: the raw vertices, x negated where mirrored)
+        if self.smooth is not None:      # (ONE launch in place of mesh_finish's: the mesh, and both signals filtered)
+            state, dt = self._smooth_state(at.lifted.numel() // self.hands)
+            mesh = ops.mesh_finish_smooth(raw, self.perm, xyz, at.lifted, has_hand, at.track_id, dt, state, *self.smooth,
+                                          mirror=mirror, out=at.mesh, smooth_xyz=at.smooth_xyz, smooth_mesh=at.smooth_mesh)[0]
+        elif mirror is not None:      # (also without perm_reverse: the raw vertices, x negated where mirrored)
             mesh = ops.mesh_finish(raw, self.perm, xyz if self.perm is not None else None, valid=at.lifted, out=at.mesh,
                                    mirror=mirror)
         elif self.perm is None:
@@ -486,7 +591,9 @@ class LiveHandsEngine(_LiveStep):
         n, k = layout.frames, layout.hands
         parts["mesh"] = parts["mesh"].view(n, k, self.vertices, 3)
         return LiveHandsOutput(hands=out, lifted=at.lifted.view(n, k), host=host, n=n, k=k, side=out.side, mirror=out.mirror,
-                               layout=layout, track_id=out.track_id, track_age=out.track_age, **parts)
+                               layout=layout, track_id=out.track_id, track_age=out.track_age,
+                               smooth_xyz=None if self.smooth is None else at.smooth_xyz.view(n, k, SMOOTH_JOINTS, 3),
+                               smooth_mesh=None if self.smooth is None else at.smooth_mesh.view(n, k, self.vertices, 3), **parts)
 
 
 @dataclass

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 
@@ -1837,6 +1838,76 @@ def mesh_finish(mesh, perm, xyz_mm, valid=None, out=None, mirror=None):
     check(_lib.load().hn_mesh_finish_f32(ptr(mesh), ptr(perm), ptr(xyz_mm), ptr(valid), n, v0, v, xyz_mm.shape[1], ptr(out), _stream()),
           "hn_mesh_finish_f32")
     return out
+
+
+SMOOTH_WORDS = 4           # int32 words of a record of the filter's state: {xh, dxh as fp32 bits, track id, 0}
+SMOOTH_JOINTS = 21         # joints of a slot in the live step's filter state
+
+
+def check_smooth_options(min_cutoff=1.0, beta=0.007, d_cutoff=1.0, rate=30.0):
+    """(min_cutoff, beta, d_cutoff, rate) of the smoothed step as floats: min_cutoff, d_cutoff (Hz) and rate (steps per second,
+    dt = 1 / rate) finite and > 0, beta (stated for speeds in mm/s) finite and >= 0 -- also after the rounding to fp32 that the
+    kernel's arguments get, and so is the vertices' beta, float32(1000 * beta) --, else ValueError."""
+    def number(name, value, low_ok):
+        try:
+            f = float(value)
+        except (TypeError, ValueError):
+            f = math.nan
+        with np.errstate(over="ignore"):
+            g = float(np.float32(f))
+        if not (math.isfinite(f) and math.isfinite(g) and (g >= 0 if low_ok else g > 0)):
+            raise ValueError(f"{name} must be finite and {'>= 0' if low_ok else '> 0'} as fp32 (got {value!r})")
+        return f
+    mc, b, dc = number("smooth_min_cutoff", min_cutoff, False), number("smooth_beta", beta, True), number("smooth_d_cutoff", d_cutoff, False)
+    number("smooth_beta * 1000", b * 1000.0, True)
+    r = number("smooth_rate", rate, False)
+    number("1 / smooth_rate", 1.0 / r, False)
+    return mc, b, dc, r
+
+
+def smooth_state(slots, joints, v, device):
+    """The empty filter of `slots` hand slots with `joints` joints and v vertices each: zeroed int32 [slots, joints + v, 3, 4]
+    (one 16-byte record per coordinate, a slot's joints first, then its vertices; reset: state.zero_())."""
+    slots, joints, v = int(slots), int(joints), int(v)
+    if slots <= 0 or joints <= 0 or v <= 0:
+        raise ValueError(f"smooth_state: slots, joints and v must be positive (got {slots}, {joints}, {v})")
+    return torch.zeros((slots, joints + v, 3, SMOOTH_WORDS), device=device, dtype=torch.int32)
+
+
+def mesh_finish_smooth(mesh, perm, xyz_mm, lifted, has_hand, track_id, dt, state, min_cutoff=1.0, beta=0.007, d_cutoff=1.0,
+                       mirror=None, out=None, smooth_xyz=None, smooth_mesh=None):
+    """mesh_finish(mesh, perm, xyz_mm, valid=lifted, mirror=mirror) and, in the same launch (hn_mesh_finish_smooth_f32), a One
+    Euro filter over time on every coordinate of that final mesh (gate: lifted == 1) and of xyz_mm (gate: has_hand == 1)
+    -> (mesh [N,V,3], smooth_xyz [N,J,3], smooth_mesh [N,V,3]).  lifted, has_hand, track_id: int32 [N]; dt: ONE fp32 word on
+    the device (seconds since the last step); state: smooth_state(N, J, V), updated in place.  A row's filter restarts when
+    its gate was off or its track id changed; beta is stated for mm/s, the vertices (metres) use float32(1000 * beta)."""
+    mc, b, dc, _ = check_smooth_options(min_cutoff, beta, d_cutoff)
+    _req(mesh, name="mesh"); _req(perm, torch.int64, "perm"); _req(xyz_mm, name="xyz_mm")
+    n, v0, _ = mesh.shape
+    v, joints = perm.shape[0], xyz_mm.shape[1]
+    if xyz_mm.shape[0] != n:
+        raise ValueError("xyz_mm must hold one row per mesh")
+    for name, t in (("lifted", lifted), ("has_hand", has_hand), ("track_id", track_id)) + ((("mirror", mirror),) if mirror is not None else ()):
+        if _req(t, torch.int32, name).numel() != n:
+            raise ValueError(f"{name} must hold one int32 per row")
+    if _req(dt, name="dt").numel() != 1:
+        raise ValueError("dt must be one fp32 word on the device")
+    if _req(state, torch.int32, "state").numel() != n * (joints + v) * 3 * SMOOTH_WORDS:
+        raise ValueError(f"state must be smooth_state({n}, {joints}, {v}): int32 [{n},{joints + v},3,{SMOOTH_WORDS}]")
+    if out is None:
+        out = torch.empty((n, v, 3), device=mesh.device, dtype=torch.float32)
+    if smooth_xyz is None:
+        smooth_xyz = torch.empty((n, joints, 3), device=mesh.device, dtype=torch.float32)
+    if smooth_mesh is None:
+        smooth_mesh = torch.empty((n, v, 3), device=mesh.device, dtype=torch.float32)
+    _req(out, name="out"); _req(smooth_xyz, name="smooth_xyz"); _req(smooth_mesh, name="smooth_mesh")
+    if out.numel() != n * v * 3 or smooth_mesh.numel() != n * v * 3 or smooth_xyz.numel() != n * joints * 3:
+        raise ValueError("out / smooth_mesh must hold [N,V,3] and smooth_xyz [N,J,3] values")
+    check(_lib.load().hn_mesh_finish_smooth_f32(ptr(mesh), ptr(perm), ptr(xyz_mm), ptr(lifted), ptr(has_hand), ptr(mirror),
+                                                ptr(track_id), ptr(dt), ptr(state), n, v0, v, joints, mc, b,
+                                                float(np.float32(b * 1000.0)), dc, ptr(out), ptr(smooth_xyz), ptr(smooth_mesh),
+                                                _stream()), "hn_mesh_finish_smooth_f32")
+    return out, smooth_xyz, smooth_mesh
 
 
 def mesh_faces(faces, vertices, device):

@@ -35,8 +35,8 @@ extern "C" {
 /* ABI version; bumped whenever a struct below changes (functions added without touching a struct or an existing signature
  * keep it: hn_lifter_input_gated_f32 and hn_mesh_render_u8 came under 36, and so did the mirror / handedness entries
  * hn_ingest_u8bgr_u16mm_flip, hn_flip_w_f32, hn_crop_resize_hands_sided, hn_a2j_aggregate_convert_mirror_f32,
- * hn_lifter_input_gated_mirror_f32 and hn_mesh_finish_mirror_f32, and the tracked slots' hn_crop_resize_hands_tracked and
- * hn_track_state_bytes). */
+ * hn_lifter_input_gated_mirror_f32 and hn_mesh_finish_mirror_f32, the tracked slots' hn_crop_resize_hands_tracked and
+ * hn_track_state_bytes, and the smoothed step's hn_mesh_finish_smooth_f32 and hn_smooth_state_bytes). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -743,6 +743,31 @@ int hn_mesh_finish_f32(const float* mesh, const int64_t* perm, const float* xyz_
 int hn_mesh_finish_mirror_f32(const float* mesh, const int64_t* perm /* or NULL */, const float* xyz_mm /* or NULL */,
                               const int32_t* valid /* or NULL */, const int32_t* mirror, int n, int v0, int v, int joints,
                               float* out, void* stream);
+/* hn_mesh_finish_mirror_f32 (perm and xyz_mm given) and, in the same launch, a One Euro filter (Casiez et al. 2012) over time
+ * on every coordinate of two signals of every row (= tracked hand slot): the final mesh as written to `out` (metres; gate:
+ * lifted[i] == 1) -> smooth_mesh [n][v][3], and xyz_mm (camera millimetres; gate: has_hand[i] == 1) -> smooth_xyz
+ * [n][joints][3].  `out` is hn_mesh_finish_mirror_f32's, bit for bit (valid = lifted; mirror may be NULL).
+ * state: hn_smooth_state_bytes(n, joints, v) bytes on the device, 16-byte aligned, updated in place: one 16-byte record
+ * {float xh, float dxh, int32 id, int32 0} per element, [n][joints + v][3] -- a row's joints first, then its vertices.  All
+ * zeros = the empty filter (reset: a memset).  Every thread reads and writes its own record only.
+ * Per element, x = the unfiltered value, t = track_id[i] (device int32 [n]):
+ *   1. gate off: the output is 0 and the record is zeroed (a hand that returns restarts);
+ *   2. x not finite: the output is x and the record is zeroed;
+ *   3. record id == 0, or id != t, or t == 0, or a stored xh / dxh that is not finite: the output is x, the record {x, 0, t};
+ *   4. else, with (xp, dxp) = the record's (xh, dxh), in fp32 with one rounding per operation and in this order:
+ *        rd = (TWO_PI * d_cutoff) * dt;  ad = rd / (rd + 1);  dx = (x - xp) / dt;  edx = dxp + ad * (dx - dxp);
+ *        fc = min_cutoff + beta * |edx|;  r = (TWO_PI * fc) * dt;  a = r / (r + 1);  xh = xp + a * (x - xp)
+ *      (TWO_PI = 6.2831855f): the output is xh, the record {xh, edx, t}.
+ * dt: ONE fp32 word on the device (seconds between steps, finite and > 0: the caller's to check), read by every thread and
+ * never written -- a captured step takes another dt without a new capture.  min_cutoff, d_cutoff: finite and > 0; beta_xyz
+ * (the joints' beta, speeds in mm/s) and beta_mesh (the vertices', speeds in m/s: 1000 * beta_xyz for the same behaviour):
+ * finite and >= 0; else HN_ERR_ARG.  Added under ABI 36. */
+int hn_mesh_finish_smooth_f32(const float* mesh, const int64_t* perm, const float* xyz_mm, const int32_t* lifted,
+                              const int32_t* has_hand, const int32_t* mirror /* or NULL */, const int32_t* track_id,
+                              const float* dt, void* state, int n, int v0, int v, int joints, float min_cutoff, float beta_xyz,
+                              float beta_mesh, float d_cutoff, float* out, float* smooth_xyz, float* smooth_mesh, void* stream);
+/* bytes of the filter state of `slots` rows with `joints` joints and v vertices each (0 for arguments that are not positive) */
+int64_t hn_smooth_state_bytes(int slots, int joints, int v);
 /* The live caller's last call, render(out, paras, h, w, full_image, face) (ros_demo.py:86-116,329-337), without a graphics
  * pipeline: the meshes of s = n * k hand slots (slot i * k + j = hand j of frame i) rasterised over their frames, one depth
  * buffer per frame.  mesh [s][v][3] fp32 as hn_mesh_finish_f32 writes it (metres, y and z negated), faces [f][3] int32 vertex
