@@ -21,8 +21,11 @@ slot are printed per frame -- a hand keeps its slot and id whatever its score ra
 With --smooth the same frames go through the tracked K = 2 step with the filter on (live_hands(track=True, smooth=True)): per
 frame, how far the filtered mesh and joints lie from the raw ones (0 on a slot's first frame and on a repeated frame); the
 filter's parameters are the paper's starting values, not tuned on this model.
+With --occlude the last frame also goes through the K = 2 step with faces= and occlude=True: the overlay leaves out what lies
+more than 3 cm (a starting value, not tuned) behind the frame's depth map, and for every slot the share of its mesh's pixels that
+the camera sees is printed (read().coverage), with the silhouette's pixel counts.
 usage (GPU box): python examples/live_demo.py [frames] [--overlay out.png] [--mano MANO_RIGHT.pkl] [--labels PREFIX] [--left]
-                 [--handed] [--track] [--smooth]"""
+                 [--handed] [--track] [--smooth] [--occlude]"""
 import sys
 import time
 import types
@@ -61,7 +64,8 @@ def main():
             opt[flag] = argv[i + 1]
             del argv[i:i + 2]
     left, handed, track, smooth = "--left" in argv, "--handed" in argv, "--track" in argv, "--smooth" in argv
-    argv = [a for a in argv if a not in ("--left", "--handed", "--track", "--smooth")]
+    occlude = "--occlude" in argv
+    argv = [a for a in argv if a not in ("--left", "--handed", "--track", "--smooth", "--occlude")]
     frames = int(argv[0]) if argv else 20
     faces = _faces(opt.get("--mano")) if "--overlay" in opt else None
     args = types.SimpleNamespace(pretrained_fcos="-", pretrained_a2j="-")
@@ -150,6 +154,18 @@ def main():
                 print(f"8. smooth, frame {i}: id per slot {r4.track_id[0].tolist()}, |smooth_mesh - mesh| max "
                       f"{1e3 * float((r4.smooth_mesh - r4.mesh).abs().max()):.3f} mm, |smooth_xyz - xyz_mm| max "
                       f"{float((r4.smooth_xyz - r4.xyz_mm).abs().max()):.3f} mm")
+        if occlude:                                                                       # the mesh behind nearer scene depth
+            hidden = net.live_hands(model, PARAS, max_hands=2, clamp=True, perm_reverse=rev,
+                                    faces=faces if faces is not None else _faces(opt.get("--mano")), occlude=True,
+                                    occlude_margin=0.03)
+            o5 = hidden.forward_device(s_img, s_dep)
+            torch.cuda.current_stream().synchronize()
+            r5 = o5.read()
+            for k, (under, seen) in enumerate(r5.coverage[0].tolist()):
+                share = f"{seen / under:.1%} shown" if under else "nothing drawn"
+                print(f"9. occlude, slot {k}: lifted {bool(r5.lifted[0, k])}, {under} pixels where its mesh is the nearest, {share}")
+            print(f"   silhouette {tuple(r5.silhouette.shape)} uint8: {int((r5.silhouette != 0).sum())} pixels under a mesh, "
+                  f"{int((r5.silhouette & 0x80 != 0).sum())} of them hidden")
 
 
 if __name__ == "__main__":

@@ -14,6 +14,13 @@
 // No atomics, no order dependence between workgroups: the image is a pure function of the inputs (slot-major, then face
 // order decides an exact depth tie).  The rule itself is stated in DESIGN.md ("The overlay") and restated in numpy by
 // tests/raster_ref.py.
+//
+// The occluded form (hn_mesh_render_occluded_u8; DESIGN.md "The overlay behind the scene", tests/occlude_ref.py) is the same
+// two launches with a compile-time switch: the tile kernel also keeps the winner's slot, loads the camera's depth D on covered
+// lanes only, hides the pixel where D is valid and best > D + margin, writes the silhouette byte, and adds two ballots'
+// popcounts per slot that touched the tile to the slot's two counters, which the setup kernel's thread 0 zeroed.  The only
+// atomics are those integer adds: sums of integers do not depend on their order, so the outputs stay a pure function of the
+// inputs.  The instantiations without the switch take no further argument and hold no further instruction.
 #include "hn_common.h"
 
 namespace {
@@ -40,6 +47,15 @@ struct SlotBox { int x0, x1, y0, y1; };
 __host__ __device__ inline size_t rec_offset(int s) { return (size_t)s * sizeof(SlotBox); }
 __host__ __device__ inline size_t box_offset(int s, int f) { return rec_offset(s) + (size_t)s * f * sizeof(FaceRec); }
 __host__ __device__ inline size_t scratch_total(int s, int f) { return box_offset(s, f) + (size_t)s * f * sizeof(Box); }
+
+// what the occluded form adds to both kernels' arguments
+struct Occlusion {
+  const float* depth;               // the camera's depth map, metres: frame i at depth + i * frame_stride, [h][w]
+  long long frame_stride;           // in elements (h * w; 4 * h * w for channel 3 of an RGBD tensor)
+  float margin;                     // metres
+  unsigned char* silhouette;        // [n][h][w]: 0, slot + 1 (shown) or 0x80 | (slot + 1) (hidden)
+  int* coverage;                    // [slots][2]: (pixels where the slot's mesh is the nearest, of those shown), or null
+};
 
 struct Snapped { int x, y; float z; bool ok; };
 
@@ -85,11 +101,16 @@ __device__ __forceinline__ int wave_min(int v) {
   return v;
 }
 
+template <class... Coverage>   // nothing, or -- the occluded form -- the slots' counters (int*), which thread 0 zeroes
 __global__ __launch_bounds__(256) void mesh_raster_setup(const float* __restrict__ mesh, const int* __restrict__ faces,
                                                          const int* __restrict__ lifted, int v, int f, float fx, float fy,
                                                          float cx, float cy, int h, int w, unsigned char* __restrict__ scratch,
-                                                         int slots) {
+                                                         int slots, Coverage... coverage) {
   const int slot = blockIdx.x;
+  if constexpr (sizeof...(Coverage) != 0) {
+    int* counters = (coverage, ...);
+    if (counters && threadIdx.x == 0) counters[2 * slot] = counters[2 * slot + 1] = 0;   // (the tiles launch adds to them)
+  }
   SlotBox* slot_box = reinterpret_cast<SlotBox*>(scratch + (size_t)slot * sizeof(SlotBox));
   FaceRec* recs = reinterpret_cast<FaceRec*>(scratch + rec_offset(slots)) + (size_t)slot * f;
   Box* boxes = reinterpret_cast<Box*>(scratch + box_offset(slots, f)) + (size_t)slot * f;
@@ -153,10 +174,13 @@ __device__ __forceinline__ long long edge(int ax, int ay, int bx, int by, int px
   return e;
 }
 
-template <int FMT>   // HN_FRAME_F32_CHW / HN_FRAME_U8_BGR_HWC
+// FMT: HN_FRAME_F32_CHW / HN_FRAME_U8_BGR_HWC; OCC: the occluded form, whose one further argument is an Occlusion
+template <int FMT, bool OCC = false, class... Occ>
 __global__ __launch_bounds__(256) void mesh_raster_tiles(const unsigned char* __restrict__ scratch, int slots, int f, int k,
                                                          const void* __restrict__ frame, int h, int w,
-                                                         unsigned char* __restrict__ out, float* __restrict__ depth_out) {
+                                                         unsigned char* __restrict__ out, float* __restrict__ depth_out,
+                                                         Occ... occ) {
+  static_assert(sizeof...(Occ) == (OCC ? 1 : 0), "the occluded form takes one Occlusion");
   // a workgroup is 4 tiles side by side: 32 x 8 pixels
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int tx = (blockIdx.x * 4 + wave) * 8, ty = blockIdx.y * 8, n = blockIdx.z;
@@ -169,10 +193,13 @@ __global__ __launch_bounds__(256) void mesh_raster_tiles(const unsigned char* __
   float best = 3.402823466e38f;
   unsigned rgb = 0;
   bool covered = false;
+  int winner = 0;                                             // (OCC) slot within the frame of the nearest face
+  unsigned touched = 0;                                       // (OCC) bit kk: slot kk's box meets the tile (wave-uniform)
   for (int kk = 0; kk < k; ++kk) {
     const int slot = n * k + kk;
     const SlotBox sb = *reinterpret_cast<const SlotBox*>(scratch + (size_t)slot * sizeof(SlotBox));
     if (sb.x0 > tx + 7 || sb.x1 < tx || sb.y0 > ty + 7 || sb.y1 < ty) continue;      // (wave-uniform)
+    if (OCC) touched |= 1u << kk;
     const FaceRec* recs = all_recs + (size_t)slot * f;
     const Box* boxes = all_boxes + (size_t)slot * f;
     for (int base = 0; base < f; base += 64) {
@@ -192,14 +219,40 @@ __global__ __launch_bounds__(256) void mesh_raster_tiles(const unsigned char* __
         const long long wc = edge(r.ax, r.ay, r.bx, r.by, px, py, in);
         if (in) {
           const float z = ((float)wa * r.za + (float)wb * r.zb + (float)wc * r.zc) * r.inv_area;
-          if (z < best) { best = z; rgb = r.rgb; covered = true; }
+          if (z < best) {
+            best = z; rgb = r.rgb; covered = true;
+            if (OCC) winner = kk;
+          }
         }
       }
     }
   }
+  bool shown = covered;
+  if constexpr (OCC) {
+#pragma clang fp contract(off)
+    const Occlusion o = (occ, ...);
+    if (covered) {                                            // (covered lanes are inside the frame)
+      const float d = o.depth[(size_t)n * o.frame_stride + (size_t)row * w + col];
+      const bool valid = d > 0.f && d <= 3.402823466e38f;     // (a hole -- 0, NaN --, inf or a negative value hides nothing)
+      shown = !(valid && best > __fadd_rn(d, o.margin));
+    }
+    // all 64 lanes are here: two ballots per slot that touched the tile, lane 0 adds their popcounts
+    while (touched) {
+      const int kk = __builtin_ctz(touched);
+      touched &= touched - 1;
+      const unsigned long long mine = __ballot(covered && winner == kk);
+      const unsigned long long seen = __ballot(covered && winner == kk && shown);
+      if (o.coverage && lane == 0 && mine) {
+        atomicAdd(o.coverage + 2 * (n * k + kk), __popcll(mine));
+        if (seen) atomicAdd(o.coverage + 2 * (n * k + kk) + 1, __popcll(seen));
+      }
+    }
+    if (inside_frame)
+      o.silhouette[((size_t)n * h + row) * w + col] = covered ? (unsigned char)((shown ? 0 : 0x80) | (winner + 1)) : 0;
+  }
   if (!inside_frame) return;
   const size_t pix = ((size_t)n * h + row) * w + col;
-  if (!covered) {
+  if (!shown) {
     if (FMT == HN_FRAME_F32_CHW) {
       const float* src = static_cast<const float*>(frame) + (size_t)n * 3 * h * w + (size_t)row * w + col;
       rgb = 0;
@@ -227,35 +280,75 @@ extern "C" int64_t hn_mesh_render_scratch_bytes(int s, int f) {
   return (int64_t)scratch_total(s, f);
 }
 
-extern "C" int hn_mesh_render_u8(const float* mesh, const int32_t* faces, const int32_t* faces_host, const int32_t* lifted, int s,
-                                 int v, int f, int k, const float* paras, const void* frame, int frame_format, int h, int w,
-                                 void* scratch, int64_t scratch_bytes, uint8_t* out_image, float* out_depth, void* stream) {
-  HN_CHECK_ARG(mesh && faces && paras && frame && scratch, "hn_mesh_render_u8: null pointer");
-  HN_CHECK_ARG(out_image, "hn_mesh_render_u8: out_image is NULL");
-  HN_CHECK_ARG(s > 0 && v > 0 && f > 0, "hn_mesh_render_u8: bad dims (s %d, v %d, f %d: all must be positive)", s, v, f);
-  HN_CHECK_ARG(k > 0 && s % k == 0, "hn_mesh_render_u8: %d slots are not a multiple of k = %d slots per frame", s, k);
-  HN_CHECK_ARG(h > 0 && w > 0 && h <= 16384 && w <= 16384, "hn_mesh_render_u8: bad frame size %d x %d (1..16384)", h, w);
-  HN_CHECK_ARG(s / k <= 65535, "hn_mesh_render_u8: more than 65535 frames");
-  HN_CHECK_ARG(frame_format == HN_FRAME_F32_CHW || frame_format == HN_FRAME_U8_BGR_HWC, "hn_mesh_render_u8: unknown frame format %d",
+// the argument checks both entry points share (`fn`: the name the messages carry), then the two launches
+static int render(const char* fn, const float* mesh, const int32_t* faces, const int32_t* faces_host, const int32_t* lifted, int s,
+                  int v, int f, int k, const float* paras, const void* frame, int frame_format, int h, int w, void* scratch,
+                  int64_t scratch_bytes, uint8_t* out_image, float* out_depth, const Occlusion* occ, int64_t depth_frame_stride,
+                  void* stream) {
+  HN_CHECK_ARG(mesh && faces && paras && frame && scratch, "%s: null pointer", fn);
+  HN_CHECK_ARG(out_image, "%s: out_image is NULL", fn);
+  HN_CHECK_ARG(s > 0 && v > 0 && f > 0, "%s: bad dims (s %d, v %d, f %d: all must be positive)", fn, s, v, f);
+  HN_CHECK_ARG(k > 0 && s % k == 0, "%s: %d slots are not a multiple of k = %d slots per frame", fn, s, k);
+  HN_CHECK_ARG(h > 0 && w > 0 && h <= 16384 && w <= 16384, "%s: bad frame size %d x %d (1..16384)", fn, h, w);
+  HN_CHECK_ARG(s / k <= 65535, "%s: more than 65535 frames", fn);
+  HN_CHECK_ARG(frame_format == HN_FRAME_F32_CHW || frame_format == HN_FRAME_U8_BGR_HWC, "%s: unknown frame format %d", fn,
                frame_format);
-  HN_CHECK_ARG(scratch_bytes >= (int64_t)scratch_total(s, f), "hn_mesh_render_u8: scratch of %lld bytes, %lld needed",
+  HN_CHECK_ARG(scratch_bytes >= (int64_t)scratch_total(s, f), "%s: scratch of %lld bytes, %lld needed", fn,
                (long long)scratch_bytes, (long long)scratch_total(s, f));
-  HN_CHECK_ARG(((uintptr_t)scratch & 15) == 0, "hn_mesh_render_u8: scratch must be 16-byte aligned");
+  HN_CHECK_ARG(((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", fn);
+  if (occ) {
+    HN_CHECK_ARG(occ->depth, "%s: scene_depth is NULL", fn);
+    HN_CHECK_ARG(occ->silhouette, "%s: out_silhouette is NULL", fn);
+    HN_CHECK_ARG(k <= 16, "%s: k = %d slots per frame do not fit the silhouette's byte (1..16)", fn, k);
+    HN_CHECK_ARG(depth_frame_stride >= (int64_t)h * w, "%s: depth_frame_stride %lld is less than a frame of %d x %d", fn,
+                 (long long)depth_frame_stride, h, w);
+    HN_CHECK_ARG(occ->margin == occ->margin && fabsf(occ->margin) <= 3.402823466e38f, "%s: margin must be finite", fn);
+  }
   if (faces_host)
     for (int64_t i = 0; i < (int64_t)f * 3; ++i)
-      HN_CHECK_ARG(faces_host[i] >= 0 && faces_host[i] < v, "hn_mesh_render_u8: face %lld uses vertex %d of %d", (long long)(i / 3),
+      HN_CHECK_ARG(faces_host[i] >= 0 && faces_host[i] < v, "%s: face %lld uses vertex %d of %d", fn, (long long)(i / 3),
                    faces_host[i], v);
   hipStream_t st = (hipStream_t)stream;
   unsigned char* sc = static_cast<unsigned char*>(scratch);
-  hipLaunchKernelGGL(mesh_raster_setup, dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, paras[0], paras[1], paras[2], paras[3],
-                     h, w, sc, s);
-  HN_CHECK_LAUNCH("mesh_raster_setup");
   const dim3 grid((w + 31) / 32, (h + 7) / 8, s / k);
+  if (!occ) {
+    hipLaunchKernelGGL(mesh_raster_setup<>, dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, paras[0], paras[1], paras[2],
+                       paras[3], h, w, sc, s);
+    HN_CHECK_LAUNCH("mesh_raster_setup");
+    if (frame_format == HN_FRAME_F32_CHW)
+      hipLaunchKernelGGL(mesh_raster_tiles<HN_FRAME_F32_CHW>, grid, dim3(256), 0, st, sc, s, f, k, frame, h, w, out_image, out_depth);
+    else
+      hipLaunchKernelGGL(mesh_raster_tiles<HN_FRAME_U8_BGR_HWC>, grid, dim3(256), 0, st, sc, s, f, k, frame, h, w, out_image,
+                         out_depth);
+    HN_CHECK_LAUNCH("mesh_raster_tiles");
+    return HN_OK;
+  }
+  hipLaunchKernelGGL(mesh_raster_setup<int*>, dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, paras[0], paras[1], paras[2],
+                     paras[3], h, w, sc, s, occ->coverage);
+  HN_CHECK_LAUNCH("mesh_raster_setup");
   if (frame_format == HN_FRAME_F32_CHW)
-    hipLaunchKernelGGL(mesh_raster_tiles<HN_FRAME_F32_CHW>, grid, dim3(256), 0, st, sc, s, f, k, frame, h, w, out_image, out_depth);
+    hipLaunchKernelGGL((mesh_raster_tiles<HN_FRAME_F32_CHW, true, Occlusion>), grid, dim3(256), 0, st, sc, s, f, k, frame, h, w,
+                       out_image, out_depth, *occ);
   else
-    hipLaunchKernelGGL(mesh_raster_tiles<HN_FRAME_U8_BGR_HWC>, grid, dim3(256), 0, st, sc, s, f, k, frame, h, w, out_image,
-                       out_depth);
+    hipLaunchKernelGGL((mesh_raster_tiles<HN_FRAME_U8_BGR_HWC, true, Occlusion>), grid, dim3(256), 0, st, sc, s, f, k, frame, h, w,
+                       out_image, out_depth, *occ);
   HN_CHECK_LAUNCH("mesh_raster_tiles");
   return HN_OK;
+}
+
+extern "C" int hn_mesh_render_u8(const float* mesh, const int32_t* faces, const int32_t* faces_host, const int32_t* lifted, int s,
+                                 int v, int f, int k, const float* paras, const void* frame, int frame_format, int h, int w,
+                                 void* scratch, int64_t scratch_bytes, uint8_t* out_image, float* out_depth, void* stream) {
+  return render("hn_mesh_render_u8", mesh, faces, faces_host, lifted, s, v, f, k, paras, frame, frame_format, h, w, scratch,
+                scratch_bytes, out_image, out_depth, nullptr, 0, stream);
+}
+
+extern "C" int hn_mesh_render_occluded_u8(const float* mesh, const int32_t* faces, const int32_t* faces_host, const int32_t* lifted,
+                                          int s, int v, int f, int k, const float* paras, const void* frame, int frame_format,
+                                          int h, int w, const float* scene_depth, int64_t depth_frame_stride, float margin,
+                                          void* scratch, int64_t scratch_bytes, uint8_t* out_image, float* out_depth,
+                                          uint8_t* out_silhouette, int32_t* out_coverage, void* stream) {
+  const Occlusion occ = {scene_depth, (long long)depth_frame_stride, margin, out_silhouette, out_coverage};
+  return render("hn_mesh_render_occluded_u8", mesh, faces, faces_host, lifted, s, v, f, k, paras, frame, frame_format, h, w,
+                scratch, scratch_bytes, out_image, out_depth, &occ, depth_frame_stride, stream);
 }

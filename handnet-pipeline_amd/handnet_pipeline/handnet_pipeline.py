@@ -102,7 +102,8 @@ class HandNet(EngineOwner):
         self.last_converted = None
         return self
 
-    def live(self, lifter, paras, clamp: bool = True, perm_reverse=None, faces=None, labels: bool = False, left: bool = False):
+    def live(self, lifter, paras, clamp: bool = True, perm_reverse=None, faces=None, labels: bool = False, left: bool = False,
+             occlude: bool = False, occlude_margin: float = 0.03):
         """The live caller's chain as ONE step (hn_amd.live.LiveHandEngine; ros_demo.py:270-290,329-337): this network, the
         caller's clamp + convert_joints (in the aggregation's epilogue), the lifter's input, Pose2Mesh, one device -> host copy.
         lifter: the drop-in `models.pose2mesh_net.get_model(...)` module (on the GPU) or a Pose2MeshEngine; paras = (fx, fy,
@@ -113,17 +114,21 @@ class HandNet(EngineOwner):
         box) and pose_label (the 176 x 176 colour crop with the skeleton), out.box_label / .pose_label, read() likewise.
         left: the caller's ImageListener(left=True) (ros_demo.py:259-262): frame and depth map are mirrored along the width
         before anything else runs -- inside the ingest kernel for forward_raw -- and every result is in the mirrored frame.
+        occlude (needs faces): the overlay leaves out the mesh where it lies more than occlude_margin metres behind the step's
+        own depth map (holes -- 0, NaN -- hide nothing), and read() ends with silhouette [N,H,W] uint8 (0 no mesh, 1 shown,
+        0x81 hidden) and coverage [N,2] int32 (pixels under the mesh, of those shown).  0.03 m is a starting value, NOT tuned.
         The returned engine owns this network's step from then on (forward() of this module keeps working and
         carries the converted joints: set_convert)."""
         from hn_amd.live import LiveHandEngine
         self._convert_cfg = (tuple(paras), bool(clamp))
         return LiveHandEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, clamp, perm_reverse,
-                              faces, labels, left)
+                              faces, labels, left, occlude, occlude_margin)
 
     def live_hands(self, lifter, paras, max_hands: int = 2, clamp: bool = True, perm_reverse=None, faces=None,
                    labels: bool = False, left: bool = False, handed: bool = False, left_side: int = 0, track: bool = False,
-                   track_iou: float = 0.3, track_hold: int = 5, smooth: bool = False, smooth_min_cutoff: float = 1.0,
-                   smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0, smooth_rate: float = 30.0):
+                   track_iou: float = 0.3, track_hold: int = 5, occlude: bool = False, occlude_margin: float = 0.03,
+                   smooth: bool = False, smooth_min_cutoff: float = 1.0, smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0,
+                   smooth_rate: float = 30.0):
         """live() for up to max_hands (1..16) hands per frame (hn_amd.live.LiveHandsEngine): forward_hands' slots, the
         caller's clamp + convert_joints, the lifter's input with the caller's skip rule per slot (a hand whose 2D box
         process_bbox refuses is not lifted: ros_demo.py:288-300), Pose2Mesh on every slot, one device -> host copy.
@@ -145,15 +150,19 @@ class HandNet(EngineOwner):
         read().smooth_mesh [N,K,V,3] behind track_id, and the overlay is drawn from smooth_mesh; everything else stays
         unfiltered.  smooth_min_cutoff, smooth_beta (per mm/s), smooth_d_cutoff and smooth_rate (steps per second) are the
         paper's starting values, NOT tuned on this model; engine.smooth_dt(seconds) follows the camera's real frame time and
-        engine.smooth_reset() restarts the filters.  max_hands=1, track=True, smooth=True is the smoothed sticky top-1."""
+        engine.smooth_reset() restarts the filters.  max_hands=1, track=True, smooth=True is the smoothed sticky top-1.
+        occlude (needs faces): as live()'s, for all K slots against the frame's one depth map: read() ends with silhouette
+        [N,H,W] uint8 (0 no mesh, k + 1 slot k shown, 0x80 | (k + 1) hidden) and coverage [N,K,2] int32 (per slot: pixels where
+        its mesh is the nearest, of those shown).  occlude_margin = 0.03 m is a starting value, NOT tuned on this model."""
         from hn_amd.live import LiveHandsEngine
         k = ops.check_max_hands(max_hands)
         if left and handed:
             raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
         self._convert_cfg = (tuple(paras), bool(clamp))
         return LiveHandsEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, k, clamp,
-                               perm_reverse, faces, labels, left, handed, left_side, track, track_iou, track_hold, smooth,
-                               smooth_min_cutoff, smooth_beta, smooth_d_cutoff, smooth_rate)
+                               perm_reverse, faces, labels, left, handed, left_side, track, track_iou, track_hold,
+                               occlude=occlude, occlude_margin=occlude_margin, smooth=smooth, smooth_min_cutoff=smooth_min_cutoff,
+                               smooth_beta=smooth_beta, smooth_d_cutoff=smooth_d_cutoff, smooth_rate=smooth_rate)
 
     # forward() switches ITSELF to hipGraph replay once the same input shapes have come in a few times in a row -- the live
     # caller's case (ros_demo.py:270-273: one 640x480 frame per call, ~150 dependent launches whose host cost is 8 % of the

@@ -231,6 +231,9 @@ SIGNATURES = {
     # the smoothed live step (new functions under ABI 36)
     "hn_mesh_finish_smooth_f32": (C.c_int, [VP] * 9 + [C.c_int] * 4 + [C.c_float] * 4 + [VP] * 4),
     "hn_smooth_state_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    # the overlay hidden behind nearer scene depth (a new function under ABI 36)
+    "hn_mesh_render_occluded_u8": (C.c_int, [VP, VP, VP, VP] + [C.c_int] * 4 + [c_f32p, VP, C.c_int, C.c_int, C.c_int, VP, C.c_int64,
+                                             C.c_float, VP, C.c_int64, VP, VP, VP, VP, VP]),
 }
 
 _lock = threading.Lock()

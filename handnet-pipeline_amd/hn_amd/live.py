@@ -60,6 +60,12 @@ LiveSmoothedViews = collections.namedtuple("LiveSmoothedViews", LiveTrackedViews
 SMOOTH_JOINTS = ops.SMOOTH_JOINTS
 
 
+@functools.lru_cache(maxsize=None)
+def _occluded_views(kind):
+    """... and of an occluded step: the fields of its step without the option, then the silhouette and the coverage"""
+    return collections.namedtuple(kind.__name__.replace("Views", "OccludedViews"), kind._fields + ("silhouette", "coverage"))
+
+
 @dataclass(frozen=True)
 class LiveLayout:
     """Byte layout of a live step's one copy buffer, in this order: the records (one-hand step: a wide record per frame + the
@@ -67,7 +73,8 @@ class LiveLayout:
     detection ranks: hands_record_rows), `side` int32 [slots] (handed steps: the detector's side per slot), `track_id` and
     `track_age` int32 [slots] each (tracked steps), `lifted` int32 [slots] (K-hand steps), the mesh fp32 [slots,V,3], the overlay uint8 [frames,h,w,3], box_label uint8 [frames,h,w,3] and
     pose_label uint8 [slots,176,176,3] (each label image starts on a dword: the kernels store three dwords per four pixels),
-    and -- smoothed steps -- `smooth_xyz` fp32 [slots,21,3] and `smooth_mesh` fp32 [slots,V,3], each on a dword, as the last parts.
+    and -- smoothed steps -- `smooth_xyz` fp32 [slots,21,3] and `smooth_mesh` fp32 [slots,V,3], each on a dword, and -- occluded
+    steps -- `silhouette` uint8 [frames,h,w] and `coverage` int32 [slots,2], each on a dword, as the last parts.
     slots = frames for the one-hand step (hands None), frames * hands for the K-hand step.  A part the step does not have takes
     no bytes and its offset is None; every part in front of it stays where a step without the option has it."""
     frames: int
@@ -79,6 +86,7 @@ class LiveLayout:
     handed: bool = False
     tracked: bool = False
     smoothed: bool = False
+    occluded: bool = False       # (keyword: the overlay hidden behind nearer scene depth; needs overlay)
     record_rows: int = field(init=False)
     record_bytes: int = field(init=False)
     side_at: int = field(init=False)
@@ -91,6 +99,8 @@ class LiveLayout:
     pose_label_at: int = field(init=False)
     smooth_xyz_at: int = field(init=False)
     smooth_mesh_at: int = field(init=False)
+    silhouette_at: int = field(init=False)
+    coverage_at: int = field(init=False)
     nbytes: int = field(init=False)
 
     def __post_init__(self):
@@ -98,6 +108,8 @@ class LiveLayout:
             raise ValueError("an overlay or label images need the frames' (h, w), and handed / tracked are a K-hand step's options")
         if self.smoothed and not self.tracked:
             raise ValueError("a smoothed step is a tracked step: the filters follow the track ids")
+        if self.occluded and not self.overlay:
+            raise ValueError("an occluded step is a step with an overlay: the silhouette is the overlay's by-product")
         s, rb = self.slots, record_bytes(3)
         rows = self.frames + 1 if self.hands is None else hands_record_rows(s, rb)
         image = None if self.hw is None else (self.frames, *self.hw, 3)
@@ -113,7 +125,9 @@ class LiveLayout:
                                                    ("box_label", self.labels, torch.uint8, image, 4),
                                                    ("pose_label", self.labels, torch.uint8, (s, POSE_LABEL, POSE_LABEL, 3), 4),
                                                    ("smooth_xyz", self.smoothed, torch.float32, (s, SMOOTH_JOINTS, 3), 4),
-                                                   ("smooth_mesh", self.smoothed, torch.float32, (s, self.vertices, 3), 4)):
+                                                   ("smooth_mesh", self.smoothed, torch.float32, (s, self.vertices, 3), 4),
+                                                   ("silhouette", self.occluded, torch.uint8, image and image[:3], 4),
+                                                   ("coverage", self.occluded, torch.int32, (s, 2), 4)):
             start = None
             if present:
                 start = (end + align - 1) // align * align
@@ -134,19 +148,23 @@ class LiveLayout:
         """The parts of a step's flat uint8 buffer (the device buffer or its pinned copy), typed and shaped; None: not there."""
         cut = {name: buf[a:b].view(dtype).view(shape) for name, (a, b, dtype, shape) in self._spans.items()}
         kind = LiveSmoothedViews if self.smoothed else LiveTrackedViews if self.tracked else LiveViews
+        if self.occluded:
+            kind = _occluded_views(kind)
         return kind(*(cut.get(name) for name in kind._fields))
 
 
 @functools.lru_cache(maxsize=None)
-def _read_type(step: str, base: tuple, overlay: bool, labels: bool, side: bool, tracked: bool = False, smoothed: bool = False):
+def _read_type(step: str, base: tuple, overlay: bool, labels: bool, side: bool, tracked: bool = False, smoothed: bool = False,
+               occluded: bool = False):
     """The namedtuple a step's read() returns: the base fields, then overlay, box_label + pose_label, side, track_age +
-    track_id and smooth_xyz + smooth_mesh, each only when the step has it; an absent image (overlay / box_label / pose_label)
-    reads as a None class attribute.  (One class per combination: call it with positional arguments only, the cache keys on
-    them.)"""
+    track_id, smooth_xyz + smooth_mesh and silhouette + coverage, each only when the step has it; an absent image (overlay /
+    box_label / pose_label) reads as a None class attribute.  (One class per combination: call it with positional arguments
+    only and without trailing defaults, the cache keys on them.)"""
     has = dict(overlay=overlay, box_label=labels, pose_label=labels, side=side, track_age=tracked, track_id=tracked,
-               smooth_xyz=smoothed, smooth_mesh=smoothed)
+               smooth_xyz=smoothed, smooth_mesh=smoothed, silhouette=occluded, coverage=occluded)
     fields = base + tuple(f for f, on in has.items() if on)
-    name = step + "Overlay" * overlay + "Labels" * labels + "Sided" * side + "Tracked" * tracked + "Smoothed" * smoothed + "Read"
+    name = (step + "Overlay" * overlay + "Labels" * labels + "Sided" * side + "Tracked" * tracked + "Smoothed" * smoothed
+            + "Occluded" * occluded + "Read")
     absent = {f: None for f, on in has.items() if not on and f in ("overlay", "box_label", "pose_label")}
     doc = f"{step}Output.read(): {' '.join(base)}" + "".join(f" + {f}" for f in fields[len(base):]) + "."
     return type(name, (collections.namedtuple(name, fields),), dict(absent, __slots__=(), __doc__=doc))
@@ -160,13 +178,17 @@ def _read(step, base, values, layout, v, per_slot=lambda t: t):
         values += (v.box_label.clone(), per_slot(v.pose_label).clone())
     if layout.handed:
         values += (per_slot(v.side).clone(),)
+    key = (layout.overlay, layout.labels, layout.handed)
     if layout.tracked:
         values += (per_slot(v.track_age).clone(), per_slot(v.track_id).clone())
+        key += (True,)
         if layout.smoothed:
             values += (per_slot(v.smooth_xyz).clone(), per_slot(v.smooth_mesh).clone())
-            return _read_type(step, base, layout.overlay, layout.labels, layout.handed, True, True)(*values)
-        return _read_type(step, base, layout.overlay, layout.labels, layout.handed, True)(*values)
-    return _read_type(step, base, layout.overlay, layout.labels, layout.handed)(*values)
+            key += (True,)
+    if layout.occluded:
+        values += (v.silhouette.clone(), per_slot(v.coverage).clone())
+        key = key + (False,) * (5 - len(key)) + (True,)
+    return _read_type(step, base, *key)(*values)
 
 
 _LIVE_FIELDS = ("keypoints", "has_hand", "crop_box", "words", "more", "mesh")      # the six a plain step always had
@@ -189,12 +211,15 @@ class LiveOutput:
     box_label: torch.Tensor = None  # [N,H,W,3] uint8 RGB on the device: the frame with the hand's crop box (engines with labels)
     pose_label: torch.Tensor = None  # [N,176,176,3] uint8 RGB on the device: the colour crop with the skeleton (zeros: no hand)
     layout: LiveLayout = None        # where everything lies in `host`
+    silhouette: torch.Tensor = None  # occluded steps: [N,H,W] uint8 on the device (0 no mesh, 1 shown, 0x81 hidden)
+    coverage: torch.Tensor = None    # occluded steps: [N,2] int32 on the device (pixels under the mesh, of those shown)
 
     def read(self):
         """After the stream is synchronised: (keypoints, has_hand, crop_box, range words, [image_uvd, xyz_mm], mesh) as fresh CPU
         tensors (LiveRead; `.overlay`, `.box_label`, `.pose_label` are None).  A step with faces= appends the overlay [N,H,W,3]
         uint8 (LiveOverlayRead); a step with labels appends box_label [N,H,W,3] and pose_label [N,176,176,3] (LiveLabelsRead,
-        LiveOverlayLabelsRead)."""
+        LiveOverlayLabelsRead); a step with occlude appends silhouette [N,H,W] uint8 and coverage [N,2] int32 as the last
+        fields."""
         v = self.layout.views(self.host)
         kp, has, box, words, more = read_host_record(v.records, self.layout.frames, extras=True)
         return _read("Live", _LIVE_FIELDS, (kp, has, box, words, more, v.mesh.clone()), self.layout, v)
@@ -211,7 +236,7 @@ class _LiveStep:
     smooth = None                # the smoothed K-hand step: (min_cutoff, beta, d_cutoff)
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None,
-                 labels: bool = False, left: bool = False):
+                 labels: bool = False, left: bool = False, occlude: bool = False, occlude_margin: float = ops.OCCLUDE_MARGIN):
         if not _same_device(hand.device, lifter.device):
             raise ValueError(f"HandNet on {hand.device} but the lifter on {lifter.device}")
         self.hand, self.lifter, self.device = hand, lifter, hand.device
@@ -226,6 +251,14 @@ class _LiveStep:
                                  "vertex order); the lifter's raw output has no camera offset to project")
             with ops.on_device(self.device):
                 self.faces = ops.mesh_faces(faces, self.vertices, self.device)
+        # occlude: the overlay leaves out what lies behind the step's own depth map by more than the margin, and the step also
+        # hands out which pixels belong to which hand (silhouette) and how much of each mesh the camera sees (coverage)
+        self.occlude = None
+        if occlude:
+            if faces is None or self.perm is None:
+                raise ValueError("occlude=True needs faces= (and therefore perm_reverse=): it is the overlay that is tested "
+                                 "against the depth map")
+            self.occlude = ops.check_occlude_margin(occlude_margin)
         # labels: the step ends with the caller's other two images (ops.draw_labels: ros_demo.py:310-326), behind the overlay
         self.labels, self.clamp = bool(labels), bool(clamp)
         # left: the caller's mirror mode (ImageListener(left=True), ros_demo.py:259-262): the step runs on the frame and the
@@ -260,19 +293,24 @@ class _LiveStep:
                     owned = self._mirrored[key] = (torch.empty_like(images), torch.empty_like(depth))
         return ops.flip_w(images, depth, out=owned[0], out_other=owned[1])
 
-    def _draw(self, mesh, lifted, frames, k, out):
+    def _draw(self, mesh, lifted, frames, k, out, depth=None, at=None):
         s = mesh.shape[0]
         scratch = self._render_scratch.get(s)
         if scratch is None:
             with torch.inference_mode(False):
                 scratch = self._render_scratch[s] = torch.empty(
                     (ops.mesh_render_scratch_bytes(s, self.faces.shape[0]),), dtype=torch.uint8, device=self.device)
-        return ops.mesh_render(mesh, self.faces, self.paras, frames, lifted=lifted, k=k, out=out, scratch=scratch)
+        if self.occlude is None:
+            return ops.mesh_render(mesh, self.faces, self.paras, frames, lifted=lifted, k=k, out=out, scratch=scratch), None, None
+        # (the depth map the step itself ran on: mirrored in a `left` step, channel 3 of an RGBD step's tensor)
+        return ops.mesh_render(mesh, self.faces, self.paras, frames, lifted=lifted, k=k, out=out, scratch=scratch,
+                               scene_depth=depth, margin=self.occlude, silhouette_out=at.silhouette, coverage_out=at.coverage)
 
     def _layout(self, n, hw=None) -> LiveLayout:
         """The buffer of a step over n frames (hw: of a step that draws, the frames' size)."""
         return LiveLayout(n, self.hands, self.vertices, hw, hw is not None and self.faces is not None,
-                          hw is not None and self.labels, self.handed, self.track is not None, self.smooth is not None)
+                          hw is not None and self.labels, self.handed, self.track is not None, self.smooth is not None,
+                          occluded=self.occlude is not None)
 
     def _new_buffers(self, n, hw=None):
         """A fresh (layout, device buffer, pinned host buffer) of a step over n frames."""
@@ -308,19 +346,22 @@ class _LiveStep:
         out = self._hand_step(images, depth, at, lift)
         p2d, mesh, pose3d, raw = out.tail
         drawn, k = out.has_hand.view(-1) if self.hands is None else at.lifted, self.hands or 1
-        overlay = box_label = pose_label = None
-        if layout.overlay:      # (a smoothed step draws what it smoothed)
-            overlay = self._draw(at.smooth_mesh if layout.smoothed else mesh, drawn, frames, k, at.overlay)
+        overlay = box_label = pose_label = silhouette = coverage = None
+        if layout.overlay:      # (a smoothed step draws, and an occluded one tests, what it smoothed)
+            overlay, silhouette, coverage = self._draw(at.smooth_mesh if layout.smoothed else mesh, drawn, frames, k, at.overlay,
+                                                       depth, at)
         if layout.labels:
             box_label, pose_label = ops.draw_labels(out.keypoints, out.crop_box, frames, drawn=drawn, k=k, clamp=self.clamp,
                                                     out_box=at.box_label, out_pose=at.pose_label)
         host.copy_(dev, non_blocking=True)
+        more = {} if coverage is None else dict(silhouette=silhouette, coverage=coverage)
         return self._output(out, at, layout, host, dict(pose2d=p2d, mesh=mesh, pose3d=pose3d, raw_mesh=raw, overlay=overlay,
-                                                        box_label=box_label, pose_label=pose_label))
+                                                        box_label=box_label, pose_label=pose_label, **more))
 
     def _key_options(self) -> tuple:
-        """What a capture's key carries behind the shapes (the smoothed step: its filter's parameters, kernel arguments)."""
-        return ()
+        """What a capture's key carries behind the shapes (the smoothed step: its filter's parameters; the occluded step: its
+        margin -- kernel arguments)."""
+        return () if self.occlude is None else ("occluded", self.occlude)
 
     def _smooth_untouched(self, n):
         return contextlib.nullcontext()
@@ -383,7 +424,13 @@ class LiveHandEngine(_LiveStep):
     left: the reference's mirror mode for a left-handed subject (ImageListener(left=True), ros_demo.py:259-262) -- every
     output equals the one of this engine without `left` on frames and depth flipped along the width, bit for bit (boxes,
     keypoints, mesh and images are in the mirrored frame, as the reference publishes them).  forward_raw mirrors inside the
-    ingest kernel (no launch added); fp32 feeds (forward_device / graphed) cost one launch."""
+    ingest kernel (no launch added); fp32 feeds (forward_device / graphed) cost one launch.
+    occlude (needs faces): a pixel of the mesh that lies more than occlude_margin metres behind the step's own
+    depth map keeps the frame's pixel, and the step also hands out LiveOutput.silhouette / .coverage (read() likewise, as the
+    last fields): silhouette [N,H,W] uint8 -- 0 no mesh, 1 mesh shown, 0x81 mesh hidden --, coverage [N,2] int32 -- pixels
+    under the mesh, and of those the shown ones.  Holes of the depth map (0, NaN) hide nothing.  The default margin of 0.03 m
+    is a starting value, NOT tuned on this model: a hand is 2-3 cm thick and the mesh's absolute Z hangs on the wrist key
+    point's single depth reading."""
 
     def _hand_step(self, images, depth, at, lift):
         return self.hand.forward_device(images, depth, _record=(None, at.records), _tail=lift)
@@ -427,6 +474,8 @@ class LiveHandsOutput:
     layout: LiveLayout = None        # where everything lies in `host`
     track_id: torch.Tensor = None    # tracked steps: [N,K] int32 on the device, the slot's track id (held slots included; 0: free)
     track_age: torch.Tensor = None   # tracked steps: [N,K] int32 on the device, the steps on which the slot's track was seen again
+    silhouette: torch.Tensor = None  # occluded steps: [N,H,W] uint8 on the device (0 no mesh, k + 1 slot k shown, 0x80 | (k + 1) hidden)
+    coverage: torch.Tensor = None    # occluded steps: [N,K,2] int32 on the device (pixels where the slot's mesh is nearest, of those shown)
     smooth_xyz: torch.Tensor = None  # smoothed steps: [N,K,21,3] on the device, xyz_mm filtered over time (zeros: has_hand != 1)
     smooth_mesh: torch.Tensor = None  # smoothed steps: [N,K,V,3] on the device, `mesh` filtered over time (zeros: not lifted)
 
@@ -435,7 +484,8 @@ class LiveHandsOutput:
         lifted as bool, words = the step's range words; a step with faces=: LiveHandsOverlayRead, + overlay [N,H,W,3] uint8; a
         step with labels: + box_label [N,H,W,3], pose_label [N,K,176,176,3] -- LiveHandsLabelsRead, LiveHandsOverlayLabelsRead;
         a handed step: the same with `side` [N,K] int32 behind them; a tracked step: track_age and then track_id [N,K] int32
-        as the last fields; a smoothed step: behind those, smooth_xyz [N,K,21,3] and smooth_mesh [N,K,V,3])."""
+        as the last fields; a smoothed step: behind those, smooth_xyz [N,K,21,3] and smooth_mesh [N,K,V,3]; an occluded step:
+        behind everything else, silhouette [N,H,W] uint8 and coverage [N,K,2] int32)."""
         v, s = self.layout.views(self.host), self.layout.slots
         per = lambda t: t.reshape((self.layout.frames, self.layout.hands) + tuple(t.shape[1:]))
         kp, has, box, words, (img, xyz) = read_host_record(v.records, s, extras=True)
@@ -455,9 +505,9 @@ class LiveHandsEngine(_LiveStep):
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, max_hands: int = 2, clamp: bool = True,
                  perm_reverse=None, faces=None, labels: bool = False, left: bool = False, handed: bool = False,
-                 left_side: int = 0, track: bool = False, track_iou: float = 0.3, track_hold: int = 5, smooth: bool = False,
-                 smooth_min_cutoff: float = 1.0, smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0,
-                 smooth_rate: float = 30.0):
+                 left_side: int = 0, track: bool = False, track_iou: float = 0.3, track_hold: int = 5, occlude: bool = False,
+                 occlude_margin: float = ops.OCCLUDE_MARGIN, smooth: bool = False, smooth_min_cutoff: float = 1.0,
+                 smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0, smooth_rate: float = 30.0):
         """faces: mesh_model.face ([F,3]; needs perm_reverse) -- given, the step ends with the overlay: every lifted mesh of a
         frame drawn over it with one depth buffer per frame (LiveHandsOutput.overlay, read().overlay), in the same copy.
         labels: the step ends with box_label (the crop box of every lifted slot on its frame) and one pose_label per slot
@@ -485,7 +535,13 @@ class LiveHandsEngine(_LiveStep):
         smooth_rate = steps per second (dt = 1 / rate; smooth_dt(seconds) sets another dt, also between replays).  The
         defaults are the paper's starting values and have NOT been tuned on this model.  This engine owns one filter state and
         one dt word per (N, K), shared by forward_device, graphed and forward_raw; smooth_reset() -- and track_reset() --
-        empties the state."""
+        empties the state.
+        occlude (needs faces): as LiveHandEngine's, for all K slots of a frame against the frame's one depth map
+        -- silhouette [N,H,W] uint8: 0 no mesh, k + 1 where slot k's mesh is the nearest and shown, 0x80 | (k + 1) where it is
+        hidden; coverage [N,K,2] int32: per slot, the pixels where its mesh is the nearest mesh and those of them that are
+        shown ((0, 0): not lifted).  A `left` step tests against the mirrored depth map, a `handed` step against the frame's
+        own, a smoothed step tests the smoothed mesh it draws.  occlude_margin (metres, default 0.03) is a starting value, NOT
+        tuned on this model."""
         self.hands = self.max_hands = ops.check_max_hands(max_hands)
         if left and handed:
             raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
@@ -500,7 +556,7 @@ class LiveHandsEngine(_LiveStep):
                 raise ValueError("smooth=True needs perm_reverse=: the filter runs in the launch that finishes the mesh")
             mc, beta, dc, rate = ops.check_smooth_options(smooth_min_cutoff, smooth_beta, smooth_d_cutoff, smooth_rate)
             self.smooth, self._dt, self._smooth_states = (mc, beta, dc), 1.0 / rate, {}
-        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left)
+        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left, occlude, occlude_margin)
 
     def _hand_step(self, images, depth, at, lift):
         # (the per-slot records, range words, scores and ranks go straight into the buffer, the handed step's sides behind them)
@@ -551,7 +607,7 @@ class LiveHandsEngine(_LiveStep):
         return self
 
     def _key_options(self) -> tuple:
-        return () if self.smooth is None else ("smoothed",) + self.smooth
+        return (() if self.smooth is None else ("smoothed",) + self.smooth) + super()._key_options()
 
     def _smooth_untouched(self, n):
         """Context manager around the capture of a smoothed step over n frames: the warm-up steps run the filters, so the
@@ -590,6 +646,8 @@ class LiveHandsEngine(_LiveStep):
     def _output(self, out, at, layout, host, parts) -> LiveHandsOutput:
         n, k = layout.frames, layout.hands
         parts["mesh"] = parts["mesh"].view(n, k, self.vertices, 3)
+        if "coverage" in parts:
+            parts["coverage"] = parts["coverage"].view(n, k, 2)
         return LiveHandsOutput(hands=out, lifted=at.lifted.view(n, k), host=host, n=n, k=k, side=out.side, mirror=out.mirror,
                                layout=layout, track_id=out.track_id, track_age=out.track_age,
                                smooth_xyz=None if self.smooth is None else at.smooth_xyz.view(n, k, SMOOTH_JOINTS, 3),

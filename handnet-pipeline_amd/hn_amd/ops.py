@@ -1925,13 +1925,32 @@ def mesh_render_scratch_bytes(slots, faces):
     return int(_lib.load().hn_mesh_render_scratch_bytes(slots, faces))
 
 
-def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out=None, scratch=None):
+OCCLUDE_MARGIN = 0.03      # metres; a starting value, NOT tuned on this model
+
+
+def check_occlude_margin(margin) -> float:
+    """occlude_margin as a float that is finite in fp32 (it is a kernel argument)."""
+    m = float(margin)
+    if not math.isfinite(m) or abs(m) > float(np.finfo(np.float32).max):
+        raise ValueError(f"occlude_margin: a finite number of metres (got {margin!r})")
+    return m
+
+
+def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out=None, scratch=None, *, scene_depth=None,
+                margin=OCCLUDE_MARGIN, silhouette_out=None, coverage_out=None):
     """The meshes drawn over their frames (hn_mesh_render_u8; render() of ros_demo.py:86-116 without a graphics pipeline):
     mesh fp32 [S,V,3] or [N,K,V,3] as mesh_finish writes it, S = N * k slots; faces [F,3]: an int32 GPU tensor (mesh_faces) or
     a host list (checked index by index and uploaded by THIS call: a caller that renders repeatedly uploads once with mesh_faces
     and passes the tensor, as the live engines do); paras (fx, fy, cx, cy); frame fp32 [N,3,H,W] in 0..1 or uint8 [N,H,W,3]
     'bgr8', on the GPU; lifted int32 [S] (0: the slot is not drawn).  Returns the overlay uint8 [N,H,W,3] RGB (`out`);
-    depth_out fp32 [N,H,W], when given, receives the drawn Z (0 where nothing was drawn)."""
+    depth_out fp32 [N,H,W], when given, receives the drawn Z (0 where nothing was drawn).
+    scene_depth (hn_mesh_render_occluded_u8): the camera's depth map in metres, fp32 [N,1,H,W], [N,H,W]
+    or an [N,4,H,W] RGBD tensor (channel 3 is read in place), on the mesh's device and of the frames' size.  A covered pixel
+    whose depth value D is finite and > 0 and whose nearest mesh Z > D + margin (fp32, strict) is hidden: it keeps the frame's
+    pixel.  The call then returns (overlay, silhouette uint8 [N,H,W]: 0 no mesh, slot + 1 shown, 0x80 | (slot + 1) hidden --
+    slot within the frame, k <= 16 --, coverage int32 [S,2]: per slot, the pixels where its mesh is the nearest and those of
+    them that are shown), written into silhouette_out / coverage_out when given; depth_out holds the nearest mesh Z on every
+    covered pixel, hidden or not.  Without scene_depth the call is the plain one and the three other keywords must stay unset."""
     _req(mesh, name="mesh")
     if mesh.dim() == 4:
         mesh = mesh.view(-1, mesh.shape[2], 3)
@@ -1978,10 +1997,40 @@ def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out
         scratch = torch.empty((need,), device=mesh.device, dtype=torch.uint8)
     _req(scratch, torch.uint8, "scratch")
     p4 = (C.c_float * 4)(*[float(x) for x in paras])
-    check(_lib.load().hn_mesh_render_u8(ptr(mesh), ptr(faces), faces_host.ctypes.data if faces_host is not None else None,
-                                        ptr(lifted), s, v, f, k, p4, ptr(frame), fmt, h, w, ptr(scratch), scratch.numel(),
-                                        ptr(out), ptr(depth_out), _stream()), "hn_mesh_render_u8")
-    return out.view(n, h, w, 3)
+    fh = faces_host.ctypes.data if faces_host is not None else None
+    if scene_depth is None:
+        if silhouette_out is not None or coverage_out is not None:
+            raise ValueError("silhouette_out / coverage_out belong to the occluded call: give scene_depth")
+        check(_lib.load().hn_mesh_render_u8(ptr(mesh), ptr(faces), fh, ptr(lifted), s, v, f, k, p4, ptr(frame), fmt, h, w,
+                                            ptr(scratch), scratch.numel(), ptr(out), ptr(depth_out), _stream()),
+              "hn_mesh_render_u8")
+        return out.view(n, h, w, 3)
+    margin = check_occlude_margin(margin)
+    _req(scene_depth, name="scene_depth")
+    if scene_depth.device != mesh.device:
+        raise ValueError(f"scene_depth on {scene_depth.device} but the mesh on {mesh.device}")
+    shape = tuple(scene_depth.shape)
+    if shape not in ((n, 1, h, w), (n, h, w), (n, 4, h, w)):
+        raise ValueError(f"scene_depth: expected fp32 [{n},1,{h},{w}], [{n},{h},{w}] or RGBD [{n},4,{h},{w}], got {shape}")
+    if k > 16:
+        raise ValueError(f"the silhouette's byte holds at most 16 slots per frame (k = {k})")
+    rgbd = len(shape) == 4 and shape[1] == 4
+    depth_ptr = scene_depth.data_ptr() + (3 * h * w * 4 if rgbd else 0)
+    if silhouette_out is None:
+        silhouette_out = torch.empty((n, h, w), device=mesh.device, dtype=torch.uint8)
+    _req(silhouette_out, torch.uint8, "silhouette_out")
+    if silhouette_out.numel() != n * h * w:
+        raise ValueError(f"silhouette_out: expected uint8 [{n},{h},{w}], got {tuple(silhouette_out.shape)}")
+    if coverage_out is None:
+        coverage_out = torch.empty((s, 2), device=mesh.device, dtype=torch.int32)
+    _req(coverage_out, torch.int32, "coverage_out")
+    if coverage_out.numel() != s * 2:
+        raise ValueError(f"coverage_out: expected int32 [{s},2], got {tuple(coverage_out.shape)}")
+    check(_lib.load().hn_mesh_render_occluded_u8(ptr(mesh), ptr(faces), fh, ptr(lifted), s, v, f, k, p4, ptr(frame), fmt, h, w,
+                                                 depth_ptr, (4 if rgbd else 1) * h * w, margin, ptr(scratch), scratch.numel(),
+                                                 ptr(out), ptr(depth_out), ptr(silhouette_out), ptr(coverage_out), _stream()),
+          "hn_mesh_render_occluded_u8")
+    return out.view(n, h, w, 3), silhouette_out.view(n, h, w), coverage_out.view(s, 2)
 
 
 LABEL_CROP = 176      # side of a pose_label image

@@ -791,6 +791,24 @@ int hn_mesh_render_u8(const float* mesh, const int32_t* faces, const int32_t* fa
                       const int32_t* lifted /* or NULL */, int s, int v, int f, int k, const float* paras, const void* frame,
                       int frame_format, int h, int w, void* scratch, int64_t scratch_bytes, uint8_t* out_image,
                       float* out_depth /* or NULL */, void* stream);
+/* hn_mesh_render_u8 with the mesh hidden behind nearer scene depth: the same arguments, rule and two
+ * launches, plus scene_depth = the camera's depth map in metres, fp32, frame i at scene_depth + i * depth_frame_stride as
+ * [h][w] (depth_frame_stride in elements, >= h * w: channel 3 of an [n][4][h][w] RGBD tensor is passed as its address with
+ * 4 * h * w), and margin in metres (finite).  For a pixel covered by a mesh, with best = the nearest mesh Z and D = the depth
+ * map's value: D is valid when it is finite and > 0 (holes -- 0 or NaN -- hide nothing), and the pixel is hidden when D is
+ * valid and best > D + margin (one fp32 addition, a strict comparison).  out_image: the face's colour where covered and not
+ * hidden, the frame's pixel elsewhere.  out_depth (or NULL): the nearest mesh Z on every covered pixel, hidden or not, else 0.
+ * out_silhouette [n][h][w] uint8: 0 = no mesh, slot + 1 = covered and shown, 0x80 | (slot + 1) = covered and hidden, slot =
+ * the winning face's slot within its frame (k <= 16).  out_coverage [s][2] int32 or NULL: per slot, (pixels where its mesh is
+ * the nearest mesh, of those the shown ones); (0, 0) for a slot with lifted == 0.  The counters are zeroed by the first launch
+ * and filled by integer atomic adds of the second: exact, and the same in every run.  No allocation, no launch beyond the two.
+ * Added under ABI 36: a new function only. */
+int hn_mesh_render_occluded_u8(const float* mesh, const int32_t* faces, const int32_t* faces_host /* or NULL */,
+                               const int32_t* lifted /* or NULL */, int s, int v, int f, int k, const float* paras,
+                               const void* frame, int frame_format, int h, int w, const float* scene_depth,
+                               int64_t depth_frame_stride, float margin, void* scratch, int64_t scratch_bytes,
+                               uint8_t* out_image, float* out_depth /* or NULL */, uint8_t* out_silhouette,
+                               int32_t* out_coverage /* or NULL */, void* stream);
 /* The live caller's two other images (ros_demo.py:310-326) for s = n * k hand slots: out_box [n][h][w][3] uint8 RGB = the frame
  * with the crop rectangle of every drawn slot of the frame in (0,255,0), thickness 1, inclusive corners (cv2.rectangle);
  * out_pose [s][176][176][3] uint8 RGB = frame[y1:y2, x1:x2] (clipped to the frame, exclusive ends) resized to 176 x 176 with
