@@ -24,8 +24,10 @@ filter's parameters are the paper's starting values, not tuned on this model.
 With --occlude the last frame also goes through the K = 2 step with faces= and occlude=True: the overlay leaves out what lies
 more than 3 cm (a starting value, not tuned) behind the frame's depth map, and for every slot the share of its mesh's pixels that
 the camera sees is printed (read().coverage), with the silhouette's pixel counts.
+With --cameras N the last frame goes N times through ONE captured K = 2 step built with N slightly different intrinsics
+(paras [N,4]: a rig of N cameras), and once more after set_cameras() swapped them, without a recapture.
 usage (GPU box): python examples/live_demo.py [frames] [--overlay out.png] [--mano MANO_RIGHT.pkl] [--labels PREFIX] [--left]
-                 [--handed] [--track] [--smooth] [--occlude]"""
+                 [--handed] [--track] [--smooth] [--occlude] [--cameras N]"""
 import sys
 import time
 import types
@@ -58,7 +60,7 @@ def _faces(mano_file):
 def main():
     argv = sys.argv[1:]
     opt = {}
-    for flag in ("--overlay", "--mano", "--labels"):
+    for flag in ("--overlay", "--mano", "--labels", "--cameras"):
         if flag in argv:
             i = argv.index(flag)
             opt[flag] = argv[i + 1]
@@ -166,6 +168,19 @@ def main():
                 print(f"9. occlude, slot {k}: lifted {bool(r5.lifted[0, k])}, {under} pixels where its mesh is the nearest, {share}")
             print(f"   silhouette {tuple(r5.silhouette.shape)} uint8: {int((r5.silhouette != 0).sum())} pixels under a mesh, "
                   f"{int((r5.silhouette & 0x80 != 0).sum())} of them hidden")
+        if "--cameras" in opt:                                                            # a rig of N cameras in ONE step
+            n = int(opt["--cameras"])
+            cams = np.asarray(PARAS)[None] + 12.0 * np.arange(n)[:, None] * np.array([1.0, -1.0, 1.5, -0.5])     # [N,4]
+            rig = net.live_hands(model, cams, max_hands=2, clamp=True, perm_reverse=rev)
+            run, c_img, c_dep, o6 = rig.graphed(s_img.expand(n, -1, -1, -1).contiguous(), s_dep.expand(n, -1, -1, -1).contiguous())
+            for label, values in (("as built", None), ("after set_cameras", cams[::-1].copy())):
+                if values is not None:
+                    rig.set_cameras(values)                                               # (no recapture: the kernels read tables)
+                run()
+                torch.cuda.current_stream().synchronize()
+                r6 = o6.read()
+                print(f"10. cameras {label}: the same frame through {n} intrinsics in one captured step: wrist x (mm) per camera "
+                      f"{[round(float(v), 1) for v in r6.xyz_mm[:, 0, 0, 0]]}, image u {[round(float(v), 1) for v in r6.image_uvd[:, 0, 0, 0]]}")
 
 
 if __name__ == "__main__":

@@ -118,12 +118,15 @@ class A2JModel(EngineOwner):
         return outs[0], outs[1], (outs[2] if xyz is not None else None)
 
 
-    def mesh(self, lifter, clamp: bool = True, perm_reverse=None):
+    def mesh(self, lifter, clamp: bool = True, perm_reverse=None, faces=None):
         """The stand-alone mesh demo's loop body as ONE step (hn_amd.live.CropMeshEngine; a2j_mesh.py:58-80): this network, np.clip
         + convert_joints in the aggregation's epilogue, the lifter's input, Pose2Mesh, the caller's last lines, one copy.
-        lifter: the drop-in `models.pose2mesh_net.get_model(...)` module (on the GPU) or a Pose2MeshEngine."""
+        lifter: the drop-in `models.pose2mesh_net.get_model(...)` module (on the GPU) or a Pose2MeshEngine.
+        faces = mesh_model.face (needs perm_reverse): forward_device / graphed(crops, box, paras, frames) then also draw every
+        sample's mesh over its own full image (frames: fp32 [K,3,H,W] in 0..1 or uint8 [K,H,W,3] 'bgr8') with its own
+        intrinsics, the loop's render() call: out.overlay on the device, read().overlay [K,H,W,3] uint8 RGB on the host."""
         from hn_amd.live import CropMeshEngine
-        return CropMeshEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, clamp, perm_reverse)
+        return CropMeshEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, clamp, perm_reverse, faces)
 
 
 class A2JModelLightning(EngineOwner):

@@ -21,7 +21,13 @@
 // popcounts per slot that touched the tile to the slot's two counters, which the setup kernel's thread 0 zeroed.  The only
 // atomics are those integer adds: sums of integers do not depend on their order, so the outputs stay a pure function of the
 // inputs.  The instantiations without the switch take no further argument and hold no further instruction.
+//
+// The per-frame cameras (hn_mesh_render_cams_u8 / _cams_occluded_u8; DESIGN.md "A camera per frame", tests/cams_ref.py) are a
+// second compile-time switch, of the setup kernel alone: slot s of a step with k slots per frame reads row s / k of a device
+// table [frames][4] where the other instantiations read four scalar arguments.  The projection and the tile kernel are the same.
 #include "hn_common.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -101,11 +107,20 @@ __device__ __forceinline__ int wave_min(int v) {
   return v;
 }
 
-template <class... Coverage>   // nothing, or -- the occluded form -- the slots' counters (int*), which thread 0 zeroes
+// Where the setup kernel gets its intrinsics.  CAMS off: the four scalars fx, fy, cx, cy, by value, one camera for every slot.
+// CAMS on -- the per-frame form (DESIGN.md "A camera per frame") --: the first two arguments are a table on the device, fp32
+// [frames][4] with rows (fx, fy, cx, cy), and k, the slots per frame; slot s belongs to frame s / k and reads row s / k, and a
+// captured graph reads the table anew at every replay.  (The scalars stay plain float arguments, not a struct: the
+// instantiations without CAMS are then the kernels they were before the switch existed, instruction for instruction.)
+template <bool CAMS> using CamA = std::conditional_t<CAMS, const float*, float>;   // the table, or fx
+template <bool CAMS> using CamB = std::conditional_t<CAMS, int, float>;            // k, or fy
+
+// Coverage: nothing, or -- the occluded form -- the slots' counters (int*), which thread 0 zeroes
+template <bool CAMS, class... Coverage>
 __global__ __launch_bounds__(256) void mesh_raster_setup(const float* __restrict__ mesh, const int* __restrict__ faces,
-                                                         const int* __restrict__ lifted, int v, int f, float fx, float fy,
-                                                         float cx, float cy, int h, int w, unsigned char* __restrict__ scratch,
-                                                         int slots, Coverage... coverage) {
+                                                         const int* __restrict__ lifted, int v, int f, CamA<CAMS> fx_or_cams,
+                                                         CamB<CAMS> fy_or_k, float cx, float cy, int h, int w,
+                                                         unsigned char* __restrict__ scratch, int slots, Coverage... coverage) {
   const int slot = blockIdx.x;
   if constexpr (sizeof...(Coverage) != 0) {
     int* counters = (coverage, ...);
@@ -115,6 +130,13 @@ __global__ __launch_bounds__(256) void mesh_raster_setup(const float* __restrict
   FaceRec* recs = reinterpret_cast<FaceRec*>(scratch + rec_offset(slots)) + (size_t)slot * f;
   Box* boxes = reinterpret_cast<Box*>(scratch + box_offset(slots, f)) + (size_t)slot * f;
   const bool drawn = !lifted || lifted[slot] != 0;        // (uniform over the workgroup)
+  float fx, fy;
+  if constexpr (CAMS) {             // (the row's address depends on blockIdx alone: uniform, four scalar loads; cx, cy unused)
+    const float* __restrict__ row = fx_or_cams + 4 * (size_t)(slot / fy_or_k);
+    fx = row[0]; fy = row[1]; cx = row[2]; cy = row[3];
+  } else {
+    fx = fx_or_cams; fy = fy_or_k;
+  }
   int bx0 = w, bx1 = -1, by0 = h, by1 = -1;
   for (int i = threadIdx.x; i < f && drawn; i += blockDim.x) {
     const int i0 = faces[3 * i], i1 = faces[3 * i + 1], i2 = faces[3 * i + 2];
@@ -280,12 +302,13 @@ extern "C" int64_t hn_mesh_render_scratch_bytes(int s, int f) {
   return (int64_t)scratch_total(s, f);
 }
 
-// the argument checks both entry points share (`fn`: the name the messages carry), then the two launches
+// the argument checks every entry point shares (`fn`: the name the messages carry), then the two launches; exactly one of
+// paras (host, one camera) and cams (device, a row per frame) is given
 static int render(const char* fn, const float* mesh, const int32_t* faces, const int32_t* faces_host, const int32_t* lifted, int s,
-                  int v, int f, int k, const float* paras, const void* frame, int frame_format, int h, int w, void* scratch,
-                  int64_t scratch_bytes, uint8_t* out_image, float* out_depth, const Occlusion* occ, int64_t depth_frame_stride,
-                  void* stream) {
-  HN_CHECK_ARG(mesh && faces && paras && frame && scratch, "%s: null pointer", fn);
+                  int v, int f, int k, const float* paras, const float* cams, const void* frame, int frame_format, int h, int w,
+                  void* scratch, int64_t scratch_bytes, uint8_t* out_image, float* out_depth, const Occlusion* occ,
+                  int64_t depth_frame_stride, void* stream) {
+  HN_CHECK_ARG(mesh && faces && (paras || cams) && frame && scratch, "%s: null pointer", fn);
   HN_CHECK_ARG(out_image, "%s: out_image is NULL", fn);
   HN_CHECK_ARG(s > 0 && v > 0 && f > 0, "%s: bad dims (s %d, v %d, f %d: all must be positive)", fn, s, v, f);
   HN_CHECK_ARG(k > 0 && s % k == 0, "%s: %d slots are not a multiple of k = %d slots per frame", fn, s, k);
@@ -296,6 +319,7 @@ static int render(const char* fn, const float* mesh, const int32_t* faces, const
   HN_CHECK_ARG(scratch_bytes >= (int64_t)scratch_total(s, f), "%s: scratch of %lld bytes, %lld needed", fn,
                (long long)scratch_bytes, (long long)scratch_total(s, f));
   HN_CHECK_ARG(((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", fn);
+  HN_CHECK_ARG(!cams || ((uintptr_t)cams & 3) == 0, "%s: cams must be aligned to a float", fn);
   if (occ) {
     HN_CHECK_ARG(occ->depth, "%s: scene_depth is NULL", fn);
     HN_CHECK_ARG(occ->silhouette, "%s: out_silhouette is NULL", fn);
@@ -312,8 +336,10 @@ static int render(const char* fn, const float* mesh, const int32_t* faces, const
   unsigned char* sc = static_cast<unsigned char*>(scratch);
   const dim3 grid((w + 31) / 32, (h + 7) / 8, s / k);
   if (!occ) {
-    hipLaunchKernelGGL(mesh_raster_setup<>, dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, paras[0], paras[1], paras[2],
-                       paras[3], h, w, sc, s);
+    if (cams)
+      hipLaunchKernelGGL((mesh_raster_setup<true>), dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, cams, k, 0.f, 0.f, h, w, sc, s);
+    else
+      hipLaunchKernelGGL((mesh_raster_setup<false>), dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, paras[0], paras[1], paras[2], paras[3], h, w, sc, s);
     HN_CHECK_LAUNCH("mesh_raster_setup");
     if (frame_format == HN_FRAME_F32_CHW)
       hipLaunchKernelGGL(mesh_raster_tiles<HN_FRAME_F32_CHW>, grid, dim3(256), 0, st, sc, s, f, k, frame, h, w, out_image, out_depth);
@@ -323,8 +349,12 @@ static int render(const char* fn, const float* mesh, const int32_t* faces, const
     HN_CHECK_LAUNCH("mesh_raster_tiles");
     return HN_OK;
   }
-  hipLaunchKernelGGL(mesh_raster_setup<int*>, dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, paras[0], paras[1], paras[2],
-                     paras[3], h, w, sc, s, occ->coverage);
+  if (cams)
+    hipLaunchKernelGGL((mesh_raster_setup<true, int*>), dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, cams, k, 0.f, 0.f, h, w, sc, s,
+                       occ->coverage);
+  else
+    hipLaunchKernelGGL((mesh_raster_setup<false, int*>), dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, paras[0], paras[1], paras[2], paras[3], h, w, sc, s,
+                       occ->coverage);
   HN_CHECK_LAUNCH("mesh_raster_setup");
   if (frame_format == HN_FRAME_F32_CHW)
     hipLaunchKernelGGL((mesh_raster_tiles<HN_FRAME_F32_CHW, true, Occlusion>), grid, dim3(256), 0, st, sc, s, f, k, frame, h, w,
@@ -339,8 +369,9 @@ static int render(const char* fn, const float* mesh, const int32_t* faces, const
 extern "C" int hn_mesh_render_u8(const float* mesh, const int32_t* faces, const int32_t* faces_host, const int32_t* lifted, int s,
                                  int v, int f, int k, const float* paras, const void* frame, int frame_format, int h, int w,
                                  void* scratch, int64_t scratch_bytes, uint8_t* out_image, float* out_depth, void* stream) {
-  return render("hn_mesh_render_u8", mesh, faces, faces_host, lifted, s, v, f, k, paras, frame, frame_format, h, w, scratch,
-                scratch_bytes, out_image, out_depth, nullptr, 0, stream);
+  HN_CHECK_ARG(paras, "hn_mesh_render_u8: null pointer");
+  return render("hn_mesh_render_u8", mesh, faces, faces_host, lifted, s, v, f, k, paras, nullptr, frame, frame_format, h, w,
+                scratch, scratch_bytes, out_image, out_depth, nullptr, 0, stream);
 }
 
 extern "C" int hn_mesh_render_occluded_u8(const float* mesh, const int32_t* faces, const int32_t* faces_host, const int32_t* lifted,
@@ -348,7 +379,30 @@ extern "C" int hn_mesh_render_occluded_u8(const float* mesh, const int32_t* face
                                           int h, int w, const float* scene_depth, int64_t depth_frame_stride, float margin,
                                           void* scratch, int64_t scratch_bytes, uint8_t* out_image, float* out_depth,
                                           uint8_t* out_silhouette, int32_t* out_coverage, void* stream) {
+  HN_CHECK_ARG(paras, "hn_mesh_render_occluded_u8: null pointer");
   const Occlusion occ = {scene_depth, (long long)depth_frame_stride, margin, out_silhouette, out_coverage};
-  return render("hn_mesh_render_occluded_u8", mesh, faces, faces_host, lifted, s, v, f, k, paras, frame, frame_format, h, w,
-                scratch, scratch_bytes, out_image, out_depth, &occ, depth_frame_stride, stream);
+  return render("hn_mesh_render_occluded_u8", mesh, faces, faces_host, lifted, s, v, f, k, paras, nullptr, frame, frame_format, h,
+                w, scratch, scratch_bytes, out_image, out_depth, &occ, depth_frame_stride, stream);
+}
+
+// the two entries above with a camera per frame: cams = DEVICE fp32 [s / k][4] in place of the host's four values
+extern "C" int hn_mesh_render_cams_u8(const float* mesh, const int32_t* faces, const int32_t* faces_host, const int32_t* lifted,
+                                      int s, int v, int f, int k, const float* cams, const void* frame, int frame_format, int h,
+                                      int w, void* scratch, int64_t scratch_bytes, uint8_t* out_image, float* out_depth,
+                                      void* stream) {
+  HN_CHECK_ARG(cams, "hn_mesh_render_cams_u8: null pointer");
+  return render("hn_mesh_render_cams_u8", mesh, faces, faces_host, lifted, s, v, f, k, nullptr, cams, frame, frame_format, h, w,
+                scratch, scratch_bytes, out_image, out_depth, nullptr, 0, stream);
+}
+
+extern "C" int hn_mesh_render_cams_occluded_u8(const float* mesh, const int32_t* faces, const int32_t* faces_host,
+                                               const int32_t* lifted, int s, int v, int f, int k, const float* cams,
+                                               const void* frame, int frame_format, int h, int w, const float* scene_depth,
+                                               int64_t depth_frame_stride, float margin, void* scratch, int64_t scratch_bytes,
+                                               uint8_t* out_image, float* out_depth, uint8_t* out_silhouette,
+                                               int32_t* out_coverage, void* stream) {
+  HN_CHECK_ARG(cams, "hn_mesh_render_cams_occluded_u8: null pointer");
+  const Occlusion occ = {scene_depth, (long long)depth_frame_stride, margin, out_silhouette, out_coverage};
+  return render("hn_mesh_render_cams_occluded_u8", mesh, faces, faces_host, lifted, s, v, f, k, nullptr, cams, frame, frame_format,
+                h, w, scratch, scratch_bytes, out_image, out_depth, &occ, depth_frame_stride, stream);
 }

@@ -95,7 +95,9 @@ class HandNet(EngineOwner):
         """What the reference's caller does with every result (ros_demo.py:279-290,329-330: clamp, convert_joints to image
         (u,v,d), uvd2xyz to camera millimetres) as part of the step: the aggregation's own launch writes them and the call's one
         device -> host record carries them.  After each forward(): `net.last_converted` = {"image_uvd": [N,21,3] CPU,
-        "xyz_mm": [N,21,3] CPU or None (no intrinsics)}; forward()'s tuple itself is unchanged.  paras = (fx, fy, cx, cy)."""
+        "xyz_mm": [N,21,3] CPU or None (no intrinsics)}; forward()'s tuple itself is unchanged.  paras = (fx, fy, cx, cy), or a
+        camera per frame [N,4] (frame i is converted with row i; a call over another number of frames raises ValueError)."""
+        paras = ops.camera_paras(paras)
         self._convert_cfg = (paras, bool(clamp)) if on else None
         if self._engine is not None:
             self._engine.set_convert(paras, clamp, on)
@@ -107,7 +109,9 @@ class HandNet(EngineOwner):
         """The live caller's chain as ONE step (hn_amd.live.LiveHandEngine; ros_demo.py:270-290,329-337): this network, the
         caller's clamp + convert_joints (in the aggregation's epilogue), the lifter's input, Pose2Mesh, one device -> host copy.
         lifter: the drop-in `models.pose2mesh_net.get_model(...)` module (on the GPU) or a Pose2MeshEngine; paras = (fx, fy,
-        cx, cy); perm_reverse = graph_perm_reverse[:V]: the step then also does ros_demo.py:162,332-337 and hands over out['mesh'].
+        cx, cy), or a camera per frame [N,4] (a nested sequence, an ndarray or a tensor, rounded to fp32): the step then takes
+        exactly N frames, frame i is converted and drawn with row i, and engine.set_cameras(new [N,4]) changes the values
+        without recapturing anything; perm_reverse = graph_perm_reverse[:V]: the step then also does ros_demo.py:162,332-337 and hands over out['mesh'].
         faces = mesh_model.face (needs perm_reverse): the step also draws the mesh over the frame, the caller's render()
         (ros_demo.py:86-116,341): out.overlay on the device, read().overlay on the host.
         labels: the step also draws the caller's other two images (ros_demo.py:310-326): box_label (the frame with the crop
@@ -120,7 +124,8 @@ class HandNet(EngineOwner):
         The returned engine owns this network's step from then on (forward() of this module keeps working and
         carries the converted joints: set_convert)."""
         from hn_amd.live import LiveHandEngine
-        self._convert_cfg = (tuple(paras), bool(clamp))
+        paras = ops.camera_paras(paras)
+        self._convert_cfg = (paras, bool(clamp))
         return LiveHandEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, clamp, perm_reverse,
                               faces, labels, left, occlude, occlude_margin)
 
@@ -133,6 +138,7 @@ class HandNet(EngineOwner):
         caller's clamp + convert_joints, the lifter's input with the caller's skip rule per slot (a hand whose 2D box
         process_bbox refuses is not lifted: ros_demo.py:288-300), Pose2Mesh on every slot, one device -> host copy.
         read() of a step's output gives keypoints / boxes / scores per slot, `lifted` [N,K] and the mesh [N,K,V,3].
+        paras: as for live(); with a camera per frame [N,4], all K slots of frame i use row i.
         faces = mesh_model.face (needs perm_reverse): every lifted mesh of a frame is drawn over it (one depth buffer per frame):
         out.overlay / read().overlay [N,H,W,3] uint8 RGB.
         labels: as for live(): box_label [N,H,W,3] with the crop box of every lifted slot, pose_label [N,K,176,176,3] (zeros
@@ -158,7 +164,8 @@ class HandNet(EngineOwner):
         k = ops.check_max_hands(max_hands)
         if left and handed:
             raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
-        self._convert_cfg = (tuple(paras), bool(clamp))
+        paras = ops.camera_paras(paras)
+        self._convert_cfg = (paras, bool(clamp))
         return LiveHandsEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, k, clamp,
                                perm_reverse, faces, labels, left, handed, left_side, track, track_iou, track_hold,
                                occlude=occlude, occlude_margin=occlude_margin, smooth=smooth, smooth_min_cutoff=smooth_min_cutoff,

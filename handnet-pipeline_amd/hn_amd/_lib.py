@@ -234,6 +234,11 @@ SIGNATURES = {
     # the overlay hidden behind nearer scene depth (a new function under ABI 36)
     "hn_mesh_render_occluded_u8": (C.c_int, [VP, VP, VP, VP] + [C.c_int] * 4 + [c_f32p, VP, C.c_int, C.c_int, C.c_int, VP, C.c_int64,
                                              C.c_float, VP, C.c_int64, VP, VP, VP, VP, VP]),
+    # (cams: a device pointer where the two entries above take the host's four floats)
+    "hn_mesh_render_cams_u8": (C.c_int, [VP, VP, VP, VP] + [C.c_int] * 4 + [VP, VP, C.c_int, C.c_int, C.c_int, VP, C.c_int64, VP,
+                                         VP, VP]),
+    "hn_mesh_render_cams_occluded_u8": (C.c_int, [VP, VP, VP, VP] + [C.c_int] * 4 + [VP, VP, C.c_int, C.c_int, C.c_int, VP,
+                                                  C.c_int64, C.c_float, VP, C.c_int64, VP, VP, VP, VP, VP]),
 }
 
 _lock = threading.Lock()

@@ -244,7 +244,16 @@ class _LiveStep:
         self.perm, self.vertices = _final_mesh_perm(perm_reverse, lifter, self.device)
         # faces: the mesh's triangles (mesh_model.face) -- given, the step ends with the overlay (ops.mesh_render: the caller's
         # render(), ros_demo.py:86-116) and the image rides behind the mesh in the step's one copy
-        self.faces, self.paras = None, tuple(float(p) for p in paras)
+        # paras: one camera for every frame, or a camera per frame [N,4] -- then the engine keeps the rows in
+        # device tables that its kernels read, so set_cameras() changes them under captured steps: this one, a row per frame,
+        # for the raster; the hand engine's, a row per slot, for the conversion
+        paras = ops.camera_paras(paras)
+        self.faces, self.paras, self.cams = None, paras, None
+        if isinstance(paras, np.ndarray):
+            # (kept by this engine: its captured steps hold the tables' addresses, whatever the hand engine is told later)
+            self._cameras = hand._convert["cams"]
+            with ops.on_device(self.device):
+                self.paras, self.cams = None, self._cameras.rows(1)
         if faces is not None:
             if self.perm is None:
                 raise ValueError("faces= needs perm_reverse=: the overlay projects out['mesh'] (camera frame, the real mesh's "
@@ -300,11 +309,27 @@ class _LiveStep:
             with torch.inference_mode(False):
                 scratch = self._render_scratch[s] = torch.empty(
                     (ops.mesh_render_scratch_bytes(s, self.faces.shape[0]),), dtype=torch.uint8, device=self.device)
+        paras = self.paras if self.cams is None else self.cams      # (the table: row i for the k slots of frame i)
         if self.occlude is None:
-            return ops.mesh_render(mesh, self.faces, self.paras, frames, lifted=lifted, k=k, out=out, scratch=scratch), None, None
+            return ops.mesh_render(mesh, self.faces, paras, frames, lifted=lifted, k=k, out=out, scratch=scratch), None, None
         # (the depth map the step itself ran on: mirrored in a `left` step, channel 3 of an RGBD step's tensor)
-        return ops.mesh_render(mesh, self.faces, self.paras, frames, lifted=lifted, k=k, out=out, scratch=scratch,
+        return ops.mesh_render(mesh, self.faces, paras, frames, lifted=lifted, k=k, out=out, scratch=scratch,
                                scene_depth=depth, margin=self.occlude, silhouette_out=at.silhouette, coverage_out=at.coverage)
+
+    def _check_frames(self, n):
+        if self.cams is not None and n != self.cams.shape[0]:
+            raise ValueError(f"a step over {n} frames, but the engine was built with {self.cams.shape[0]} cameras, one per frame")
+
+    @ops.device_guarded
+    def set_cameras(self, paras):
+        """New intrinsics for an engine built with a camera per frame (paras [N,4]; same N): the values are copied into the
+        engine's device tables on the current stream, and eager steps and every already captured step use them from the next
+        step on -- the kernels read the tables, so nothing is recaptured.  An engine built with one camera raises ValueError:
+        its four values are kernel arguments."""
+        if self.cams is None:
+            raise ValueError("set_cameras needs an engine built with a camera per frame: paras [N,4]")
+        self._cameras.update(paras)      # (the raster's table, a row per frame, and the conversion's, a row per slot)
+        return self
 
     def _layout(self, n, hw=None) -> LiveLayout:
         """The buffer of a step over n frames (hw: of a step that draws, the frames' size)."""
@@ -330,6 +355,7 @@ class _LiveStep:
         """images [N,3,H,W] 0..1 (or a list), depth [N,1,H,W] metres on the GPU -> the step's output (no sync).
         (_mirror: a `left` capture's own mirrored-input buffers; False: the inputs are mirrored already.)"""
         n = len(images)
+        self._check_frames(n)
         if self.left and _mirror is not False:
             images, depth = self._mirror_inputs(images, depth, _mirror)
         frames = self._frames(images)
@@ -375,6 +401,7 @@ class _LiveStep:
         staged = []
         bgr, dep = self.hand._device_readable(bgr_u8, staged), self.hand._device_readable(depth_raw, staged)
         n, h, w, _ = bgr.shape
+        self._check_frames(n)
         # (a `left` step: the ingest kernel mirrors while it converts, so this capture -- keyed apart from graphed()'s -- takes
         # its inputs as already mirrored and holds no mirror launch)
         key = ((n, 3, h, w), (n, 1, h, w)) + (("mirrored",) if self.left else ()) + self._key_options()
@@ -390,6 +417,7 @@ class _LiveStep:
         key = (tuple(images.shape), tuple(depth.shape)) + (("mirrored",) if _mirrored else ()) + self._key_options()
         hit = self._graphs.get(key)
         if hit is None:
+            self._check_frames(images.shape[0])
             with torch.inference_mode(False), torch.no_grad():
                 s_img, s_dep = torch.empty_like(images), torch.empty_like(depth)
                 s_img.copy_(images)
@@ -413,7 +441,9 @@ class _LiveStep:
 
 
 class LiveHandEngine(_LiveStep):
-    """paras = (fx, fy, cx, cy) of the depth camera (ros_demo.py:191-196); clamp: the caller's clamps before the
+    """paras = (fx, fy, cx, cy) of the depth camera (ros_demo.py:191-196), or a camera per frame [N,4] (frame i
+    of every step is converted and drawn with row i, every other option unchanged; the step takes exactly N frames, and
+    set_cameras() changes the values under captured steps); clamp: the caller's clamps before the
     conversion (ros_demo.py:279-283).  perm_reverse: graph_perm_reverse[:V] (int64, V = vertices of the real mesh,
     ros_demo.py:162) -- given, the step also does the caller's last three lines (vertex order, camera offset by the first
     joint, y / z negated: ros_demo.py:332-337) and `mesh` of the outputs IS out['mesh'], [N,V,3]; else the lifter's raw
@@ -508,7 +538,8 @@ class LiveHandsEngine(_LiveStep):
                  left_side: int = 0, track: bool = False, track_iou: float = 0.3, track_hold: int = 5, occlude: bool = False,
                  occlude_margin: float = ops.OCCLUDE_MARGIN, smooth: bool = False, smooth_min_cutoff: float = 1.0,
                  smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0, smooth_rate: float = 30.0):
-        """faces: mesh_model.face ([F,3]; needs perm_reverse) -- given, the step ends with the overlay: every lifted mesh of a
+        """paras: as LiveHandEngine's -- with a camera per frame [N,4], all K slots of frame i use row i.
+        faces: mesh_model.face ([F,3]; needs perm_reverse) -- given, the step ends with the overlay: every lifted mesh of a
         frame drawn over it with one depth buffer per frame (LiveHandsOutput.overlay, read().overlay), in the same copy.
         labels: the step ends with box_label (the crop box of every lifted slot on its frame) and one pose_label per slot
         (zeros where the slot is not lifted: the reference's condition, ros_demo.py:294), in the same copy.
@@ -654,6 +685,17 @@ class LiveHandsEngine(_LiveStep):
                                smooth_mesh=None if self.smooth is None else at.smooth_mesh.view(n, k, self.vertices, 3), **parts)
 
 
+class CropMeshRead(collections.namedtuple("CropMeshRead", "keypoints image_uvd xyz_mm mesh words")):
+    """CropMeshOutput.read(): the five items it always returned -- same length, unpacking and equality as that tuple -- and
+    `.overlay`: uint8 [K,H,W,3] RGB of a step with faces= and frames, else None."""
+    overlay = None
+
+    def __new__(cls, *values, overlay=None):
+        self = super().__new__(cls, *values)
+        self.overlay = overlay
+        return self
+
+
 @dataclass
 class CropMeshOutput:
     keypoints: torch.Tensor      # [K,21,3] crop (u,v,d) as the network returns it, on the device
@@ -666,14 +708,19 @@ class CropMeshOutput:
     host: torch.Tensor           # pinned fp32: keypoints | image_uvd | xyz_mm | mesh | 4 range words (as bits) -- ONE copy; the
     #                              engine's buffer for this batch size: the next call overwrites it (read() returns copies)
     k: int = 0
+    overlay: torch.Tensor = None        # [K,H,W,3] uint8 RGB on the device: sample i's mesh over its own image with its own
+    #                                     intrinsics (engines with faces=, steps with frames; a2j_mesh.py's demo_mesh_{idx}.png)
+    host_overlay: torch.Tensor = None   # its pinned copy, a second copy enqueued behind `host`'s
 
-    def read(self):
-        """After the stream is synchronised: (keypoints, image_uvd, xyz_mm, mesh, range words) as fresh CPU tensors."""
+    def read(self) -> CropMeshRead:
+        """After the stream is synchronised: (keypoints, image_uvd, xyz_mm, mesh, range words) as fresh CPU tensors; `.overlay`
+        of the result: the images [K,H,W,3] uint8 of a step that drew them, else None."""
         k, j3 = self.k, self.keypoints.shape[1] * 3
         h = self.host
         parts = [h[i * k * j3:(i + 1) * k * j3].reshape(k, -1, 3).clone() for i in range(3)]
         mesh = h[3 * k * j3:-4].reshape(k, -1, 3).clone()
-        return parts[0], parts[1], parts[2], mesh, h[-4:].view(torch.int32).tolist()
+        return CropMeshRead(parts[0], parts[1], parts[2], mesh, h[-4:].view(torch.int32).tolist(),
+                            overlay=None if self.host_overlay is None else self.host_overlay.clone())
 
 
 class CropMeshEngine:
@@ -681,21 +728,51 @@ class CropMeshEngine:
     [0, 176] + convert_joints twice (image uv; camera xyz with the sample's intrinsics -- the dataset's float32 box, fractional
     corners: a2jdataset.py:293) in the aggregation's epilogue -> the lifter's input (predict_mesh, ros_demo.py:148-157) ->
     Pose2Mesh -> the caller's last lines (vertex order, camera offset by the first joint, y / z negated: a2j_mesh.py:77-80) ->
-    ONE device -> host copy.  The reference goes to the CPU after A2J, converts in numpy and uploads the normalised joints."""
+    ONE device -> host copy.  The reference goes to the CPU after A2J, converts in numpy and uploads the normalised joints.
+    faces: mesh_model.face ([F,3]; needs perm_reverse) -- given, a step that is handed the samples' full images (frames) ends
+    with the loop's last call, render(out, paras, h, w, full_image, face) (a2j_mesh.py): sample i's mesh drawn over frames[i]
+    with ITS intrinsics paras[i] (ops.mesh_render with a camera per frame, one slot per frame) ->
+    CropMeshOutput.overlay, read().overlay."""
 
-    def __init__(self, a2j, lifter: Pose2MeshEngine, clamp: bool = True, perm_reverse=None):
+    def __init__(self, a2j, lifter: Pose2MeshEngine, clamp: bool = True, perm_reverse=None, faces=None):
         if not _same_device(a2j.device, lifter.device):
             raise ValueError(f"A2J on {a2j.device} but the lifter on {lifter.device}")
         self.a2j, self.lifter, self.device, self.clamp = a2j, lifter, a2j.device, bool(clamp)
         self.perm, self.vertices = _final_mesh_perm(perm_reverse, lifter, self.device)
+        self.faces = None
+        if faces is not None:
+            if self.perm is None:
+                raise ValueError("faces= needs perm_reverse=: the overlay projects out['mesh'] (camera frame, the real mesh's "
+                                 "vertex order); the lifter's raw output has no camera offset to project")
+            with ops.on_device(self.device):
+                self.faces = ops.mesh_faces(faces, self.vertices, self.device)
         self._block = None
         self._graphs = {}
         self._hosts = {}
+        self._overlays = {}
+        self._render_scratch = {}
+
+    def _new_overlay(self, frames):
+        """(device, pinned) overlay buffers of a step over these frames: uint8 [K,H,W,3]"""
+        k, (h, w) = frames.shape[0], frames.shape[1:3] if frames.dtype == torch.uint8 else frames.shape[2:]
+        return (torch.empty((k, h, w, 3), dtype=torch.uint8, device=self.device),
+                torch.zeros((k, h, w, 3), dtype=torch.uint8, pin_memory=True))
+
+    def _check_frames(self, frames, k):
+        if frames is None:
+            return
+        if self.faces is None:
+            raise ValueError("frames are what an engine with faces= draws over: build the engine with faces=")
+        if not torch.is_tensor(frames) or frames.dim() != 4 or frames.shape[0] != k:
+            raise ValueError(f"frames: one full image per sample, fp32 [{k},3,H,W] or uint8 [{k},H,W,3]")
 
     @ops.device_guarded
-    def forward_device(self, crops, box_f32, paras, _host=None) -> CropMeshOutput:
-        """crops [K,1,176,176] (or [K,4,..] for the RGB-D network), box_f32 [K,4] float32, paras [K,4] float32, on the GPU."""
+    def forward_device(self, crops, box_f32, paras, frames=None, _host=None, _overlay=None) -> CropMeshOutput:
+        """crops [K,1,176,176] (or [K,4,..] for the RGB-D network), box_f32 [K,4] float32, paras [K,4] float32, on the GPU.
+        frames (an engine with faces=): the samples' full images, fp32 [K,3,H,W] in 0..1 or uint8 [K,H,W,3] 'bgr8', on the GPU
+        -- the step then ends with the two raster launches and hands out `overlay`."""
         k = crops.shape[0]
+        self._check_frames(frames, k)
         if self._block is None:
             self._block = torch.zeros((4,), device=self.device, dtype=torch.int32)
         conv = dict(sample_box=box_f32, sample_paras=paras, clamp_keypoints=self.clamp)
@@ -712,7 +789,25 @@ class CropMeshEngine:
                 with torch.inference_mode(False):
                     _host = self._hosts[dev.numel()] = self._new_host(k)
         _host.copy_(dev, non_blocking=True)
-        return CropMeshOutput(kp, img, xyz, p2d, mesh, pose3d, raw, _host, k)
+        overlay = host_overlay = None
+        if frames is not None:
+            frames = frames.contiguous()
+            key = (tuple(frames.shape), frames.dtype)
+            if _overlay is None:
+                _overlay = self._overlays.get(key)
+                if _overlay is None:
+                    with torch.inference_mode(False):
+                        _overlay = self._overlays[key] = self._new_overlay(frames)
+            scratch = self._render_scratch.get(k)
+            if scratch is None:
+                with torch.inference_mode(False):
+                    scratch = self._render_scratch[k] = torch.empty(
+                        (ops.mesh_render_scratch_bytes(k, self.faces.shape[0]),), dtype=torch.uint8, device=self.device)
+            # (the samples' intrinsics are the table: one slot per frame, sample i reads row i)
+            overlay = ops.mesh_render(mesh, self.faces, paras, frames, k=1, out=_overlay[0], scratch=scratch)
+            host_overlay = _overlay[1]
+            host_overlay.copy_(overlay, non_blocking=True)
+        return CropMeshOutput(kp, img, xyz, p2d, mesh, pose3d, raw, _host, k, overlay, host_overlay)
 
     def _new_host(self, k):
         """The pinned buffer of a step over k crops, as forward_device's torch.cat fills it: three [k,J,3] fields (keypoints,
@@ -720,18 +815,23 @@ class CropMeshEngine:
         return torch.zeros((3 * k * self.a2j.joints * 3 + k * self.vertices * 3 + 4,), dtype=torch.float32, pin_memory=True)
 
     @ops.device_guarded
-    def graphed(self, crops, box_f32, paras):
+    def graphed(self, crops, box_f32, paras, frames=None):
         """(run, static crops, static boxes, static intrinsics, static CropMeshOutput): copy a new batch into the static inputs and
-        call run() -- every launch of the step and its copy replay from one hipGraph."""
-        key = (tuple(crops.shape),)
+        call run() -- every launch of the step and its copy replay from one hipGraph.  With frames (an engine with faces=) the
+        captured step draws, and the static frames are a fourth static input: (run, static crops, static boxes, static
+        intrinsics, static frames, static CropMeshOutput).  The raster reads the static intrinsics from the device, so new
+        values copied into them move the next replay's meshes AND images."""
+        self._check_frames(frames, crops.shape[0])
+        key = (tuple(crops.shape),) + (() if frames is None else (tuple(frames.shape), frames.dtype))
         hit = self._graphs.get(key)
         if hit is None:
             with torch.inference_mode(False), torch.no_grad():
-                s = [torch.empty_like(t) for t in (crops, box_f32, paras)]
-                for a, b in zip(s, (crops, box_f32, paras)):
+                inputs = (crops, box_f32, paras) + (() if frames is None else (frames.contiguous(),))
+                s = [torch.empty_like(t) for t in inputs]
+                for a, b in zip(s, inputs):
                     a.copy_(b)
                 host = self._new_host(crops.shape[0])
-                g, out = ops.capture_step(lambda: self.forward_device(*s, _host=host))
-            hit = self._graphs[key] = (g, s[0], s[1], s[2], out)
-        g, s_crops, s_box, s_paras, out = hit
-        return g.replay, s_crops, s_box, s_paras, out
+                overlay = None if frames is None else self._new_overlay(s[3])
+                g, out = ops.capture_step(lambda: self.forward_device(*s, _host=host, _overlay=overlay))
+            hit = self._graphs[key] = (g, *s, out)
+        return (hit[0].replay,) + tuple(hit[1:])

@@ -1910,6 +1910,22 @@ def mesh_finish_smooth(mesh, perm, xyz_mm, lifted, has_hand, track_id, dt, state
     return out, smooth_xyz, smooth_mesh
 
 
+def camera_paras(paras):
+    """The caller's intrinsics as the engines keep them: one camera (fx, fy, cx, cy) -> a tuple of four floats, as ever; a
+    camera per frame -- a nested sequence, an ndarray or a tensor [N,4] -- -> a float32 ndarray [N,4] (the rounding to fp32 that
+    the one camera's values get when they are passed to a kernel).  None stays None."""
+    if paras is None:
+        return None
+    if torch.is_tensor(paras):
+        paras = paras.detach().cpu().numpy()
+    if np.ndim(paras) < 2:
+        return tuple(float(v) for v in paras)
+    table = np.ascontiguousarray(np.asarray(paras, dtype=np.float64).astype(np.float32))
+    if table.ndim != 2 or table.shape[1] != 4 or table.shape[0] == 0:
+        raise ValueError(f"paras: one camera (fx, fy, cx, cy) or a camera per frame [N,4], got shape {tuple(table.shape)}")
+    return table
+
+
 def mesh_faces(faces, vertices, device):
     """The caller's face list (mesh_model.face: numpy / tensor / list, [F,3] vertex indices) checked ON THE HOST against the
     vertex count and uploaded once: int32 [F,3] on `device`, what mesh_render and the live engines draw with."""
@@ -1941,7 +1957,9 @@ def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out
     """The meshes drawn over their frames (hn_mesh_render_u8; render() of ros_demo.py:86-116 without a graphics pipeline):
     mesh fp32 [S,V,3] or [N,K,V,3] as mesh_finish writes it, S = N * k slots; faces [F,3]: an int32 GPU tensor (mesh_faces) or
     a host list (checked index by index and uploaded by THIS call: a caller that renders repeatedly uploads once with mesh_faces
-    and passes the tensor, as the live engines do); paras (fx, fy, cx, cy); frame fp32 [N,3,H,W] in 0..1 or uint8 [N,H,W,3]
+    and passes the tensor, as the live engines do); paras (fx, fy, cx, cy), or -- a camera per frame, hn_mesh_render_cams_u8 /
+    _cams_occluded_u8, DESIGN.md section 9h -- an fp32 tensor [N,4] on the mesh's device, row i for the k slots of frame i
+    (ValueError for another shape, dtype or device); frame fp32 [N,3,H,W] in 0..1 or uint8 [N,H,W,3]
     'bgr8', on the GPU; lifted int32 [S] (0: the slot is not drawn).  Returns the overlay uint8 [N,H,W,3] RGB (`out`);
     depth_out fp32 [N,H,W], when given, receives the drawn Z (0 where nothing was drawn).
     scene_depth (hn_mesh_render_occluded_u8): the camera's depth map in metres, fp32 [N,1,H,W], [N,H,W]
@@ -1996,14 +2014,24 @@ def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out
     if scratch is None:
         scratch = torch.empty((need,), device=mesh.device, dtype=torch.uint8)
     _req(scratch, torch.uint8, "scratch")
-    p4 = (C.c_float * 4)(*[float(x) for x in paras])
+    # a camera per frame: a device table [N,4] (hn_mesh_render_cams_*); else the one camera's four values, passed by value
+    cams = torch.is_tensor(paras) and paras.dim() != 1
+    if cams:
+        if paras.dtype != torch.float32 or tuple(paras.shape) != (n, 4):
+            raise ValueError(f"paras: a camera per frame is fp32 [{n},4] (fx, fy, cx, cy), got {paras.dtype} {tuple(paras.shape)}")
+        if paras.device != mesh.device:
+            raise ValueError(f"paras on {paras.device} but the mesh on {mesh.device}")
+        p4 = ptr(_req(paras, torch.float32, "paras"))
+    else:
+        p4 = (C.c_float * 4)(*[float(x) for x in paras])
+    plain, occluded = ("hn_mesh_render_cams_u8", "hn_mesh_render_cams_occluded_u8") if cams else (
+        "hn_mesh_render_u8", "hn_mesh_render_occluded_u8")
     fh = faces_host.ctypes.data if faces_host is not None else None
     if scene_depth is None:
         if silhouette_out is not None or coverage_out is not None:
             raise ValueError("silhouette_out / coverage_out belong to the occluded call: give scene_depth")
-        check(_lib.load().hn_mesh_render_u8(ptr(mesh), ptr(faces), fh, ptr(lifted), s, v, f, k, p4, ptr(frame), fmt, h, w,
-                                            ptr(scratch), scratch.numel(), ptr(out), ptr(depth_out), _stream()),
-              "hn_mesh_render_u8")
+        check(getattr(_lib.load(), plain)(ptr(mesh), ptr(faces), fh, ptr(lifted), s, v, f, k, p4, ptr(frame), fmt, h, w,
+                                          ptr(scratch), scratch.numel(), ptr(out), ptr(depth_out), _stream()), plain)
         return out.view(n, h, w, 3)
     margin = check_occlude_margin(margin)
     _req(scene_depth, name="scene_depth")
@@ -2026,10 +2054,9 @@ def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out
     _req(coverage_out, torch.int32, "coverage_out")
     if coverage_out.numel() != s * 2:
         raise ValueError(f"coverage_out: expected int32 [{s},2], got {tuple(coverage_out.shape)}")
-    check(_lib.load().hn_mesh_render_occluded_u8(ptr(mesh), ptr(faces), fh, ptr(lifted), s, v, f, k, p4, ptr(frame), fmt, h, w,
-                                                 depth_ptr, (4 if rgbd else 1) * h * w, margin, ptr(scratch), scratch.numel(),
-                                                 ptr(out), ptr(depth_out), ptr(silhouette_out), ptr(coverage_out), _stream()),
-          "hn_mesh_render_occluded_u8")
+    check(getattr(_lib.load(), occluded)(ptr(mesh), ptr(faces), fh, ptr(lifted), s, v, f, k, p4, ptr(frame), fmt, h, w,
+                                         depth_ptr, (4 if rgbd else 1) * h * w, margin, ptr(scratch), scratch.numel(),
+                                         ptr(out), ptr(depth_out), ptr(silhouette_out), ptr(coverage_out), _stream()), occluded)
     return out.view(n, h, w, 3), silhouette_out.view(n, h, w), coverage_out.view(s, 2)
 
 

@@ -13,6 +13,7 @@ from dataclasses import dataclass
 
 import os
 
+import numpy as np
 import torch
 
 from . import ops
@@ -20,6 +21,39 @@ from .a2j_engine import A2JEngine
 from .fcos_engine import FCOSEngine
 
 CROP = 176
+
+
+class CameraTables:
+    """A camera per frame as the kernels read it: the caller's [N,4] fp32 values and, per number of slots per frame, a device
+    table with one row per slot (frame-major: slot i * k + j holds row i), made on first use.  update() copies new values
+    into the SAME tables, so a captured step that holds their addresses uses them at its next replay; whoever captured such a
+    step keeps this object, and with it the tables, alive."""
+
+    def __init__(self, values, device):
+        self.values, self.device, self.tables = values, device, {}
+
+    @property
+    def frames(self) -> int:
+        return self.values.shape[0]
+
+    def _expanded(self, k):
+        return torch.from_numpy(np.repeat(self.values, k, axis=0))
+
+    def rows(self, k=1):
+        table = self.tables.get(k)
+        if table is None:
+            with torch.inference_mode(False):
+                table = self.tables[k] = self._expanded(k).to(self.device)
+        return table
+
+    def update(self, paras):
+        new = ops.camera_paras(paras)
+        if not isinstance(new, np.ndarray) or new.shape != self.values.shape:
+            raise ValueError(f"set_cameras: expected [{self.frames},4] values, one row per frame")
+        self.values = new
+        for k, table in self.tables.items():
+            table.copy_(self._expanded(k))
+        return self
 
 
 @dataclass
@@ -210,24 +244,46 @@ class HandNetEngine:
         every result): HandNetOutput.image_uvd, and .xyz_mm when the camera intrinsics paras = (fx, fy, cx, cy) are given, are
         written by the aggregation's own launch, and to_host steps carry them in a wide record.  clamp: the live caller's
         clamps before the conversion (keypoints to [0, 176], box to the frame: ros_demo.py:279-283).  Captured steps are
-        dropped (their launch sequence changes)."""
-        self._convert = None if not on else {"paras": None if paras is None else tuple(float(v) for v in paras), "clamp": bool(clamp)}
+        dropped (their launch sequence changes).
+        paras may also be a camera per frame, [N,4] (a nested sequence, an ndarray or a tensor; rounded to fp32 as the one
+        camera's values are): frame i -- every slot of frame i in forward_hands -- is converted with row i.
+        The rows live in a table on the device that the aggregation reads (sample_paras of its conversion spec, one row per
+        slot), so set_cameras() changes them under captured steps; a step over another number of frames raises ValueError."""
+        paras = ops.camera_paras(paras)
+        table = isinstance(paras, np.ndarray)
+        self._convert = None if not on else {"paras": None if table else paras, "clamp": bool(clamp),
+                                             "cams": CameraTables(paras, self.device) if table else None}
         self._graphs.clear()
         self._host_records.clear()
         return self
 
-    def _convert_spec(self, crop_box, frame_hw):
+    @ops.device_guarded
+    def set_cameras(self, paras):
+        """New values for the per-frame cameras of set_convert(paras=[N,4]): copied into the same device tables (on the current
+        stream), so eager steps and every already captured step convert with them from the next step on -- nothing is
+        recaptured.  Same N; ValueError on an engine whose conversion has one camera or none."""
+        c = self._convert
+        if c is None or c["cams"] is None:
+            raise ValueError("set_cameras needs a camera per frame: set_convert(paras=[N,4])")
+        c["cams"].update(paras)
+        return self
+
+    def _convert_spec(self, crop_box, frame_hw, n=None, hands=None):
         c = self._convert
         if c is None:
             return None
         spec = {"crop_box": crop_box, "paras": c["paras"], "crop": CROP}
+        if c["cams"] is not None:
+            if n != c["cams"].frames:
+                raise ValueError(f"a step over {n} frames, but set_convert was given {c['cams'].frames} cameras, one per frame")
+            spec["sample_paras"] = c["cams"].rows(hands or 1)
         if c["clamp"]:
             spec.update(clamp_keypoints=True, clamp_box=frame_hw)
         return spec
 
     def _fields(self) -> int:
         c = self._convert
-        return 1 if c is None else (3 if c["paras"] is not None else 2)
+        return 1 if c is None else (3 if c["paras"] is not None or c["cams"] is not None else 2)
 
     @ops.device_guarded
     def forward_device(self, images, depth: torch.Tensor, to_host: bool = False, _record=None, _tail=None) -> HandNetOutput:
@@ -350,7 +406,7 @@ class HandNetEngine:
                         reorder_bgr=self.a2j.rgbd, handed=True, left_side=handed[0], side=side)
                     side, mirror = side.view(n, hands), mirror.view(n, hands)
                 box_rows, has_rows = crop_box.view(rows, 4), has_hand.view(rows)
-            conv = self._convert_spec(box_rows, tuple(depth.shape[-2:]))
+            conv = self._convert_spec(box_rows, tuple(depth.shape[-2:]), n, hands)
             unconverted = hands is not None and mirror is not None and conv is None
             if unconverted:     # (the un-mirror is part of the converting aggregation: its image (u,v,d) is not handed out)
                 conv = {"crop_box": box_rows, "paras": None, "crop": CROP}
@@ -422,13 +478,14 @@ class HandNetEngine:
         if k * 2 >= n:
             self._sparse_hint = False
             return None
-        fields = 1 if conv is None else (3 if conv["paras"] is not None else 2)
+        fields = 1 if conv is None else (3 if conv["paras"] is not None or conv.get("sample_paras") is not None else 2)
         outs = [torch.zeros((n, self.a2j.joints, 3), device=crops.device, dtype=torch.float32) for _ in range(fields)]
         if k:
             v = has_hand[idx].contiguous()
             sub = None if conv is None else dict(conv, crop_box=conv["crop_box"][idx].contiguous())
-            if sub is not None and sub.get("mirror") is not None:
-                sub["mirror"] = sub["mirror"][idx].contiguous()
+            for per_row in ("mirror", "sample_paras"):
+                if sub is not None and sub.get(per_row) is not None:
+                    sub[per_row] = sub[per_row][idx].contiguous()
             res = self.a2j.forward_nhwc(crops[idx].contiguous(), valid=v, convert=sub)
             for o, r in zip(outs, res if conv is not None else (res,)):
                 o[idx] = r

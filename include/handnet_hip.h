@@ -36,7 +36,8 @@ extern "C" {
  * keep it: hn_lifter_input_gated_f32 and hn_mesh_render_u8 came under 36, and so did the mirror / handedness entries
  * hn_ingest_u8bgr_u16mm_flip, hn_flip_w_f32, hn_crop_resize_hands_sided, hn_a2j_aggregate_convert_mirror_f32,
  * hn_lifter_input_gated_mirror_f32 and hn_mesh_finish_mirror_f32, the tracked slots' hn_crop_resize_hands_tracked and
- * hn_track_state_bytes, and the smoothed step's hn_mesh_finish_smooth_f32 and hn_smooth_state_bytes). */
+ * hn_track_state_bytes, the smoothed step's hn_mesh_finish_smooth_f32 and hn_smooth_state_bytes, and the per-frame cameras'
+ * hn_mesh_render_cams_u8 and hn_mesh_render_cams_occluded_u8). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -809,6 +810,22 @@ int hn_mesh_render_occluded_u8(const float* mesh, const int32_t* faces, const in
                                int64_t depth_frame_stride, float margin, void* scratch, int64_t scratch_bytes,
                                uint8_t* out_image, float* out_depth /* or NULL */, uint8_t* out_silhouette,
                                int32_t* out_coverage /* or NULL */, void* stream);
+/* hn_mesh_render_u8 / hn_mesh_render_occluded_u8 with a camera per frame: the same arguments, rule and
+ * two launches, with cams = DEVICE fp32 [s / k][4], rows (fx, fy, cx, cy), in place of the host's paras.  Slot i * k + j (hand j
+ * of frame i) is projected with row i.  The table is read by the first launch, on the stream: a captured graph holds its
+ * address, not its values, so new values copied into it (on the same stream, or before the replay is enqueued) take effect at
+ * the next replay.  A table of equal rows gives the bytes of the one-camera entries.  The occluded form is an entry of its own
+ * beside the plain one, as hn_mesh_render_occluded_u8 is beside hn_mesh_render_u8.  Added under ABI 36: new functions only. */
+int hn_mesh_render_cams_u8(const float* mesh, const int32_t* faces, const int32_t* faces_host /* or NULL */,
+                           const int32_t* lifted /* or NULL */, int s, int v, int f, int k, const float* cams, const void* frame,
+                           int frame_format, int h, int w, void* scratch, int64_t scratch_bytes, uint8_t* out_image,
+                           float* out_depth /* or NULL */, void* stream);
+int hn_mesh_render_cams_occluded_u8(const float* mesh, const int32_t* faces, const int32_t* faces_host /* or NULL */,
+                                    const int32_t* lifted /* or NULL */, int s, int v, int f, int k, const float* cams,
+                                    const void* frame, int frame_format, int h, int w, const float* scene_depth,
+                                    int64_t depth_frame_stride, float margin, void* scratch, int64_t scratch_bytes,
+                                    uint8_t* out_image, float* out_depth /* or NULL */, uint8_t* out_silhouette,
+                                    int32_t* out_coverage /* or NULL */, void* stream);
 /* The live caller's two other images (ros_demo.py:310-326) for s = n * k hand slots: out_box [n][h][w][3] uint8 RGB = the frame
  * with the crop rectangle of every drawn slot of the frame in (0,255,0), thickness 1, inclusive corners (cv2.rectangle);
  * out_pose [s][176][176][3] uint8 RGB = frame[y1:y2, x1:x2] (clipped to the frame, exclusive ends) resized to 176 x 176 with
