@@ -26,8 +26,12 @@ more than 3 cm (a starting value, not tuned) behind the frame's depth map, and f
 the camera sees is printed (read().coverage), with the silhouette's pixel counts.
 With --cameras N the last frame goes N times through ONE captured K = 2 step built with N slightly different intrinsics
 (paras [N,4]: a rig of N cameras), and once more after set_cameras() swapped them, without a recapture.
+With --rig the last frame goes twice, as two cameras, through ONE captured K = 2 step built with extrinsics= (camera -> rig
+transforms): first with both cameras at one place -- every hand is seen twice and fused into one rig hand --, then, after
+set_extrinsics() moved camera 1 a metre aside without a recapture, as two hands a metre apart.  The association radius of
+8 cm is a starting value, not tuned on this model.
 usage (GPU box): python examples/live_demo.py [frames] [--overlay out.png] [--mano MANO_RIGHT.pkl] [--labels PREFIX] [--left]
-                 [--handed] [--track] [--smooth] [--occlude] [--cameras N]"""
+                 [--handed] [--track] [--smooth] [--occlude] [--cameras N] [--rig]"""
 import sys
 import time
 import types
@@ -66,8 +70,8 @@ def main():
             opt[flag] = argv[i + 1]
             del argv[i:i + 2]
     left, handed, track, smooth = "--left" in argv, "--handed" in argv, "--track" in argv, "--smooth" in argv
-    occlude = "--occlude" in argv
-    argv = [a for a in argv if a not in ("--left", "--handed", "--track", "--smooth", "--occlude")]
+    occlude, rig_frame = "--occlude" in argv, "--rig" in argv
+    argv = [a for a in argv if a not in ("--left", "--handed", "--track", "--smooth", "--occlude", "--rig")]
     frames = int(argv[0]) if argv else 20
     faces = _faces(opt.get("--mano")) if "--overlay" in opt else None
     args = types.SimpleNamespace(pretrained_fcos="-", pretrained_a2j="-")
@@ -181,6 +185,21 @@ def main():
                 r6 = o6.read()
                 print(f"10. cameras {label}: the same frame through {n} intrinsics in one captured step: wrist x (mm) per camera "
                       f"{[round(float(v), 1) for v in r6.xyz_mm[:, 0, 0, 0]]}, image u {[round(float(v), 1) for v in r6.image_uvd[:, 0, 0, 0]]}")
+        if rig_frame:                                                                     # two cameras, one entry per physical hand
+            same = np.tile(np.hstack([np.eye(3), np.zeros((3, 1))]), (2, 1, 1))           # camera -> rig [R | t], [N,3,4]
+            aside = same.copy()
+            aside[1, 0, 3] = 1.0
+            two_cams = net.live_hands(model, PARAS, max_hands=2, clamp=True, perm_reverse=rev, extrinsics=same, rig_radius=0.08)
+            run, r_img, r_dep, o7 = two_cams.graphed(s_img.expand(2, -1, -1, -1).contiguous(), s_dep.expand(2, -1, -1, -1).contiguous())
+            for label, values in (("both cameras at one place", None), ("camera 1 a metre aside (set_extrinsics)", aside)):
+                if values is not None:
+                    two_cams.set_extrinsics(values)                                       # (no recapture: the kernels read the table)
+                run()
+                torch.cuda.current_stream().synchronize()
+                r7 = o7.read()
+                wrists = [[round(float(v), 3) for v in r7.fused_xyz[g, 0]] for g in range(r7.rig_count)]
+                print(f"11. rig, {label}: {int(r7.lifted.sum())} lifted slots -> {r7.rig_count} rig hands, views "
+                      f"{r7.rig_views[:r7.rig_count].tolist()}, rig hand per slot {r7.rig_hand.tolist()}, fused wrist (m, rig frame) {wrists}")
 
 
 if __name__ == "__main__":

@@ -132,7 +132,7 @@ class HandNet(EngineOwner):
     def live_hands(self, lifter, paras, max_hands: int = 2, clamp: bool = True, perm_reverse=None, faces=None,
                    labels: bool = False, left: bool = False, handed: bool = False, left_side: int = 0, track: bool = False,
                    track_iou: float = 0.3, track_hold: int = 5, occlude: bool = False, occlude_margin: float = 0.03,
-                   smooth: bool = False, smooth_min_cutoff: float = 1.0, smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0,
+                   extrinsics=None, rig_radius: float = 0.08, smooth: bool = False, smooth_min_cutoff: float = 1.0, smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0,
                    smooth_rate: float = 30.0):
         """live() for up to max_hands (1..16) hands per frame (hn_amd.live.LiveHandsEngine): forward_hands' slots, the
         caller's clamp + convert_joints, the lifter's input with the caller's skip rule per slot (a hand whose 2D box
@@ -159,7 +159,13 @@ class HandNet(EngineOwner):
         engine.smooth_reset() restarts the filters.  max_hands=1, track=True, smooth=True is the smoothed sticky top-1.
         occlude (needs faces): as live()'s, for all K slots against the frame's one depth map: read() ends with silhouette
         [N,H,W] uint8 (0 no mesh, k + 1 slot k shown, 0x80 | (k + 1) hidden) and coverage [N,K,2] int32 (per slot: pixels where
-        its mesh is the nearest, of those shown).  occlude_margin = 0.03 m is a starting value, NOT tuned on this model."""
+        its mesh is the nearest, of those shown).  occlude_margin = 0.03 m is a starting value, NOT tuned on this model.
+        extrinsics (needs perm_reverse): a rig of N cameras -- one camera -> rig transform [R | t] per
+        frame, [N,3,4] or [N,4,4] (t in metres), N * max_hands <= 256.  read() then ends with the hands in the rig frame
+        (rig_xyz [N,K,21,3], rig_mesh [N,K,V,3], metres), one entry per physical hand (rig_hand [N,K], rig_count, rig_views,
+        rig_seed: lifted slots of different frames within rig_radius metres of each other, with handed=True of one side) and
+        their score-weighted fusion (fused_xyz, fused_mesh [N*K,...]); engine.set_extrinsics(new) changes the values without
+        recapturing anything.  rig_radius = 0.08 m is a starting value, NOT tuned on this model.  left=True: ValueError."""
         from hn_amd.live import LiveHandsEngine
         k = ops.check_max_hands(max_hands)
         if left and handed:
@@ -168,7 +174,8 @@ class HandNet(EngineOwner):
         self._convert_cfg = (paras, bool(clamp))
         return LiveHandsEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, k, clamp,
                                perm_reverse, faces, labels, left, handed, left_side, track, track_iou, track_hold,
-                               occlude=occlude, occlude_margin=occlude_margin, smooth=smooth, smooth_min_cutoff=smooth_min_cutoff,
+                               occlude=occlude, occlude_margin=occlude_margin, extrinsics=extrinsics, rig_radius=rig_radius,
+                               smooth=smooth, smooth_min_cutoff=smooth_min_cutoff,
                                smooth_beta=smooth_beta, smooth_d_cutoff=smooth_d_cutoff, smooth_rate=smooth_rate)
 
     # forward() switches ITSELF to hipGraph replay once the same input shapes have come in a few times in a row -- the live

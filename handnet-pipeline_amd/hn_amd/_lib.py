@@ -239,6 +239,8 @@ SIGNATURES = {
                                          VP, VP]),
     "hn_mesh_render_cams_occluded_u8": (C.c_int, [VP, VP, VP, VP] + [C.c_int] * 4 + [VP, VP, C.c_int, C.c_int, C.c_int, VP,
                                                   C.c_int64, C.c_float, VP, C.c_int64, VP, VP, VP, VP, VP]),
+    # the rig frame of a multi-camera step: transform, association across cameras, fusion (a new function under ABI 36)
+    "hn_rig_fuse_f32": (C.c_int, [VP] * 7 + [C.c_int] * 4 + [C.c_float] + [VP] * 9),
 }
 
 _lock = threading.Lock()

@@ -66,6 +66,15 @@ def _occluded_views(kind):
     return collections.namedtuple(kind.__name__.replace("Views", "OccludedViews"), kind._fields + ("silhouette", "coverage"))
 
 
+RIG_FIELDS = ops.RIG_FIELDS
+
+
+@functools.lru_cache(maxsize=None)
+def _rig_views(kind):
+    """... and of a rig step: the fields of its step without the option, then the eight parts of the rig frame"""
+    return collections.namedtuple(kind.__name__.replace("Views", "RigViews"), kind._fields + RIG_FIELDS)
+
+
 @dataclass(frozen=True)
 class LiveLayout:
     """Byte layout of a live step's one copy buffer, in this order: the records (one-hand step: a wide record per frame + the
@@ -74,7 +83,9 @@ class LiveLayout:
     `track_age` int32 [slots] each (tracked steps), `lifted` int32 [slots] (K-hand steps), the mesh fp32 [slots,V,3], the overlay uint8 [frames,h,w,3], box_label uint8 [frames,h,w,3] and
     pose_label uint8 [slots,176,176,3] (each label image starts on a dword: the kernels store three dwords per four pixels),
     and -- smoothed steps -- `smooth_xyz` fp32 [slots,21,3] and `smooth_mesh` fp32 [slots,V,3], each on a dword, and -- occluded
-    steps -- `silhouette` uint8 [frames,h,w] and `coverage` int32 [slots,2], each on a dword, as the last parts.
+    steps -- `silhouette` uint8 [frames,h,w] and `coverage` int32 [slots,2], each on a dword, and -- rig steps --
+    `rig_xyz` fp32 [slots,21,3], `rig_mesh` fp32 [slots,V,3], `rig_hand` int32 [slots], `rig_count` int32 [1], `rig_views` and
+    `rig_seed` int32 [slots], `fused_xyz` fp32 [slots,21,3] and `fused_mesh` fp32 [slots,V,3], each on a dword, as the last parts.
     slots = frames for the one-hand step (hands None), frames * hands for the K-hand step.  A part the step does not have takes
     no bytes and its offset is None; every part in front of it stays where a step without the option has it."""
     frames: int
@@ -87,6 +98,7 @@ class LiveLayout:
     tracked: bool = False
     smoothed: bool = False
     occluded: bool = False       # (keyword: the overlay hidden behind nearer scene depth; needs overlay)
+    rig: bool = False            # (keyword: the slots in the rig frame, associated across frames and fused; a K-hand step's)
     record_rows: int = field(init=False)
     record_bytes: int = field(init=False)
     side_at: int = field(init=False)
@@ -101,6 +113,14 @@ class LiveLayout:
     smooth_mesh_at: int = field(init=False)
     silhouette_at: int = field(init=False)
     coverage_at: int = field(init=False)
+    rig_xyz_at: int = field(init=False)
+    rig_mesh_at: int = field(init=False)
+    rig_hand_at: int = field(init=False)
+    rig_count_at: int = field(init=False)
+    rig_views_at: int = field(init=False)
+    rig_seed_at: int = field(init=False)
+    fused_xyz_at: int = field(init=False)
+    fused_mesh_at: int = field(init=False)
     nbytes: int = field(init=False)
 
     def __post_init__(self):
@@ -110,6 +130,10 @@ class LiveLayout:
             raise ValueError("a smoothed step is a tracked step: the filters follow the track ids")
         if self.occluded and not self.overlay:
             raise ValueError("an occluded step is a step with an overlay: the silhouette is the overlay's by-product")
+        if self.rig:
+            if self.hands is None:
+                raise ValueError("rig is a K-hand step's option: the rig frame puts the slots of several frames together")
+            ops.check_rig_slots(self.frames, self.hands)
         s, rb = self.slots, record_bytes(3)
         rows = self.frames + 1 if self.hands is None else hands_record_rows(s, rb)
         image = None if self.hw is None else (self.frames, *self.hw, 3)
@@ -127,7 +151,15 @@ class LiveLayout:
                                                    ("smooth_xyz", self.smoothed, torch.float32, (s, SMOOTH_JOINTS, 3), 4),
                                                    ("smooth_mesh", self.smoothed, torch.float32, (s, self.vertices, 3), 4),
                                                    ("silhouette", self.occluded, torch.uint8, image and image[:3], 4),
-                                                   ("coverage", self.occluded, torch.int32, (s, 2), 4)):
+                                                   ("coverage", self.occluded, torch.int32, (s, 2), 4),
+                                                   ("rig_xyz", self.rig, torch.float32, (s, SMOOTH_JOINTS, 3), 4),
+                                                   ("rig_mesh", self.rig, torch.float32, (s, self.vertices, 3), 4),
+                                                   ("rig_hand", self.rig, torch.int32, (s,), 4),
+                                                   ("rig_count", self.rig, torch.int32, (1,), 4),
+                                                   ("rig_views", self.rig, torch.int32, (s,), 4),
+                                                   ("rig_seed", self.rig, torch.int32, (s,), 4),
+                                                   ("fused_xyz", self.rig, torch.float32, (s, SMOOTH_JOINTS, 3), 4),
+                                                   ("fused_mesh", self.rig, torch.float32, (s, self.vertices, 3), 4)):
             start = None
             if present:
                 start = (end + align - 1) // align * align
@@ -150,21 +182,23 @@ class LiveLayout:
         kind = LiveSmoothedViews if self.smoothed else LiveTrackedViews if self.tracked else LiveViews
         if self.occluded:
             kind = _occluded_views(kind)
+        if self.rig:
+            kind = _rig_views(kind)
         return kind(*(cut.get(name) for name in kind._fields))
 
 
 @functools.lru_cache(maxsize=None)
 def _read_type(step: str, base: tuple, overlay: bool, labels: bool, side: bool, tracked: bool = False, smoothed: bool = False,
-               occluded: bool = False):
+               occluded: bool = False, rig: bool = False):
     """The namedtuple a step's read() returns: the base fields, then overlay, box_label + pose_label, side, track_age +
-    track_id, smooth_xyz + smooth_mesh and silhouette + coverage, each only when the step has it; an absent image (overlay /
-    box_label / pose_label) reads as a None class attribute.  (One class per combination: call it with positional arguments
-    only and without trailing defaults, the cache keys on them.)"""
+    track_id, smooth_xyz + smooth_mesh, silhouette + coverage and the rig frame's eight, each only when the step has it; an
+    absent image (overlay / box_label / pose_label) reads as a None class attribute.  (One class per combination: call it with
+    positional arguments only and without trailing defaults, the cache keys on them.)"""
     has = dict(overlay=overlay, box_label=labels, pose_label=labels, side=side, track_age=tracked, track_id=tracked,
-               smooth_xyz=smoothed, smooth_mesh=smoothed, silhouette=occluded, coverage=occluded)
+               smooth_xyz=smoothed, smooth_mesh=smoothed, silhouette=occluded, coverage=occluded, **{f: rig for f in RIG_FIELDS})
     fields = base + tuple(f for f, on in has.items() if on)
     name = (step + "Overlay" * overlay + "Labels" * labels + "Sided" * side + "Tracked" * tracked + "Smoothed" * smoothed
-            + "Occluded" * occluded + "Read")
+            + "Occluded" * occluded + "Rig" * rig + "Read")
     absent = {f: None for f, on in has.items() if not on and f in ("overlay", "box_label", "pose_label")}
     doc = f"{step}Output.read(): {' '.join(base)}" + "".join(f" + {f}" for f in fields[len(base):]) + "."
     return type(name, (collections.namedtuple(name, fields),), dict(absent, __slots__=(), __doc__=doc))
@@ -188,6 +222,10 @@ def _read(step, base, values, layout, v, per_slot=lambda t: t):
     if layout.occluded:
         values += (v.silhouette.clone(), per_slot(v.coverage).clone())
         key = key + (False,) * (5 - len(key)) + (True,)
+    if layout.rig:      # (per slot [N,K,...]; per rig hand [N*K,...]; the count as a Python int)
+        values += (per_slot(v.rig_xyz).clone(), per_slot(v.rig_mesh).clone(), per_slot(v.rig_hand).clone(), int(v.rig_count[0]),
+                   v.rig_views.clone(), v.rig_seed.clone(), v.fused_xyz.clone(), v.fused_mesh.clone())
+        key = key + (False,) * (6 - len(key)) + (True,)
     return _read_type(step, base, *key)(*values)
 
 
@@ -234,6 +272,8 @@ class _LiveStep:
     handed = False
     track = None                 # the tracked K-hand step: (track_iou, track_hold)
     smooth = None                # the smoothed K-hand step: (min_cutoff, beta, d_cutoff)
+    rig = None                   # the rig K-hand step: its radius (metres); `extrinsics` is the device table [N,12]
+    extrinsics = None
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None,
                  labels: bool = False, left: bool = False, occlude: bool = False, occlude_margin: float = ops.OCCLUDE_MARGIN):
@@ -319,6 +359,9 @@ class _LiveStep:
     def _check_frames(self, n):
         if self.cams is not None and n != self.cams.shape[0]:
             raise ValueError(f"a step over {n} frames, but the engine was built with {self.cams.shape[0]} cameras, one per frame")
+        if self.extrinsics is not None and n != self.extrinsics.shape[0]:
+            raise ValueError(f"a step over {n} frames, but the engine was built with {self.extrinsics.shape[0]} extrinsics, one "
+                             "per frame")
 
     @ops.device_guarded
     def set_cameras(self, paras):
@@ -331,11 +374,22 @@ class _LiveStep:
         self._cameras.update(paras)      # (the raster's table, a row per frame, and the conversion's, a row per slot)
         return self
 
+    @ops.device_guarded
+    def set_extrinsics(self, extrinsics):
+        """New camera -> rig extrinsics for an engine built with extrinsics= ([N,3,4] or [N,4,4]; same N, checked like the
+        constructor's): the values are copied into the engine's device table on the current stream, and eager steps and every
+        already captured step use them from the next step on -- the kernels read the table, so nothing is recaptured.  An engine
+        built without extrinsics raises ValueError."""
+        if self.extrinsics is None:
+            raise ValueError("set_extrinsics needs an engine built with extrinsics=: one [R | t] per frame")
+        self.extrinsics.copy_(torch.from_numpy(ops.rig_extrinsics(extrinsics, self.extrinsics.shape[0])))
+        return self
+
     def _layout(self, n, hw=None) -> LiveLayout:
         """The buffer of a step over n frames (hw: of a step that draws, the frames' size)."""
         return LiveLayout(n, self.hands, self.vertices, hw, hw is not None and self.faces is not None,
                           hw is not None and self.labels, self.handed, self.track is not None, self.smooth is not None,
-                          occluded=self.occlude is not None)
+                          occluded=self.occlude is not None, rig=self.rig is not None)
 
     def _new_buffers(self, n, hw=None):
         """A fresh (layout, device buffer, pinned host buffer) of a step over n frames."""
@@ -379,15 +433,19 @@ class _LiveStep:
         if layout.labels:
             box_label, pose_label = ops.draw_labels(out.keypoints, out.crop_box, frames, drawn=drawn, k=k, clamp=self.clamp,
                                                     out_box=at.box_label, out_pose=at.pose_label)
-        host.copy_(dev, non_blocking=True)
         more = {} if coverage is None else dict(silhouette=silhouette, coverage=coverage)
+        if layout.rig:      # (a smoothed step moves and fuses what it smoothed, the signals its overlay draws)
+            more["rig"] = ops.rig_fuse(at.smooth_xyz if layout.smoothed else out.xyz_mm, at.smooth_mesh if layout.smoothed else mesh,
+                                       out.has_hand, at.lifted, out.score, self.extrinsics, k, self.rig,
+                                       side=out.side if self.handed else None, out=at)
+        host.copy_(dev, non_blocking=True)
         return self._output(out, at, layout, host, dict(pose2d=p2d, mesh=mesh, pose3d=pose3d, raw_mesh=raw, overlay=overlay,
                                                         box_label=box_label, pose_label=pose_label, **more))
 
     def _key_options(self) -> tuple:
         """What a capture's key carries behind the shapes (the smoothed step: its filter's parameters; the occluded step: its
         margin -- kernel arguments)."""
-        return () if self.occlude is None else ("occluded", self.occlude)
+        return (() if self.occlude is None else ("occluded", self.occlude)) + (() if self.rig is None else ("rig", self.rig))
 
     def _smooth_untouched(self, n):
         return contextlib.nullcontext()
@@ -506,6 +564,14 @@ class LiveHandsOutput:
     track_age: torch.Tensor = None   # tracked steps: [N,K] int32 on the device, the steps on which the slot's track was seen again
     silhouette: torch.Tensor = None  # occluded steps: [N,H,W] uint8 on the device (0 no mesh, k + 1 slot k shown, 0x80 | (k + 1) hidden)
     coverage: torch.Tensor = None    # occluded steps: [N,K,2] int32 on the device (pixels where the slot's mesh is nearest, of those shown)
+    rig_xyz: torch.Tensor = None     # rig steps, on the device: [N,K,21,3] the joints in the rig frame, metres
+    rig_mesh: torch.Tensor = None    # [N,K,V,3] the mesh in the rig frame, metres (zero rows: not lifted)
+    rig_hand: torch.Tensor = None    # [N,K] int32 the slot's rig hand (-1: none)
+    rig_count: torch.Tensor = None   # [1] int32 the number of rig hands
+    rig_views: torch.Tensor = None   # [N*K] int32 members per rig hand (0 beyond the count)
+    rig_seed: torch.Tensor = None    # [N*K] int32 the rig hand's seed slot i * K + k (-1 beyond the count): the way to its track_id
+    fused_xyz: torch.Tensor = None   # [N*K,21,3] per rig hand: its members' joints, weighted by their scores
+    fused_mesh: torch.Tensor = None  # [N*K,V,3] per rig hand: its members' meshes, weighted by their scores
     smooth_xyz: torch.Tensor = None  # smoothed steps: [N,K,21,3] on the device, xyz_mm filtered over time (zeros: has_hand != 1)
     smooth_mesh: torch.Tensor = None  # smoothed steps: [N,K,V,3] on the device, `mesh` filtered over time (zeros: not lifted)
 
@@ -515,7 +581,9 @@ class LiveHandsOutput:
         step with labels: + box_label [N,H,W,3], pose_label [N,K,176,176,3] -- LiveHandsLabelsRead, LiveHandsOverlayLabelsRead;
         a handed step: the same with `side` [N,K] int32 behind them; a tracked step: track_age and then track_id [N,K] int32
         as the last fields; a smoothed step: behind those, smooth_xyz [N,K,21,3] and smooth_mesh [N,K,V,3]; an occluded step:
-        behind everything else, silhouette [N,H,W] uint8 and coverage [N,K,2] int32)."""
+        behind everything else, silhouette [N,H,W] uint8 and coverage [N,K,2] int32; a rig step: behind those, rig_xyz
+        [N,K,21,3], rig_mesh [N,K,V,3], rig_hand [N,K] int32, rig_count (a Python int), rig_views and rig_seed [N*K] int32,
+        fused_xyz [N*K,21,3] and fused_mesh [N*K,V,3])."""
         v, s = self.layout.views(self.host), self.layout.slots
         per = lambda t: t.reshape((self.layout.frames, self.layout.hands) + tuple(t.shape[1:]))
         kp, has, box, words, (img, xyz) = read_host_record(v.records, s, extras=True)
@@ -536,8 +604,9 @@ class LiveHandsEngine(_LiveStep):
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, max_hands: int = 2, clamp: bool = True,
                  perm_reverse=None, faces=None, labels: bool = False, left: bool = False, handed: bool = False,
                  left_side: int = 0, track: bool = False, track_iou: float = 0.3, track_hold: int = 5, occlude: bool = False,
-                 occlude_margin: float = ops.OCCLUDE_MARGIN, smooth: bool = False, smooth_min_cutoff: float = 1.0,
-                 smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0, smooth_rate: float = 30.0):
+                 occlude_margin: float = ops.OCCLUDE_MARGIN, extrinsics=None, rig_radius: float = ops.RIG_RADIUS,
+                 smooth: bool = False, smooth_min_cutoff: float = 1.0, smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0,
+                 smooth_rate: float = 30.0):
         """paras: as LiveHandEngine's -- with a camera per frame [N,4], all K slots of frame i use row i.
         faces: mesh_model.face ([F,3]; needs perm_reverse) -- given, the step ends with the overlay: every lifted mesh of a
         frame drawn over it with one depth buffer per frame (LiveHandsOutput.overlay, read().overlay), in the same copy.
@@ -572,7 +641,17 @@ class LiveHandsEngine(_LiveStep):
         hidden; coverage [N,K,2] int32: per slot, the pixels where its mesh is the nearest mesh and those of them that are
         shown ((0, 0): not lifted).  A `left` step tests against the mirrored depth map, a `handed` step against the frame's
         own, a smoothed step tests the smoothed mesh it draws.  occlude_margin (metres, default 0.03) is a starting value, NOT
-        tuned on this model."""
+        tuned on this model.
+        extrinsics (needs paras and perm_reverse): the rig of a multi-camera step -- one camera -> rig transform
+        [R | t] per frame, [N,3,4] or [N,4,4] (p_rig = R p_cam + t, t in metres; checked on the host: finite, last row
+        (0, 0, 0, 1), R orthonormal within 1e-4 with det > 0), N * max_hands <= 256.  The step then takes exactly N frames and
+        ends with three more launches (ops.rig_fuse) whose results ride in the same copy: every slot's joints and mesh in the
+        rig frame (metres, no OpenGL flip: rig_xyz, rig_mesh), the lifted slots of DIFFERENT frames whose centres lie within
+        rig_radius metres of each other put into one rig hand (rig_hand, rig_count, rig_views, rig_seed; greedy, at most one
+        slot per frame, with handed=True only slots of one side), and per rig hand the members' score-weighted mean (fused_xyz,
+        fused_mesh) -- LiveHandsOutput and read() likewise, behind every other field.  A smoothed step moves and fuses
+        smooth_xyz / smooth_mesh.  rig_radius = 0.08 m is a starting value, NOT tuned on this model.  left=True: ValueError (a
+        mirrored frame is not the camera's frame).  set_extrinsics(new) rewrites the device table under captured steps."""
         self.hands = self.max_hands = ops.check_max_hands(max_hands)
         if left and handed:
             raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
@@ -587,7 +666,24 @@ class LiveHandsEngine(_LiveStep):
                 raise ValueError("smooth=True needs perm_reverse=: the filter runs in the launch that finishes the mesh")
             mc, beta, dc, rate = ops.check_smooth_options(smooth_min_cutoff, smooth_beta, smooth_d_cutoff, smooth_rate)
             self.smooth, self._dt, self._smooth_states = (mc, beta, dc), 1.0 / rate, {}
+        table = None
+        if extrinsics is not None:
+            if paras is None or perm_reverse is None:
+                raise ValueError("extrinsics= needs paras= and perm_reverse=: the rig frame moves xyz_mm and the final mesh "
+                                 "(out['mesh']), and a step without them has neither")
+            if left:
+                raise ValueError("extrinsics= with left=True: a mirrored frame is not the camera's frame (handed=True mirrors per "
+                                 "slot and keeps the frame's own coordinates)")
+            table = ops.rig_extrinsics(extrinsics)
+            ops.check_rig_slots(table.shape[0], self.hands)
+            self.rig = ops.check_rig_radius(rig_radius)
         super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left, occlude, occlude_margin)
+        if table is not None:
+            if self.cams is not None and self.cams.shape[0] != table.shape[0]:
+                raise ValueError(f"{table.shape[0]} extrinsics for a step built with {self.cams.shape[0]} cameras: one [R | t] per "
+                                 "frame")
+            with ops.on_device(self.device), torch.inference_mode(False):
+                self.extrinsics = torch.from_numpy(table).to(self.device)
 
     def _hand_step(self, images, depth, at, lift):
         # (the per-slot records, range words, scores and ranks go straight into the buffer, the handed step's sides behind them)
@@ -679,6 +775,7 @@ class LiveHandsEngine(_LiveStep):
         parts["mesh"] = parts["mesh"].view(n, k, self.vertices, 3)
         if "coverage" in parts:
             parts["coverage"] = parts["coverage"].view(n, k, 2)
+        parts.update(parts.pop("rig", ops.RigFused(*(None,) * 8))._asdict())
         return LiveHandsOutput(hands=out, lifted=at.lifted.view(n, k), host=host, n=n, k=k, side=out.side, mirror=out.mirror,
                                layout=layout, track_id=out.track_id, track_age=out.track_age,
                                smooth_xyz=None if self.smooth is None else at.smooth_xyz.view(n, k, SMOOTH_JOINTS, 3),

@@ -6,6 +6,7 @@ there is deliberately no CPU or eager fallback.
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
 import math
@@ -2058,6 +2059,109 @@ def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out
                                          depth_ptr, (4 if rgbd else 1) * h * w, margin, ptr(scratch), scratch.numel(),
                                          ptr(out), ptr(depth_out), ptr(silhouette_out), ptr(coverage_out), _stream()), occluded)
     return out.view(n, h, w, 3), silhouette_out.view(n, h, w), coverage_out.view(s, 2)
+
+
+RIG_RADIUS = 0.08          # metres; a starting value, NOT tuned on this model
+RIG_MAX_SLOTS = 256        # frames * hands of a rig step: the association runs in one 256-thread workgroup
+RIG_ORTHO_TOL = 1e-4       # max |R^T R - I| of a caller's rotation (an fp32-rounded rotation sits near 1e-7)
+
+RIG_FIELDS = ("rig_xyz", "rig_mesh", "rig_hand", "rig_count", "rig_views", "rig_seed", "fused_xyz", "fused_mesh")
+RigFused = collections.namedtuple("RigFused", RIG_FIELDS)
+
+
+def rig_extrinsics(ext, frames=None):
+    """The caller's camera -> rig extrinsics, checked ON THE HOST and rounded to fp32 once (as camera_paras rounds the
+    intrinsics): one [R | t] per frame, [N,3,4] or [N,4,4] with the last row (0, 0, 0, 1) -- a nested sequence, an ndarray or a
+    tensor; p_rig = R p_cam + t, t in metres -- -> a float32 ndarray [N,12], the rows of [R | t], what the device table holds.
+    ValueError: another shape (or N != frames), a value that is not finite as fp32, another last row, a rotation with
+    max |R^T R - I| > 1e-4 or det R <= 0 (a scaled or reflected frame)."""
+    if torch.is_tensor(ext):
+        ext = ext.detach().cpu().numpy()
+    try:
+        e = np.asarray(ext, dtype=np.float64)
+    except (TypeError, ValueError) as err:
+        raise ValueError(f"extrinsics: one [R | t] per frame, [N,3,4] or [N,4,4] ({err})") from None
+    if e.ndim != 3 or e.shape[0] == 0 or tuple(e.shape[1:]) not in ((3, 4), (4, 4)) or (frames is not None and e.shape[0] != frames):
+        raise ValueError(f"extrinsics: one [R | t] per frame, [N,3,4] or [N,4,4]"
+                         + (f" with N = {frames}" if frames is not None else "") + f", got shape {tuple(e.shape)}")
+    with np.errstate(over="ignore"):
+        rows = e[:, :3, :].astype(np.float32)
+    if not (np.isfinite(e).all() and np.isfinite(rows).all()):
+        raise ValueError("extrinsics: every value must be finite as fp32")
+    if e.shape[1] == 4 and not np.array_equal(e[:, 3, :], np.tile([0.0, 0.0, 0.0, 1.0], (e.shape[0], 1))):
+        raise ValueError("extrinsics: the last row of a [4,4] transform must be (0, 0, 0, 1)")
+    r = rows[:, :, :3].astype(np.float64)
+    off = np.abs(np.swapaxes(r, 1, 2) @ r - np.eye(3)).max(axis=(1, 2))
+    det = np.linalg.det(r)
+    for i in range(e.shape[0]):
+        if not off[i] <= RIG_ORTHO_TOL or not det[i] > 0:
+            raise ValueError(f"extrinsics: row {i} is no rotation (max |R^T R - I| = {off[i]:.3g}, det R = {det[i]:.3g}): a rigid "
+                             "camera -> rig transform has an orthonormal R with det +1")
+    return np.ascontiguousarray(rows.reshape(e.shape[0], 12))
+
+
+def check_rig_radius(radius) -> float:
+    """rig_radius as a float that is finite and > 0, also as the fp32 kernel argument it becomes, else ValueError."""
+    try:
+        r = float(radius)
+    except (TypeError, ValueError):
+        r = math.nan
+    with np.errstate(over="ignore"):
+        g = float(np.float32(r))
+    if not (math.isfinite(r) and math.isfinite(g) and g > 0):
+        raise ValueError(f"rig_radius: a finite number of metres > 0 as fp32 (got {radius!r})")
+    return r
+
+
+def check_rig_slots(frames, hands) -> int:
+    """frames * hands of a rig step, at most 256 (the association's one workgroup), else ValueError."""
+    slots = int(frames) * int(hands)
+    if int(frames) < 1 or int(hands) < 1 or slots > RIG_MAX_SLOTS:
+        raise ValueError(f"a rig step holds at most {RIG_MAX_SLOTS} slots: {frames} frames x {hands} hands = {slots}")
+    return slots
+
+
+def rig_fuse(xyz_mm, mesh, has_hand, lifted, score, extrinsics_table, k, radius=RIG_RADIUS, side=None, out=None) -> RigFused:
+    """The hands of N cameras x k slots in ONE frame, one entry per physical hand (hn_rig_fuse_f32: three launches; DESIGN.md
+    section 9i, tests/rig_ref.py is the rule and the outputs equal it bit for bit).  xyz_mm fp32 [S,J,3] or [N,k,J,3] (camera
+    frame, millimetres), mesh fp32 [S,V,3] or [N,k,V,3] (the final mesh, out['mesh']), has_hand / lifted int32 [S], score fp32
+    [S], S = N * k <= 256; extrinsics_table fp32 [N,12] on the same device (rig_extrinsics(...) uploaded); side int32 [S]: only
+    slots of one side are put together (None: no gate).  Returns RigFused: rig_xyz [N,k,J,3], rig_mesh [N,k,V,3], rig_hand
+    [N,k] int32, rig_count [1] int32, rig_views / rig_seed [S] int32, fused_xyz [S,J,3], fused_mesh [S,V,3] -- allocated, or
+    `out`'s attributes of these names (the live step's buffer views), every one fully written."""
+    _req(xyz_mm, name="xyz_mm"); _req(mesh, name="mesh"); _req(extrinsics_table, name="extrinsics_table")
+    if xyz_mm.dim() == 4:
+        xyz_mm = xyz_mm.view(-1, xyz_mm.shape[2], 3)
+    if mesh.dim() == 4:
+        mesh = mesh.view(-1, mesh.shape[2], 3)
+    if xyz_mm.dim() != 3 or mesh.dim() != 3 or xyz_mm.shape[2] != 3 or mesh.shape[2] != 3 or xyz_mm.shape[0] != mesh.shape[0]:
+        raise ValueError(f"xyz_mm [S,J,3] and mesh [S,V,3] of the same S slots, got {tuple(xyz_mm.shape)} and {tuple(mesh.shape)}")
+    s, joints, _ = xyz_mm.shape
+    v, k = mesh.shape[1], int(k)
+    if k < 1 or s % k or s == 0 or joints == 0 or v == 0:
+        raise ValueError(f"{s} slots with k = {k} slots per frame, {joints} joints, {v} vertices")
+    n = s // k
+    check_rig_slots(n, k)
+    if extrinsics_table.dim() != 2 or tuple(extrinsics_table.shape) != (n, 12):
+        raise ValueError(f"extrinsics_table: fp32 [{n},12], a row per frame, got {tuple(extrinsics_table.shape)}")
+    radius = check_rig_radius(radius)
+    for name, t, dtype in (("has_hand", has_hand, torch.int32), ("lifted", lifted, torch.int32), ("score", score, torch.float32)) + (
+            (("side", side, torch.int32),) if side is not None else ()):
+        if _req(t, dtype, name).numel() != s:
+            raise ValueError(f"{name} must hold one value per slot ({s}), got {t.numel()}")
+    shapes = dict(rig_xyz=(n, k, joints, 3), rig_mesh=(n, k, v, 3), rig_hand=(n, k), rig_count=(1,), rig_views=(s,), rig_seed=(s,),
+                  fused_xyz=(s, joints, 3), fused_mesh=(s, v, 3))
+    parts = []
+    for name in RIG_FIELDS:
+        dtype = torch.float32 if name.endswith(("xyz", "mesh")) else torch.int32
+        t = torch.empty(shapes[name], device=mesh.device, dtype=dtype) if out is None else getattr(out, name)
+        if _req(t, dtype, name).numel() != math.prod(shapes[name]):
+            raise ValueError(f"{name}: expected {dtype} {list(shapes[name])}, got {tuple(t.shape)}")
+        parts.append(t.view(shapes[name]))
+    check(_lib.load().hn_rig_fuse_f32(ptr(xyz_mm), ptr(mesh), ptr(has_hand), ptr(lifted), ptr(score), ptr(side),
+                                      ptr(extrinsics_table), n, k, joints, v, radius, *(ptr(t) for t in parts), _stream()),
+          "hn_rig_fuse_f32")
+    return RigFused(*parts)
 
 
 LABEL_CROP = 176      # side of a pose_label image

@@ -36,8 +36,8 @@ extern "C" {
  * keep it: hn_lifter_input_gated_f32 and hn_mesh_render_u8 came under 36, and so did the mirror / handedness entries
  * hn_ingest_u8bgr_u16mm_flip, hn_flip_w_f32, hn_crop_resize_hands_sided, hn_a2j_aggregate_convert_mirror_f32,
  * hn_lifter_input_gated_mirror_f32 and hn_mesh_finish_mirror_f32, the tracked slots' hn_crop_resize_hands_tracked and
- * hn_track_state_bytes, the smoothed step's hn_mesh_finish_smooth_f32 and hn_smooth_state_bytes, and the per-frame cameras'
- * hn_mesh_render_cams_u8 and hn_mesh_render_cams_occluded_u8). */
+ * hn_track_state_bytes, the smoothed step's hn_mesh_finish_smooth_f32 and hn_smooth_state_bytes, the per-frame cameras'
+ * hn_mesh_render_cams_u8 and hn_mesh_render_cams_occluded_u8, and the rig frame's hn_rig_fuse_f32). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -840,6 +840,22 @@ int hn_mesh_render_cams_occluded_u8(const float* mesh, const int32_t* faces, con
 int hn_draw_labels_u8(const float* keypoints, const int64_t* crop_box, const int32_t* drawn /* or NULL */, int s, int k,
                       const void* frame, int frame_format, int h, int w, int clamp, uint8_t* out_box /* or NULL */,
                       uint8_t* out_pose /* or NULL */, void* stream);
+/* The rig frame of a multi-camera K-hand step (tests/rig_ref.py is the rule in numpy float32, and the
+ * outputs equal it bit for bit: fp32, one rounding per operation, fixed summation order, no atomics).  n cameras x k slots,
+ * slot s = i * k + j uses row i of `extrinsics` (device, [n][12] = the rows of [R | t], camera -> rig, t in metres).
+ *   rig_xyz  [n*k][joints][3]  transform of xyz_mm / 1000 where has_hand == 1, zero rows elsewhere
+ *   rig_mesh [n*k][v][3]       transform of (x, -y, -z) of the final mesh (out['mesh']) where lifted == 1, zero rows elsewhere
+ *   rig_hand [n*k]             the slot's rig hand, -1 for none: lifted slots of DIFFERENT cameras whose centres (mean rig_xyz)
+ *                              lie within `radius` metres of the seed slot's centre -- greedy, frame-major, at most one slot
+ *                              per camera, and of the same `side` when side is given (NULL: no side gate)
+ *   rig_count [1], rig_views [n*k] (members per rig hand, 0 beyond the count), rig_seed [n*k] (seed slot, -1 beyond the count)
+ *   fused_xyz [n*k][joints][3], fused_mesh [n*k][v][3]   per rig hand: its one member copied, or its members' mean weighted by
+ *                              `score`, summed in slot order; zero rows beyond the count
+ * Every output is fully written.  Three launches on `stream`; n * k <= 256 and every other size are checked before the first. */
+int hn_rig_fuse_f32(const float* xyz_mm, const float* mesh, const int32_t* has_hand, const int32_t* lifted, const float* score,
+                    const int32_t* side /* or NULL */, const float* extrinsics, int n, int k, int joints, int v, float radius,
+                    float* rig_xyz, float* rig_mesh, int32_t* rig_hand, int32_t* rig_count, int32_t* rig_views,
+                    int32_t* rig_seed, float* fused_xyz, float* fused_mesh, void* stream);
 /* A Linear layer on 1..4 rows as a matrix-vector product on the vector ALU (PoseNet at the live caller's batch, posenet.py:24-41,
  * 78-88: 67 MB of filter bank per 17 M MACs): y[m][:] = act(W (pre(x[m])) + bias (+ residual[m])), pre = relu(x * scale + shift)
  * when scale / shift ([k_real] fp32: the pre-activation BatchNorm) are given.  x fp32 [batch][x_stride] (k_real columns used), w16 =
