@@ -30,8 +30,12 @@ With --rig the last frame goes twice, as two cameras, through ONE captured K = 2
 transforms): first with both cameras at one place -- every hand is seen twice and fused into one rig hand --, then, after
 set_extrinsics() moved camera 1 a metre aside without a recapture, as two hands a metre apart.  The association radius of
 8 cm is a starting value, not tuned on this model.
+With --cloud the last frame also goes through the K = 2 step with faces=, occlude=True and cloud=True: every slot's measured
+depth pixels (every second row and column under its silhouette, within 3 cm of the mesh; at most 4096 points; starting values,
+not tuned) as 3-D points in the camera frame -- per slot, the number of matching pixels, the rows written and the mean residual
+depth - mesh Z in millimetres (how far the mesh sits from the surface the camera sees).
 usage (GPU box): python examples/live_demo.py [frames] [--overlay out.png] [--mano MANO_RIGHT.pkl] [--labels PREFIX] [--left]
-                 [--handed] [--track] [--smooth] [--occlude] [--cameras N] [--rig]"""
+                 [--handed] [--track] [--smooth] [--occlude] [--cameras N] [--rig] [--cloud]"""
 import sys
 import time
 import types
@@ -70,8 +74,8 @@ def main():
             opt[flag] = argv[i + 1]
             del argv[i:i + 2]
     left, handed, track, smooth = "--left" in argv, "--handed" in argv, "--track" in argv, "--smooth" in argv
-    occlude, rig_frame = "--occlude" in argv, "--rig" in argv
-    argv = [a for a in argv if a not in ("--left", "--handed", "--track", "--smooth", "--occlude", "--rig")]
+    occlude, rig_frame, cloud = "--occlude" in argv, "--rig" in argv, "--cloud" in argv
+    argv = [a for a in argv if a not in ("--left", "--handed", "--track", "--smooth", "--occlude", "--rig", "--cloud")]
     frames = int(argv[0]) if argv else 20
     faces = _faces(opt.get("--mano")) if "--overlay" in opt else None
     args = types.SimpleNamespace(pretrained_fcos="-", pretrained_a2j="-")
@@ -200,6 +204,18 @@ def main():
                 wrists = [[round(float(v), 3) for v in r7.fused_xyz[g, 0]] for g in range(r7.rig_count)]
                 print(f"11. rig, {label}: {int(r7.lifted.sum())} lifted slots -> {r7.rig_count} rig hands, views "
                       f"{r7.rig_views[:r7.rig_count].tolist()}, rig hand per slot {r7.rig_hand.tolist()}, fused wrist (m, rig frame) {wrists}")
+        if cloud:                                                                         # each hand's measured depth points
+            cut = net.live_hands(model, PARAS, max_hands=2, clamp=True, perm_reverse=rev,
+                                 faces=faces if faces is not None else _faces(opt.get("--mano")), occlude=True, cloud=True,
+                                 cloud_points=4096, cloud_band=0.03, cloud_stride=2)
+            o8 = cut.forward_device(s_img, s_dep)
+            torch.cuda.current_stream().synchronize()
+            r8 = o8.read()
+            for k, ((total, written), resid) in enumerate(zip(r8.cloud_count[0].tolist(), r8.cloud_resid[0].tolist())):
+                mean = f"mean residual {resid / total / 1000.0:+.2f} mm" if total else "no point"
+                print(f"12. cloud, slot {k}: {total} matching pixels, {written} points written, {mean}")
+            print(f"    cloud {tuple(r8.cloud.shape)} fp32 metres (x right, y down, z forward), first point of slot 0 "
+                  f"{[round(float(v), 4) for v in r8.cloud[0, 0, 0]]}")
 
 
 if __name__ == "__main__":

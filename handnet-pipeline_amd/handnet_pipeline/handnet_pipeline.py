@@ -105,7 +105,8 @@ class HandNet(EngineOwner):
         return self
 
     def live(self, lifter, paras, clamp: bool = True, perm_reverse=None, faces=None, labels: bool = False, left: bool = False,
-             occlude: bool = False, occlude_margin: float = 0.03):
+             occlude: bool = False, occlude_margin: float = 0.03, cloud: bool = False, cloud_points: int = 4096,
+             cloud_band: float = 0.03, cloud_stride: int = 2):
         """The live caller's chain as ONE step (hn_amd.live.LiveHandEngine; ros_demo.py:270-290,329-337): this network, the
         caller's clamp + convert_joints (in the aggregation's epilogue), the lifter's input, Pose2Mesh, one device -> host copy.
         lifter: the drop-in `models.pose2mesh_net.get_model(...)` module (on the GPU) or a Pose2MeshEngine; paras = (fx, fy,
@@ -121,18 +122,26 @@ class HandNet(EngineOwner):
         occlude (needs faces): the overlay leaves out the mesh where it lies more than occlude_margin metres behind the step's
         own depth map (holes -- 0, NaN -- hide nothing), and read() ends with silhouette [N,H,W] uint8 (0 no mesh, 1 shown,
         0x81 hidden) and coverage [N,2] int32 (pixels under the mesh, of those shown).  0.03 m is a starting value, NOT tuned.
+        cloud (needs occlude): the step also cuts the hand's measured depth pixels out of its depth map --
+        every cloud_stride-th row and column under the silhouette whose depth lies within cloud_band metres of the mesh --
+        and read() ends with cloud [N,P,3] fp32 (P = cloud_points; metres in the camera frame of xyz_mm, x right, y down, z
+        forward, the pixel centre at +0.5; the first P matches in row-major order, zero rows behind them), cloud_count [N,2]
+        int32 (matches, rows written) and cloud_resid [N] int64 (the summed depth - mesh Z over all matches, micrometres).
+        cloud_points = 4096, cloud_band = 0.03 m and cloud_stride = 2 are starting values, NOT tuned on this model.
         The returned engine owns this network's step from then on (forward() of this module keeps working and
         carries the converted joints: set_convert)."""
         from hn_amd.live import LiveHandEngine
         paras = ops.camera_paras(paras)
         self._convert_cfg = (paras, bool(clamp))
         return LiveHandEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, clamp, perm_reverse,
-                              faces, labels, left, occlude, occlude_margin)
+                              faces, labels, left, occlude, occlude_margin, cloud, cloud_points, cloud_band, cloud_stride)
 
     def live_hands(self, lifter, paras, max_hands: int = 2, clamp: bool = True, perm_reverse=None, faces=None,
                    labels: bool = False, left: bool = False, handed: bool = False, left_side: int = 0, track: bool = False,
                    track_iou: float = 0.3, track_hold: int = 5, occlude: bool = False, occlude_margin: float = 0.03,
-                   extrinsics=None, rig_radius: float = 0.08, smooth: bool = False, smooth_min_cutoff: float = 1.0, smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0,
+                   extrinsics=None, rig_radius: float = 0.08, cloud: bool = False, cloud_points: int = 4096,
+                   cloud_band: float = 0.03, cloud_stride: int = 2, cloud_frame: str = "camera",
+                   smooth: bool = False, smooth_min_cutoff: float = 1.0, smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0,
                    smooth_rate: float = 30.0):
         """live() for up to max_hands (1..16) hands per frame (hn_amd.live.LiveHandsEngine): forward_hands' slots, the
         caller's clamp + convert_joints, the lifter's input with the caller's skip rule per slot (a hand whose 2D box
@@ -165,7 +174,10 @@ class HandNet(EngineOwner):
         (rig_xyz [N,K,21,3], rig_mesh [N,K,V,3], metres), one entry per physical hand (rig_hand [N,K], rig_count, rig_views,
         rig_seed: lifted slots of different frames within rig_radius metres of each other, with handed=True of one side) and
         their score-weighted fusion (fused_xyz, fused_mesh [N*K,...]); engine.set_extrinsics(new) changes the values without
-        recapturing anything.  rig_radius = 0.08 m is a starting value, NOT tuned on this model.  left=True: ValueError."""
+        recapturing anything.  rig_radius = 0.08 m is a starting value, NOT tuned on this model.  left=True: ValueError.
+        cloud (needs occlude): as live()'s, per slot: read() ends with cloud [N,K,P,3], cloud_count
+        [N,K,2] and cloud_resid [N,K]; cloud_frame="rig" (needs extrinsics) hands the points out in the rig frame.
+        cloud_points = 4096, cloud_band = 0.03 m and cloud_stride = 2 are starting values, NOT tuned on this model."""
         from hn_amd.live import LiveHandsEngine
         k = ops.check_max_hands(max_hands)
         if left and handed:
@@ -175,6 +187,8 @@ class HandNet(EngineOwner):
         return LiveHandsEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, k, clamp,
                                perm_reverse, faces, labels, left, handed, left_side, track, track_iou, track_hold,
                                occlude=occlude, occlude_margin=occlude_margin, extrinsics=extrinsics, rig_radius=rig_radius,
+                               cloud=cloud, cloud_points=cloud_points, cloud_band=cloud_band, cloud_stride=cloud_stride,
+                               cloud_frame=cloud_frame,
                                smooth=smooth, smooth_min_cutoff=smooth_min_cutoff,
                                smooth_beta=smooth_beta, smooth_d_cutoff=smooth_d_cutoff, smooth_rate=smooth_rate)
 

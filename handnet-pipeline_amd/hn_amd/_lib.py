@@ -241,6 +241,9 @@ SIGNATURES = {
                                                   C.c_int64, C.c_float, VP, C.c_int64, VP, VP, VP, VP, VP]),
     # the rig frame of a multi-camera step: transform, association across cameras, fusion (a new function under ABI 36)
     "hn_rig_fuse_f32": (C.c_int, [VP] * 7 + [C.c_int] * 4 + [C.c_float] + [VP] * 9),
+    # each hand's depth pixels as a point cloud: count + write (new functions under ABI 36)
+    "hn_hand_cloud_scratch_bytes": (C.c_int64, [C.c_int] * 3),
+    "hn_hand_cloud_f32": (C.c_int, [VP] * 3 + [C.c_int64] + [VP] * 3 + [C.c_int] * 6 + [C.c_float, VP, C.c_int64] + [VP] * 4),
 }
 
 _lock = threading.Lock()

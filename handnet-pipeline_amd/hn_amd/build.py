@@ -33,9 +33,10 @@ ARCH = "gfx950"
 # mesh_raster.hip: the overlay's projection is specified one rounding per operation (tests/raster_ref.py restates it in numpy).
 # label_draw.hip: the same for the resize's sample positions (tests/draw_ref.py).
 # rig_ops.hip: the same for the rig frame's transform, distances and weighted means (tests/rig_ref.py).
+# hand_cloud.hip: the same for the cloud's residual, back-projection and transform (tests/cloud_ref.py).
 EXTRA_FLAGS = {"fcos_post.hip": ["-ffp-contract=off", "-fno-slp-vectorize"], "graph_ops.hip": ["-fno-slp-vectorize"],
                "mesh_raster.hip": ["-ffp-contract=off"], "label_draw.hip": ["-ffp-contract=off"],
-               "rig_ops.hip": ["-ffp-contract=off"]}
+               "rig_ops.hip": ["-ffp-contract=off"], "hand_cloud.hip": ["-ffp-contract=off"]}
 
 # Kernels that request operands with `asm volatile` loads / LDS-DMA and retire them with hand-counted s_waitcnt: the
 # compiler cannot see that such a register is still in flight, so a SPILL of it stores garbage (profiles/NOTEBOOK.md, round

@@ -75,6 +75,15 @@ def _rig_views(kind):
     return collections.namedtuple(kind.__name__.replace("Views", "RigViews"), kind._fields + RIG_FIELDS)
 
 
+CLOUD_FIELDS = ("cloud", "cloud_count", "cloud_resid")
+
+
+@functools.lru_cache(maxsize=None)
+def _cloud_views(kind):
+    """... and of a cloud step: the fields of its step without the option, then the three parts of the hand clouds"""
+    return collections.namedtuple(kind.__name__.replace("Views", "CloudViews"), kind._fields + CLOUD_FIELDS)
+
+
 @dataclass(frozen=True)
 class LiveLayout:
     """Byte layout of a live step's one copy buffer, in this order: the records (one-hand step: a wide record per frame + the
@@ -85,7 +94,10 @@ class LiveLayout:
     and -- smoothed steps -- `smooth_xyz` fp32 [slots,21,3] and `smooth_mesh` fp32 [slots,V,3], each on a dword, and -- occluded
     steps -- `silhouette` uint8 [frames,h,w] and `coverage` int32 [slots,2], each on a dword, and -- rig steps --
     `rig_xyz` fp32 [slots,21,3], `rig_mesh` fp32 [slots,V,3], `rig_hand` int32 [slots], `rig_count` int32 [1], `rig_views` and
-    `rig_seed` int32 [slots], `fused_xyz` fp32 [slots,21,3] and `fused_mesh` fp32 [slots,V,3], each on a dword, as the last parts.
+    `rig_seed` int32 [slots], `fused_xyz` fp32 [slots,21,3] and `fused_mesh` fp32 [slots,V,3], each on a dword, and -- cloud steps
+    (cloud = P, the rows per slot) -- `cloud` fp32 [slots,P,3] and `cloud_count` int32 [slots,2], each on a dword,
+    and `cloud_resid` int64 [slots] on 8 bytes, as the last parts (their offsets cloud_at, cloud_count_at, cloud_resid_at are
+    properties, not fields).
     slots = frames for the one-hand step (hands None), frames * hands for the K-hand step.  A part the step does not have takes
     no bytes and its offset is None; every part in front of it stays where a step without the option has it."""
     frames: int
@@ -98,6 +110,7 @@ class LiveLayout:
     tracked: bool = False
     smoothed: bool = False
     occluded: bool = False       # (keyword: the overlay hidden behind nearer scene depth; needs overlay)
+    cloud: int = 0               # (keyword: rows per slot of the hand clouds, 0: none; needs occluded)
     rig: bool = False            # (keyword: the slots in the rig frame, associated across frames and fused; a K-hand step's)
     record_rows: int = field(init=False)
     record_bytes: int = field(init=False)
@@ -130,6 +143,10 @@ class LiveLayout:
             raise ValueError("a smoothed step is a tracked step: the filters follow the track ids")
         if self.occluded and not self.overlay:
             raise ValueError("an occluded step is a step with an overlay: the silhouette is the overlay's by-product")
+        if isinstance(self.cloud, bool) or not isinstance(self.cloud, (int, np.integer)) or self.cloud < 0:
+            raise ValueError(f"cloud: the rows per slot, an integer >= 0 (got {self.cloud!r})")
+        if self.cloud and not self.occluded:
+            raise ValueError("a cloud step is an occluded step: the clouds are cut out with the silhouette")
         if self.rig:
             if self.hands is None:
                 raise ValueError("rig is a K-hand step's option: the rig frame puts the slots of several frames together")
@@ -159,13 +176,16 @@ class LiveLayout:
                                                    ("rig_views", self.rig, torch.int32, (s,), 4),
                                                    ("rig_seed", self.rig, torch.int32, (s,), 4),
                                                    ("fused_xyz", self.rig, torch.float32, (s, SMOOTH_JOINTS, 3), 4),
-                                                   ("fused_mesh", self.rig, torch.float32, (s, self.vertices, 3), 4)):
+                                                   ("fused_mesh", self.rig, torch.float32, (s, self.vertices, 3), 4),
+                                                   ("cloud", self.cloud, torch.float32, (s, self.cloud, 3), 4),
+                                                   ("cloud_count", self.cloud, torch.int32, (s, 2), 4),
+                                                   ("cloud_resid", self.cloud, torch.int64, (s,), 8)):
             start = None
             if present:
                 start = (end + align - 1) // align * align
                 end = start + math.prod(shape) * dtype.itemsize
                 spans[name] = (start, end, dtype, shape)
-            if name != "records":
+            if name != "records" and name not in CLOUD_FIELDS:
                 put(name + "_at", start)
         put("record_rows", rows)
         put("record_bytes", rb)
@@ -176,6 +196,14 @@ class LiveLayout:
     def slots(self) -> int:
         return self.frames * (self.hands or 1)
 
+    def _part_at(self, name):
+        span = self._spans.get(name)
+        return None if span is None else span[0]
+
+    cloud_at = property(lambda self: self._part_at("cloud"))
+    cloud_count_at = property(lambda self: self._part_at("cloud_count"))
+    cloud_resid_at = property(lambda self: self._part_at("cloud_resid"))
+
     def views(self, buf) -> LiveViews:
         """The parts of a step's flat uint8 buffer (the device buffer or its pinned copy), typed and shaped; None: not there."""
         cut = {name: buf[a:b].view(dtype).view(shape) for name, (a, b, dtype, shape) in self._spans.items()}
@@ -184,21 +212,24 @@ class LiveLayout:
             kind = _occluded_views(kind)
         if self.rig:
             kind = _rig_views(kind)
+        if self.cloud:
+            kind = _cloud_views(kind)
         return kind(*(cut.get(name) for name in kind._fields))
 
 
 @functools.lru_cache(maxsize=None)
 def _read_type(step: str, base: tuple, overlay: bool, labels: bool, side: bool, tracked: bool = False, smoothed: bool = False,
-               occluded: bool = False, rig: bool = False):
+               occluded: bool = False, rig: bool = False, cloud: bool = False):
     """The namedtuple a step's read() returns: the base fields, then overlay, box_label + pose_label, side, track_age +
-    track_id, smooth_xyz + smooth_mesh, silhouette + coverage and the rig frame's eight, each only when the step has it; an
+    track_id, smooth_xyz + smooth_mesh, silhouette + coverage, the rig frame's eight and the clouds' three, each only when the step has it; an
     absent image (overlay / box_label / pose_label) reads as a None class attribute.  (One class per combination: call it with
     positional arguments only and without trailing defaults, the cache keys on them.)"""
     has = dict(overlay=overlay, box_label=labels, pose_label=labels, side=side, track_age=tracked, track_id=tracked,
-               smooth_xyz=smoothed, smooth_mesh=smoothed, silhouette=occluded, coverage=occluded, **{f: rig for f in RIG_FIELDS})
+               smooth_xyz=smoothed, smooth_mesh=smoothed, silhouette=occluded, coverage=occluded, **{f: rig for f in RIG_FIELDS},
+               **{f: cloud for f in CLOUD_FIELDS})
     fields = base + tuple(f for f, on in has.items() if on)
     name = (step + "Overlay" * overlay + "Labels" * labels + "Sided" * side + "Tracked" * tracked + "Smoothed" * smoothed
-            + "Occluded" * occluded + "Rig" * rig + "Read")
+            + "Occluded" * occluded + "Rig" * rig + "Cloud" * cloud + "Read")
     absent = {f: None for f, on in has.items() if not on and f in ("overlay", "box_label", "pose_label")}
     doc = f"{step}Output.read(): {' '.join(base)}" + "".join(f" + {f}" for f in fields[len(base):]) + "."
     return type(name, (collections.namedtuple(name, fields),), dict(absent, __slots__=(), __doc__=doc))
@@ -226,6 +257,9 @@ def _read(step, base, values, layout, v, per_slot=lambda t: t):
         values += (per_slot(v.rig_xyz).clone(), per_slot(v.rig_mesh).clone(), per_slot(v.rig_hand).clone(), int(v.rig_count[0]),
                    v.rig_views.clone(), v.rig_seed.clone(), v.fused_xyz.clone(), v.fused_mesh.clone())
         key = key + (False,) * (6 - len(key)) + (True,)
+    if layout.cloud:    # (per slot: [N,K,P,3], [N,K,2], [N,K]; the one-hand step: [N,P,3], [N,2], [N])
+        values += (per_slot(v.cloud).clone(), per_slot(v.cloud_count).clone(), per_slot(v.cloud_resid).clone())
+        key = key + (False,) * (7 - len(key)) + (True,)
     return _read_type(step, base, *key)(*values)
 
 
@@ -251,13 +285,17 @@ class LiveOutput:
     layout: LiveLayout = None        # where everything lies in `host`
     silhouette: torch.Tensor = None  # occluded steps: [N,H,W] uint8 on the device (0 no mesh, 1 shown, 0x81 hidden)
     coverage: torch.Tensor = None    # occluded steps: [N,2] int32 on the device (pixels under the mesh, of those shown)
+    cloud: torch.Tensor = None       # cloud steps, on the device: [N,P,3] fp32 the hand's measured depth points, metres
+    cloud_count: torch.Tensor = None  # [N,2] int32 (matching pixels, rows written)
+    cloud_resid: torch.Tensor = None  # [N] int64 the summed residual depth - mesh Z over all matching pixels, micrometres
+    mesh_depth: torch.Tensor = None  # [N,H,W] fp32 the nearest mesh Z per pixel (0: no mesh); the engine's buffer, not in the copy
 
     def read(self):
         """After the stream is synchronised: (keypoints, has_hand, crop_box, range words, [image_uvd, xyz_mm], mesh) as fresh CPU
         tensors (LiveRead; `.overlay`, `.box_label`, `.pose_label` are None).  A step with faces= appends the overlay [N,H,W,3]
         uint8 (LiveOverlayRead); a step with labels appends box_label [N,H,W,3] and pose_label [N,176,176,3] (LiveLabelsRead,
-        LiveOverlayLabelsRead); a step with occlude appends silhouette [N,H,W] uint8 and coverage [N,2] int32 as the last
-        fields."""
+        LiveOverlayLabelsRead); a step with occlude appends silhouette [N,H,W] uint8 and coverage [N,2] int32; a step with
+        cloud appends cloud [N,P,3] fp32, cloud_count [N,2] int32 and cloud_resid [N] int64 as the last fields."""
         v = self.layout.views(self.host)
         kp, has, box, words, more = read_host_record(v.records, self.layout.frames, extras=True)
         return _read("Live", _LIVE_FIELDS, (kp, has, box, words, more, v.mesh.clone()), self.layout, v)
@@ -274,9 +312,12 @@ class _LiveStep:
     smooth = None                # the smoothed K-hand step: (min_cutoff, beta, d_cutoff)
     rig = None                   # the rig K-hand step: its radius (metres); `extrinsics` is the device table [N,12]
     extrinsics = None
+    cloud_frame = "camera"       # the frame of a cloud step's points ("rig": a K-hand step's with extrinsics)
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None,
-                 labels: bool = False, left: bool = False, occlude: bool = False, occlude_margin: float = ops.OCCLUDE_MARGIN):
+                 labels: bool = False, left: bool = False, occlude: bool = False, occlude_margin: float = ops.OCCLUDE_MARGIN,
+                 cloud: bool = False, cloud_points: int = ops.CLOUD_POINTS, cloud_band: float = ops.CLOUD_BAND,
+                 cloud_stride: int = ops.CLOUD_STRIDE):
         if not _same_device(hand.device, lifter.device):
             raise ValueError(f"HandNet on {hand.device} but the lifter on {lifter.device}")
         self.hand, self.lifter, self.device = hand, lifter, hand.device
@@ -308,6 +349,14 @@ class _LiveStep:
                 raise ValueError("occlude=True needs faces= (and therefore perm_reverse=): it is the overlay that is tested "
                                  "against the depth map")
             self.occlude = ops.check_occlude_margin(occlude_margin)
+        # cloud: the step also cuts every hand's measured depth pixels out of its depth map (ops.hand_cloud: the pixels of the
+        # hand's silhouette within cloud_band of the mesh, back-projected) -- (points, band, stride), or None
+        self.cloud = None
+        if cloud:
+            if self.occlude is None:
+                raise ValueError("cloud=True needs occlude=True (and therefore faces= and perm_reverse=): the clouds are cut out "
+                                 "with the silhouette")
+            self.cloud = ops.check_cloud(cloud_points, cloud_band, cloud_stride)
         # labels: the step ends with the caller's other two images (ops.draw_labels: ros_demo.py:310-326), behind the overlay
         self.labels, self.clamp = bool(labels), bool(clamp)
         # left: the caller's mirror mode (ImageListener(left=True), ros_demo.py:259-262): the step runs on the frame and the
@@ -342,7 +391,7 @@ class _LiveStep:
                     owned = self._mirrored[key] = (torch.empty_like(images), torch.empty_like(depth))
         return ops.flip_w(images, depth, out=owned[0], out_other=owned[1])
 
-    def _draw(self, mesh, lifted, frames, k, out, depth=None, at=None):
+    def _draw(self, mesh, lifted, frames, k, out, depth=None, at=None, mesh_depth=None):
         s = mesh.shape[0]
         scratch = self._render_scratch.get(s)
         if scratch is None:
@@ -353,8 +402,16 @@ class _LiveStep:
         if self.occlude is None:
             return ops.mesh_render(mesh, self.faces, paras, frames, lifted=lifted, k=k, out=out, scratch=scratch), None, None
         # (the depth map the step itself ran on: mirrored in a `left` step, channel 3 of an RGBD step's tensor)
-        return ops.mesh_render(mesh, self.faces, paras, frames, lifted=lifted, k=k, out=out, scratch=scratch,
+        return ops.mesh_render(mesh, self.faces, paras, frames, lifted=lifted, k=k, out=out, scratch=scratch, depth_out=mesh_depth,
                                scene_depth=depth, margin=self.occlude, silhouette_out=at.silhouette, coverage_out=at.coverage)
+
+    def _cloud(self, work, silhouette, depth, k, at):
+        """The cloud step's last two launches: the clouds of the slots from the raster's nearest Z, the silhouette and the
+        depth map, camera table and extrinsics table the step itself used, straight into the copy buffer."""
+        points, band, stride = self.cloud
+        paras = self.paras if self.cams is None else self.cams
+        return ops.hand_cloud(work[0], silhouette, depth, paras, k, points=points, band=band, stride=stride,
+                              extrinsics_table=self.extrinsics if self.cloud_frame == "rig" else None, out=at, scratch=work[1])
 
     def _check_frames(self, n):
         if self.cams is not None and n != self.cams.shape[0]:
@@ -389,13 +446,19 @@ class _LiveStep:
         """The buffer of a step over n frames (hw: of a step that draws, the frames' size)."""
         return LiveLayout(n, self.hands, self.vertices, hw, hw is not None and self.faces is not None,
                           hw is not None and self.labels, self.handed, self.track is not None, self.smooth is not None,
-                          occluded=self.occlude is not None, rig=self.rig is not None)
+                          occluded=self.occlude is not None, cloud=self.cloud[0] if self.cloud and hw is not None else 0,
+                          rig=self.rig is not None)
 
     def _new_buffers(self, n, hw=None):
-        """A fresh (layout, device buffer, pinned host buffer) of a step over n frames."""
+        """A fresh (layout, device buffer, pinned host buffer, work) of a step over n frames; work: a cloud step's (mesh depth
+        fp32 [n,h,w], the cloud launches' scratch) on the device -- not part of the copy --, else None."""
         layout = self._layout(n, hw)
+        work = None
+        if layout.cloud:
+            work = (torch.zeros((n, *hw), dtype=torch.float32, device=self.device),
+                    torch.empty((ops.hand_cloud_scratch_bytes(n, self.hands or 1, hw[0]),), dtype=torch.uint8, device=self.device))
         return (layout, torch.zeros((layout.nbytes,), dtype=torch.uint8, device=self.device),
-                torch.zeros((layout.nbytes,), dtype=torch.uint8, pin_memory=True))
+                torch.zeros((layout.nbytes,), dtype=torch.uint8, pin_memory=True), work)
 
     def _out_buffers(self, n, hw=None):
         b = self._buffers.get((n, hw))
@@ -413,7 +476,7 @@ class _LiveStep:
         if self.left and _mirror is not False:
             images, depth = self._mirror_inputs(images, depth, _mirror)
         frames = self._frames(images)
-        layout, dev, host = _buffers if _buffers is not None else self._out_buffers(n, self._hw(frames))
+        layout, dev, host, work = _buffers if _buffers is not None else self._out_buffers(n, self._hw(frames))
         at = layout.views(dev)
 
         def lift(_kp, image_uvd, xyz, has_hand, mirror=None):
@@ -429,7 +492,7 @@ class _LiveStep:
         overlay = box_label = pose_label = silhouette = coverage = None
         if layout.overlay:      # (a smoothed step draws, and an occluded one tests, what it smoothed)
             overlay, silhouette, coverage = self._draw(at.smooth_mesh if layout.smoothed else mesh, drawn, frames, k, at.overlay,
-                                                       depth, at)
+                                                       depth, at, work and work[0])
         if layout.labels:
             box_label, pose_label = ops.draw_labels(out.keypoints, out.crop_box, frames, drawn=drawn, k=k, clamp=self.clamp,
                                                     out_box=at.box_label, out_pose=at.pose_label)
@@ -438,6 +501,9 @@ class _LiveStep:
             more["rig"] = ops.rig_fuse(at.smooth_xyz if layout.smoothed else out.xyz_mm, at.smooth_mesh if layout.smoothed else mesh,
                                        out.has_hand, at.lifted, out.score, self.extrinsics, k, self.rig,
                                        side=out.side if self.handed else None, out=at)
+        if layout.cloud:    # (against the mesh the overlay drew and the depth map it was tested against)
+            cloud = self._cloud(work, silhouette, depth, k, at)
+            more.update(cloud=cloud.cloud, cloud_count=cloud.count, cloud_resid=cloud.resid, mesh_depth=work[0])
         host.copy_(dev, non_blocking=True)
         return self._output(out, at, layout, host, dict(pose2d=p2d, mesh=mesh, pose3d=pose3d, raw_mesh=raw, overlay=overlay,
                                                         box_label=box_label, pose_label=pose_label, **more))
@@ -445,7 +511,9 @@ class _LiveStep:
     def _key_options(self) -> tuple:
         """What a capture's key carries behind the shapes (the smoothed step: its filter's parameters; the occluded step: its
         margin -- kernel arguments)."""
-        return (() if self.occlude is None else ("occluded", self.occlude)) + (() if self.rig is None else ("rig", self.rig))
+        return ((() if self.occlude is None else ("occluded", self.occlude))
+                + (() if self.cloud is None else ("cloud",) + self.cloud + (self.cloud_frame,))
+                + (() if self.rig is None else ("rig", self.rig)))
 
     def _smooth_untouched(self, n):
         return contextlib.nullcontext()
@@ -482,6 +550,8 @@ class _LiveStep:
                 s_dep.copy_(depth)
                 # the capture's own buffers, never the eager cache's (addresses are baked into the graph)
                 bufs = self._new_buffers(images.shape[0], self._hw(self._frames(images)))
+                if bufs[3] is not None:      # (a cloud step's scratch: its address is baked into the graph and nothing the step
+                    self._mirrored[("cloud work",) + key] = bufs[3]      # hands out refers to it -- owned like the mirrored inputs)
                 flipped = None
                 if self.left and not _mirrored:
                     # the capture's mirrored inputs: owned by the engine for as long as the capture lives (their addresses are
@@ -518,7 +588,16 @@ class LiveHandEngine(_LiveStep):
     last fields): silhouette [N,H,W] uint8 -- 0 no mesh, 1 mesh shown, 0x81 mesh hidden --, coverage [N,2] int32 -- pixels
     under the mesh, and of those the shown ones.  Holes of the depth map (0, NaN) hide nothing.  The default margin of 0.03 m
     is a starting value, NOT tuned on this model: a hand is 2-3 cm thick and the mesh's absolute Z hangs on the wrist key
-    point's single depth reading."""
+    point's single depth reading.
+    cloud (needs occlude): the step ends with two more launches (ops.hand_cloud) that cut the hand's measured
+    depth pixels out of the step's own depth map -- the candidates (every cloud_stride-th row and column) under the mesh's
+    silhouette, hidden or not, whose depth D is finite and > 0 and lies within cloud_band metres of the mesh Z drawn there --
+    and back-project them: ((c + 0.5 - cx) D / fx, (r + 0.5 - cy) D / fy, D), metres in the frame of xyz_mm (x right, y down,
+    z forward), the pixel centre at +0.5.  LiveOutput.cloud [N,P,3] holds the first P = cloud_points matches in row-major
+    order (zero rows behind them), .cloud_count [N,2] (matches, rows written), .cloud_resid [N] int64 the summed D - mesh Z over
+    all matches in micrometres, read() likewise as the last fields, in the step's one copy; .mesh_depth [N,H,W] is the nearest
+    mesh Z per pixel on the device.  cloud_points = 4096, cloud_band = 0.03 m and cloud_stride = 2 are starting values, NOT
+    tuned on this model."""
 
     def _hand_step(self, images, depth, at, lift):
         return self.hand.forward_device(images, depth, _record=(None, at.records), _tail=lift)
@@ -572,6 +651,10 @@ class LiveHandsOutput:
     rig_seed: torch.Tensor = None    # [N*K] int32 the rig hand's seed slot i * K + k (-1 beyond the count): the way to its track_id
     fused_xyz: torch.Tensor = None   # [N*K,21,3] per rig hand: its members' joints, weighted by their scores
     fused_mesh: torch.Tensor = None  # [N*K,V,3] per rig hand: its members' meshes, weighted by their scores
+    cloud: torch.Tensor = None       # cloud steps, on the device: [N,K,P,3] fp32 each slot's measured depth points, metres
+    cloud_count: torch.Tensor = None  # [N,K,2] int32 (matching pixels, rows written)
+    cloud_resid: torch.Tensor = None  # [N,K] int64 the summed residual depth - mesh Z over all matching pixels, micrometres
+    mesh_depth: torch.Tensor = None  # [N,H,W] fp32 the nearest mesh Z per pixel (0: no mesh); the engine's buffer, not in the copy
     smooth_xyz: torch.Tensor = None  # smoothed steps: [N,K,21,3] on the device, xyz_mm filtered over time (zeros: has_hand != 1)
     smooth_mesh: torch.Tensor = None  # smoothed steps: [N,K,V,3] on the device, `mesh` filtered over time (zeros: not lifted)
 
@@ -583,7 +666,8 @@ class LiveHandsOutput:
         as the last fields; a smoothed step: behind those, smooth_xyz [N,K,21,3] and smooth_mesh [N,K,V,3]; an occluded step:
         behind everything else, silhouette [N,H,W] uint8 and coverage [N,K,2] int32; a rig step: behind those, rig_xyz
         [N,K,21,3], rig_mesh [N,K,V,3], rig_hand [N,K] int32, rig_count (a Python int), rig_views and rig_seed [N*K] int32,
-        fused_xyz [N*K,21,3] and fused_mesh [N*K,V,3])."""
+        fused_xyz [N*K,21,3] and fused_mesh [N*K,V,3]; a cloud step: behind those, cloud [N,K,P,3] fp32, cloud_count [N,K,2]
+        int32 and cloud_resid [N,K] int64)."""
         v, s = self.layout.views(self.host), self.layout.slots
         per = lambda t: t.reshape((self.layout.frames, self.layout.hands) + tuple(t.shape[1:]))
         kp, has, box, words, (img, xyz) = read_host_record(v.records, s, extras=True)
@@ -605,7 +689,8 @@ class LiveHandsEngine(_LiveStep):
                  perm_reverse=None, faces=None, labels: bool = False, left: bool = False, handed: bool = False,
                  left_side: int = 0, track: bool = False, track_iou: float = 0.3, track_hold: int = 5, occlude: bool = False,
                  occlude_margin: float = ops.OCCLUDE_MARGIN, extrinsics=None, rig_radius: float = ops.RIG_RADIUS,
-                 smooth: bool = False, smooth_min_cutoff: float = 1.0, smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0,
+                 cloud: bool = False, cloud_points: int = ops.CLOUD_POINTS, cloud_band: float = ops.CLOUD_BAND,
+                 cloud_stride: int = ops.CLOUD_STRIDE, cloud_frame: str = "camera", smooth: bool = False, smooth_min_cutoff: float = 1.0, smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0,
                  smooth_rate: float = 30.0):
         """paras: as LiveHandEngine's -- with a camera per frame [N,4], all K slots of frame i use row i.
         faces: mesh_model.face ([F,3]; needs perm_reverse) -- given, the step ends with the overlay: every lifted mesh of a
@@ -651,7 +736,19 @@ class LiveHandsEngine(_LiveStep):
         slot per frame, with handed=True only slots of one side), and per rig hand the members' score-weighted mean (fused_xyz,
         fused_mesh) -- LiveHandsOutput and read() likewise, behind every other field.  A smoothed step moves and fuses
         smooth_xyz / smooth_mesh.  rig_radius = 0.08 m is a starting value, NOT tuned on this model.  left=True: ValueError (a
-        mirrored frame is not the camera's frame).  set_extrinsics(new) rewrites the device table under captured steps."""
+        mirrored frame is not the camera's frame).  set_extrinsics(new) rewrites the device table under captured steps.
+        cloud (needs occlude): the step ends with two more launches (ops.hand_cloud) that cut every slot's
+        measured depth pixels out of the step's own depth map -- the candidates (every cloud_stride-th row and column) whose
+        silhouette byte names the slot, hidden or not, whose depth D is finite and > 0 and lies within cloud_band metres of
+        the mesh Z drawn there -- and back-project them with the frame's camera: ((c + 0.5 - cx) D / fx, (r + 0.5 - cy) D / fy,
+        D), metres in the frame of xyz_mm (x right, y down, z forward), the pixel centre at +0.5.  LiveHandsOutput.cloud
+        [N,K,P,3] holds each slot's first P = cloud_points matches in row-major order (zero rows behind them), .cloud_count
+        [N,K,2] (matches, rows written), .cloud_resid [N,K] int64 the summed D - mesh Z over all matches in micrometres (how
+        far the mesh sits from the surface the camera sees), read() likewise behind every other field, in the step's one copy;
+        .mesh_depth [N,H,W] is the nearest mesh Z per pixel on the device.  cloud_frame="rig" (needs extrinsics=) hands the
+        points out in the rig frame.  A `left` step cuts the mirrored depth map, a smoothed step works against the smoothed
+        mesh it draws.  cloud_points = 4096, cloud_band = 0.03 m and cloud_stride = 2 are starting values, NOT tuned on this
+        model."""
         self.hands = self.max_hands = ops.check_max_hands(max_hands)
         if left and handed:
             raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
@@ -677,7 +774,13 @@ class LiveHandsEngine(_LiveStep):
             table = ops.rig_extrinsics(extrinsics)
             ops.check_rig_slots(table.shape[0], self.hands)
             self.rig = ops.check_rig_radius(rig_radius)
-        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left, occlude, occlude_margin)
+        if cloud_frame not in ("camera", "rig"):
+            raise ValueError(f'cloud_frame: "camera" or "rig" (got {cloud_frame!r})')
+        if cloud_frame == "rig" and extrinsics is None:
+            raise ValueError('cloud_frame="rig" needs extrinsics=: the camera -> rig transforms the points go through')
+        self.cloud_frame = cloud_frame
+        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left, occlude, occlude_margin, cloud,
+                         cloud_points, cloud_band, cloud_stride)
         if table is not None:
             if self.cams is not None and self.cams.shape[0] != table.shape[0]:
                 raise ValueError(f"{table.shape[0]} extrinsics for a step built with {self.cams.shape[0]} cameras: one [R | t] per "
@@ -776,6 +879,9 @@ class LiveHandsEngine(_LiveStep):
         if "coverage" in parts:
             parts["coverage"] = parts["coverage"].view(n, k, 2)
         parts.update(parts.pop("rig", ops.RigFused(*(None,) * 8))._asdict())
+        if "cloud" in parts:
+            parts.update(cloud=parts["cloud"].view(n, k, -1, 3), cloud_count=parts["cloud_count"].view(n, k, 2),
+                         cloud_resid=parts["cloud_resid"].view(n, k))
         return LiveHandsOutput(hands=out, lifted=at.lifted.view(n, k), host=host, n=n, k=k, side=out.side, mirror=out.mirror,
                                layout=layout, track_id=out.track_id, track_age=out.track_age,
                                smooth_xyz=None if self.smooth is None else at.smooth_xyz.view(n, k, SMOOTH_JOINTS, 3),

@@ -2164,6 +2164,102 @@ def rig_fuse(xyz_mm, mesh, has_hand, lifted, score, extrinsics_table, k, radius=
     return RigFused(*parts)
 
 
+CLOUD_POINTS = 4096        # rows per slot of a hand cloud; a starting value, NOT tuned on this model
+CLOUD_BAND = 0.03          # metres between the measured depth and the mesh Z; a starting value, NOT tuned on this model
+CLOUD_STRIDE = 2           # every second row and column is a candidate; a starting value, NOT tuned on this model
+CLOUD_MAX_BAND = 100.0     # metres: the residual in micrometres then fits an int32
+
+HandCloud = collections.namedtuple("HandCloud", "cloud count resid")
+
+
+def check_cloud(points=CLOUD_POINTS, band=CLOUD_BAND, stride=CLOUD_STRIDE):
+    """A hand cloud's three parameters as (int points >= 1, float band, int stride >= 1), the band finite and in (0, 100] metres
+    also as the fp32 kernel argument it becomes; else ValueError.  The defaults (4096 rows, 0.03 m, every second row and column)
+    are starting values, NOT tuned on this model."""
+    for name, value in (("cloud_points", points), ("cloud_stride", stride)):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= 2 ** 31 - 1:
+            raise ValueError(f"{name}: an integer >= 1 (got {value!r})")
+    try:
+        b = float(band)
+    except (TypeError, ValueError):
+        b = math.nan
+    with np.errstate(over="ignore"):
+        g = float(np.float32(b))
+    if not (math.isfinite(b) and 0.0 < g <= CLOUD_MAX_BAND and b <= CLOUD_MAX_BAND):
+        raise ValueError(f"cloud_band: a finite number of metres in (0, {CLOUD_MAX_BAND:g}] as fp32 (got {band!r})")
+    return int(points), b, int(stride)
+
+
+def hand_cloud_scratch_bytes(frames, k, h):
+    return int(_lib.load().hn_hand_cloud_scratch_bytes(frames, k, h))
+
+
+def hand_cloud(mesh_depth, silhouette, scene_depth, paras, k, *, points=CLOUD_POINTS, band=CLOUD_BAND, stride=CLOUD_STRIDE,
+               extrinsics_table=None, out=None, scratch=None) -> HandCloud:
+    """Each hand's measured depth pixels as a compact 3-D point cloud (hn_hand_cloud_f32: two launches, csrc/hand_cloud.hip;
+    DESIGN.md section 9j, tests/cloud_ref.py is the rule and the outputs equal it bit for bit).  mesh_depth fp32 [N,H,W] and
+    silhouette uint8 [N,H,W] are what the occluded mesh_render leaves (depth_out, the silhouette); scene_depth is the depth map
+    it was given: fp32 [N,1,H,W], [N,H,W] or an RGB-D [N,4,H,W] (channel 3 is read in place); paras (fx, fy, cx, cy) on the
+    host, or an fp32 tensor [N,4] on the device, a camera per frame, as mesh_render takes it; k slots per frame (1..16).
+    A pixel (r, c) with r % stride == 0 and c % stride == 0 matches slot j of frame i when (silhouette & 0x7F) == j + 1 (hidden
+    or not), its depth D is finite and > 0 and |D - mesh_depth| <= band metres; its point is ((c + 0.5 - cx) D / fx,
+    (r + 0.5 - cy) D / fy, D): metres in the camera frame of xyz_mm (x right, y down, z forward), the pixel centre at +0.5 as
+    the raster samples it -- or, with extrinsics_table (fp32 [N,12] on the device, rig_extrinsics(...) uploaded), that point in
+    the rig frame.  Returns HandCloud: cloud fp32 [N*k,points,3] -- slot s = i * k + j: its first min(total, points) matches in
+    row-major order, zero rows behind them --, count int32 [N*k,2] = (total matches, rows written), resid int64 [N*k] = the sum
+    of rint((D - mesh_depth) * 1e6) over ALL matches, micrometres: how far the mesh sits from the surface the camera sees.
+    Allocated, or `out`'s attributes cloud / cloud_count / cloud_resid (the live step's buffer views), every one fully written.
+    points = 4096, band = 0.03 m and stride = 2 are starting values, NOT tuned on this model."""
+    points, band, stride = check_cloud(points, band, stride)
+    _req(mesh_depth, name="mesh_depth"); _req(silhouette, torch.uint8, "silhouette"); _req(scene_depth, name="scene_depth")
+    if silhouette.dim() != 3:
+        raise ValueError(f"silhouette: expected uint8 [N,H,W], got {tuple(silhouette.shape)}")
+    n, h, w = (int(v) for v in silhouette.shape)
+    if mesh_depth.numel() != n * h * w:
+        raise ValueError(f"mesh_depth: expected fp32 [{n},{h},{w}], got {tuple(mesh_depth.shape)}")
+    k = int(k)
+    if not 1 <= k <= 16:
+        raise ValueError(f"the silhouette's byte holds at most 16 slots per frame (k = {k})")
+    for name, t in (("mesh_depth", mesh_depth), ("scene_depth", scene_depth)):
+        if t.device != silhouette.device:
+            raise ValueError(f"{name} on {t.device} but the silhouette on {silhouette.device}")
+    shape = tuple(scene_depth.shape)
+    if shape not in ((n, 1, h, w), (n, h, w), (n, 4, h, w)):
+        raise ValueError(f"scene_depth: expected fp32 [{n},1,{h},{w}], [{n},{h},{w}] or RGBD [{n},4,{h},{w}], got {shape}")
+    rgbd = len(shape) == 4 and shape[1] == 4
+    depth_ptr = scene_depth.data_ptr() + (3 * h * w * 4 if rgbd else 0)
+    host4 = table = None
+    if torch.is_tensor(paras) and paras.dim() != 1:
+        if paras.dtype != torch.float32 or tuple(paras.shape) != (n, 4):
+            raise ValueError(f"paras: a camera per frame is fp32 [{n},4] (fx, fy, cx, cy), got {paras.dtype} {tuple(paras.shape)}")
+        if paras.device != silhouette.device:
+            raise ValueError(f"paras on {paras.device} but the silhouette on {silhouette.device}")
+        table = ptr(_req(paras, torch.float32, "paras"))
+    else:
+        host4 = (C.c_float * 4)(*[float(x) for x in paras])
+    if extrinsics_table is not None:
+        _req(extrinsics_table, name="extrinsics_table")
+        if tuple(extrinsics_table.shape) != (n, 12) or extrinsics_table.device != silhouette.device:
+            raise ValueError(f"extrinsics_table: fp32 [{n},12] on {silhouette.device}, a row per frame, got "
+                             f"{tuple(extrinsics_table.shape)} on {extrinsics_table.device}")
+    s = n * k
+    parts = []
+    for name, dtype, shp in (("cloud", torch.float32, (s, points, 3)), ("cloud_count", torch.int32, (s, 2)),
+                             ("cloud_resid", torch.int64, (s,))):
+        t = torch.empty(shp, device=silhouette.device, dtype=dtype) if out is None else getattr(out, name)
+        if _req(t, dtype, name).numel() != math.prod(shp):
+            raise ValueError(f"{name}: expected {dtype} {list(shp)}, got {tuple(t.shape)}")
+        parts.append(t.view(shp))
+    need = hand_cloud_scratch_bytes(n, k, h)
+    if scratch is None:
+        scratch = torch.empty((need,), device=silhouette.device, dtype=torch.uint8)
+    _req(scratch, torch.uint8, "scratch")
+    check(_lib.load().hn_hand_cloud_f32(ptr(mesh_depth), ptr(silhouette), depth_ptr, (4 if rgbd else 1) * h * w, host4, table,
+                                        ptr(extrinsics_table), n, k, h, w, points, stride, band, ptr(scratch), scratch.numel(),
+                                        *(ptr(t) for t in parts), _stream()), "hn_hand_cloud_f32")
+    return HandCloud(*parts)
+
+
 LABEL_CROP = 176      # side of a pose_label image
 
 

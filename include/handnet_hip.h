@@ -37,7 +37,8 @@ extern "C" {
  * hn_ingest_u8bgr_u16mm_flip, hn_flip_w_f32, hn_crop_resize_hands_sided, hn_a2j_aggregate_convert_mirror_f32,
  * hn_lifter_input_gated_mirror_f32 and hn_mesh_finish_mirror_f32, the tracked slots' hn_crop_resize_hands_tracked and
  * hn_track_state_bytes, the smoothed step's hn_mesh_finish_smooth_f32 and hn_smooth_state_bytes, the per-frame cameras'
- * hn_mesh_render_cams_u8 and hn_mesh_render_cams_occluded_u8, and the rig frame's hn_rig_fuse_f32). */
+ * hn_mesh_render_cams_u8 and hn_mesh_render_cams_occluded_u8, the rig frame's hn_rig_fuse_f32, and the hand cloud's
+ * hn_hand_cloud_f32 and hn_hand_cloud_scratch_bytes). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -856,6 +857,25 @@ int hn_rig_fuse_f32(const float* xyz_mm, const float* mesh, const int32_t* has_h
                     const int32_t* side /* or NULL */, const float* extrinsics, int n, int k, int joints, int v, float radius,
                     float* rig_xyz, float* rig_mesh, int32_t* rig_hand, int32_t* rig_count, int32_t* rig_views,
                     int32_t* rig_seed, float* fused_xyz, float* fused_mesh, void* stream);
+/* Each hand's depth pixels as a compact 3-D point cloud (tests/cloud_ref.py is the rule in numpy float32,
+ * and the outputs equal it bit for bit: fp32, one rounding per operation, integer sums, no atomics).  Inputs are what the occluded
+ * overlay leaves on the device: mesh_depth = its out_depth [n][h][w], silhouette = its out_silhouette [n][h][w], scene_depth and
+ * depth_frame_stride as hn_mesh_render_occluded_u8 takes them; exactly one of paras (HOST, 4 floats: one camera) and cams (DEVICE,
+ * [n][4]: a camera per frame); extrinsics DEVICE [n][12] = the rows of [R | t] (the points in the rig frame) or NULL (the camera
+ * frame: x right, y down, z forward, metres).  A pixel (r, c) with r % stride == 0 and c % stride == 0 matches slot j of frame i
+ * when (silhouette & 0x7F) == j + 1, D = scene_depth is finite and > 0, and |D - mesh_depth| <= band; its point is
+ * ((c + 0.5 - cx) * D / fx, (r + 0.5 - cy) * D / fy, D) -- the pixel centre at +0.5, the raster's sample point.
+ *   out_cloud [n*k][points][3]  slot s = i * k + j: its first min(total, points) matches in row-major order, zero rows behind them
+ *   out_count [n*k][2]          (total matches, rows written)
+ *   out_resid [n*k]             the sum of (int32)rint((D - mesh_depth) * 1e6) over ALL matches: micrometres, int64
+ * Every output is fully written.  Two launches on `stream`; every argument is checked before the first (k 1..16, h and w
+ * 1..16384, points and stride >= 1, 0 < band <= 100, scratch of hn_hand_cloud_scratch_bytes(n, k, h) bytes, 8-byte aligned). */
+int64_t hn_hand_cloud_scratch_bytes(int n, int k, int h);
+int hn_hand_cloud_f32(const float* mesh_depth, const uint8_t* silhouette, const float* scene_depth, int64_t depth_frame_stride,
+                      const float* paras /* host, or NULL */, const float* cams /* device [n][4], or NULL */,
+                      const float* extrinsics /* device [n][12] or NULL: camera frame */, int n, int k, int h, int w, int points,
+                      int stride, float band, void* scratch, int64_t scratch_bytes, float* out_cloud, int32_t* out_count,
+                      int64_t* out_resid, void* stream);
 /* A Linear layer on 1..4 rows as a matrix-vector product on the vector ALU (PoseNet at the live caller's batch, posenet.py:24-41,
  * 78-88: 67 MB of filter bank per 17 M MACs): y[m][:] = act(W (pre(x[m])) + bias (+ residual[m])), pre = relu(x * scale + shift)
  * when scale / shift ([k_real] fp32: the pre-activation BatchNorm) are given.  x fp32 [batch][x_stride] (k_real columns used), w16 =
