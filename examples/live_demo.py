@@ -34,8 +34,11 @@ With --cloud the last frame also goes through the K = 2 step with faces=, occlud
 depth pixels (every second row and column under its silhouette, within 3 cm of the mesh; at most 4096 points; starting values,
 not tuned) as 3-D points in the camera frame -- per slot, the number of matching pixels, the rows written and the mean residual
 depth - mesh Z in millimetres (how far the mesh sits from the surface the camera sees).
+With --fit the last frame also goes through the K = 2 step with faces=, occlude=True and fit=True: every slot's mesh and joints
+moved onto its measured depth pixels by one Gauss-Newton step of point-to-plane alignment (starting values, not tuned) -- per
+slot, the matching pixels, the status, the RMS residual along the normals before the step and the shift found, in millimetres.
 usage (GPU box): python examples/live_demo.py [frames] [--overlay out.png] [--mano MANO_RIGHT.pkl] [--labels PREFIX] [--left]
-                 [--handed] [--track] [--smooth] [--occlude] [--cameras N] [--rig] [--cloud]"""
+                 [--handed] [--track] [--smooth] [--occlude] [--cameras N] [--rig] [--cloud] [--fit]"""
 import sys
 import time
 import types
@@ -74,8 +77,8 @@ def main():
             opt[flag] = argv[i + 1]
             del argv[i:i + 2]
     left, handed, track, smooth = "--left" in argv, "--handed" in argv, "--track" in argv, "--smooth" in argv
-    occlude, rig_frame, cloud = "--occlude" in argv, "--rig" in argv, "--cloud" in argv
-    argv = [a for a in argv if a not in ("--left", "--handed", "--track", "--smooth", "--occlude", "--rig", "--cloud")]
+    occlude, rig_frame, cloud, fit = "--occlude" in argv, "--rig" in argv, "--cloud" in argv, "--fit" in argv
+    argv = [a for a in argv if a not in ("--left", "--handed", "--track", "--smooth", "--occlude", "--rig", "--cloud", "--fit")]
     frames = int(argv[0]) if argv else 20
     faces = _faces(opt.get("--mano")) if "--overlay" in opt else None
     args = types.SimpleNamespace(pretrained_fcos="-", pretrained_a2j="-")
@@ -216,6 +219,17 @@ def main():
                 print(f"12. cloud, slot {k}: {total} matching pixels, {written} points written, {mean}")
             print(f"    cloud {tuple(r8.cloud.shape)} fp32 metres (x right, y down, z forward), first point of slot 0 "
                   f"{[round(float(v), 4) for v in r8.cloud[0, 0, 0]]}")
+        if fit:                                                                           # each hand's mesh moved onto its depth pixels
+            fitted = net.live_hands(model, PARAS, max_hands=2, clamp=True, perm_reverse=rev,
+                                    faces=faces if faces is not None else _faces(opt.get("--mano")), occlude=True, fit=True)
+            o9 = fitted.forward_device(s_img, s_dep)
+            torch.cuda.current_stream().synchronize()
+            r9 = o9.read()
+            words = {0: "fitted", 1: "too few matches", 2: "no solution", 3: "beyond the caps"}
+            for k, ((matches, status), cost) in enumerate(zip(r9.fit_count[0].tolist(), r9.fit_cost[0].tolist())):
+                rms = f"{1000.0 * (cost / 2 ** 30 / matches) ** 0.5:.2f} mm" if matches else "-"
+                print(f"13. fit, slot {k}: {matches} matching pixels, {words[status]}, RMS residual before {rms}, shift (mm) "
+                      f"{[round(1000.0 * float(v), 2) for v in r9.fit_rt[0, k, 9:]]}")
 
 
 if __name__ == "__main__":

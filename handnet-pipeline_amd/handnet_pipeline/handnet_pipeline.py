@@ -106,7 +106,8 @@ class HandNet(EngineOwner):
 
     def live(self, lifter, paras, clamp: bool = True, perm_reverse=None, faces=None, labels: bool = False, left: bool = False,
              occlude: bool = False, occlude_margin: float = 0.03, cloud: bool = False, cloud_points: int = 4096,
-             cloud_band: float = 0.03, cloud_stride: int = 2):
+             cloud_band: float = 0.03, cloud_stride: int = 2, fit: bool = False, fit_band: float = 0.03, fit_stride: int = 2,
+             fit_min_points: int = 200, fit_damp: float = 1e-3, fit_max_shift: float = 0.05, fit_max_angle: float = 0.35):
         """The live caller's chain as ONE step (hn_amd.live.LiveHandEngine; ros_demo.py:270-290,329-337): this network, the
         caller's clamp + convert_joints (in the aggregation's epilogue), the lifter's input, Pose2Mesh, one device -> host copy.
         lifter: the drop-in `models.pose2mesh_net.get_model(...)` module (on the GPU) or a Pose2MeshEngine; paras = (fx, fy,
@@ -128,19 +129,30 @@ class HandNet(EngineOwner):
         forward, the pixel centre at +0.5; the first P matches in row-major order, zero rows behind them), cloud_count [N,2]
         int32 (matches, rows written) and cloud_resid [N] int64 (the summed depth - mesh Z over all matches, micrometres).
         cloud_points = 4096, cloud_band = 0.03 m and cloud_stride = 2 are starting values, NOT tuned on this model.
+        fit (needs occlude): the step also fits the hand's mesh to its measured depth -- one Gauss-Newton
+        step of point-to-plane alignment over every fit_stride-th row and column under the silhouette whose depth lies within
+        fit_band metres of the mesh -- and read() ends with fit_mesh [N,V,3], fit_xyz [N,21,3] (camera millimetres), fit_rt
+        [N,12] fp32 (R row-major, then t in metres: the motion about the root joint, camera frame), fit_count [N,2] int32
+        (matches, status: 0 fitted, 1 fewer than fit_min_points matches, 2 no solution, 3 beyond fit_max_shift metres or
+        fit_max_angle radians: the mesh is left as it is) and fit_cost [N] int64 (the summed squared residual, 2^-30 m^2).
+        fit_band = 0.03 m, fit_stride = 2, fit_min_points = 200, fit_damp = 1e-3, fit_max_shift = 0.05 m and fit_max_angle =
+        0.35 rad are starting values, NOT tuned on this model.
         The returned engine owns this network's step from then on (forward() of this module keeps working and
         carries the converted joints: set_convert)."""
         from hn_amd.live import LiveHandEngine
         paras = ops.camera_paras(paras)
         self._convert_cfg = (paras, bool(clamp))
         return LiveHandEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, clamp, perm_reverse,
-                              faces, labels, left, occlude, occlude_margin, cloud, cloud_points, cloud_band, cloud_stride)
+                              faces, labels, left, occlude, occlude_margin, cloud, cloud_points, cloud_band, cloud_stride, fit,
+                              fit_band, fit_stride, fit_min_points, fit_damp, fit_max_shift, fit_max_angle)
 
     def live_hands(self, lifter, paras, max_hands: int = 2, clamp: bool = True, perm_reverse=None, faces=None,
                    labels: bool = False, left: bool = False, handed: bool = False, left_side: int = 0, track: bool = False,
                    track_iou: float = 0.3, track_hold: int = 5, occlude: bool = False, occlude_margin: float = 0.03,
                    extrinsics=None, rig_radius: float = 0.08, cloud: bool = False, cloud_points: int = 4096,
-                   cloud_band: float = 0.03, cloud_stride: int = 2, cloud_frame: str = "camera",
+                   cloud_band: float = 0.03, cloud_stride: int = 2, cloud_frame: str = "camera", fit: bool = False,
+                   fit_band: float = 0.03, fit_stride: int = 2, fit_min_points: int = 200, fit_damp: float = 1e-3,
+                   fit_max_shift: float = 0.05, fit_max_angle: float = 0.35,
                    smooth: bool = False, smooth_min_cutoff: float = 1.0, smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0,
                    smooth_rate: float = 30.0):
         """live() for up to max_hands (1..16) hands per frame (hn_amd.live.LiveHandsEngine): forward_hands' slots, the
@@ -177,7 +189,10 @@ class HandNet(EngineOwner):
         recapturing anything.  rig_radius = 0.08 m is a starting value, NOT tuned on this model.  left=True: ValueError.
         cloud (needs occlude): as live()'s, per slot: read() ends with cloud [N,K,P,3], cloud_count
         [N,K,2] and cloud_resid [N,K]; cloud_frame="rig" (needs extrinsics) hands the points out in the rig frame.
-        cloud_points = 4096, cloud_band = 0.03 m and cloud_stride = 2 are starting values, NOT tuned on this model."""
+        cloud_points = 4096, cloud_band = 0.03 m and cloud_stride = 2 are starting values, NOT tuned on this model.
+        fit (needs occlude): as live()'s, per slot: read() ends with fit_mesh [N,K,V,3], fit_xyz
+        [N,K,21,3], fit_rt [N,K,12], fit_count [N,K,2] and fit_cost [N,K].  fit_band = 0.03 m, fit_stride = 2, fit_min_points =
+        200, fit_damp = 1e-3, fit_max_shift = 0.05 m and fit_max_angle = 0.35 rad are starting values, NOT tuned on this model."""
         from hn_amd.live import LiveHandsEngine
         k = ops.check_max_hands(max_hands)
         if left and handed:
@@ -188,7 +203,9 @@ class HandNet(EngineOwner):
                                perm_reverse, faces, labels, left, handed, left_side, track, track_iou, track_hold,
                                occlude=occlude, occlude_margin=occlude_margin, extrinsics=extrinsics, rig_radius=rig_radius,
                                cloud=cloud, cloud_points=cloud_points, cloud_band=cloud_band, cloud_stride=cloud_stride,
-                               cloud_frame=cloud_frame,
+                               cloud_frame=cloud_frame, fit=fit, fit_band=fit_band, fit_stride=fit_stride,
+                               fit_min_points=fit_min_points, fit_damp=fit_damp, fit_max_shift=fit_max_shift,
+                               fit_max_angle=fit_max_angle,
                                smooth=smooth, smooth_min_cutoff=smooth_min_cutoff,
                                smooth_beta=smooth_beta, smooth_d_cutoff=smooth_d_cutoff, smooth_rate=smooth_rate)
 

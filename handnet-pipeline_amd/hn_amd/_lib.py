@@ -244,6 +244,10 @@ SIGNATURES = {
     # each hand's depth pixels as a point cloud: count + write (new functions under ABI 36)
     "hn_hand_cloud_scratch_bytes": (C.c_int64, [C.c_int] * 3),
     "hn_hand_cloud_f32": (C.c_int, [VP] * 3 + [C.c_int64] + [VP] * 3 + [C.c_int] * 6 + [C.c_float, VP, C.c_int64] + [VP] * 4),
+    # each hand's mesh fitted to its measured depth: accumulate + apply (new functions under ABI 36)
+    "hn_mesh_fit_scratch_bytes": (C.c_int64, [C.c_int] * 3),
+    "hn_mesh_fit_f32": (C.c_int, [VP] * 3 + [C.c_int64] + [VP] * 4 + [C.c_int] * 7 + [C.c_float, C.c_int] + [C.c_double] * 3
+                        + [VP, C.c_int64] + [VP] * 6),
 }
 
 _lock = threading.Lock()

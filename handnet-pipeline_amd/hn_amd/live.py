@@ -84,6 +84,15 @@ def _cloud_views(kind):
     return collections.namedtuple(kind.__name__.replace("Views", "CloudViews"), kind._fields + CLOUD_FIELDS)
 
 
+FIT_FIELDS = ("fit_mesh", "fit_xyz", "fit_rt", "fit_count", "fit_cost")
+
+
+@functools.lru_cache(maxsize=None)
+def _fit_views(kind):
+    """... and of a fit step: the fields of its step without the option, then the five parts of the fitted meshes"""
+    return collections.namedtuple(kind.__name__.replace("Views", "FitViews"), kind._fields + FIT_FIELDS)
+
+
 @dataclass(frozen=True)
 class LiveLayout:
     """Byte layout of a live step's one copy buffer, in this order: the records (one-hand step: a wide record per frame + the
@@ -96,8 +105,10 @@ class LiveLayout:
     `rig_xyz` fp32 [slots,21,3], `rig_mesh` fp32 [slots,V,3], `rig_hand` int32 [slots], `rig_count` int32 [1], `rig_views` and
     `rig_seed` int32 [slots], `fused_xyz` fp32 [slots,21,3] and `fused_mesh` fp32 [slots,V,3], each on a dword, and -- cloud steps
     (cloud = P, the rows per slot) -- `cloud` fp32 [slots,P,3] and `cloud_count` int32 [slots,2], each on a dword,
-    and `cloud_resid` int64 [slots] on 8 bytes, as the last parts (their offsets cloud_at, cloud_count_at, cloud_resid_at are
-    properties, not fields).
+    and `cloud_resid` int64 [slots] on 8 bytes (their offsets cloud_at, cloud_count_at, cloud_resid_at are properties, not
+    fields), and -- fit steps -- `fit_mesh` fp32 [slots,V,3], `fit_xyz` fp32 [slots,21,3], `fit_rt` fp32 [slots,12]
+    and `fit_count` int32 [slots,2], each on a dword, and `fit_cost` int64 [slots] on 8 bytes, as the last parts (fit_mesh_at,
+    fit_xyz_at, fit_rt_at, fit_count_at, fit_cost_at: properties too).
     slots = frames for the one-hand step (hands None), frames * hands for the K-hand step.  A part the step does not have takes
     no bytes and its offset is None; every part in front of it stays where a step without the option has it."""
     frames: int
@@ -110,6 +121,7 @@ class LiveLayout:
     tracked: bool = False
     smoothed: bool = False
     occluded: bool = False       # (keyword: the overlay hidden behind nearer scene depth; needs overlay)
+    fit: bool = False            # (keyword: every slot's mesh and joints fitted to the measured depth; needs occluded)
     cloud: int = 0               # (keyword: rows per slot of the hand clouds, 0: none; needs occluded)
     rig: bool = False            # (keyword: the slots in the rig frame, associated across frames and fused; a K-hand step's)
     record_rows: int = field(init=False)
@@ -147,6 +159,8 @@ class LiveLayout:
             raise ValueError(f"cloud: the rows per slot, an integer >= 0 (got {self.cloud!r})")
         if self.cloud and not self.occluded:
             raise ValueError("a cloud step is an occluded step: the clouds are cut out with the silhouette")
+        if self.fit and not self.occluded:
+            raise ValueError("a fit step is an occluded step: the mesh is fitted to the depth pixels under its silhouette")
         if self.rig:
             if self.hands is None:
                 raise ValueError("rig is a K-hand step's option: the rig frame puts the slots of several frames together")
@@ -179,13 +193,18 @@ class LiveLayout:
                                                    ("fused_mesh", self.rig, torch.float32, (s, self.vertices, 3), 4),
                                                    ("cloud", self.cloud, torch.float32, (s, self.cloud, 3), 4),
                                                    ("cloud_count", self.cloud, torch.int32, (s, 2), 4),
-                                                   ("cloud_resid", self.cloud, torch.int64, (s,), 8)):
+                                                   ("cloud_resid", self.cloud, torch.int64, (s,), 8),
+                                                   ("fit_mesh", self.fit, torch.float32, (s, self.vertices, 3), 4),
+                                                   ("fit_xyz", self.fit, torch.float32, (s, SMOOTH_JOINTS, 3), 4),
+                                                   ("fit_rt", self.fit, torch.float32, (s, 12), 4),
+                                                   ("fit_count", self.fit, torch.int32, (s, 2), 4),
+                                                   ("fit_cost", self.fit, torch.int64, (s,), 8)):
             start = None
             if present:
                 start = (end + align - 1) // align * align
                 end = start + math.prod(shape) * dtype.itemsize
                 spans[name] = (start, end, dtype, shape)
-            if name != "records" and name not in CLOUD_FIELDS:
+            if name != "records" and name not in CLOUD_FIELDS + FIT_FIELDS:
                 put(name + "_at", start)
         put("record_rows", rows)
         put("record_bytes", rb)
@@ -203,6 +222,11 @@ class LiveLayout:
     cloud_at = property(lambda self: self._part_at("cloud"))
     cloud_count_at = property(lambda self: self._part_at("cloud_count"))
     cloud_resid_at = property(lambda self: self._part_at("cloud_resid"))
+    fit_mesh_at = property(lambda self: self._part_at("fit_mesh"))
+    fit_xyz_at = property(lambda self: self._part_at("fit_xyz"))
+    fit_rt_at = property(lambda self: self._part_at("fit_rt"))
+    fit_count_at = property(lambda self: self._part_at("fit_count"))
+    fit_cost_at = property(lambda self: self._part_at("fit_cost"))
 
     def views(self, buf) -> LiveViews:
         """The parts of a step's flat uint8 buffer (the device buffer or its pinned copy), typed and shaped; None: not there."""
@@ -214,6 +238,8 @@ class LiveLayout:
             kind = _rig_views(kind)
         if self.cloud:
             kind = _cloud_views(kind)
+        if self.fit:
+            kind = _fit_views(kind)
         return kind(*(cut.get(name) for name in kind._fields))
 
 
@@ -233,6 +259,15 @@ def _read_type(step: str, base: tuple, overlay: bool, labels: bool, side: bool, 
     absent = {f: None for f, on in has.items() if not on and f in ("overlay", "box_label", "pose_label")}
     doc = f"{step}Output.read(): {' '.join(base)}" + "".join(f" + {f}" for f in fields[len(base):]) + "."
     return type(name, (collections.namedtuple(name, fields),), dict(absent, __slots__=(), __doc__=doc))
+
+
+@functools.lru_cache(maxsize=None)
+def _fit_read_type(kind):
+    """The read type of a fit step: the fields of `kind` -- the read type of its step without the option --, then the fit's five."""
+    name = kind.__name__[:-len("Read")] + "FitRead"
+    absent = {f: None for f in ("overlay", "box_label", "pose_label") if f not in kind._fields}
+    doc = kind.__doc__.rstrip(".") + "".join(f" + {f}" for f in FIT_FIELDS) + "."
+    return type(name, (collections.namedtuple(name, kind._fields + FIT_FIELDS),), dict(absent, __slots__=(), __doc__=doc))
 
 
 def _read(step, base, values, layout, v, per_slot=lambda t: t):
@@ -260,7 +295,11 @@ def _read(step, base, values, layout, v, per_slot=lambda t: t):
     if layout.cloud:    # (per slot: [N,K,P,3], [N,K,2], [N,K]; the one-hand step: [N,P,3], [N,2], [N])
         values += (per_slot(v.cloud).clone(), per_slot(v.cloud_count).clone(), per_slot(v.cloud_resid).clone())
         key = key + (False,) * (7 - len(key)) + (True,)
-    return _read_type(step, base, *key)(*values)
+    kind = _read_type(step, base, *key)
+    if layout.fit:      # (per slot: [N,K,V,3], [N,K,21,3], [N,K,12], [N,K,2], [N,K]; the one-hand step without the K)
+        values += tuple(per_slot(getattr(v, f)).clone() for f in FIT_FIELDS)
+        kind = _fit_read_type(kind)
+    return kind(*values)
 
 
 _LIVE_FIELDS = ("keypoints", "has_hand", "crop_box", "words", "more", "mesh")      # the six a plain step always had
@@ -289,13 +328,19 @@ class LiveOutput:
     cloud_count: torch.Tensor = None  # [N,2] int32 (matching pixels, rows written)
     cloud_resid: torch.Tensor = None  # [N] int64 the summed residual depth - mesh Z over all matching pixels, micrometres
     mesh_depth: torch.Tensor = None  # [N,H,W] fp32 the nearest mesh Z per pixel (0: no mesh); the engine's buffer, not in the copy
+    fit_mesh: torch.Tensor = None    # fit steps, on the device: [N,V,3] fp32 the mesh fitted to the measured depth
+    fit_xyz: torch.Tensor = None     # [N,21,3] fp32 the joints moved with it, camera millimetres
+    fit_rt: torch.Tensor = None      # [N,12] fp32 R row-major, then t (metres): the motion about the root joint, camera frame
+    fit_count: torch.Tensor = None   # [N,2] int32 (matching pixels, status: 0 fitted, 1 too few, 2 no solution, 3 beyond the caps)
+    fit_cost: torch.Tensor = None    # [N] int64 the summed squared residual along the normals, 2^-30 m^2
 
     def read(self):
         """After the stream is synchronised: (keypoints, has_hand, crop_box, range words, [image_uvd, xyz_mm], mesh) as fresh CPU
         tensors (LiveRead; `.overlay`, `.box_label`, `.pose_label` are None).  A step with faces= appends the overlay [N,H,W,3]
         uint8 (LiveOverlayRead); a step with labels appends box_label [N,H,W,3] and pose_label [N,176,176,3] (LiveLabelsRead,
         LiveOverlayLabelsRead); a step with occlude appends silhouette [N,H,W] uint8 and coverage [N,2] int32; a step with
-        cloud appends cloud [N,P,3] fp32, cloud_count [N,2] int32 and cloud_resid [N] int64 as the last fields."""
+        cloud appends cloud [N,P,3] fp32, cloud_count [N,2] int32 and cloud_resid [N] int64; a step with fit appends fit_mesh
+        [N,V,3], fit_xyz [N,21,3], fit_rt [N,12] fp32, fit_count [N,2] int32 and fit_cost [N] int64 as the last fields."""
         v = self.layout.views(self.host)
         kp, has, box, words, more = read_host_record(v.records, self.layout.frames, extras=True)
         return _read("Live", _LIVE_FIELDS, (kp, has, box, words, more, v.mesh.clone()), self.layout, v)
@@ -317,7 +362,9 @@ class _LiveStep:
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None,
                  labels: bool = False, left: bool = False, occlude: bool = False, occlude_margin: float = ops.OCCLUDE_MARGIN,
                  cloud: bool = False, cloud_points: int = ops.CLOUD_POINTS, cloud_band: float = ops.CLOUD_BAND,
-                 cloud_stride: int = ops.CLOUD_STRIDE):
+                 cloud_stride: int = ops.CLOUD_STRIDE, fit: bool = False, fit_band: float = ops.FIT_BAND,
+                 fit_stride: int = ops.FIT_STRIDE, fit_min_points: int = ops.FIT_MIN_POINTS, fit_damp: float = ops.FIT_DAMP,
+                 fit_max_shift: float = ops.FIT_MAX_SHIFT, fit_max_angle: float = ops.FIT_MAX_ANGLE):
         if not _same_device(hand.device, lifter.device):
             raise ValueError(f"HandNet on {hand.device} but the lifter on {lifter.device}")
         self.hand, self.lifter, self.device = hand, lifter, hand.device
@@ -357,6 +404,14 @@ class _LiveStep:
                 raise ValueError("cloud=True needs occlude=True (and therefore faces= and perm_reverse=): the clouds are cut out "
                                  "with the silhouette")
             self.cloud = ops.check_cloud(cloud_points, cloud_band, cloud_stride)
+        # fit: the step also fits every hand's mesh and joints to the depth pixels under its silhouette (ops.mesh_fit: one
+        # Gauss-Newton step of point-to-plane alignment) -- (band, stride, min_points, damp, max_shift, max_angle), or None
+        self.fit = None
+        if fit:
+            if self.occlude is None:
+                raise ValueError("fit=True needs occlude=True (and therefore faces= and perm_reverse=): the mesh is fitted to the "
+                                 "depth pixels under its silhouette")
+            self.fit = ops.check_fit(fit_band, fit_stride, fit_min_points, fit_damp, fit_max_shift, fit_max_angle)
         # labels: the step ends with the caller's other two images (ops.draw_labels: ros_demo.py:310-326), behind the overlay
         self.labels, self.clamp = bool(labels), bool(clamp)
         # left: the caller's mirror mode (ImageListener(left=True), ros_demo.py:259-262): the step runs on the frame and the
@@ -413,6 +468,16 @@ class _LiveStep:
         return ops.hand_cloud(work[0], silhouette, depth, paras, k, points=points, band=band, stride=stride,
                               extrinsics_table=self.extrinsics if self.cloud_frame == "rig" else None, out=at, scratch=work[1])
 
+    def _fit(self, work, silhouette, depth, mesh, xyz_mm, k, at):
+        """The fit step's last two launches: every slot's mesh and joints moved onto the depth pixels under its silhouette,
+        from the raster's nearest Z, the silhouette, and the depth map, camera table, mesh and joints the step itself used,
+        straight into the copy buffer."""
+        band, stride, min_points, damp, max_shift, max_angle = self.fit
+        paras = self.paras if self.cams is None else self.cams
+        mesh, xyz_mm = mesh.view(-1, self.vertices, 3), xyz_mm.view(-1, SMOOTH_JOINTS, 3)      # (a row per slot)
+        return ops.mesh_fit(work[0], silhouette, depth, paras, mesh, xyz_mm, k, band=band, stride=stride, min_points=min_points,
+                            damp=damp, max_shift=max_shift, max_angle=max_angle, out=at, scratch=work[2])
+
     def _check_frames(self, n):
         if self.cams is not None and n != self.cams.shape[0]:
             raise ValueError(f"a step over {n} frames, but the engine was built with {self.cams.shape[0]} cameras, one per frame")
@@ -446,17 +511,20 @@ class _LiveStep:
         """The buffer of a step over n frames (hw: of a step that draws, the frames' size)."""
         return LiveLayout(n, self.hands, self.vertices, hw, hw is not None and self.faces is not None,
                           hw is not None and self.labels, self.handed, self.track is not None, self.smooth is not None,
-                          occluded=self.occlude is not None, cloud=self.cloud[0] if self.cloud and hw is not None else 0,
-                          rig=self.rig is not None)
+                          occluded=self.occlude is not None, fit=self.fit is not None and hw is not None,
+                          cloud=self.cloud[0] if self.cloud and hw is not None else 0, rig=self.rig is not None)
 
     def _new_buffers(self, n, hw=None):
-        """A fresh (layout, device buffer, pinned host buffer, work) of a step over n frames; work: a cloud step's (mesh depth
-        fp32 [n,h,w], the cloud launches' scratch) on the device -- not part of the copy --, else None."""
+        """A fresh (layout, device buffer, pinned host buffer, work) of a step over n frames; work: a cloud or fit step's (mesh
+        depth fp32 [n,h,w], the cloud launches' scratch or None, the fit launches' scratch or None) on the device -- not part
+        of the copy --, else None."""
         layout = self._layout(n, hw)
         work = None
-        if layout.cloud:
+        if layout.cloud or layout.fit:
+            scratch = lambda nbytes: torch.empty((nbytes,), dtype=torch.uint8, device=self.device)  # noqa: E731
             work = (torch.zeros((n, *hw), dtype=torch.float32, device=self.device),
-                    torch.empty((ops.hand_cloud_scratch_bytes(n, self.hands or 1, hw[0]),), dtype=torch.uint8, device=self.device))
+                    scratch(ops.hand_cloud_scratch_bytes(n, self.hands or 1, hw[0])) if layout.cloud else None,
+                    scratch(ops.mesh_fit_scratch_bytes(n, self.hands or 1, hw[0])) if layout.fit else None)
         return (layout, torch.zeros((layout.nbytes,), dtype=torch.uint8, device=self.device),
                 torch.zeros((layout.nbytes,), dtype=torch.uint8, pin_memory=True), work)
 
@@ -504,6 +572,10 @@ class _LiveStep:
         if layout.cloud:    # (against the mesh the overlay drew and the depth map it was tested against)
             cloud = self._cloud(work, silhouette, depth, k, at)
             more.update(cloud=cloud.cloud, cloud_count=cloud.count, cloud_resid=cloud.resid, mesh_depth=work[0])
+        if layout.fit:      # (the mesh the overlay drew and the joints that go with it: the smoothed signals on a smoothed step)
+            fit = self._fit(work, silhouette, depth, at.smooth_mesh if layout.smoothed else mesh,
+                            at.smooth_xyz if layout.smoothed else out.xyz_mm, k, at)
+            more.update(fit_mesh=fit.mesh, fit_xyz=fit.xyz, fit_rt=fit.rt, fit_count=fit.count, fit_cost=fit.cost, mesh_depth=work[0])
         host.copy_(dev, non_blocking=True)
         return self._output(out, at, layout, host, dict(pose2d=p2d, mesh=mesh, pose3d=pose3d, raw_mesh=raw, overlay=overlay,
                                                         box_label=box_label, pose_label=pose_label, **more))
@@ -513,6 +585,7 @@ class _LiveStep:
         margin -- kernel arguments)."""
         return ((() if self.occlude is None else ("occluded", self.occlude))
                 + (() if self.cloud is None else ("cloud",) + self.cloud + (self.cloud_frame,))
+                + (() if self.fit is None else ("fit",) + self.fit)
                 + (() if self.rig is None else ("rig", self.rig)))
 
     def _smooth_untouched(self, n):
@@ -550,7 +623,7 @@ class _LiveStep:
                 s_dep.copy_(depth)
                 # the capture's own buffers, never the eager cache's (addresses are baked into the graph)
                 bufs = self._new_buffers(images.shape[0], self._hw(self._frames(images)))
-                if bufs[3] is not None:      # (a cloud step's scratch: its address is baked into the graph and nothing the step
+                if bufs[3] is not None:      # (a cloud or fit step's scratch: its address is baked into the graph and nothing the step
                     self._mirrored[("cloud work",) + key] = bufs[3]      # hands out refers to it -- owned like the mirrored inputs)
                 flipped = None
                 if self.left and not _mirrored:
@@ -597,7 +670,18 @@ class LiveHandEngine(_LiveStep):
     order (zero rows behind them), .cloud_count [N,2] (matches, rows written), .cloud_resid [N] int64 the summed D - mesh Z over
     all matches in micrometres, read() likewise as the last fields, in the step's one copy; .mesh_depth [N,H,W] is the nearest
     mesh Z per pixel on the device.  cloud_points = 4096, cloud_band = 0.03 m and cloud_stride = 2 are starting values, NOT
-    tuned on this model."""
+    tuned on this model.
+    fit (needs occlude): the step ends with two more launches (ops.mesh_fit) that fit the hand's mesh to its
+    measured depth -- ONE Gauss-Newton step of projective point-to-plane alignment over the candidates (every fit_stride-th
+    row and column) under the mesh's silhouette whose depth is valid and within fit_band metres of the mesh Z drawn there,
+    damped by fit_damp per match -- and move the mesh and the joints by the rigid motion found: LiveOutput.fit_mesh [N,V,3],
+    .fit_xyz [N,21,3] (camera millimetres), .fit_rt [N,12] (R row-major, then t in metres: x' = R (x - c0) + c0 + t about the
+    root joint c0, camera frame), .fit_count [N,2] (matches, status: 0 fitted; 1 fewer than fit_min_points matches; 2 no
+    solution; 3 a step beyond fit_max_shift metres or fit_max_angle radians -- then R = I, t = 0 and fit_mesh / fit_xyz are
+    byte copies) and .fit_cost [N] int64 (the summed squared residual, 2^-30 m^2), read() likewise as the last fields, in the
+    step's one copy.  The overlay, the silhouette and the cloud are NOT redrawn from the fitted mesh.  fit_band = 0.03 m,
+    fit_stride = 2, fit_min_points = 200, fit_damp = 1e-3, fit_max_shift = 0.05 m and fit_max_angle = 0.35 rad are starting
+    values, NOT tuned on this model."""
 
     def _hand_step(self, images, depth, at, lift):
         return self.hand.forward_device(images, depth, _record=(None, at.records), _tail=lift)
@@ -655,6 +739,11 @@ class LiveHandsOutput:
     cloud_count: torch.Tensor = None  # [N,K,2] int32 (matching pixels, rows written)
     cloud_resid: torch.Tensor = None  # [N,K] int64 the summed residual depth - mesh Z over all matching pixels, micrometres
     mesh_depth: torch.Tensor = None  # [N,H,W] fp32 the nearest mesh Z per pixel (0: no mesh); the engine's buffer, not in the copy
+    fit_mesh: torch.Tensor = None    # fit steps, on the device: [N,K,V,3] fp32 the mesh fitted to the measured depth
+    fit_xyz: torch.Tensor = None     # [N,K,21,3] fp32 the joints moved with it, camera millimetres
+    fit_rt: torch.Tensor = None      # [N,K,12] fp32 R row-major, then t (metres): the motion about the root joint, camera frame
+    fit_count: torch.Tensor = None   # [N,K,2] int32 (matching pixels, status: 0 fitted, 1 too few, 2 no solution, 3 beyond the caps)
+    fit_cost: torch.Tensor = None    # [N,K] int64 the summed squared residual along the normals, 2^-30 m^2
     smooth_xyz: torch.Tensor = None  # smoothed steps: [N,K,21,3] on the device, xyz_mm filtered over time (zeros: has_hand != 1)
     smooth_mesh: torch.Tensor = None  # smoothed steps: [N,K,V,3] on the device, `mesh` filtered over time (zeros: not lifted)
 
@@ -667,7 +756,8 @@ class LiveHandsOutput:
         behind everything else, silhouette [N,H,W] uint8 and coverage [N,K,2] int32; a rig step: behind those, rig_xyz
         [N,K,21,3], rig_mesh [N,K,V,3], rig_hand [N,K] int32, rig_count (a Python int), rig_views and rig_seed [N*K] int32,
         fused_xyz [N*K,21,3] and fused_mesh [N*K,V,3]; a cloud step: behind those, cloud [N,K,P,3] fp32, cloud_count [N,K,2]
-        int32 and cloud_resid [N,K] int64)."""
+        int32 and cloud_resid [N,K] int64; a fit step: behind those, fit_mesh [N,K,V,3], fit_xyz [N,K,21,3], fit_rt [N,K,12]
+        fp32, fit_count [N,K,2] int32 and fit_cost [N,K] int64)."""
         v, s = self.layout.views(self.host), self.layout.slots
         per = lambda t: t.reshape((self.layout.frames, self.layout.hands) + tuple(t.shape[1:]))
         kp, has, box, words, (img, xyz) = read_host_record(v.records, s, extras=True)
@@ -690,7 +780,10 @@ class LiveHandsEngine(_LiveStep):
                  left_side: int = 0, track: bool = False, track_iou: float = 0.3, track_hold: int = 5, occlude: bool = False,
                  occlude_margin: float = ops.OCCLUDE_MARGIN, extrinsics=None, rig_radius: float = ops.RIG_RADIUS,
                  cloud: bool = False, cloud_points: int = ops.CLOUD_POINTS, cloud_band: float = ops.CLOUD_BAND,
-                 cloud_stride: int = ops.CLOUD_STRIDE, cloud_frame: str = "camera", smooth: bool = False, smooth_min_cutoff: float = 1.0, smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0,
+                 cloud_stride: int = ops.CLOUD_STRIDE, cloud_frame: str = "camera", fit: bool = False,
+                 fit_band: float = ops.FIT_BAND, fit_stride: int = ops.FIT_STRIDE, fit_min_points: int = ops.FIT_MIN_POINTS,
+                 fit_damp: float = ops.FIT_DAMP, fit_max_shift: float = ops.FIT_MAX_SHIFT,
+                 fit_max_angle: float = ops.FIT_MAX_ANGLE, smooth: bool = False, smooth_min_cutoff: float = 1.0, smooth_beta: float = 0.007, smooth_d_cutoff: float = 1.0,
                  smooth_rate: float = 30.0):
         """paras: as LiveHandEngine's -- with a camera per frame [N,4], all K slots of frame i use row i.
         faces: mesh_model.face ([F,3]; needs perm_reverse) -- given, the step ends with the overlay: every lifted mesh of a
@@ -748,7 +841,14 @@ class LiveHandsEngine(_LiveStep):
         .mesh_depth [N,H,W] is the nearest mesh Z per pixel on the device.  cloud_frame="rig" (needs extrinsics=) hands the
         points out in the rig frame.  A `left` step cuts the mirrored depth map, a smoothed step works against the smoothed
         mesh it draws.  cloud_points = 4096, cloud_band = 0.03 m and cloud_stride = 2 are starting values, NOT tuned on this
-        model."""
+        model.
+        fit (needs occlude): as LiveHandEngine's, per slot against the frame's one depth map and with the frame's
+        camera: LiveHandsOutput.fit_mesh [N,K,V,3], .fit_xyz [N,K,21,3], .fit_rt [N,K,12], .fit_count [N,K,2] (matches, status)
+        and .fit_cost [N,K] int64, read() likewise behind every other field, in the step's one copy.  Only pixels whose own and
+        whose four neighbours' silhouette bytes name the slot enter, so a slot's border with another hand does not.  A `left`
+        step fits to the mirrored depth map, a smoothed step moves the smoothed mesh and joints it draws; the rig outputs, the
+        overlay and the cloud stay what they are.  fit_band = 0.03 m, fit_stride = 2, fit_min_points = 200, fit_damp = 1e-3,
+        fit_max_shift = 0.05 m and fit_max_angle = 0.35 rad are starting values, NOT tuned on this model."""
         self.hands = self.max_hands = ops.check_max_hands(max_hands)
         if left and handed:
             raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
@@ -780,7 +880,8 @@ class LiveHandsEngine(_LiveStep):
             raise ValueError('cloud_frame="rig" needs extrinsics=: the camera -> rig transforms the points go through')
         self.cloud_frame = cloud_frame
         super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left, occlude, occlude_margin, cloud,
-                         cloud_points, cloud_band, cloud_stride)
+                         cloud_points, cloud_band, cloud_stride, fit, fit_band, fit_stride, fit_min_points, fit_damp, fit_max_shift,
+                         fit_max_angle)
         if table is not None:
             if self.cams is not None and self.cams.shape[0] != table.shape[0]:
                 raise ValueError(f"{table.shape[0]} extrinsics for a step built with {self.cams.shape[0]} cameras: one [R | t] per "
@@ -882,6 +983,10 @@ class LiveHandsEngine(_LiveStep):
         if "cloud" in parts:
             parts.update(cloud=parts["cloud"].view(n, k, -1, 3), cloud_count=parts["cloud_count"].view(n, k, 2),
                          cloud_resid=parts["cloud_resid"].view(n, k))
+        if "fit_mesh" in parts:
+            parts.update(fit_mesh=parts["fit_mesh"].view(n, k, self.vertices, 3), fit_xyz=parts["fit_xyz"].view(n, k, SMOOTH_JOINTS, 3),
+                         fit_rt=parts["fit_rt"].view(n, k, 12), fit_count=parts["fit_count"].view(n, k, 2),
+                         fit_cost=parts["fit_cost"].view(n, k))
         return LiveHandsOutput(hands=out, lifted=at.lifted.view(n, k), host=host, n=n, k=k, side=out.side, mirror=out.mirror,
                                layout=layout, track_id=out.track_id, track_age=out.track_age,
                                smooth_xyz=None if self.smooth is None else at.smooth_xyz.view(n, k, SMOOTH_JOINTS, 3),

@@ -2260,6 +2260,127 @@ def hand_cloud(mesh_depth, silhouette, scene_depth, paras, k, *, points=CLOUD_PO
     return HandCloud(*parts)
 
 
+FIT_BAND = 0.03            # metres between the measured depth and the mesh Z; a starting value, NOT tuned on this model
+FIT_STRIDE = 2             # every second row and column is a candidate; a starting value, NOT tuned on this model
+FIT_MIN_POINTS = 200       # fewer matches: the slot is left as it is; a starting value, NOT tuned on this model
+FIT_DAMP = 1e-3            # Levenberg damping per match; a starting value, NOT tuned on this model
+FIT_MAX_SHIFT = 0.05       # metres: a larger step is refused; a starting value, NOT tuned on this model
+FIT_MAX_ANGLE = 0.35       # radians: a larger step is refused; a starting value, NOT tuned on this model
+FIT_MAX_BAND = 100.0       # metres
+
+MeshFit = collections.namedtuple("MeshFit", "mesh xyz rt count cost")
+
+
+def check_fit(band=FIT_BAND, stride=FIT_STRIDE, min_points=FIT_MIN_POINTS, damp=FIT_DAMP, max_shift=FIT_MAX_SHIFT,
+              max_angle=FIT_MAX_ANGLE):
+    """A mesh fit's six parameters as (float band, int stride >= 1, int min_points >= 1, float damp >= 0, float max_shift > 0,
+    float max_angle in (0, pi)), the band finite and in (0, 100] metres also as the fp32 kernel argument it becomes; else
+    ValueError.  The defaults (0.03 m, every second row and column, 200 matches, 1e-3, 0.05 m, 0.35 rad) are starting values,
+    NOT tuned on this model."""
+    for name, value in (("fit_stride", stride), ("fit_min_points", min_points)):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= 2 ** 31 - 1:
+            raise ValueError(f"{name}: an integer >= 1 (got {value!r})")
+
+    def number(value):
+        try:
+            return math.nan if isinstance(value, bool) else float(value)
+        except (TypeError, ValueError):
+            return math.nan
+    b, lam, shift, angle = number(band), number(damp), number(max_shift), number(max_angle)
+    with np.errstate(over="ignore"):
+        g = float(np.float32(b))
+    if not (math.isfinite(b) and 0.0 < g <= FIT_MAX_BAND and b <= FIT_MAX_BAND):
+        raise ValueError(f"fit_band: a finite number of metres in (0, {FIT_MAX_BAND:g}] as fp32 (got {band!r})")
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError(f"fit_damp: a finite number >= 0 (got {damp!r})")
+    if not (math.isfinite(shift) and shift > 0.0 and math.isfinite(shift * shift) and shift * shift > 0.0):
+        raise ValueError(f"fit_max_shift: a finite number of metres > 0 whose square is finite and > 0 (got {max_shift!r})")
+    if not (math.isfinite(angle) and 0.0 < angle < math.pi and 0.0 < math.tan(angle / 2.0) ** 2 < math.inf):
+        raise ValueError(f"fit_max_angle: radians in (0, pi) (got {max_angle!r})")
+    return b, int(stride), int(min_points), lam, shift, angle
+
+
+def fit_caps(max_shift, max_angle):
+    """the two caps as the doubles the kernel takes: max_shift^2 and tan^2(max_angle / 2)"""
+    half = math.tan(max_angle / 2.0)
+    return max_shift * max_shift, half * half
+
+
+def mesh_fit_scratch_bytes(frames, k, h):
+    return int(_lib.load().hn_mesh_fit_scratch_bytes(frames, k, h))
+
+
+def mesh_fit(mesh_depth, silhouette, scene_depth, paras, mesh, xyz_mm, k, *, band=FIT_BAND, stride=FIT_STRIDE,
+             min_points=FIT_MIN_POINTS, damp=FIT_DAMP, max_shift=FIT_MAX_SHIFT, max_angle=FIT_MAX_ANGLE, out=None,
+             scratch=None) -> MeshFit:
+    """Each hand's mesh fitted to its measured depth: one Gauss-Newton step of projective point-to-plane alignment per hand
+    slot (hn_mesh_fit_f32: two launches, csrc/mesh_fit.hip; DESIGN.md section 9k, tests/fit_ref.py is the rule and the outputs
+    equal it bit for bit).  mesh_depth fp32 [N,H,W], silhouette uint8 [N,H,W], scene_depth and paras: as hand_cloud takes
+    them; mesh fp32 [N*k,V,3]: the meshes the raster drew (metres, (x, -y, -z) of the camera point); xyz_mm fp32 [N*k,J,3]:
+    camera millimetres, joint 0 the root the motion turns about; k slots per frame (1..16).
+    A pixel (r, c) off the frame's border with r % stride == 0 and c % stride == 0 matches slot j of frame i when
+    (silhouette & 0x7F) == j + 1 there and at its four neighbours, mesh_depth > 0 at all five, its depth D is finite and > 0,
+    |D - mesh_depth| <= band metres, its normal (from mesh_depth) is not seen at a grazing angle and its lever and residual
+    are bounded.  The damped (damp per match) normal equations are summed as integers and solved in fp64.  Returns MeshFit:
+    mesh fp32 [N*k,V,3] and xyz fp32 [N*k,J,3] -- moved by x' = R (x - c0) + c0 + t, c0 the root joint --, rt fp32 [N*k,12] = R
+    row-major, then t (metres, camera frame), count int32 [N*k,2] = (matches, status: 0 fitted, 1 fewer than min_points
+    matches, 2 no solution, 3 beyond max_shift metres or max_angle radians; != 0: R = I, t = 0, mesh and xyz are byte copies),
+    cost int64 [N*k] = the summed squared residual in 2^-30 m^2 (RMS = sqrt(cost / 2^30 / matches)).
+    Allocated, or `out`'s attributes fit_mesh / fit_xyz / fit_rt / fit_count / fit_cost (the live step's buffer views), every
+    one fully written.  band = 0.03 m, stride = 2, min_points = 200, damp = 1e-3, max_shift = 0.05 m and max_angle = 0.35 rad
+    are starting values, NOT tuned on this model."""
+    band, stride, min_points, damp, max_shift, max_angle = check_fit(band, stride, min_points, damp, max_shift, max_angle)
+    _req(mesh_depth, name="mesh_depth"); _req(silhouette, torch.uint8, "silhouette"); _req(scene_depth, name="scene_depth")
+    _req(mesh, name="mesh"); _req(xyz_mm, name="xyz_mm")
+    if silhouette.dim() != 3:
+        raise ValueError(f"silhouette: expected uint8 [N,H,W], got {tuple(silhouette.shape)}")
+    n, h, w = (int(v) for v in silhouette.shape)
+    if mesh_depth.numel() != n * h * w:
+        raise ValueError(f"mesh_depth: expected fp32 [{n},{h},{w}], got {tuple(mesh_depth.shape)}")
+    k = int(k)
+    if not 1 <= k <= 16:
+        raise ValueError(f"the silhouette's byte holds at most 16 slots per frame (k = {k})")
+    s = n * k
+    if mesh.dim() != 3 or mesh.shape[0] != s or mesh.shape[2] != 3 or mesh.shape[1] < 1:
+        raise ValueError(f"mesh: expected fp32 [{s},V,3], got {tuple(mesh.shape)}")
+    if xyz_mm.dim() != 3 or xyz_mm.shape[0] != s or xyz_mm.shape[2] != 3 or xyz_mm.shape[1] < 1:
+        raise ValueError(f"xyz_mm: expected fp32 [{s},J,3], got {tuple(xyz_mm.shape)}")
+    v, joints = int(mesh.shape[1]), int(xyz_mm.shape[1])
+    for name, t in (("mesh_depth", mesh_depth), ("scene_depth", scene_depth), ("mesh", mesh), ("xyz_mm", xyz_mm)):
+        if t.device != silhouette.device:
+            raise ValueError(f"{name} on {t.device} but the silhouette on {silhouette.device}")
+    shape = tuple(scene_depth.shape)
+    if shape not in ((n, 1, h, w), (n, h, w), (n, 4, h, w)):
+        raise ValueError(f"scene_depth: expected fp32 [{n},1,{h},{w}], [{n},{h},{w}] or RGBD [{n},4,{h},{w}], got {shape}")
+    rgbd = len(shape) == 4 and shape[1] == 4
+    depth_ptr = scene_depth.data_ptr() + (3 * h * w * 4 if rgbd else 0)
+    host4 = table = None
+    if torch.is_tensor(paras) and paras.dim() != 1:
+        if paras.dtype != torch.float32 or tuple(paras.shape) != (n, 4):
+            raise ValueError(f"paras: a camera per frame is fp32 [{n},4] (fx, fy, cx, cy), got {paras.dtype} {tuple(paras.shape)}")
+        if paras.device != silhouette.device:
+            raise ValueError(f"paras on {paras.device} but the silhouette on {silhouette.device}")
+        table = ptr(_req(paras, torch.float32, "paras"))
+    else:
+        host4 = (C.c_float * 4)(*[float(x) for x in paras])
+    parts = []
+    for name, dtype, shp in (("fit_mesh", torch.float32, (s, v, 3)), ("fit_xyz", torch.float32, (s, joints, 3)),
+                             ("fit_rt", torch.float32, (s, 12)), ("fit_count", torch.int32, (s, 2)), ("fit_cost", torch.int64, (s,))):
+        t = torch.empty(shp, device=silhouette.device, dtype=dtype) if out is None else getattr(out, name)
+        if _req(t, dtype, name).numel() != math.prod(shp):
+            raise ValueError(f"{name}: expected {dtype} {list(shp)}, got {tuple(t.shape)}")
+        parts.append(t.view(shp))
+    need = mesh_fit_scratch_bytes(n, k, h)
+    if scratch is None:
+        scratch = torch.empty((need,), device=silhouette.device, dtype=torch.uint8)
+    _req(scratch, torch.uint8, "scratch")
+    shift2, tan2 = fit_caps(max_shift, max_angle)
+    check(_lib.load().hn_mesh_fit_f32(ptr(mesh_depth), ptr(silhouette), depth_ptr, (4 if rgbd else 1) * h * w, host4, table,
+                                      ptr(mesh), ptr(xyz_mm), n, k, h, w, v, joints, stride, band, min_points, damp, shift2, tan2,
+                                      ptr(scratch), scratch.numel(), *(ptr(t) for t in parts), _stream()), "hn_mesh_fit_f32")
+    return MeshFit(*parts)
+
+
 LABEL_CROP = 176      # side of a pose_label image
 
 

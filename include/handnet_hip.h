@@ -37,8 +37,8 @@ extern "C" {
  * hn_ingest_u8bgr_u16mm_flip, hn_flip_w_f32, hn_crop_resize_hands_sided, hn_a2j_aggregate_convert_mirror_f32,
  * hn_lifter_input_gated_mirror_f32 and hn_mesh_finish_mirror_f32, the tracked slots' hn_crop_resize_hands_tracked and
  * hn_track_state_bytes, the smoothed step's hn_mesh_finish_smooth_f32 and hn_smooth_state_bytes, the per-frame cameras'
- * hn_mesh_render_cams_u8 and hn_mesh_render_cams_occluded_u8, the rig frame's hn_rig_fuse_f32, and the hand cloud's
- * hn_hand_cloud_f32 and hn_hand_cloud_scratch_bytes). */
+ * hn_mesh_render_cams_u8 and hn_mesh_render_cams_occluded_u8, the rig frame's hn_rig_fuse_f32, the hand cloud's
+ * hn_hand_cloud_f32 and hn_hand_cloud_scratch_bytes, and the mesh fit's hn_mesh_fit_f32 and hn_mesh_fit_scratch_bytes). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -876,6 +876,30 @@ int hn_hand_cloud_f32(const float* mesh_depth, const uint8_t* silhouette, const 
                       const float* extrinsics /* device [n][12] or NULL: camera frame */, int n, int k, int h, int w, int points,
                       int stride, float band, void* scratch, int64_t scratch_bytes, float* out_cloud, int32_t* out_count,
                       int64_t* out_resid, void* stream);
+/* Each hand's mesh fitted to its measured depth: ONE Gauss-Newton step of projective point-to-plane alignment per hand slot
+ * (tests/fit_ref.py is the rule in numpy, and the outputs equal it bit for bit: one rounding per fp32 and
+ * fp64 operation, integer sums, no atomics).  mesh_depth, silhouette, scene_depth, depth_frame_stride, paras / cams: as
+ * hn_hand_cloud_f32 takes them (exactly one of paras -- HOST, 4 floats -- and cams -- DEVICE [n][4]).  mesh DEVICE [n*k][v][3]: the
+ * meshes the raster drew (metres, (x, -y, -z) of the camera point); xyz_mm DEVICE [n*k][joints][3]: camera millimetres (x right, y
+ * down, z forward); joint 0 is the root the motion turns about.  A pixel (r, c), 1 <= r <= h - 2, 1 <= c <= w - 2, r % stride == 0
+ * and c % stride == 0, matches slot j of frame i when (silhouette & 0x7F) == j + 1 there and at its four neighbours, mesh_depth > 0
+ * at all five, D = scene_depth is finite and > 0, |D - mesh_depth| <= band, and its normal (from mesh_depth), lever and residual
+ * pass the rule's bounds.  The 6 x 6 normal equations are damped by damp * matches (rotation rows: times 0.1^2 m^2), solved in
+ * fp64; a step with fewer than min_points matches (status 1), a failed pivot or a non-finite solution (2) or a motion beyond
+ * max_shift2 = max_shift^2 (metres^2) or tan2_half_angle = tan^2(max_angle / 2) (3) leaves the slot as it is.
+ *   out_mesh [n*k][v][3], out_xyz [n*k][joints][3]   the moved mesh and joints (status != 0: byte copies of the inputs)
+ *   out_rt [n*k][12]      R row-major, then t: x' = R (x - c0) + c0 + t in the camera frame, c0 = the root joint in metres
+ *   out_count [n*k][2]    (matches, status)
+ *   out_cost [n*k]        the sum of rint(rho^2 * 2^30) over the matches, int64: RMS = sqrt(cost / 2^30 / matches) metres
+ * Every output is fully written.  Two launches on `stream`; every argument is checked before the first (k 1..16, h and w
+ * 1..16384, v 1..2^24, joints 1..4096, stride and min_points >= 1, 0 < band <= 100, damp >= 0 and finite, both caps finite and > 0,
+ * scratch of hn_mesh_fit_scratch_bytes(n, k, h) bytes, 8-byte aligned). */
+int64_t hn_mesh_fit_scratch_bytes(int n, int k, int h);
+int hn_mesh_fit_f32(const float* mesh_depth, const uint8_t* silhouette, const float* scene_depth, int64_t depth_frame_stride,
+                    const float* paras /* host, or NULL */, const float* cams /* device [n][4], or NULL */, const float* mesh,
+                    const float* xyz_mm, int n, int k, int h, int w, int v, int joints, int stride, float band, int min_points,
+                    double damp, double max_shift2, double tan2_half_angle, void* scratch, int64_t scratch_bytes, float* out_mesh,
+                    float* out_xyz, float* out_rt, int32_t* out_count, int64_t* out_cost, void* stream);
 /* A Linear layer on 1..4 rows as a matrix-vector product on the vector ALU (PoseNet at the live caller's batch, posenet.py:24-41,
  * 78-88: 67 MB of filter bank per 17 M MACs): y[m][:] = act(W (pre(x[m])) + bias (+ residual[m])), pre = relu(x * scale + shift)
  * when scale / shift ([k_real] fp32: the pre-activation BatchNorm) are given.  x fp32 [batch][x_stride] (k_real columns used), w16 =
