@@ -37,8 +37,11 @@ depth - mesh Z in millimetres (how far the mesh sits from the surface the camera
 With --fit the last frame also goes through the K = 2 step with faces=, occlude=True and fit=True: every slot's mesh and joints
 moved onto its measured depth pixels by one Gauss-Newton step of point-to-plane alignment (starting values, not tuned) -- per
 slot, the matching pixels, the status, the RMS residual along the normals before the step and the shift found, in millimetres.
+--fit-iters I (1..8) runs I such steps, the moved mesh drawn again before every further one, and prints every step's matches,
+status and RMS residual (the trace); --fit-draw draws the overlay and the silhouette from the fitted mesh and prints how many
+silhouette pixels that changed.  Both imply --fit.
 usage (GPU box): python examples/live_demo.py [frames] [--overlay out.png] [--mano MANO_RIGHT.pkl] [--labels PREFIX] [--left]
-                 [--handed] [--track] [--smooth] [--occlude] [--cameras N] [--rig] [--cloud] [--fit]"""
+                 [--handed] [--track] [--smooth] [--occlude] [--cameras N] [--rig] [--cloud] [--fit] [--fit-iters I] [--fit-draw]"""
 import sys
 import time
 import types
@@ -71,14 +74,16 @@ def _faces(mano_file):
 def main():
     argv = sys.argv[1:]
     opt = {}
-    for flag in ("--overlay", "--mano", "--labels", "--cameras"):
+    for flag in ("--overlay", "--mano", "--labels", "--cameras", "--fit-iters"):
         if flag in argv:
             i = argv.index(flag)
             opt[flag] = argv[i + 1]
             del argv[i:i + 2]
     left, handed, track, smooth = "--left" in argv, "--handed" in argv, "--track" in argv, "--smooth" in argv
     occlude, rig_frame, cloud, fit = "--occlude" in argv, "--rig" in argv, "--cloud" in argv, "--fit" in argv
-    argv = [a for a in argv if a not in ("--left", "--handed", "--track", "--smooth", "--occlude", "--rig", "--cloud", "--fit")]
+    fit_iters, fit_draw = int(opt.get("--fit-iters", 1)), "--fit-draw" in argv
+    fit = fit or fit_draw or "--fit-iters" in opt
+    argv = [a for a in argv if a not in ("--left", "--handed", "--track", "--smooth", "--occlude", "--rig", "--cloud", "--fit", "--fit-draw")]
     frames = int(argv[0]) if argv else 20
     faces = _faces(opt.get("--mano")) if "--overlay" in opt else None
     args = types.SimpleNamespace(pretrained_fcos="-", pretrained_a2j="-")
@@ -221,7 +226,8 @@ def main():
                   f"{[round(float(v), 4) for v in r8.cloud[0, 0, 0]]}")
         if fit:                                                                           # each hand's mesh moved onto its depth pixels
             fitted = net.live_hands(model, PARAS, max_hands=2, clamp=True, perm_reverse=rev,
-                                    faces=faces if faces is not None else _faces(opt.get("--mano")), occlude=True, fit=True)
+                                    faces=faces if faces is not None else _faces(opt.get("--mano")), occlude=True, fit=True,
+                                    fit_iters=fit_iters, fit_draw=fit_draw)
             o9 = fitted.forward_device(s_img, s_dep)
             torch.cuda.current_stream().synchronize()
             r9 = o9.read()
@@ -230,6 +236,16 @@ def main():
                 rms = f"{1000.0 * (cost / 2 ** 30 / matches) ** 0.5:.2f} mm" if matches else "-"
                 print(f"13. fit, slot {k}: {matches} matching pixels, {words[status]}, RMS residual before {rms}, shift (mm) "
                       f"{[round(1000.0 * float(v), 2) for v in r9.fit_rt[0, k, 9:]]}")
+                for t, (m, st, c) in enumerate(r9.fit_trace[0, k].tolist() if fit_iters > 1 else ()):
+                    print(f"    step {t + 1}: {m} matching pixels, {words[st]}, RMS residual before "
+                          + (f"{1000.0 * (c / 2 ** 30 / m) ** 0.5:.2f} mm" if m else "-"))
+            if fit_draw:
+                plain = net.live_hands(model, PARAS, max_hands=2, clamp=True, perm_reverse=rev, faces=fitted.faces.cpu().numpy(),
+                                       occlude=True, fit=True, fit_iters=fit_iters).forward_device(s_img, s_dep)
+                torch.cuda.current_stream().synchronize()
+                moved = int((plain.read().silhouette != r9.silhouette).sum())
+                print(f"    fit_draw: overlay and silhouette are drawn from the fitted mesh; {moved} silhouette pixels differ from "
+                      "the unfitted mesh's")
 
 
 if __name__ == "__main__":

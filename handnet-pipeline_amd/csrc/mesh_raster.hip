@@ -25,6 +25,11 @@
 // The per-frame cameras (hn_mesh_render_cams_u8 / _cams_occluded_u8; DESIGN.md "A camera per frame", tests/cams_ref.py) are a
 // second compile-time switch, of the setup kernel alone: slot s of a step with k slots per frame reads row s / k of a device
 // table [frames][4] where the other instantiations read four scalar arguments.  The projection and the tile kernel are the same.
+//
+// The geometry pass (hn_mesh_geometry_f32; DESIGN.md section 9l, tests/refit_ref.py::geometry) is a third tile kernel behind the
+// same setup launch: mesh_geometry_tiles makes the same slot walk, box test, ballot walk and edge functions and keeps the nearest
+// Z and its slot, and that is all it writes -- fp32 Z (0: nothing drawn) and the byte slot + 1 (0: nothing drawn) per pixel.  It
+// reads no frame and no scene depth and stores no image: what the iterated fit needs to see its moved mesh again.
 #include "hn_common.h"
 
 #include <type_traits>
@@ -295,6 +300,55 @@ __global__ __launch_bounds__(256) void mesh_raster_tiles(const unsigned char* __
   if (depth_out) depth_out[pix] = covered ? best : 0.f;
 }
 
+// The geometry pass: the walk of mesh_raster_tiles, the nearest Z and its slot, nothing else.  Every pixel of the frame is
+// written on every call.
+__global__ __launch_bounds__(256) void mesh_geometry_tiles(const unsigned char* __restrict__ scratch, int slots, int f, int k, int h,
+                                                           int w, float* __restrict__ out_depth,
+                                                           unsigned char* __restrict__ out_who) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int tx = (blockIdx.x * 4 + wave) * 8, ty = blockIdx.y * 8, n = blockIdx.z;
+  if (tx >= w) return;                                        // (wave-uniform)
+  const int col = tx + (lane & 7), row = ty + (lane >> 3);
+  const bool inside_frame = col < w && row < h;
+  const int px = col * kSub + kHalf, py = row * kSub + kHalf;
+  const FaceRec* all_recs = reinterpret_cast<const FaceRec*>(scratch + rec_offset(slots));
+  const Box* all_boxes = reinterpret_cast<const Box*>(scratch + box_offset(slots, f));
+  float best = 3.402823466e38f;
+  int who = 0;                                                // 0, or the nearest face's slot within the frame + 1
+  for (int kk = 0; kk < k; ++kk) {
+    const int slot = n * k + kk;
+    const SlotBox sb = *reinterpret_cast<const SlotBox*>(scratch + (size_t)slot * sizeof(SlotBox));
+    if (sb.x0 > tx + 7 || sb.x1 < tx || sb.y0 > ty + 7 || sb.y1 < ty) continue;      // (wave-uniform)
+    const FaceRec* recs = all_recs + (size_t)slot * f;
+    const Box* boxes = all_boxes + (size_t)slot * f;
+    for (int base = 0; base < f; base += 64) {
+      bool hit = false;
+      if (base + lane < f) {
+        const Box b = boxes[base + lane];
+        hit = b.x0 <= tx + 7 && b.x1 >= tx && b.y0 <= ty + 7 && b.y1 >= ty;
+      }
+      unsigned long long todo = __ballot(hit);
+      while (todo) {                                          // ascending face order: the lower index wins an exact tie
+        const int bit = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const FaceRec r = recs[__builtin_amdgcn_readfirstlane(base + bit)];
+        bool in = inside_frame;
+        const long long wa = edge(r.bx, r.by, r.cx, r.cy, px, py, in);
+        const long long wb = edge(r.cx, r.cy, r.ax, r.ay, px, py, in);
+        const long long wc = edge(r.ax, r.ay, r.bx, r.by, px, py, in);
+        if (in) {
+          const float z = ((float)wa * r.za + (float)wb * r.zb + (float)wc * r.zc) * r.inv_area;
+          if (z < best) { best = z; who = kk + 1; }
+        }
+      }
+    }
+  }
+  if (!inside_frame) return;
+  const size_t pix = ((size_t)n * h + row) * w + col;
+  out_depth[pix] = who ? best : 0.f;
+  out_who[pix] = (unsigned char)who;
+}
+
 }  // namespace
 
 extern "C" int64_t hn_mesh_render_scratch_bytes(int s, int f) {
@@ -405,4 +459,39 @@ extern "C" int hn_mesh_render_cams_occluded_u8(const float* mesh, const int32_t*
   const Occlusion occ = {scene_depth, (long long)depth_frame_stride, margin, out_silhouette, out_coverage};
   return render("hn_mesh_render_cams_occluded_u8", mesh, faces, faces_host, lifted, s, v, f, k, nullptr, cams, frame, frame_format,
                 h, w, scratch, scratch_bytes, out_image, out_depth, &occ, depth_frame_stride, stream);
+}
+
+// the geometry pass: render()'s argument checks without a frame, an image or a scene depth, the setup launch as it is, and
+// mesh_geometry_tiles in place of the raster
+extern "C" int hn_mesh_geometry_f32(const float* mesh, const int32_t* faces, const int32_t* faces_host, const int32_t* lifted, int s,
+                                    int v, int f, int k, const float* paras, const float* cams, int h, int w, void* scratch,
+                                    int64_t scratch_bytes, float* out_depth, uint8_t* out_who, void* stream) {
+  const char* fn = "hn_mesh_geometry_f32";
+  HN_CHECK_ARG(mesh && faces && scratch && out_depth && out_who, "%s: null pointer", fn);
+  HN_CHECK_ARG((paras != nullptr) != (cams != nullptr), "%s: exactly one of paras (host) and cams (device) must be given", fn);
+  HN_CHECK_ARG(s > 0 && v > 0 && f > 0, "%s: bad dims (s %d, v %d, f %d: all must be positive)", fn, s, v, f);
+  HN_CHECK_ARG(k > 0 && s % k == 0, "%s: %d slots are not a multiple of k = %d slots per frame", fn, s, k);
+  HN_CHECK_ARG(k <= 16, "%s: k = %d slots per frame do not fit the slot byte (1..16)", fn, k);
+  HN_CHECK_ARG(h > 0 && w > 0 && h <= 16384 && w <= 16384, "%s: bad frame size %d x %d (1..16384)", fn, h, w);
+  HN_CHECK_ARG(s / k <= 65535, "%s: more than 65535 frames", fn);
+  HN_CHECK_ARG(scratch_bytes >= (int64_t)scratch_total(s, f), "%s: scratch of %lld bytes, %lld needed", fn,
+               (long long)scratch_bytes, (long long)scratch_total(s, f));
+  HN_CHECK_ARG(((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", fn);
+  HN_CHECK_ARG(!cams || ((uintptr_t)cams & 3) == 0, "%s: cams must be aligned to a float", fn);
+  HN_CHECK_ARG(((uintptr_t)out_depth & 3) == 0, "%s: out_depth must be aligned to a float", fn);
+  if (faces_host)
+    for (int64_t i = 0; i < (int64_t)f * 3; ++i)
+      HN_CHECK_ARG(faces_host[i] >= 0 && faces_host[i] < v, "%s: face %lld uses vertex %d of %d", fn, (long long)(i / 3),
+                   faces_host[i], v);
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* sc = static_cast<unsigned char*>(scratch);
+  if (cams)
+    hipLaunchKernelGGL((mesh_raster_setup<true>), dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, cams, k, 0.f, 0.f, h, w, sc, s);
+  else
+    hipLaunchKernelGGL((mesh_raster_setup<false>), dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, paras[0], paras[1], paras[2], paras[3], h, w, sc, s);
+  HN_CHECK_LAUNCH("mesh_raster_setup");
+  hipLaunchKernelGGL(mesh_geometry_tiles, dim3((w + 31) / 32, (h + 7) / 8, s / k), dim3(256), 0, st, sc, s, f, k, h, w, out_depth,
+                     out_who);
+  HN_CHECK_LAUNCH("mesh_geometry_tiles");
+  return HN_OK;
 }

@@ -105,7 +105,8 @@ class HandNet(EngineOwner):
         return self
 
     def live(self, lifter, paras, clamp: bool = True, perm_reverse=None, faces=None, labels: bool = False, left: bool = False,
-             occlude: bool = False, occlude_margin: float = 0.03, cloud: bool = False, cloud_points: int = 4096,
+             occlude: bool = False, occlude_margin: float = 0.03, fit_iters: int = 1, fit_draw: bool = False,
+             cloud: bool = False, cloud_points: int = 4096,
              cloud_band: float = 0.03, cloud_stride: int = 2, fit: bool = False, fit_band: float = 0.03, fit_stride: int = 2,
              fit_min_points: int = 200, fit_damp: float = 1e-3, fit_max_shift: float = 0.05, fit_max_angle: float = 0.35):
         """The live caller's chain as ONE step (hn_amd.live.LiveHandEngine; ros_demo.py:270-290,329-337): this network, the
@@ -135,6 +136,9 @@ class HandNet(EngineOwner):
         [N,12] fp32 (R row-major, then t in metres: the motion about the root joint, camera frame), fit_count [N,2] int32
         (matches, status: 0 fitted, 1 fewer than fit_min_points matches, 2 no solution, 3 beyond fit_max_shift metres or
         fit_max_angle radians: the mesh is left as it is) and fit_cost [N] int64 (the summed squared residual, 2^-30 m^2).
+        fit_iters = I (1..8; DESIGN.md section 9l) runs I such steps, the moved mesh drawn again before every further one;
+        read() then also ends with fit_trace [N,I,3] int64 (matches, status, cost of every step; I >= 2).  fit_draw=True draws
+        the overlay, silhouette and coverage, and cuts the cloud, from the fitted mesh.  Either without fit=True: ValueError.
         fit_band = 0.03 m, fit_stride = 2, fit_min_points = 200, fit_damp = 1e-3, fit_max_shift = 0.05 m and fit_max_angle =
         0.35 rad are starting values, NOT tuned on this model.
         The returned engine owns this network's step from then on (forward() of this module keeps working and
@@ -143,13 +147,16 @@ class HandNet(EngineOwner):
         paras = ops.camera_paras(paras)
         self._convert_cfg = (paras, bool(clamp))
         return LiveHandEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, clamp, perm_reverse,
-                              faces, labels, left, occlude, occlude_margin, cloud, cloud_points, cloud_band, cloud_stride, fit,
-                              fit_band, fit_stride, fit_min_points, fit_damp, fit_max_shift, fit_max_angle)
+                              faces, labels, left, occlude, occlude_margin, fit_iters=fit_iters, fit_draw=fit_draw, cloud=cloud,
+                              cloud_points=cloud_points, cloud_band=cloud_band, cloud_stride=cloud_stride, fit=fit,
+                              fit_band=fit_band, fit_stride=fit_stride, fit_min_points=fit_min_points, fit_damp=fit_damp,
+                              fit_max_shift=fit_max_shift, fit_max_angle=fit_max_angle)
 
     def live_hands(self, lifter, paras, max_hands: int = 2, clamp: bool = True, perm_reverse=None, faces=None,
                    labels: bool = False, left: bool = False, handed: bool = False, left_side: int = 0, track: bool = False,
                    track_iou: float = 0.3, track_hold: int = 5, occlude: bool = False, occlude_margin: float = 0.03,
-                   extrinsics=None, rig_radius: float = 0.08, cloud: bool = False, cloud_points: int = 4096,
+                   extrinsics=None, rig_radius: float = 0.08, fit_iters: int = 1, fit_draw: bool = False, cloud: bool = False,
+                   cloud_points: int = 4096,
                    cloud_band: float = 0.03, cloud_stride: int = 2, cloud_frame: str = "camera", fit: bool = False,
                    fit_band: float = 0.03, fit_stride: int = 2, fit_min_points: int = 200, fit_damp: float = 1e-3,
                    fit_max_shift: float = 0.05, fit_max_angle: float = 0.35,
@@ -191,7 +198,8 @@ class HandNet(EngineOwner):
         [N,K,2] and cloud_resid [N,K]; cloud_frame="rig" (needs extrinsics) hands the points out in the rig frame.
         cloud_points = 4096, cloud_band = 0.03 m and cloud_stride = 2 are starting values, NOT tuned on this model.
         fit (needs occlude): as live()'s, per slot: read() ends with fit_mesh [N,K,V,3], fit_xyz
-        [N,K,21,3], fit_rt [N,K,12], fit_count [N,K,2] and fit_cost [N,K].  fit_band = 0.03 m, fit_stride = 2, fit_min_points =
+        [N,K,21,3], fit_rt [N,K,12], fit_count [N,K,2] and fit_cost [N,K]; fit_iters / fit_draw as
+        live()'s, fit_trace [N,K,I,3].  fit_band = 0.03 m, fit_stride = 2, fit_min_points =
         200, fit_damp = 1e-3, fit_max_shift = 0.05 m and fit_max_angle = 0.35 rad are starting values, NOT tuned on this model."""
         from hn_amd.live import LiveHandsEngine
         k = ops.check_max_hands(max_hands)
@@ -202,7 +210,7 @@ class HandNet(EngineOwner):
         return LiveHandsEngine(self.engine(), lifter.engine() if hasattr(lifter, "engine") else lifter, paras, k, clamp,
                                perm_reverse, faces, labels, left, handed, left_side, track, track_iou, track_hold,
                                occlude=occlude, occlude_margin=occlude_margin, extrinsics=extrinsics, rig_radius=rig_radius,
-                               cloud=cloud, cloud_points=cloud_points, cloud_band=cloud_band, cloud_stride=cloud_stride,
+                               fit_iters=fit_iters, fit_draw=fit_draw, cloud=cloud, cloud_points=cloud_points, cloud_band=cloud_band, cloud_stride=cloud_stride,
                                cloud_frame=cloud_frame, fit=fit, fit_band=fit_band, fit_stride=fit_stride,
                                fit_min_points=fit_min_points, fit_damp=fit_damp, fit_max_shift=fit_max_shift,
                                fit_max_angle=fit_max_angle,

@@ -248,6 +248,11 @@ SIGNATURES = {
     "hn_mesh_fit_scratch_bytes": (C.c_int64, [C.c_int] * 3),
     "hn_mesh_fit_f32": (C.c_int, [VP] * 3 + [C.c_int64] + [VP] * 4 + [C.c_int] * 7 + [C.c_float, C.c_int] + [C.c_double] * 3
                         + [VP, C.c_int64] + [VP] * 6),
+    # the raster's geometry pass and the fit iterated over it (new functions under ABI 36)
+    "hn_mesh_geometry_f32": (C.c_int, [VP] * 4 + [C.c_int] * 4 + [c_f32p, VP, C.c_int, C.c_int, VP, C.c_int64, VP, VP, VP]),
+    "hn_mesh_fit_iters_scratch_bytes": (C.c_int64, [C.c_int] * 8),
+    "hn_mesh_fit_iters_f32": (C.c_int, [VP] * 3 + [C.c_int64] + [VP] * 7 + [C.c_int] * 9 + [C.c_float, C.c_int] + [C.c_double] * 3
+                              + [VP, C.c_int64, VP, C.c_int64] + [VP] * 7),
 }
 
 _lock = threading.Lock()

@@ -93,6 +93,12 @@ def _fit_views(kind):
     return collections.namedtuple(kind.__name__.replace("Views", "FitViews"), kind._fields + FIT_FIELDS)
 
 
+@functools.lru_cache(maxsize=None)
+def _fit_trace_views(kind):
+    """... and of a fit step of two iterations or more: the fields of its fit step, then the trace"""
+    return collections.namedtuple(kind.__name__.replace("Views", "TraceViews"), kind._fields + ("fit_trace",))
+
+
 @dataclass(frozen=True)
 class LiveLayout:
     """Byte layout of a live step's one copy buffer, in this order: the records (one-hand step: a wide record per frame + the
@@ -108,7 +114,9 @@ class LiveLayout:
     and `cloud_resid` int64 [slots] on 8 bytes (their offsets cloud_at, cloud_count_at, cloud_resid_at are properties, not
     fields), and -- fit steps -- `fit_mesh` fp32 [slots,V,3], `fit_xyz` fp32 [slots,21,3], `fit_rt` fp32 [slots,12]
     and `fit_count` int32 [slots,2], each on a dword, and `fit_cost` int64 [slots] on 8 bytes, as the last parts (fit_mesh_at,
-    fit_xyz_at, fit_rt_at, fit_count_at, fit_cost_at: properties too).
+    fit_xyz_at, fit_rt_at, fit_count_at, fit_cost_at: properties too), and -- fit steps of I = 2..8 iterations, for
+    which `fit` holds the integer I where a step of one iteration holds True -- `fit_trace` int64 [slots,I,3] on 8 bytes as the
+    last part (fit_trace_at: a property).
     slots = frames for the one-hand step (hands None), frames * hands for the K-hand step.  A part the step does not have takes
     no bytes and its offset is None; every part in front of it stays where a step without the option has it."""
     frames: int
@@ -121,7 +129,8 @@ class LiveLayout:
     tracked: bool = False
     smoothed: bool = False
     occluded: bool = False       # (keyword: the overlay hidden behind nearer scene depth; needs overlay)
-    fit: bool = False            # (keyword: every slot's mesh and joints fitted to the measured depth; needs occluded)
+    fit: bool = False            # (keyword: every slot's mesh and joints fitted to the measured depth; needs occluded; an
+    #                              integer 2..8: that many iterations, and the trace as the last part)
     cloud: int = 0               # (keyword: rows per slot of the hand clouds, 0: none; needs occluded)
     rig: bool = False            # (keyword: the slots in the rig frame, associated across frames and fused; a K-hand step's)
     record_rows: int = field(init=False)
@@ -161,6 +170,9 @@ class LiveLayout:
             raise ValueError("a cloud step is an occluded step: the clouds are cut out with the silhouette")
         if self.fit and not self.occluded:
             raise ValueError("a fit step is an occluded step: the mesh is fitted to the depth pixels under its silhouette")
+        if not isinstance(self.fit, bool) and (not isinstance(self.fit, (int, np.integer)) or not 2 <= self.fit <= ops.FIT_MAX_ITERS):
+            raise ValueError(f"fit: False, True (one iteration) or the iterations as an integer 2..{ops.FIT_MAX_ITERS} "
+                             f"(got {self.fit!r})")
         if self.rig:
             if self.hands is None:
                 raise ValueError("rig is a K-hand step's option: the rig frame puts the slots of several frames together")
@@ -198,13 +210,14 @@ class LiveLayout:
                                                    ("fit_xyz", self.fit, torch.float32, (s, SMOOTH_JOINTS, 3), 4),
                                                    ("fit_rt", self.fit, torch.float32, (s, 12), 4),
                                                    ("fit_count", self.fit, torch.int32, (s, 2), 4),
-                                                   ("fit_cost", self.fit, torch.int64, (s,), 8)):
+                                                   ("fit_cost", self.fit, torch.int64, (s,), 8),
+                                                   ("fit_trace", self.fit_iters > 1, torch.int64, (s, self.fit_iters, 3), 8)):
             start = None
             if present:
                 start = (end + align - 1) // align * align
                 end = start + math.prod(shape) * dtype.itemsize
                 spans[name] = (start, end, dtype, shape)
-            if name != "records" and name not in CLOUD_FIELDS + FIT_FIELDS:
+            if name != "records" and name not in CLOUD_FIELDS + FIT_FIELDS + ("fit_trace",):
                 put(name + "_at", start)
         put("record_rows", rows)
         put("record_bytes", rb)
@@ -214,6 +227,11 @@ class LiveLayout:
     @property
     def slots(self) -> int:
         return self.frames * (self.hands or 1)
+
+    @property
+    def fit_iters(self) -> int:
+        """the iterations of a fit step (0: the step does not fit)"""
+        return int(self.fit)
 
     def _part_at(self, name):
         span = self._spans.get(name)
@@ -227,6 +245,7 @@ class LiveLayout:
     fit_rt_at = property(lambda self: self._part_at("fit_rt"))
     fit_count_at = property(lambda self: self._part_at("fit_count"))
     fit_cost_at = property(lambda self: self._part_at("fit_cost"))
+    fit_trace_at = property(lambda self: self._part_at("fit_trace"))
 
     def views(self, buf) -> LiveViews:
         """The parts of a step's flat uint8 buffer (the device buffer or its pinned copy), typed and shaped; None: not there."""
@@ -240,6 +259,8 @@ class LiveLayout:
             kind = _cloud_views(kind)
         if self.fit:
             kind = _fit_views(kind)
+        if self.fit_iters > 1:
+            kind = _fit_trace_views(kind)
         return kind(*(cut.get(name) for name in kind._fields))
 
 
@@ -268,6 +289,15 @@ def _fit_read_type(kind):
     absent = {f: None for f in ("overlay", "box_label", "pose_label") if f not in kind._fields}
     doc = kind.__doc__.rstrip(".") + "".join(f" + {f}" for f in FIT_FIELDS) + "."
     return type(name, (collections.namedtuple(name, kind._fields + FIT_FIELDS),), dict(absent, __slots__=(), __doc__=doc))
+
+
+@functools.lru_cache(maxsize=None)
+def _fit_trace_read_type(kind):
+    """The read type of a fit step of two iterations or more: the fields of `kind` -- its fit step's read type --, then fit_trace."""
+    name = kind.__name__[:-len("Read")] + "TraceRead"
+    absent = {f: None for f in ("overlay", "box_label", "pose_label") if f not in kind._fields}
+    doc = kind.__doc__.rstrip(".") + " + fit_trace."
+    return type(name, (collections.namedtuple(name, kind._fields + ("fit_trace",)),), dict(absent, __slots__=(), __doc__=doc))
 
 
 def _read(step, base, values, layout, v, per_slot=lambda t: t):
@@ -299,6 +329,9 @@ def _read(step, base, values, layout, v, per_slot=lambda t: t):
     if layout.fit:      # (per slot: [N,K,V,3], [N,K,21,3], [N,K,12], [N,K,2], [N,K]; the one-hand step without the K)
         values += tuple(per_slot(getattr(v, f)).clone() for f in FIT_FIELDS)
         kind = _fit_read_type(kind)
+        if layout.fit_iters > 1:      # (per slot: [N,K,I,3]; the one-hand step: [N,I,3])
+            values += (per_slot(v.fit_trace).clone(),)
+            kind = _fit_trace_read_type(kind)
     return kind(*values)
 
 
@@ -333,6 +366,7 @@ class LiveOutput:
     fit_rt: torch.Tensor = None      # [N,12] fp32 R row-major, then t (metres): the motion about the root joint, camera frame
     fit_count: torch.Tensor = None   # [N,2] int32 (matching pixels, status: 0 fitted, 1 too few, 2 no solution, 3 beyond the caps)
     fit_cost: torch.Tensor = None    # [N] int64 the summed squared residual along the normals, 2^-30 m^2
+    fit_trace: torch.Tensor = None   # fit steps of I >= 2 iterations: [N,I,3] int64 (matches, status, cost) of each
 
     def read(self):
         """After the stream is synchronised: (keypoints, has_hand, crop_box, range words, [image_uvd, xyz_mm], mesh) as fresh CPU
@@ -340,7 +374,8 @@ class LiveOutput:
         uint8 (LiveOverlayRead); a step with labels appends box_label [N,H,W,3] and pose_label [N,176,176,3] (LiveLabelsRead,
         LiveOverlayLabelsRead); a step with occlude appends silhouette [N,H,W] uint8 and coverage [N,2] int32; a step with
         cloud appends cloud [N,P,3] fp32, cloud_count [N,2] int32 and cloud_resid [N] int64; a step with fit appends fit_mesh
-        [N,V,3], fit_xyz [N,21,3], fit_rt [N,12] fp32, fit_count [N,2] int32 and fit_cost [N] int64 as the last fields."""
+        [N,V,3], fit_xyz [N,21,3], fit_rt [N,12] fp32, fit_count [N,2] int32 and fit_cost [N] int64 as the last fields, and --
+        fit_iters >= 2 -- fit_trace [N,I,3] int64 behind them."""
         v = self.layout.views(self.host)
         kp, has, box, words, more = read_host_record(v.records, self.layout.frames, extras=True)
         return _read("Live", _LIVE_FIELDS, (kp, has, box, words, more, v.mesh.clone()), self.layout, v)
@@ -361,8 +396,8 @@ class _LiveStep:
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None,
                  labels: bool = False, left: bool = False, occlude: bool = False, occlude_margin: float = ops.OCCLUDE_MARGIN,
-                 cloud: bool = False, cloud_points: int = ops.CLOUD_POINTS, cloud_band: float = ops.CLOUD_BAND,
-                 cloud_stride: int = ops.CLOUD_STRIDE, fit: bool = False, fit_band: float = ops.FIT_BAND,
+                 fit_iters: int = 1, fit_draw: bool = False, cloud: bool = False, cloud_points: int = ops.CLOUD_POINTS,
+                 cloud_band: float = ops.CLOUD_BAND, cloud_stride: int = ops.CLOUD_STRIDE, fit: bool = False, fit_band: float = ops.FIT_BAND,
                  fit_stride: int = ops.FIT_STRIDE, fit_min_points: int = ops.FIT_MIN_POINTS, fit_damp: float = ops.FIT_DAMP,
                  fit_max_shift: float = ops.FIT_MAX_SHIFT, fit_max_angle: float = ops.FIT_MAX_ANGLE):
         if not _same_device(hand.device, lifter.device):
@@ -412,6 +447,14 @@ class _LiveStep:
                 raise ValueError("fit=True needs occlude=True (and therefore faces= and perm_reverse=): the mesh is fitted to the "
                                  "depth pixels under its silhouette")
             self.fit = ops.check_fit(fit_band, fit_stride, fit_min_points, fit_damp, fit_max_shift, fit_max_angle)
+        # fit_iters: that many Gauss-Newton steps, the moved mesh drawn again (ops.mesh_geometry) before every further one
+        # (ops.mesh_fit_iters); fit_draw: overlay, silhouette, coverage, mesh depth and cloud from the FITTED mesh
+        if not isinstance(fit_draw, (bool, np.bool_)):
+            raise ValueError(f"fit_draw: True or False (got {fit_draw!r})")
+        if not fit and (fit_draw or not (isinstance(fit_iters, (int, np.integer)) and not isinstance(fit_iters, bool)
+                                         and fit_iters == 1)):
+            raise ValueError("fit_iters / fit_draw need fit=True: they say how the fit runs and what is drawn from it")
+        self.fit_iters, self.fit_draw = ops.check_fit_iters(fit_iters), bool(fit_draw)
         # labels: the step ends with the caller's other two images (ops.draw_labels: ros_demo.py:310-326), behind the overlay
         self.labels, self.clamp = bool(labels), bool(clamp)
         # left: the caller's mirror mode (ImageListener(left=True), ros_demo.py:259-262): the step runs on the frame and the
@@ -478,6 +521,30 @@ class _LiveStep:
         return ops.mesh_fit(work[0], silhouette, depth, paras, mesh, xyz_mm, k, band=band, stride=stride, min_points=min_points,
                             damp=damp, max_shift=max_shift, max_angle=max_angle, out=at, scratch=work[2])
 
+    def _fit_iters(self, work, best, who, depth, mesh, xyz_mm, drawn, k, at):
+        """The iterated fit's launches (ops.mesh_fit_iters): fit_iters steps from the mesh depth `best` and the slot byte `who`
+        that show `mesh`, the moved meshes drawn again into work buffers of their own before every further step; the results
+        and the trace straight into the copy buffer."""
+        band, stride, min_points, damp, max_shift, max_angle = self.fit
+        paras = self.paras if self.cams is None else self.cams
+        mesh, xyz_mm = mesh.view(-1, self.vertices, 3), xyz_mm.view(-1, SMOOTH_JOINTS, 3)      # (a row per slot)
+        return ops.mesh_fit_iters(best, who, depth, paras, mesh, xyz_mm, self.faces, k, iters=self.fit_iters, lifted=drawn, band=band,
+                                  stride=stride, min_points=min_points, damp=damp, max_shift=max_shift, max_angle=max_angle, out=at,
+                                  scratch=work[2], work=work[3])
+
+    def _geometry(self, work, mesh, drawn, k):
+        """A fit_draw step's first two launches, in place of the raster: the nearest Z and the slot byte of the unfitted mesh,
+        into work buffers of their own -- what the fit reads."""
+        s = mesh.shape[0]
+        scratch = self._render_scratch.get(s)
+        if scratch is None:
+            with torch.inference_mode(False):
+                scratch = self._render_scratch[s] = torch.empty(
+                    (ops.mesh_render_scratch_bytes(s, self.faces.shape[0]),), dtype=torch.uint8, device=self.device)
+        paras = self.paras if self.cams is None else self.cams
+        hw = tuple(work[4].shape[1:])
+        return ops.mesh_geometry(mesh, self.faces, paras, hw, lifted=drawn, k=k, out_depth=work[4], out_who=work[5], scratch=scratch)
+
     def _check_frames(self, n):
         if self.cams is not None and n != self.cams.shape[0]:
             raise ValueError(f"a step over {n} frames, but the engine was built with {self.cams.shape[0]} cameras, one per frame")
@@ -511,20 +578,26 @@ class _LiveStep:
         """The buffer of a step over n frames (hw: of a step that draws, the frames' size)."""
         return LiveLayout(n, self.hands, self.vertices, hw, hw is not None and self.faces is not None,
                           hw is not None and self.labels, self.handed, self.track is not None, self.smooth is not None,
-                          occluded=self.occlude is not None, fit=self.fit is not None and hw is not None,
+                          occluded=self.occlude is not None,
+                          fit=(True if self.fit_iters == 1 else self.fit_iters) if self.fit is not None and hw is not None else False,
                           cloud=self.cloud[0] if self.cloud and hw is not None else 0, rig=self.rig is not None)
 
     def _new_buffers(self, n, hw=None):
         """A fresh (layout, device buffer, pinned host buffer, work) of a step over n frames; work: a cloud or fit step's (mesh
-        depth fp32 [n,h,w], the cloud launches' scratch or None, the fit launches' scratch or None) on the device -- not part
-        of the copy --, else None."""
+        depth fp32 [n,h,w], the cloud launches' scratch or None, the fit launches' scratch or None, the iterated fit's work or
+        None, a fit_draw step's geometry depth fp32 [n,h,w] and slot byte uint8 [n,h,w] or None) on the device -- not part of
+        the copy --, else None."""
         layout = self._layout(n, hw)
         work = None
         if layout.cloud or layout.fit:
             scratch = lambda nbytes: torch.empty((nbytes,), dtype=torch.uint8, device=self.device)  # noqa: E731
             work = (torch.zeros((n, *hw), dtype=torch.float32, device=self.device),
                     scratch(ops.hand_cloud_scratch_bytes(n, self.hands or 1, hw[0])) if layout.cloud else None,
-                    scratch(ops.mesh_fit_scratch_bytes(n, self.hands or 1, hw[0])) if layout.fit else None)
+                    scratch(ops.mesh_fit_scratch_bytes(n, self.hands or 1, hw[0])) if layout.fit else None,
+                    scratch(ops.mesh_fit_iters_scratch_bytes(n, self.hands or 1, hw[0], hw[1], self.vertices, self.faces.shape[0],
+                                                             SMOOTH_JOINTS, self.fit_iters)) if layout.fit_iters > 1 else None,
+                    torch.zeros((n, *hw), dtype=torch.float32, device=self.device) if layout.fit and self.fit_draw else None,
+                    torch.zeros((n, *hw), dtype=torch.uint8, device=self.device) if layout.fit and self.fit_draw else None)
         return (layout, torch.zeros((layout.nbytes,), dtype=torch.uint8, device=self.device),
                 torch.zeros((layout.nbytes,), dtype=torch.uint8, pin_memory=True), work)
 
@@ -558,13 +631,20 @@ class _LiveStep:
         p2d, mesh, pose3d, raw = out.tail
         drawn, k = out.has_hand.view(-1) if self.hands is None else at.lifted, self.hands or 1
         overlay = box_label = pose_label = silhouette = coverage = None
-        if layout.overlay:      # (a smoothed step draws, and an occluded one tests, what it smoothed)
-            overlay, silhouette, coverage = self._draw(at.smooth_mesh if layout.smoothed else mesh, drawn, frames, k, at.overlay,
-                                                       depth, at, work and work[0])
+        shown = at.smooth_mesh if layout.smoothed else mesh      # (a smoothed step draws, tests and fits what it smoothed)
+        more, redraw = {}, bool(layout.fit and self.fit_draw)
+        if redraw:      # (the geometry of the unfitted mesh, the fit, then everything drawn from the fitted mesh)
+            best, who = self._geometry(work, shown, drawn, k)
+            more.update(self._fit_parts(work, best, who, depth, shown, at.smooth_xyz if layout.smoothed else out.xyz_mm, drawn, k,
+                                        at, layout))
+            overlay, silhouette, coverage = self._draw(at.fit_mesh, drawn, frames, k, at.overlay, depth, at, work[0])
+        elif layout.overlay:
+            overlay, silhouette, coverage = self._draw(shown, drawn, frames, k, at.overlay, depth, at, work and work[0])
         if layout.labels:
             box_label, pose_label = ops.draw_labels(out.keypoints, out.crop_box, frames, drawn=drawn, k=k, clamp=self.clamp,
                                                     out_box=at.box_label, out_pose=at.pose_label)
-        more = {} if coverage is None else dict(silhouette=silhouette, coverage=coverage)
+        if coverage is not None:
+            more.update(silhouette=silhouette, coverage=coverage)
         if layout.rig:      # (a smoothed step moves and fuses what it smoothed, the signals its overlay draws)
             more["rig"] = ops.rig_fuse(at.smooth_xyz if layout.smoothed else out.xyz_mm, at.smooth_mesh if layout.smoothed else mesh,
                                        out.has_hand, at.lifted, out.score, self.extrinsics, k, self.rig,
@@ -572,13 +652,24 @@ class _LiveStep:
         if layout.cloud:    # (against the mesh the overlay drew and the depth map it was tested against)
             cloud = self._cloud(work, silhouette, depth, k, at)
             more.update(cloud=cloud.cloud, cloud_count=cloud.count, cloud_resid=cloud.resid, mesh_depth=work[0])
-        if layout.fit:      # (the mesh the overlay drew and the joints that go with it: the smoothed signals on a smoothed step)
-            fit = self._fit(work, silhouette, depth, at.smooth_mesh if layout.smoothed else mesh,
-                            at.smooth_xyz if layout.smoothed else out.xyz_mm, k, at)
-            more.update(fit_mesh=fit.mesh, fit_xyz=fit.xyz, fit_rt=fit.rt, fit_count=fit.count, fit_cost=fit.cost, mesh_depth=work[0])
+        if layout.fit and not redraw:      # (the mesh the overlay drew and the joints that go with it)
+            more.update(self._fit_parts(work, work[0], silhouette, depth, shown, at.smooth_xyz if layout.smoothed else out.xyz_mm,
+                                        drawn, k, at, layout))
         host.copy_(dev, non_blocking=True)
         return self._output(out, at, layout, host, dict(pose2d=p2d, mesh=mesh, pose3d=pose3d, raw_mesh=raw, overlay=overlay,
                                                         box_label=box_label, pose_label=pose_label, **more))
+
+    def _fit_parts(self, work, best, who, depth, mesh, xyz_mm, drawn, k, at, layout) -> dict:
+        """The fit's launches -- one iteration: ops.mesh_fit, today's two; more: ops.mesh_fit_iters -- on the mesh depth `best` and
+        the slot byte `who`, and what the step hands out of them."""
+        if layout.fit_iters == 1:
+            fit = self._fit((best,) + tuple(work[1:]), who, depth, mesh, xyz_mm, k, at)
+            trace = {}
+        else:
+            fit = self._fit_iters(work, best, who, depth, mesh, xyz_mm, drawn, k, at)
+            trace = dict(fit_trace=fit.trace)
+        return dict(fit_mesh=fit.mesh, fit_xyz=fit.xyz, fit_rt=fit.rt, fit_count=fit.count, fit_cost=fit.cost, mesh_depth=work[0],
+                    **trace)
 
     def _key_options(self) -> tuple:
         """What a capture's key carries behind the shapes (the smoothed step: its filter's parameters; the occluded step: its
@@ -586,6 +677,7 @@ class _LiveStep:
         return ((() if self.occlude is None else ("occluded", self.occlude))
                 + (() if self.cloud is None else ("cloud",) + self.cloud + (self.cloud_frame,))
                 + (() if self.fit is None else ("fit",) + self.fit)
+                + (() if self.fit_iters == 1 and not self.fit_draw else ("fit_iters", self.fit_iters, self.fit_draw))
                 + (() if self.rig is None else ("rig", self.rig)))
 
     def _smooth_untouched(self, n):
@@ -679,7 +771,14 @@ class LiveHandEngine(_LiveStep):
     root joint c0, camera frame), .fit_count [N,2] (matches, status: 0 fitted; 1 fewer than fit_min_points matches; 2 no
     solution; 3 a step beyond fit_max_shift metres or fit_max_angle radians -- then R = I, t = 0 and fit_mesh / fit_xyz are
     byte copies) and .fit_cost [N] int64 (the summed squared residual, 2^-30 m^2), read() likewise as the last fields, in the
-    step's one copy.  The overlay, the silhouette and the cloud are NOT redrawn from the fitted mesh.  fit_band = 0.03 m,
+    step's one copy.  The overlay, the silhouette and the cloud are NOT redrawn from the fitted mesh (fit_draw=True does that).
+    fit_iters = I (1..8) runs I such steps, the moved mesh drawn again before every further one by a raster pass
+    that keeps only the nearest Z and the slot (ops.mesh_fit_iters: 4 (I - 1) + 1 more launches): fit_mesh / fit_xyz are the
+    state after the last step, fit_rt the composed motion about the original root joint, fit_count / fit_cost those of the
+    first step, and -- I >= 2 -- .fit_trace [N,I,3] int64 holds (matches, status, cost) of every step, behind fit_cost in
+    read().  fit_draw=True draws the overlay, the silhouette, the coverage and mesh_depth, and cuts the cloud, from fit_mesh:
+    the geometry pass of the unfitted mesh runs in place of the first raster, then the fit, then the step's occluded raster
+    of fit_mesh; the fit_* fields are the same bytes with it on or off.  Either one without fit=True: ValueError.  fit_band = 0.03 m,
     fit_stride = 2, fit_min_points = 200, fit_damp = 1e-3, fit_max_shift = 0.05 m and fit_max_angle = 0.35 rad are starting
     values, NOT tuned on this model."""
 
@@ -744,6 +843,7 @@ class LiveHandsOutput:
     fit_rt: torch.Tensor = None      # [N,K,12] fp32 R row-major, then t (metres): the motion about the root joint, camera frame
     fit_count: torch.Tensor = None   # [N,K,2] int32 (matching pixels, status: 0 fitted, 1 too few, 2 no solution, 3 beyond the caps)
     fit_cost: torch.Tensor = None    # [N,K] int64 the summed squared residual along the normals, 2^-30 m^2
+    fit_trace: torch.Tensor = None   # fit steps of I >= 2 iterations: [N,K,I,3] int64 (matches, status, cost) of each
     smooth_xyz: torch.Tensor = None  # smoothed steps: [N,K,21,3] on the device, xyz_mm filtered over time (zeros: has_hand != 1)
     smooth_mesh: torch.Tensor = None  # smoothed steps: [N,K,V,3] on the device, `mesh` filtered over time (zeros: not lifted)
 
@@ -757,7 +857,7 @@ class LiveHandsOutput:
         [N,K,21,3], rig_mesh [N,K,V,3], rig_hand [N,K] int32, rig_count (a Python int), rig_views and rig_seed [N*K] int32,
         fused_xyz [N*K,21,3] and fused_mesh [N*K,V,3]; a cloud step: behind those, cloud [N,K,P,3] fp32, cloud_count [N,K,2]
         int32 and cloud_resid [N,K] int64; a fit step: behind those, fit_mesh [N,K,V,3], fit_xyz [N,K,21,3], fit_rt [N,K,12]
-        fp32, fit_count [N,K,2] int32 and fit_cost [N,K] int64)."""
+        fp32, fit_count [N,K,2] int32 and fit_cost [N,K] int64, and -- fit_iters >= 2 -- fit_trace [N,K,I,3] int64)."""
         v, s = self.layout.views(self.host), self.layout.slots
         per = lambda t: t.reshape((self.layout.frames, self.layout.hands) + tuple(t.shape[1:]))
         kp, has, box, words, (img, xyz) = read_host_record(v.records, s, extras=True)
@@ -779,7 +879,7 @@ class LiveHandsEngine(_LiveStep):
                  perm_reverse=None, faces=None, labels: bool = False, left: bool = False, handed: bool = False,
                  left_side: int = 0, track: bool = False, track_iou: float = 0.3, track_hold: int = 5, occlude: bool = False,
                  occlude_margin: float = ops.OCCLUDE_MARGIN, extrinsics=None, rig_radius: float = ops.RIG_RADIUS,
-                 cloud: bool = False, cloud_points: int = ops.CLOUD_POINTS, cloud_band: float = ops.CLOUD_BAND,
+                 fit_iters: int = 1, fit_draw: bool = False, cloud: bool = False, cloud_points: int = ops.CLOUD_POINTS, cloud_band: float = ops.CLOUD_BAND,
                  cloud_stride: int = ops.CLOUD_STRIDE, cloud_frame: str = "camera", fit: bool = False,
                  fit_band: float = ops.FIT_BAND, fit_stride: int = ops.FIT_STRIDE, fit_min_points: int = ops.FIT_MIN_POINTS,
                  fit_damp: float = ops.FIT_DAMP, fit_max_shift: float = ops.FIT_MAX_SHIFT,
@@ -847,7 +947,9 @@ class LiveHandsEngine(_LiveStep):
         and .fit_cost [N,K] int64, read() likewise behind every other field, in the step's one copy.  Only pixels whose own and
         whose four neighbours' silhouette bytes name the slot enter, so a slot's border with another hand does not.  A `left`
         step fits to the mirrored depth map, a smoothed step moves the smoothed mesh and joints it draws; the rig outputs, the
-        overlay and the cloud stay what they are.  fit_band = 0.03 m, fit_stride = 2, fit_min_points = 200, fit_damp = 1e-3,
+        overlay and the cloud stay what they are.  fit_iters / fit_draw: as LiveHandEngine's, .fit_trace
+        [N,K,I,3]; every slot that is lifted is drawn again before a further iteration, fitted or not, because it may cover
+        another slot's pixels; labels, rig outputs and the smoothing state are not touched.  fit_band = 0.03 m, fit_stride = 2, fit_min_points = 200, fit_damp = 1e-3,
         fit_max_shift = 0.05 m and fit_max_angle = 0.35 rad are starting values, NOT tuned on this model."""
         self.hands = self.max_hands = ops.check_max_hands(max_hands)
         if left and handed:
@@ -879,9 +981,9 @@ class LiveHandsEngine(_LiveStep):
         if cloud_frame == "rig" and extrinsics is None:
             raise ValueError('cloud_frame="rig" needs extrinsics=: the camera -> rig transforms the points go through')
         self.cloud_frame = cloud_frame
-        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left, occlude, occlude_margin, cloud,
-                         cloud_points, cloud_band, cloud_stride, fit, fit_band, fit_stride, fit_min_points, fit_damp, fit_max_shift,
-                         fit_max_angle)
+        super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left, occlude, occlude_margin, fit_iters,
+                         fit_draw, cloud, cloud_points, cloud_band, cloud_stride, fit, fit_band, fit_stride, fit_min_points, fit_damp,
+                         fit_max_shift, fit_max_angle)
         if table is not None:
             if self.cams is not None and self.cams.shape[0] != table.shape[0]:
                 raise ValueError(f"{table.shape[0]} extrinsics for a step built with {self.cams.shape[0]} cameras: one [R | t] per "
@@ -987,6 +1089,8 @@ class LiveHandsEngine(_LiveStep):
             parts.update(fit_mesh=parts["fit_mesh"].view(n, k, self.vertices, 3), fit_xyz=parts["fit_xyz"].view(n, k, SMOOTH_JOINTS, 3),
                          fit_rt=parts["fit_rt"].view(n, k, 12), fit_count=parts["fit_count"].view(n, k, 2),
                          fit_cost=parts["fit_cost"].view(n, k))
+        if "fit_trace" in parts:
+            parts["fit_trace"] = parts["fit_trace"].view(n, k, -1, 3)
         return LiveHandsOutput(hands=out, lifted=at.lifted.view(n, k), host=host, n=n, k=k, side=out.side, mirror=out.mirror,
                                layout=layout, track_id=out.track_id, track_age=out.track_age,
                                smooth_xyz=None if self.smooth is None else at.smooth_xyz.view(n, k, SMOOTH_JOINTS, 3),

@@ -2381,6 +2381,168 @@ def mesh_fit(mesh_depth, silhouette, scene_depth, paras, mesh, xyz_mm, k, *, ban
     return MeshFit(*parts)
 
 
+def mesh_geometry(mesh, faces, paras, hw, lifted=None, k=1, *, out_depth=None, out_who=None, scratch=None):
+    """The geometry pass of mesh_render's raster (hn_mesh_geometry_f32: two launches, csrc/mesh_raster.hip; DESIGN.md section 9l,
+    tests/refit_ref.py::geometry is the rule and the outputs equal it bit for bit): the nearest mesh Z and its slot per pixel,
+    and nothing else -- no frame is read and no image stored.  mesh, faces, paras, lifted, k (1..16), scratch: as mesh_render
+    takes them; hw = (h, w) of the frames.  Returns (depth fp32 [N,H,W]: the nearest Z, 0 where nothing was drawn; who uint8
+    [N,H,W]: 0, or the nearest slot within the frame + 1) -- the occluded mesh_render's depth_out and silhouette & 0x7F, bit for
+    bit --, allocated or out_depth / out_who, both fully written."""
+    _req(mesh, name="mesh")
+    if mesh.dim() == 4:
+        mesh = mesh.view(-1, mesh.shape[2], 3)
+    if mesh.dim() != 3 or mesh.shape[2] != 3:
+        raise ValueError(f"mesh: expected [S,V,3], got {tuple(mesh.shape)}")
+    s, v, _ = mesh.shape
+    faces_host = None
+    if not (torch.is_tensor(faces) and faces.is_cuda):
+        faces_host = np.ascontiguousarray(np.asarray(faces.cpu() if torch.is_tensor(faces) else faces).astype(np.int32))
+        if faces_host.ndim != 2 or faces_host.shape[1] != 3:
+            raise ValueError(f"faces: expected [F,3], got {tuple(faces_host.shape)}")
+        faces = torch.from_numpy(faces_host).to(mesh.device)
+    _req(faces, torch.int32, "faces")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces: expected [F,3], got {tuple(faces.shape)}")
+    f = faces.shape[0]
+    h, w = (int(x) for x in hw)
+    k = int(k)
+    if not 1 <= k <= 16:
+        raise ValueError(f"the slot byte holds at most 16 slots per frame (k = {k})")
+    if s % k or s == 0:
+        raise ValueError(f"{s} mesh slots with k = {k} slots per frame")
+    n = s // k
+    if lifted is not None:
+        _req(lifted, torch.int32, "lifted")
+        if lifted.numel() != s:
+            raise ValueError(f"lifted: expected {s} flags, got {lifted.numel()}")
+    if out_depth is None:
+        out_depth = torch.empty((n, h, w), device=mesh.device, dtype=torch.float32)
+    if out_who is None:
+        out_who = torch.empty((n, h, w), device=mesh.device, dtype=torch.uint8)
+    _req(out_depth, name="out_depth"); _req(out_who, torch.uint8, "out_who")
+    if out_depth.numel() != n * h * w or out_who.numel() != n * h * w:
+        raise ValueError(f"out_depth fp32 and out_who uint8 [{n},{h},{w}], got {tuple(out_depth.shape)} and {tuple(out_who.shape)}")
+    need = mesh_render_scratch_bytes(s, f)
+    if scratch is None:
+        scratch = torch.empty((need,), device=mesh.device, dtype=torch.uint8)
+    _req(scratch, torch.uint8, "scratch")
+    host4 = table = None
+    if torch.is_tensor(paras) and paras.dim() != 1:
+        if paras.dtype != torch.float32 or tuple(paras.shape) != (n, 4):
+            raise ValueError(f"paras: a camera per frame is fp32 [{n},4] (fx, fy, cx, cy), got {paras.dtype} {tuple(paras.shape)}")
+        if paras.device != mesh.device:
+            raise ValueError(f"paras on {paras.device} but the mesh on {mesh.device}")
+        table = ptr(_req(paras, torch.float32, "paras"))
+    else:
+        host4 = (C.c_float * 4)(*[float(x) for x in paras])
+    fh = faces_host.ctypes.data if faces_host is not None else None
+    check(_lib.load().hn_mesh_geometry_f32(ptr(mesh), ptr(faces), fh, ptr(lifted), s, v, f, k, host4, table, h, w, ptr(scratch),
+                                           scratch.numel(), ptr(out_depth), ptr(out_who), _stream()), "hn_mesh_geometry_f32")
+    return out_depth.view(n, h, w), out_who.view(n, h, w)
+
+
+FIT_MAX_ITERS = 8          # iterations of the iterated fit (DESIGN.md 9l)
+
+MeshFitIters = collections.namedtuple("MeshFitIters", "mesh xyz rt count cost trace")
+
+
+def check_fit_iters(iters) -> int:
+    """fit_iters as an int in 1..8, else ValueError."""
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= int(iters) <= FIT_MAX_ITERS:
+        raise ValueError(f"fit_iters: an integer in 1..{FIT_MAX_ITERS} (got {iters!r})")
+    return int(iters)
+
+
+def mesh_fit_iters_scratch_bytes(frames, k, h, w, vertices, faces, joints, iters):
+    return int(_lib.load().hn_mesh_fit_iters_scratch_bytes(frames, k, h, w, vertices, faces, joints, iters))
+
+
+def mesh_fit_iters(mesh_depth, silhouette, scene_depth, paras, mesh, xyz_mm, faces, k, *, iters, lifted=None, band=FIT_BAND,
+                   stride=FIT_STRIDE, min_points=FIT_MIN_POINTS, damp=FIT_DAMP, max_shift=FIT_MAX_SHIFT, max_angle=FIT_MAX_ANGLE,
+                   out=None, scratch=None, work=None) -> MeshFitIters:
+    """mesh_fit iterated (hn_mesh_fit_iters_f32: 2 + 4 (iters - 1) + 1 launches, csrc/mesh_refit.hip; DESIGN.md section 9l,
+    tests/refit_ref.py::mesh_fit_iters is the rule and the outputs equal it bit for bit): `iters` (1..8) Gauss-Newton steps.
+    Iteration 1 is mesh_fit on the given mesh_depth / silhouette; before every further one the current meshes are drawn again
+    (mesh_geometry with `faces` -- a GPU int32 tensor or a host list -- and `lifted`: a slot with lifted == 0 is not drawn) and
+    the step turns about the current root joint, with the same parameters and caps.  A slot whose iteration ends with a status
+    other than 0 keeps its bytes for that iteration and is tried again in the next; there is no early stop.  Every other
+    argument: as mesh_fit takes it.  Returns MeshFitIters: mesh and xyz after the last iteration, rt fp32 [N*k,12] the composed
+    motion about the ORIGINAL root joint (the identity when no iteration fitted), count and cost those of iteration 1 (what
+    mesh_fit hands out), trace int64 [N*k,iters,3] = (matches, status, cost) of every iteration -- the cost of iteration t is the
+    residual after t - 1 motions.  Allocated, or `out`'s attributes fit_mesh / fit_xyz / fit_rt / fit_count / fit_cost /
+    fit_trace, every one fully written."""
+    iters = check_fit_iters(iters)
+    band, stride, min_points, damp, max_shift, max_angle = check_fit(band, stride, min_points, damp, max_shift, max_angle)
+    _req(mesh_depth, name="mesh_depth"); _req(silhouette, torch.uint8, "silhouette"); _req(scene_depth, name="scene_depth")
+    _req(mesh, name="mesh"); _req(xyz_mm, name="xyz_mm")
+    if silhouette.dim() != 3:
+        raise ValueError(f"silhouette: expected uint8 [N,H,W], got {tuple(silhouette.shape)}")
+    n, h, w = (int(x) for x in silhouette.shape)
+    if mesh_depth.numel() != n * h * w:
+        raise ValueError(f"mesh_depth: expected fp32 [{n},{h},{w}], got {tuple(mesh_depth.shape)}")
+    k = int(k)
+    if not 1 <= k <= 16:
+        raise ValueError(f"the silhouette's byte holds at most 16 slots per frame (k = {k})")
+    s = n * k
+    if mesh.dim() != 3 or mesh.shape[0] != s or mesh.shape[2] != 3 or mesh.shape[1] < 1:
+        raise ValueError(f"mesh: expected fp32 [{s},V,3], got {tuple(mesh.shape)}")
+    if xyz_mm.dim() != 3 or xyz_mm.shape[0] != s or xyz_mm.shape[2] != 3 or xyz_mm.shape[1] < 1:
+        raise ValueError(f"xyz_mm: expected fp32 [{s},J,3], got {tuple(xyz_mm.shape)}")
+    v, joints = int(mesh.shape[1]), int(xyz_mm.shape[1])
+    faces_host = None
+    if not (torch.is_tensor(faces) and faces.is_cuda):
+        faces_host = np.ascontiguousarray(np.asarray(faces.cpu() if torch.is_tensor(faces) else faces).astype(np.int32))
+        if faces_host.ndim != 2 or faces_host.shape[1] != 3:
+            raise ValueError(f"faces: expected [F,3], got {tuple(faces_host.shape)}")
+        faces = torch.from_numpy(faces_host).to(mesh.device)
+    _req(faces, torch.int32, "faces")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError(f"faces: expected a non-empty [F,3], got {tuple(faces.shape)}")
+    f = int(faces.shape[0])
+    if lifted is not None:
+        _req(lifted, torch.int32, "lifted")
+        if lifted.numel() != s:
+            raise ValueError(f"lifted: expected {s} flags, got {lifted.numel()}")
+    for name, t in (("mesh_depth", mesh_depth), ("scene_depth", scene_depth), ("mesh", mesh), ("xyz_mm", xyz_mm), ("faces", faces)):
+        if t.device != silhouette.device:
+            raise ValueError(f"{name} on {t.device} but the silhouette on {silhouette.device}")
+    shape = tuple(scene_depth.shape)
+    if shape not in ((n, 1, h, w), (n, h, w), (n, 4, h, w)):
+        raise ValueError(f"scene_depth: expected fp32 [{n},1,{h},{w}], [{n},{h},{w}] or RGBD [{n},4,{h},{w}], got {shape}")
+    rgbd = len(shape) == 4 and shape[1] == 4
+    depth_ptr = scene_depth.data_ptr() + (3 * h * w * 4 if rgbd else 0)
+    host4 = table = None
+    if torch.is_tensor(paras) and paras.dim() != 1:
+        if paras.dtype != torch.float32 or tuple(paras.shape) != (n, 4):
+            raise ValueError(f"paras: a camera per frame is fp32 [{n},4] (fx, fy, cx, cy), got {paras.dtype} {tuple(paras.shape)}")
+        if paras.device != silhouette.device:
+            raise ValueError(f"paras on {paras.device} but the silhouette on {silhouette.device}")
+        table = ptr(_req(paras, torch.float32, "paras"))
+    else:
+        host4 = (C.c_float * 4)(*[float(x) for x in paras])
+    parts = []
+    for name, dtype, shp in (("fit_mesh", torch.float32, (s, v, 3)), ("fit_xyz", torch.float32, (s, joints, 3)),
+                             ("fit_rt", torch.float32, (s, 12)), ("fit_count", torch.int32, (s, 2)), ("fit_cost", torch.int64, (s,)),
+                             ("fit_trace", torch.int64, (s, iters, 3))):
+        t = torch.empty(shp, device=silhouette.device, dtype=dtype) if out is None else getattr(out, name)
+        if _req(t, dtype, name).numel() != math.prod(shp):
+            raise ValueError(f"{name}: expected {dtype} {list(shp)}, got {tuple(t.shape)}")
+        parts.append(t.view(shp))
+    if scratch is None:
+        scratch = torch.empty((mesh_fit_scratch_bytes(n, k, h),), device=silhouette.device, dtype=torch.uint8)
+    if work is None:
+        work = torch.empty((mesh_fit_iters_scratch_bytes(n, k, h, w, v, f, joints, iters),), device=silhouette.device,
+                           dtype=torch.uint8)
+    _req(scratch, torch.uint8, "scratch"); _req(work, torch.uint8, "work")
+    shift2, tan2 = fit_caps(max_shift, max_angle)
+    fh = faces_host.ctypes.data if faces_host is not None else None
+    check(_lib.load().hn_mesh_fit_iters_f32(ptr(mesh_depth), ptr(silhouette), depth_ptr, (4 if rgbd else 1) * h * w, host4, table,
+                                            ptr(mesh), ptr(xyz_mm), ptr(faces), fh, ptr(lifted), n, k, h, w, v, f, joints, iters,
+                                            stride, band, min_points, damp, shift2, tan2, ptr(scratch), scratch.numel(), ptr(work),
+                                            work.numel(), *(ptr(t) for t in parts), _stream()), "hn_mesh_fit_iters_f32")
+    return MeshFitIters(*parts)
+
+
 LABEL_CROP = 176      # side of a pose_label image
 
 

@@ -38,7 +38,8 @@ extern "C" {
  * hn_lifter_input_gated_mirror_f32 and hn_mesh_finish_mirror_f32, the tracked slots' hn_crop_resize_hands_tracked and
  * hn_track_state_bytes, the smoothed step's hn_mesh_finish_smooth_f32 and hn_smooth_state_bytes, the per-frame cameras'
  * hn_mesh_render_cams_u8 and hn_mesh_render_cams_occluded_u8, the rig frame's hn_rig_fuse_f32, the hand cloud's
- * hn_hand_cloud_f32 and hn_hand_cloud_scratch_bytes, and the mesh fit's hn_mesh_fit_f32 and hn_mesh_fit_scratch_bytes). */
+ * hn_hand_cloud_f32 and hn_hand_cloud_scratch_bytes, the mesh fit's hn_mesh_fit_f32 and hn_mesh_fit_scratch_bytes, and the
+ * iterated fit's hn_mesh_geometry_f32, hn_mesh_fit_iters_f32 and hn_mesh_fit_iters_scratch_bytes). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -900,6 +901,43 @@ int hn_mesh_fit_f32(const float* mesh_depth, const uint8_t* silhouette, const fl
                     const float* xyz_mm, int n, int k, int h, int w, int v, int joints, int stride, float band, int min_points,
                     double damp, double max_shift2, double tan2_half_angle, void* scratch, int64_t scratch_bytes, float* out_mesh,
                     float* out_xyz, float* out_rt, int32_t* out_count, int64_t* out_cost, void* stream);
+/* The geometry pass of the overlay's raster (tests/refit_ref.py::geometry is the rule in numpy float32, and
+ * the outputs equal it bit for bit): the nearest mesh Z and its slot per pixel, and nothing else -- no frame, no image, no scene
+ * depth, no hidden flag, no coverage.  mesh, faces, faces_host, lifted, s, v, f, k, h, w, scratch: as hn_mesh_render_u8 takes them
+ * (scratch of hn_mesh_render_scratch_bytes(s, f) bytes, 16-byte aligned; k 1..16); exactly one of paras (HOST, 4 floats) and cams
+ * (DEVICE [s / k][4]).  Projection, snapping, rejection, winding, boxes, coverage and depth are the raster's own: out_depth equals
+ * the occluded raster's out_depth and out_who its silhouette & 0x7F, bit for bit.
+ *   out_depth [s / k][h][w]  fp32: the nearest Z, 0 where nothing was drawn
+ *   out_who   [s / k][h][w]  uint8: 0, or the nearest slot within the frame + 1
+ * Both are fully written.  Two launches on `stream`; every argument is checked before the first. */
+int hn_mesh_geometry_f32(const float* mesh, const int32_t* faces, const int32_t* faces_host /* or NULL */,
+                         const int32_t* lifted /* or NULL */, int s, int v, int f, int k, const float* paras /* host, or NULL */,
+                         const float* cams /* device [s / k][4], or NULL */, int h, int w, void* scratch, int64_t scratch_bytes,
+                         float* out_depth, uint8_t* out_who, void* stream);
+/* The depth fit iterated (tests/refit_ref.py::mesh_fit_iters is the rule, and the outputs equal it bit for
+ * bit): `iters` (1..8) Gauss-Newton steps of hn_mesh_fit_f32.  Iteration 1 runs on the caller's mesh_depth / silhouette; before
+ * every further iteration the current meshes are drawn again by hn_mesh_geometry_f32 (faces, faces_host, lifted, f: as it takes
+ * them; a slot with lifted == 0 is not drawn) and the step turns about the current root joint.  Every iteration applies the
+ * parameters and caps on its own; a slot whose iteration ends with a status other than 0 keeps its bytes for that iteration and is
+ * tried again in the next.  There is no early stop: 2 + 4 (iters - 1) + 1 launches on `stream`, whatever the data.
+ *   out_mesh, out_xyz     the state after the last iteration
+ *   out_count, out_cost   those of iteration 1: what hn_mesh_fit_f32 hands out
+ *   out_trace [n*k][iters][3]  int64 (matches, status, cost) of every iteration; the cost of iteration t is the residual after
+ *                         t - 1 motions
+ *   out_rt [n*k][12]      the composed motion about the ORIGINAL root joint c0 (fp64, rounded to fp32 at the end): the first
+ *                         iteration with status 0 gives R = R_t, T = t_t; every further one, with u = (c0 + T) - c_t,
+ *                         T <- (((R_t u)_j + c_t_j) + t_t_j) - c0_j and R <- R_t R; none: the identity
+ * scratch: hn_mesh_fit_scratch_bytes(n, k, h) bytes, 8-byte aligned; work: hn_mesh_fit_iters_scratch_bytes(...) bytes, 16-byte
+ * aligned (the intermediate meshes and joints, every iteration's motion, the geometry pass's outputs and scratch).  Every argument
+ * is checked under this entry's name before the first launch. */
+int64_t hn_mesh_fit_iters_scratch_bytes(int n, int k, int h, int w, int v, int f, int joints, int iters);
+int hn_mesh_fit_iters_f32(const float* mesh_depth, const uint8_t* silhouette, const float* scene_depth, int64_t depth_frame_stride,
+                          const float* paras /* host, or NULL */, const float* cams /* device [n][4], or NULL */, const float* mesh,
+                          const float* xyz_mm, const int32_t* faces, const int32_t* faces_host /* or NULL */,
+                          const int32_t* lifted /* or NULL */, int n, int k, int h, int w, int v, int f, int joints, int iters,
+                          int stride, float band, int min_points, double damp, double max_shift2, double tan2_half_angle,
+                          void* scratch, int64_t scratch_bytes, void* work, int64_t work_bytes, float* out_mesh, float* out_xyz,
+                          float* out_rt, int32_t* out_count, int64_t* out_cost, int64_t* out_trace, void* stream);
 /* A Linear layer on 1..4 rows as a matrix-vector product on the vector ALU (PoseNet at the live caller's batch, posenet.py:24-41,
  * 78-88: 67 MB of filter bank per 17 M MACs): y[m][:] = act(W (pre(x[m])) + bias (+ residual[m])), pre = relu(x * scale + shift)
  * when scale / shift ([k_real] fp32: the pre-activation BatchNorm) are given.  x fp32 [batch][x_stride] (k_real columns used), w16 =
