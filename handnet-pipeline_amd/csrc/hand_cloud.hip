@@ -16,17 +16,12 @@
 //                      frame) and the zero tail [written, points) (shared among the frame's workgroups) need the table alone.
 // No workgroup waits for another inside a launch, no floating-point atomic (no atomic at all): the outputs are a pure function
 // of the inputs and two runs give the same bytes.  The file is built with -ffp-contract=off (hn_amd/build.py).
-#include "hn_common.h"
+#include "depth_pass.h"
 
 namespace {
 
-constexpr int kCloudMaxK = 16;
-constexpr int kMaxStrips = 1024;    // of a frame: the prefix over the table stays at most 64 loads per thread
+using namespace hn;                 // depth_pass.h: the strips, kMaxSlots, wave_sum, the camera, back_x / back_y, valid_depth
 
-// rows per strip, a function of the frame's height alone (hn_hand_cloud_scratch_bytes knows nothing else)
-__host__ __device__ inline int strip_rows(int h) { return max(2, (h + kMaxStrips - 1) / kMaxStrips); }
-// strips per frame, padded to whole workgroups of four
-__host__ __device__ inline int strips_padded(int h) { return ((h + strip_rows(h) - 1) / strip_rows(h) + 3) / 4 * 4; }
 // the scratch: int64 sums [n][strips][k], then int32 counts [n][strips][k]
 __host__ __device__ inline size_t table_entries(int n, int k, int h) { return (size_t)n * strips_padded(h) * k; }
 
@@ -57,19 +52,13 @@ __device__ __forceinline__ Match classify(const CloudIn& in, int i, int r, int c
   const int who = in.sil[pix] & 0x7F;                                     // (the hidden flag is ignored)
   if (who == 0 || who > in.k) return m;
   const float d = in.depth[(size_t)i * in.frame_stride + (size_t)r * in.w + c];
-  if (!(d > 0.f && d <= 3.402823466e38f)) return m;                       // (a hole -- 0, NaN --, inf or a negative value)
+  if (!valid_depth(d)) return m;
   const float e = __fsub_rn(d, in.best[pix]);
   m.hit = fabsf(e) <= in.band;                                            // (NaN fails)
   m.slot = who - 1;
   m.d = d;
   m.e = e;
   return m;
-}
-
-__device__ __forceinline__ long long wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // grid (strips / 4, frames), 256 threads: wave wv of block (b, i) walks strip 4 b + wv of frame i
@@ -111,9 +100,9 @@ __global__ __launch_bounds__(256) void hand_cloud_write(CloudIn in, const long l
                                                         int points, float* __restrict__ cloud, int* __restrict__ out_count,
                                                         long long* __restrict__ out_resid) {
 #pragma clang fp contract(off)
-  __shared__ int part_before[16][kCloudMaxK], part_total[16][kCloudMaxK];
-  __shared__ long long part_resid[16][kCloudMaxK];
-  __shared__ int before[kCloudMaxK], total[kCloudMaxK];
+  __shared__ int part_before[16][kMaxSlots], part_total[16][kMaxSlots];
+  __shared__ long long part_resid[16][kMaxSlots];
+  __shared__ int before[kMaxSlots], total[kMaxSlots];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6, i = blockIdx.y;
   const int strips = gridDim.x * 4, first = blockIdx.x * 4, u = first + wv;
   const size_t frame_at = (size_t)i * strips * in.k;
@@ -166,11 +155,7 @@ __global__ __launch_bounds__(256) void hand_cloud_write(CloudIn in, const long l
     run = before[lane];
     for (int s = first; s < u; ++s) run += counts[frame_at + (size_t)s * in.k + lane];
   }
-  float fx = in.fx, fy = in.fy, cx = in.cx, cy = in.cy;
-  if (in.cams) {                                                          // (the row's address is uniform: four scalar loads)
-    const float* row = in.cams + 4 * (size_t)i;
-    fx = row[0]; fy = row[1]; cx = row[2]; cy = row[3];
-  }
+  const Cam cam = camera(in.cams, i, in.fx, in.fy, in.cx, in.cy);
   const float* e = in.ext ? in.ext + 12 * (size_t)i : nullptr;
   const int rows = strip_rows(in.h), wc = (in.w + in.q - 1) / in.q;
   const int r1 = min(in.h, (u + 1) * rows);
@@ -186,10 +171,7 @@ __global__ __launch_bounds__(256) void hand_cloud_write(CloudIn in, const long l
         todo &= ~votes;
         const int pos = __shfl(run, kk, 64) + __popcll(votes & ((1ull << lane) - 1ull));
         if (of && pos < points) {
-          // x = (((float)c + 0.5) - cx) * D / fx: subtract, multiply, divide, each rounded on its own
-          float x = __fdiv_rn(__fmul_rn(__fsub_rn(__fadd_rn((float)c, 0.5f), cx), m.d), fx);
-          float y = __fdiv_rn(__fmul_rn(__fsub_rn(__fadd_rn((float)r, 0.5f), cy), m.d), fy);
-          float z = m.d;
+          float x = back_x(cam, c, m.d), y = back_y(cam, r, m.d), z = m.d;
           if (e) {                                                        // 9i's transform, in its operation order
             const float px = x, py = y, pz = z;
             x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(e[0], px), __fmul_rn(e[1], py)), __fmul_rn(e[2], pz)), e[3]);
@@ -210,7 +192,7 @@ __global__ __launch_bounds__(256) void hand_cloud_write(CloudIn in, const long l
 }  // namespace
 
 extern "C" int64_t hn_hand_cloud_scratch_bytes(int n, int k, int h) {
-  if (n <= 0 || k <= 0 || k > kCloudMaxK || h <= 0 || h > 16384) return 0;
+  if (n <= 0 || k <= 0 || k > kMaxSlots || h <= 0 || h > 16384) return 0;
   return (int64_t)(table_entries(n, k, h) * (sizeof(long long) + sizeof(int)));
 }
 
@@ -218,23 +200,16 @@ extern "C" int hn_hand_cloud_f32(const float* mesh_depth, const uint8_t* silhoue
                                  int64_t depth_frame_stride, const float* paras, const float* cams, const float* extrinsics, int n,
                                  int k, int h, int w, int points, int stride, float band, void* scratch, int64_t scratch_bytes,
                                  float* out_cloud, int32_t* out_count, int64_t* out_resid, void* stream) {
-  HN_CHECK_ARG(mesh_depth && silhouette && scene_depth && scratch && out_cloud && out_count && out_resid,
-               "hn_hand_cloud_f32: null pointer");
-  HN_CHECK_ARG((paras != nullptr) != (cams != nullptr), "hn_hand_cloud_f32: exactly one of paras (host) and cams (device) must be given");
-  HN_CHECK_ARG(n >= 1 && n <= 65535, "hn_hand_cloud_f32: n = %d frames (1..65535)", n);
-  HN_CHECK_ARG(k >= 1 && k <= kCloudMaxK, "hn_hand_cloud_f32: k = %d slots per frame (1..16)", k);
-  HN_CHECK_ARG(h >= 1 && w >= 1 && h <= 16384 && w <= 16384, "hn_hand_cloud_f32: bad frame size %d x %d (1..16384)", h, w);
-  HN_CHECK_ARG(depth_frame_stride >= (int64_t)h * w, "hn_hand_cloud_f32: depth_frame_stride %lld is less than a frame of %d x %d",
-               (long long)depth_frame_stride, h, w);
-  HN_CHECK_ARG(points >= 1, "hn_hand_cloud_f32: points = %d (at least 1)", points);
-  HN_CHECK_ARG(stride >= 1, "hn_hand_cloud_f32: stride = %d (at least 1)", stride);
-  HN_CHECK_ARG(band > 0.f && band <= 100.f, "hn_hand_cloud_f32: band must be finite and in (0, 100] metres (got %g)", (double)band);
-  const int64_t need = hn_hand_cloud_scratch_bytes(n, k, h);
-  HN_CHECK_ARG(scratch_bytes >= need, "hn_hand_cloud_f32: scratch of %lld bytes, %lld needed", (long long)scratch_bytes,
-               (long long)need);
-  HN_CHECK_ARG(((uintptr_t)scratch & 7) == 0, "hn_hand_cloud_f32: scratch must be 8-byte aligned");
+  const char* fn = "hn_hand_cloud_f32";
+  HN_CHECK_ARG(mesh_depth && silhouette && scene_depth && scratch && out_cloud && out_count && out_resid, "%s: null pointer", fn);
+  if (int st = check_one_camera(fn, paras, cams)) return st;
+  if (int st = check_frames(fn, n, k, h, w)) return st;
+  if (int st = check_depth_stride(fn, depth_frame_stride, h, w)) return st;
+  HN_CHECK_ARG(points >= 1, "%s: points = %d (at least 1)", fn, points);
+  if (int st = check_sampling(fn, stride, band)) return st;
+  if (int st = check_buffer(fn, "scratch", scratch, scratch_bytes, hn_hand_cloud_scratch_bytes(n, k, h), 8)) return st;
   HN_CHECK_ARG((((uintptr_t)out_resid & 7) | ((uintptr_t)out_count & 3) | ((uintptr_t)out_cloud & 3)) == 0,
-               "hn_hand_cloud_f32: out_cloud / out_count must be aligned to 4 bytes and out_resid to 8");
+               "%s: out_cloud / out_count must be aligned to 4 bytes and out_resid to 8", fn);
   CloudIn in = {mesh_depth, silhouette, scene_depth, (long long)depth_frame_stride, cams, 0.f, 0.f, 0.f, 0.f, extrinsics, k, h, w,
                 std::min(stride, 16384), band};      // (h, w <= 16384: every larger stride leaves the pixel (0, 0) alone, as this one)
   if (paras) { in.fx = paras[0]; in.fy = paras[1]; in.cx = paras[2]; in.cy = paras[3]; }

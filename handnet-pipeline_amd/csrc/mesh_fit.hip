@@ -19,22 +19,17 @@
 #include <algorithm>
 #include <cmath>
 
-#include "hn_common.h"
+#include "depth_pass.h"
 
 namespace {
 
-constexpr int kFitMaxK = 16;
-constexpr int kMaxStrips = 1024;    // of a frame: the apply kernel's sum over the table stays at most 128 loads per thread
+using namespace hn;                 // depth_pass.h: the strips, kMaxSlots, wave_sum, the camera, back_x / back_y, valid_depth
+
 constexpr int kTerms = 29;          // 21 of A (j <= k, row by row), 6 of b, the cost, the count
 constexpr float kMinCos = 0.2f;     // FIT_MIN_COS: pixels seen at a steeper grazing angle carry no usable normal
 constexpr float kReach = 1.0f;      // FIT_REACH: a hand's surface lies within a metre of its wrist -- this bounds the sums
 constexpr double kArm = 0.1;        // FIT_ARM: the lever arm that puts the rotation damping on the translation's scale
 constexpr float kQ30 = 1073741824.0f;
-
-// rows per strip, a function of the frame's height alone (hn_mesh_fit_scratch_bytes knows nothing else)
-__host__ __device__ inline int strip_rows(int h) { return max(2, (h + kMaxStrips - 1) / kMaxStrips); }
-// strips per frame, padded to whole workgroups of four
-__host__ __device__ inline int strips_padded(int h) { return ((h + strip_rows(h) - 1) / strip_rows(h) + 3) / 4 * 4; }
 
 struct FitIn {
   const float* best;                // [n][h][w] the raster's out_depth
@@ -48,34 +43,8 @@ struct FitIn {
   float band;
 };
 
-struct Cam {
-  float fx, fy, cx, cy;
-};
-
-__device__ __forceinline__ Cam camera(const FitIn& in, int i) {
-  Cam cam = {in.fx, in.fy, in.cx, in.cy};
-  if (in.cams) {                                                          // (the row's address is uniform: four scalar loads)
-    const float* row = in.cams + 4 * (size_t)i;
-    cam.fx = row[0]; cam.fy = row[1]; cam.cx = row[2]; cam.cy = row[3];
-  }
-  return cam;
-}
-
-// P(r, c, z), x and y: (((float)c + 0.5) - cx) * z / fx -- subtract, multiply, divide, each rounded on its own (9j's point)
-__device__ __forceinline__ float back_x(const Cam& cam, int c, float z) {
-  return __fdiv_rn(__fmul_rn(__fsub_rn(__fadd_rn((float)c, 0.5f), cam.cx), z), cam.fx);
-}
-__device__ __forceinline__ float back_y(const Cam& cam, int r, float z) {
-  return __fdiv_rn(__fmul_rn(__fsub_rn(__fadd_rn((float)r, 0.5f), cam.cy), z), cam.fy);
-}
 // (int64)rint(x * 2^30) of one fp32 product
 __device__ __forceinline__ long long q30(float a, float b) { return (long long)rintf(__fmul_rn(__fmul_rn(a, b), kQ30)); }
-
-__device__ __forceinline__ long long wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // grid (strips / 4, k, frames), 256 threads: wave wv of block (b, kk, i) walks strip 4 b + wv of frame i for slot kk
 __global__ __launch_bounds__(256) void mesh_fit_accumulate(FitIn in, long long* __restrict__ table) {
@@ -84,7 +53,7 @@ __global__ __launch_bounds__(256) void mesh_fit_accumulate(FitIn in, long long* 
   const int strips = gridDim.x * 4, u = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int h = in.h, w = in.w, q = in.q;
   const int rows = strip_rows(h), wc = (w + q - 1) / q;
-  const Cam cam = camera(in, i);
+  const Cam cam = camera(in.cams, i, in.fx, in.fy, in.cx, in.cy);
   const size_t slot = (size_t)i * in.k + kk;
   const float* root = in.xyz_mm + slot * in.joints * 3;
   const float c0x = __fdiv_rn(root[0], 1000.f), c0y = __fdiv_rn(root[1], 1000.f), c0z = __fdiv_rn(root[2], 1000.f);
@@ -107,7 +76,7 @@ __global__ __launch_bounds__(256) void mesh_fit_accumulate(FitIn in, long long* 
       const float b = best[at], bl = best[at - 1], br = best[at + 1], bu = best[at - w], bd = best[at + w];
       if (!(b > 0.f && bl > 0.f && br > 0.f && bu > 0.f && bd > 0.f)) continue;
       const float d = depth[at];
-      if (!(d > 0.f && d <= 3.402823466e38f)) continue;                   // (a hole -- 0, NaN --, inf or a negative value)
+      if (!valid_depth(d)) continue;
       if (!(fabsf(__fsub_rn(d, b)) <= in.band)) continue;                 // (NaN fails)
       // the normal from the mesh depth map: gx = P(r, c + 1) - P(r, c - 1), gy = P(r + 1, c) - P(r - 1, c), n = gx x gy
       const float gxx = __fsub_rn(back_x(cam, c + 1, br), back_x(cam, c - 1, bl));
@@ -340,7 +309,7 @@ __global__ __launch_bounds__(256) void mesh_fit_apply(const long long* __restric
 }  // namespace
 
 extern "C" int64_t hn_mesh_fit_scratch_bytes(int n, int k, int h) {
-  if (n <= 0 || k <= 0 || k > kFitMaxK || h <= 0 || h > 16384) return 0;
+  if (n <= 0 || k <= 0 || k > kMaxSlots || h <= 0 || h > 16384) return 0;
   return (int64_t)((size_t)n * k * strips_padded(h) * kTerms * sizeof(long long));
 }
 
@@ -350,30 +319,19 @@ extern "C" int hn_mesh_fit_f32(const float* mesh_depth, const uint8_t* silhouett
                                int min_points, double damp, double max_shift2, double tan2_half_angle, void* scratch,
                                int64_t scratch_bytes, float* out_mesh, float* out_xyz, float* out_rt, int32_t* out_count,
                                int64_t* out_cost, void* stream) {
+  const char* fn = "hn_mesh_fit_f32";
   HN_CHECK_ARG(mesh_depth && silhouette && scene_depth && mesh && xyz_mm && scratch && out_mesh && out_xyz && out_rt && out_count &&
                    out_cost,
-               "hn_mesh_fit_f32: null pointer");
-  HN_CHECK_ARG((paras != nullptr) != (cams != nullptr), "hn_mesh_fit_f32: exactly one of paras (host) and cams (device) must be given");
-  HN_CHECK_ARG(n >= 1 && n <= 65535, "hn_mesh_fit_f32: n = %d frames (1..65535)", n);
-  HN_CHECK_ARG(k >= 1 && k <= kFitMaxK, "hn_mesh_fit_f32: k = %d slots per frame (1..16)", k);
-  HN_CHECK_ARG(h >= 1 && w >= 1 && h <= 16384 && w <= 16384, "hn_mesh_fit_f32: bad frame size %d x %d (1..16384)", h, w);
-  HN_CHECK_ARG(depth_frame_stride >= (int64_t)h * w, "hn_mesh_fit_f32: depth_frame_stride %lld is less than a frame of %d x %d",
-               (long long)depth_frame_stride, h, w);
-  HN_CHECK_ARG(v >= 1 && v <= (1 << 24), "hn_mesh_fit_f32: v = %d vertices (1..2^24)", v);
-  HN_CHECK_ARG(joints >= 1 && joints <= 4096, "hn_mesh_fit_f32: joints = %d (1..4096)", joints);
-  HN_CHECK_ARG(stride >= 1, "hn_mesh_fit_f32: stride = %d (at least 1)", stride);
-  HN_CHECK_ARG(band > 0.f && band <= 100.f, "hn_mesh_fit_f32: band must be finite and in (0, 100] metres (got %g)", (double)band);
-  HN_CHECK_ARG(min_points >= 1, "hn_mesh_fit_f32: min_points = %d (at least 1)", min_points);
-  HN_CHECK_ARG(damp >= 0.0 && std::isfinite(damp), "hn_mesh_fit_f32: damp must be finite and >= 0 (got %g)", damp);
-  HN_CHECK_ARG(max_shift2 > 0.0 && std::isfinite(max_shift2), "hn_mesh_fit_f32: max_shift2 must be finite and > 0 (got %g)", max_shift2);
-  HN_CHECK_ARG(tan2_half_angle > 0.0 && std::isfinite(tan2_half_angle),
-               "hn_mesh_fit_f32: tan2_half_angle must be finite and > 0 (got %g)", tan2_half_angle);
-  const int64_t need = hn_mesh_fit_scratch_bytes(n, k, h);
-  HN_CHECK_ARG(scratch_bytes >= need, "hn_mesh_fit_f32: scratch of %lld bytes, %lld needed", (long long)scratch_bytes, (long long)need);
-  HN_CHECK_ARG(((uintptr_t)scratch & 7) == 0, "hn_mesh_fit_f32: scratch must be 8-byte aligned");
+               "%s: null pointer", fn);
+  if (int st = check_one_camera(fn, paras, cams)) return st;
+  if (int st = check_frames(fn, n, k, h, w)) return st;
+  if (int st = check_depth_stride(fn, depth_frame_stride, h, w)) return st;
+  if (int st = check_fit_sizes(fn, v, nullptr, joints)) return st;
+  if (int st = check_fit_options(fn, stride, band, min_points, damp, max_shift2, tan2_half_angle)) return st;
+  if (int st = check_buffer(fn, "scratch", scratch, scratch_bytes, hn_mesh_fit_scratch_bytes(n, k, h), 8)) return st;
   HN_CHECK_ARG((((uintptr_t)out_cost & 7) | ((uintptr_t)out_count & 3) | ((uintptr_t)out_mesh & 3) | ((uintptr_t)out_xyz & 3) |
                 ((uintptr_t)out_rt & 3)) == 0,
-               "hn_mesh_fit_f32: out_mesh / out_xyz / out_rt / out_count must be aligned to 4 bytes and out_cost to 8");
+               "%s: out_mesh / out_xyz / out_rt / out_count must be aligned to 4 bytes and out_cost to 8", fn);
   FitIn in = {mesh_depth, silhouette, scene_depth, (long long)depth_frame_stride, cams, 0.f, 0.f, 0.f, 0.f, xyz_mm, k, h, w,
               std::min(stride, 16384), joints, band};  // (h, w <= 16384: every larger stride leaves no candidate, as this one)
   if (paras) { in.fx = paras[0]; in.fy = paras[1]; in.cx = paras[2]; in.cy = paras[3]; }

@@ -27,14 +27,16 @@
 // table [frames][4] where the other instantiations read four scalar arguments.  The projection and the tile kernel are the same.
 //
 // The geometry pass (hn_mesh_geometry_f32; DESIGN.md section 9l, tests/refit_ref.py::geometry) is a third tile kernel behind the
-// same setup launch: mesh_geometry_tiles makes the same slot walk, box test, ballot walk and edge functions and keeps the nearest
-// Z and its slot, and that is all it writes -- fp32 Z (0: nothing drawn) and the byte slot + 1 (0: nothing drawn) per pixel.  It
+// same setup launch: mesh_geometry_tiles makes the same walk (walk_tile: slots, box test, ballots, edge functions, Z) and keeps
+// the nearest Z and its slot, and that is all it writes -- fp32 Z (0: nothing drawn) and the byte slot + 1 (0: nothing drawn) per pixel.  It
 // reads no frame and no scene depth and stores no image: what the iterated fit needs to see its moved mesh again.
-#include "hn_common.h"
+#include "depth_pass.h"
 
 #include <type_traits>
 
 namespace {
+
+using namespace hn;                 // depth_pass.h: kMaxSlots, valid_depth, the entries' argument checks
 
 constexpr int kSub = 256;           // sub-pixel grid: 1/256 pixel
 constexpr int kHalf = 128;          // a pixel's sample point: (256 col + 128, 256 row + 128)
@@ -201,6 +203,44 @@ __device__ __forceinline__ long long edge(int ax, int ay, int bx, int by, int px
   return e;
 }
 
+// The walk of a tile kernel (one wave per 8 x 8 tile at (tx, ty) of frame n, one pixel per lane, sampled at (px, py)): the
+// frame's k slots in order, a slot whose box misses the tile skipped, 64 face boxes tested at a time (one per lane, one
+// ballot), and for every face whose box touches the tile the three edge functions and the barycentric Z.  on_slot(kk) is
+// called once per slot that touches the tile (wave-uniform), on_hit(kk, z, rec) on the lanes whose sample the face covers, in
+// slot-major, then ascending face order: a caller that keeps `z < best` gives an exact tie to the lower index.
+template <class OnSlot, class OnHit>
+__device__ __forceinline__ void walk_tile(const unsigned char* __restrict__ scratch, int slots, int f, int k, int n, int tx, int ty,
+                                          int lane, int px, int py, bool inside_frame, OnSlot on_slot, OnHit on_hit) {
+  const FaceRec* all_recs = reinterpret_cast<const FaceRec*>(scratch + rec_offset(slots));
+  const Box* all_boxes = reinterpret_cast<const Box*>(scratch + box_offset(slots, f));
+  for (int kk = 0; kk < k; ++kk) {
+    const int slot = n * k + kk;
+    const SlotBox sb = *reinterpret_cast<const SlotBox*>(scratch + (size_t)slot * sizeof(SlotBox));
+    if (sb.x0 > tx + 7 || sb.x1 < tx || sb.y0 > ty + 7 || sb.y1 < ty) continue;      // (wave-uniform)
+    on_slot(kk);
+    const FaceRec* recs = all_recs + (size_t)slot * f;
+    const Box* boxes = all_boxes + (size_t)slot * f;
+    for (int base = 0; base < f; base += 64) {
+      bool hit = false;
+      if (base + lane < f) {
+        const Box b = boxes[base + lane];
+        hit = b.x0 <= tx + 7 && b.x1 >= tx && b.y0 <= ty + 7 && b.y1 >= ty;
+      }
+      unsigned long long todo = __ballot(hit);
+      while (todo) {
+        const int bit = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const FaceRec r = recs[__builtin_amdgcn_readfirstlane(base + bit)];
+        bool in = inside_frame;
+        const long long wa = edge(r.bx, r.by, r.cx, r.cy, px, py, in);      // weight of corner a
+        const long long wb = edge(r.cx, r.cy, r.ax, r.ay, px, py, in);
+        const long long wc = edge(r.ax, r.ay, r.bx, r.by, px, py, in);
+        if (in) on_hit(kk, ((float)wa * r.za + (float)wb * r.zb + (float)wc * r.zc) * r.inv_area, r);
+      }
+    }
+  }
+}
+
 // FMT: HN_FRAME_F32_CHW / HN_FRAME_U8_BGR_HWC; OCC: the occluded form, whose one further argument is an Occlusion
 template <int FMT, bool OCC = false, class... Occ>
 __global__ __launch_bounds__(256) void mesh_raster_tiles(const unsigned char* __restrict__ scratch, int slots, int f, int k,
@@ -215,53 +255,26 @@ __global__ __launch_bounds__(256) void mesh_raster_tiles(const unsigned char* __
   const int col = tx + (lane & 7), row = ty + (lane >> 3);
   const bool inside_frame = col < w && row < h;
   const int px = col * kSub + kHalf, py = row * kSub + kHalf;
-  const FaceRec* all_recs = reinterpret_cast<const FaceRec*>(scratch + rec_offset(slots));
-  const Box* all_boxes = reinterpret_cast<const Box*>(scratch + box_offset(slots, f));
   float best = 3.402823466e38f;
   unsigned rgb = 0;
   bool covered = false;
   int winner = 0;                                             // (OCC) slot within the frame of the nearest face
   unsigned touched = 0;                                       // (OCC) bit kk: slot kk's box meets the tile (wave-uniform)
-  for (int kk = 0; kk < k; ++kk) {
-    const int slot = n * k + kk;
-    const SlotBox sb = *reinterpret_cast<const SlotBox*>(scratch + (size_t)slot * sizeof(SlotBox));
-    if (sb.x0 > tx + 7 || sb.x1 < tx || sb.y0 > ty + 7 || sb.y1 < ty) continue;      // (wave-uniform)
-    if (OCC) touched |= 1u << kk;
-    const FaceRec* recs = all_recs + (size_t)slot * f;
-    const Box* boxes = all_boxes + (size_t)slot * f;
-    for (int base = 0; base < f; base += 64) {
-      bool hit = false;
-      if (base + lane < f) {
-        const Box b = boxes[base + lane];
-        hit = b.x0 <= tx + 7 && b.x1 >= tx && b.y0 <= ty + 7 && b.y1 >= ty;
-      }
-      unsigned long long todo = __ballot(hit);
-      while (todo) {                                          // ascending face order: the lower index wins an exact tie
-        const int bit = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const FaceRec r = recs[__builtin_amdgcn_readfirstlane(base + bit)];
-        bool in = inside_frame;
-        const long long wa = edge(r.bx, r.by, r.cx, r.cy, px, py, in);      // weight of corner a
-        const long long wb = edge(r.cx, r.cy, r.ax, r.ay, px, py, in);
-        const long long wc = edge(r.ax, r.ay, r.bx, r.by, px, py, in);
-        if (in) {
-          const float z = ((float)wa * r.za + (float)wb * r.zb + (float)wc * r.zc) * r.inv_area;
-          if (z < best) {
-            best = z; rgb = r.rgb; covered = true;
-            if (OCC) winner = kk;
-          }
+  walk_tile(
+      scratch, slots, f, k, n, tx, ty, lane, px, py, inside_frame, [&](int kk) { if (OCC) touched |= 1u << kk; },
+      [&](int kk, float z, const FaceRec& r) {
+        if (z < best) {
+          best = z; rgb = r.rgb; covered = true;
+          if (OCC) winner = kk;
         }
-      }
-    }
-  }
+      });
   bool shown = covered;
   if constexpr (OCC) {
 #pragma clang fp contract(off)
     const Occlusion o = (occ, ...);
     if (covered) {                                            // (covered lanes are inside the frame)
       const float d = o.depth[(size_t)n * o.frame_stride + (size_t)row * w + col];
-      const bool valid = d > 0.f && d <= 3.402823466e38f;     // (a hole -- 0, NaN --, inf or a negative value hides nothing)
-      shown = !(valid && best > __fadd_rn(d, o.margin));
+      shown = !(valid_depth(d) && best > __fadd_rn(d, o.margin));   // (a depth that measures nothing hides nothing)
     }
     // all 64 lanes are here: two ballots per slot that touched the tile, lane 0 adds their popcounts
     while (touched) {
@@ -311,38 +324,15 @@ __global__ __launch_bounds__(256) void mesh_geometry_tiles(const unsigned char* 
   const int col = tx + (lane & 7), row = ty + (lane >> 3);
   const bool inside_frame = col < w && row < h;
   const int px = col * kSub + kHalf, py = row * kSub + kHalf;
-  const FaceRec* all_recs = reinterpret_cast<const FaceRec*>(scratch + rec_offset(slots));
-  const Box* all_boxes = reinterpret_cast<const Box*>(scratch + box_offset(slots, f));
   float best = 3.402823466e38f;
   int who = 0;                                                // 0, or the nearest face's slot within the frame + 1
-  for (int kk = 0; kk < k; ++kk) {
-    const int slot = n * k + kk;
-    const SlotBox sb = *reinterpret_cast<const SlotBox*>(scratch + (size_t)slot * sizeof(SlotBox));
-    if (sb.x0 > tx + 7 || sb.x1 < tx || sb.y0 > ty + 7 || sb.y1 < ty) continue;      // (wave-uniform)
-    const FaceRec* recs = all_recs + (size_t)slot * f;
-    const Box* boxes = all_boxes + (size_t)slot * f;
-    for (int base = 0; base < f; base += 64) {
-      bool hit = false;
-      if (base + lane < f) {
-        const Box b = boxes[base + lane];
-        hit = b.x0 <= tx + 7 && b.x1 >= tx && b.y0 <= ty + 7 && b.y1 >= ty;
-      }
-      unsigned long long todo = __ballot(hit);
-      while (todo) {                                          // ascending face order: the lower index wins an exact tie
-        const int bit = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const FaceRec r = recs[__builtin_amdgcn_readfirstlane(base + bit)];
-        bool in = inside_frame;
-        const long long wa = edge(r.bx, r.by, r.cx, r.cy, px, py, in);
-        const long long wb = edge(r.cx, r.cy, r.ax, r.ay, px, py, in);
-        const long long wc = edge(r.ax, r.ay, r.bx, r.by, px, py, in);
-        if (in) {
-          const float z = ((float)wa * r.za + (float)wb * r.zb + (float)wc * r.zc) * r.inv_area;
-          if (z < best) { best = z; who = kk + 1; }
-        }
-      }
-    }
-  }
+  walk_tile(
+      scratch, slots, f, k, n, tx, ty, lane, px, py, inside_frame, [](int) {},
+      [&](int kk, float z, const FaceRec&) {
+        const bool nearer = z < best;       // (two selects, as the kernel had them before the walk was shared: an `if` here
+        best = nearer ? z : best;           // becomes an exec-masked branch inside the face loop)
+        who = nearer ? kk + 1 : who;
+      });
   if (!inside_frame) return;
   const size_t pix = ((size_t)n * h + row) * w + col;
   out_depth[pix] = who ? best : 0.f;
@@ -356,7 +346,20 @@ extern "C" int64_t hn_mesh_render_scratch_bytes(int s, int f) {
   return (int64_t)scratch_total(s, f);
 }
 
-// the argument checks every entry point shares (`fn`: the name the messages carry), then the two launches; exactly one of
+// the setup launch of every entry, one of four instantiations: a camera per frame (cams, device) or one (paras, host); no
+// further argument, or -- the occluded form -- the slots' counters, which the kernel zeroes
+template <class... Coverage>
+static void launch_setup(const float* mesh, const int32_t* faces, const int32_t* lifted, int s, int v, int f, int k, const float* paras,
+                         const float* cams, int h, int w, unsigned char* sc, hipStream_t st, Coverage... coverage) {
+  if (cams)
+    hipLaunchKernelGGL((mesh_raster_setup<true, Coverage...>), dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, cams, k, 0.f, 0.f, h,
+                       w, sc, s, coverage...);
+  else
+    hipLaunchKernelGGL((mesh_raster_setup<false, Coverage...>), dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, paras[0], paras[1],
+                       paras[2], paras[3], h, w, sc, s, coverage...);
+}
+
+// the argument checks every render entry shares (`fn`: the name the messages carry), then the two launches; exactly one of
 // paras (host, one camera) and cams (device, a row per frame) is given
 static int render(const char* fn, const float* mesh, const int32_t* faces, const int32_t* faces_host, const int32_t* lifted, int s,
                   int v, int f, int k, const float* paras, const float* cams, const void* frame, int frame_format, int h, int w,
@@ -364,58 +367,41 @@ static int render(const char* fn, const float* mesh, const int32_t* faces, const
                   int64_t depth_frame_stride, void* stream) {
   HN_CHECK_ARG(mesh && faces && (paras || cams) && frame && scratch, "%s: null pointer", fn);
   HN_CHECK_ARG(out_image, "%s: out_image is NULL", fn);
-  HN_CHECK_ARG(s > 0 && v > 0 && f > 0, "%s: bad dims (s %d, v %d, f %d: all must be positive)", fn, s, v, f);
-  HN_CHECK_ARG(k > 0 && s % k == 0, "%s: %d slots are not a multiple of k = %d slots per frame", fn, s, k);
-  HN_CHECK_ARG(h > 0 && w > 0 && h <= 16384 && w <= 16384, "%s: bad frame size %d x %d (1..16384)", fn, h, w);
-  HN_CHECK_ARG(s / k <= 65535, "%s: more than 65535 frames", fn);
+  if (int st = check_slots(fn, s, v, f, k)) return st;
+  if (int st = check_raster_frames(fn, s, k, h, w)) return st;
   HN_CHECK_ARG(frame_format == HN_FRAME_F32_CHW || frame_format == HN_FRAME_U8_BGR_HWC, "%s: unknown frame format %d", fn,
                frame_format);
-  HN_CHECK_ARG(scratch_bytes >= (int64_t)scratch_total(s, f), "%s: scratch of %lld bytes, %lld needed", fn,
-               (long long)scratch_bytes, (long long)scratch_total(s, f));
-  HN_CHECK_ARG(((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", fn);
-  HN_CHECK_ARG(!cams || ((uintptr_t)cams & 3) == 0, "%s: cams must be aligned to a float", fn);
+  if (int st = check_buffer(fn, "scratch", scratch, scratch_bytes, (int64_t)scratch_total(s, f), 16)) return st;
+  if (int st = check_cams_aligned(fn, cams)) return st;
   if (occ) {
     HN_CHECK_ARG(occ->depth, "%s: scene_depth is NULL", fn);
     HN_CHECK_ARG(occ->silhouette, "%s: out_silhouette is NULL", fn);
-    HN_CHECK_ARG(k <= 16, "%s: k = %d slots per frame do not fit the silhouette's byte (1..16)", fn, k);
-    HN_CHECK_ARG(depth_frame_stride >= (int64_t)h * w, "%s: depth_frame_stride %lld is less than a frame of %d x %d", fn,
-                 (long long)depth_frame_stride, h, w);
+    if (int st = check_slot_byte(fn, k, "the silhouette's byte")) return st;
+    if (int st = check_depth_stride(fn, depth_frame_stride, h, w)) return st;
     HN_CHECK_ARG(occ->margin == occ->margin && fabsf(occ->margin) <= 3.402823466e38f, "%s: margin must be finite", fn);
   }
-  if (faces_host)
-    for (int64_t i = 0; i < (int64_t)f * 3; ++i)
-      HN_CHECK_ARG(faces_host[i] >= 0 && faces_host[i] < v, "%s: face %lld uses vertex %d of %d", fn, (long long)(i / 3),
-                   faces_host[i], v);
+  if (int st = check_faces_host(fn, faces_host, f, v)) return st;
   hipStream_t st = (hipStream_t)stream;
   unsigned char* sc = static_cast<unsigned char*>(scratch);
   const dim3 grid((w + 31) / 32, (h + 7) / 8, s / k);
+  if (!occ)
+    launch_setup(mesh, faces, lifted, s, v, f, k, paras, cams, h, w, sc, st);
+  else
+    launch_setup(mesh, faces, lifted, s, v, f, k, paras, cams, h, w, sc, st, occ->coverage);
+  HN_CHECK_LAUNCH("mesh_raster_setup");
   if (!occ) {
-    if (cams)
-      hipLaunchKernelGGL((mesh_raster_setup<true>), dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, cams, k, 0.f, 0.f, h, w, sc, s);
-    else
-      hipLaunchKernelGGL((mesh_raster_setup<false>), dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, paras[0], paras[1], paras[2], paras[3], h, w, sc, s);
-    HN_CHECK_LAUNCH("mesh_raster_setup");
     if (frame_format == HN_FRAME_F32_CHW)
       hipLaunchKernelGGL(mesh_raster_tiles<HN_FRAME_F32_CHW>, grid, dim3(256), 0, st, sc, s, f, k, frame, h, w, out_image, out_depth);
     else
       hipLaunchKernelGGL(mesh_raster_tiles<HN_FRAME_U8_BGR_HWC>, grid, dim3(256), 0, st, sc, s, f, k, frame, h, w, out_image,
                          out_depth);
-    HN_CHECK_LAUNCH("mesh_raster_tiles");
-    return HN_OK;
-  }
-  if (cams)
-    hipLaunchKernelGGL((mesh_raster_setup<true, int*>), dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, cams, k, 0.f, 0.f, h, w, sc, s,
-                       occ->coverage);
-  else
-    hipLaunchKernelGGL((mesh_raster_setup<false, int*>), dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, paras[0], paras[1], paras[2], paras[3], h, w, sc, s,
-                       occ->coverage);
-  HN_CHECK_LAUNCH("mesh_raster_setup");
-  if (frame_format == HN_FRAME_F32_CHW)
+  } else if (frame_format == HN_FRAME_F32_CHW) {
     hipLaunchKernelGGL((mesh_raster_tiles<HN_FRAME_F32_CHW, true, Occlusion>), grid, dim3(256), 0, st, sc, s, f, k, frame, h, w,
                        out_image, out_depth, *occ);
-  else
+  } else {
     hipLaunchKernelGGL((mesh_raster_tiles<HN_FRAME_U8_BGR_HWC, true, Occlusion>), grid, dim3(256), 0, st, sc, s, f, k, frame, h, w,
                        out_image, out_depth, *occ);
+  }
   HN_CHECK_LAUNCH("mesh_raster_tiles");
   return HN_OK;
 }
@@ -461,34 +447,24 @@ extern "C" int hn_mesh_render_cams_occluded_u8(const float* mesh, const int32_t*
                 h, w, scratch, scratch_bytes, out_image, out_depth, &occ, depth_frame_stride, stream);
 }
 
-// the geometry pass: render()'s argument checks without a frame, an image or a scene depth, the setup launch as it is, and
+// the geometry pass: render()'s argument checks without a frame, an image or a scene depth, the same setup launch, and
 // mesh_geometry_tiles in place of the raster
 extern "C" int hn_mesh_geometry_f32(const float* mesh, const int32_t* faces, const int32_t* faces_host, const int32_t* lifted, int s,
                                     int v, int f, int k, const float* paras, const float* cams, int h, int w, void* scratch,
                                     int64_t scratch_bytes, float* out_depth, uint8_t* out_who, void* stream) {
   const char* fn = "hn_mesh_geometry_f32";
   HN_CHECK_ARG(mesh && faces && scratch && out_depth && out_who, "%s: null pointer", fn);
-  HN_CHECK_ARG((paras != nullptr) != (cams != nullptr), "%s: exactly one of paras (host) and cams (device) must be given", fn);
-  HN_CHECK_ARG(s > 0 && v > 0 && f > 0, "%s: bad dims (s %d, v %d, f %d: all must be positive)", fn, s, v, f);
-  HN_CHECK_ARG(k > 0 && s % k == 0, "%s: %d slots are not a multiple of k = %d slots per frame", fn, s, k);
-  HN_CHECK_ARG(k <= 16, "%s: k = %d slots per frame do not fit the slot byte (1..16)", fn, k);
-  HN_CHECK_ARG(h > 0 && w > 0 && h <= 16384 && w <= 16384, "%s: bad frame size %d x %d (1..16384)", fn, h, w);
-  HN_CHECK_ARG(s / k <= 65535, "%s: more than 65535 frames", fn);
-  HN_CHECK_ARG(scratch_bytes >= (int64_t)scratch_total(s, f), "%s: scratch of %lld bytes, %lld needed", fn,
-               (long long)scratch_bytes, (long long)scratch_total(s, f));
-  HN_CHECK_ARG(((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", fn);
-  HN_CHECK_ARG(!cams || ((uintptr_t)cams & 3) == 0, "%s: cams must be aligned to a float", fn);
+  if (int st = check_one_camera(fn, paras, cams)) return st;
+  if (int st = check_slots(fn, s, v, f, k)) return st;
+  if (int st = check_slot_byte(fn, k, "the slot byte")) return st;
+  if (int st = check_raster_frames(fn, s, k, h, w)) return st;
+  if (int st = check_buffer(fn, "scratch", scratch, scratch_bytes, (int64_t)scratch_total(s, f), 16)) return st;
+  if (int st = check_cams_aligned(fn, cams)) return st;
   HN_CHECK_ARG(((uintptr_t)out_depth & 3) == 0, "%s: out_depth must be aligned to a float", fn);
-  if (faces_host)
-    for (int64_t i = 0; i < (int64_t)f * 3; ++i)
-      HN_CHECK_ARG(faces_host[i] >= 0 && faces_host[i] < v, "%s: face %lld uses vertex %d of %d", fn, (long long)(i / 3),
-                   faces_host[i], v);
+  if (int st = check_faces_host(fn, faces_host, f, v)) return st;
   hipStream_t st = (hipStream_t)stream;
   unsigned char* sc = static_cast<unsigned char*>(scratch);
-  if (cams)
-    hipLaunchKernelGGL((mesh_raster_setup<true>), dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, cams, k, 0.f, 0.f, h, w, sc, s);
-  else
-    hipLaunchKernelGGL((mesh_raster_setup<false>), dim3(s), dim3(256), 0, st, mesh, faces, lifted, v, f, paras[0], paras[1], paras[2], paras[3], h, w, sc, s);
+  launch_setup(mesh, faces, lifted, s, v, f, k, paras, cams, h, w, sc, st);
   HN_CHECK_LAUNCH("mesh_raster_setup");
   hipLaunchKernelGGL(mesh_geometry_tiles, dim3((w + 31) / 32, (h + 7) / 8, s / k), dim3(256), 0, st, sc, s, f, k, h, w, out_depth,
                      out_who);

@@ -13,7 +13,7 @@
 #include <cmath>
 
 #include "handnet_hip.h"
-#include "hn_common.h"
+#include "depth_pass.h"
 
 namespace {
 
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(64) void mesh_refit_compose(const float* __restrict
 }  // namespace
 
 extern "C" int64_t hn_mesh_fit_iters_scratch_bytes(int n, int k, int h, int w, int v, int f, int joints, int iters) {
-  if (n <= 0 || n > 65535 || k <= 0 || k > 16 || h <= 0 || h > 16384 || w <= 0 || w > 16384 || v <= 0 || v > (1 << 24) || f <= 0 ||
+  if (n <= 0 || n > 65535 || k <= 0 || k > hn::kMaxSlots || h <= 0 || h > 16384 || w <= 0 || w > 16384 || v <= 0 || v > (1 << 24) || f <= 0 ||
       joints <= 0 || joints > 4096 || iters < 1 || iters > kMaxIters)
     return 0;
   return (int64_t)work_layout(n, k, h, w, v, f, joints, iters).total;
@@ -135,41 +135,25 @@ extern "C" int hn_mesh_fit_iters_f32(const float* mesh_depth, const uint8_t* sil
                                      int64_t scratch_bytes, void* work, int64_t work_bytes, float* out_mesh, float* out_xyz,
                                      float* out_rt, int32_t* out_count, int64_t* out_cost, int64_t* out_trace, void* stream) {
   const char* fn = "hn_mesh_fit_iters_f32";
-  // every check of hn_mesh_fit_f32 and of hn_mesh_geometry_f32, under this entry's name and before the first launch
+  // every check of hn_mesh_fit_f32 and of hn_mesh_geometry_f32 (depth_pass.h), under this entry's name and before the first launch
+  using namespace hn;
   HN_CHECK_ARG(mesh_depth && silhouette && scene_depth && mesh && xyz_mm && faces && scratch && work && out_mesh && out_xyz && out_rt &&
                    out_count && out_cost && out_trace,
                "%s: null pointer", fn);
-  HN_CHECK_ARG((paras != nullptr) != (cams != nullptr), "%s: exactly one of paras (host) and cams (device) must be given", fn);
+  if (int st = check_one_camera(fn, paras, cams)) return st;
   HN_CHECK_ARG(iters >= 1 && iters <= kMaxIters, "%s: iters = %d (1..%d)", fn, iters, kMaxIters);
-  HN_CHECK_ARG(n >= 1 && n <= 65535, "%s: n = %d frames (1..65535)", fn, n);
-  HN_CHECK_ARG(k >= 1 && k <= 16, "%s: k = %d slots per frame (1..16)", fn, k);
-  HN_CHECK_ARG(h >= 1 && w >= 1 && h <= 16384 && w <= 16384, "%s: bad frame size %d x %d (1..16384)", fn, h, w);
-  HN_CHECK_ARG(depth_frame_stride >= (int64_t)h * w, "%s: depth_frame_stride %lld is less than a frame of %d x %d", fn,
-               (long long)depth_frame_stride, h, w);
-  HN_CHECK_ARG(v >= 1 && v <= (1 << 24), "%s: v = %d vertices (1..2^24)", fn, v);
-  HN_CHECK_ARG(f >= 1, "%s: f = %d faces (at least 1)", fn, f);
-  HN_CHECK_ARG(joints >= 1 && joints <= 4096, "%s: joints = %d (1..4096)", fn, joints);
-  HN_CHECK_ARG(stride >= 1, "%s: stride = %d (at least 1)", fn, stride);
-  HN_CHECK_ARG(band > 0.f && band <= 100.f, "%s: band must be finite and in (0, 100] metres (got %g)", fn, (double)band);
-  HN_CHECK_ARG(min_points >= 1, "%s: min_points = %d (at least 1)", fn, min_points);
-  HN_CHECK_ARG(damp >= 0.0 && std::isfinite(damp), "%s: damp must be finite and >= 0 (got %g)", fn, damp);
-  HN_CHECK_ARG(max_shift2 > 0.0 && std::isfinite(max_shift2), "%s: max_shift2 must be finite and > 0 (got %g)", fn, max_shift2);
-  HN_CHECK_ARG(tan2_half_angle > 0.0 && std::isfinite(tan2_half_angle), "%s: tan2_half_angle must be finite and > 0 (got %g)", fn,
-               tan2_half_angle);
-  const int64_t need = hn_mesh_fit_scratch_bytes(n, k, h);
-  HN_CHECK_ARG(scratch_bytes >= need, "%s: scratch of %lld bytes, %lld needed", fn, (long long)scratch_bytes, (long long)need);
-  HN_CHECK_ARG(((uintptr_t)scratch & 7) == 0, "%s: scratch must be 8-byte aligned", fn);
+  if (int st = check_frames(fn, n, k, h, w)) return st;
+  if (int st = check_depth_stride(fn, depth_frame_stride, h, w)) return st;
+  if (int st = check_fit_sizes(fn, v, &f, joints)) return st;
+  if (int st = check_fit_options(fn, stride, band, min_points, damp, max_shift2, tan2_half_angle)) return st;
+  if (int st = check_buffer(fn, "scratch", scratch, scratch_bytes, hn_mesh_fit_scratch_bytes(n, k, h), 8)) return st;
   const Work lay = work_layout(n, k, h, w, v, f, joints, iters);
-  HN_CHECK_ARG(work_bytes >= (int64_t)lay.total, "%s: work of %lld bytes, %lld needed", fn, (long long)work_bytes, (long long)lay.total);
-  HN_CHECK_ARG(((uintptr_t)work & 15) == 0, "%s: work must be 16-byte aligned", fn);
-  HN_CHECK_ARG(!cams || ((uintptr_t)cams & 3) == 0, "%s: cams must be aligned to a float", fn);
+  if (int st = check_buffer(fn, "work", work, work_bytes, (int64_t)lay.total, 16)) return st;
+  if (int st = check_cams_aligned(fn, cams)) return st;
   HN_CHECK_ARG((((uintptr_t)out_cost & 7) | ((uintptr_t)out_trace & 7) | ((uintptr_t)out_count & 3) | ((uintptr_t)out_mesh & 3) |
                 ((uintptr_t)out_xyz & 3) | ((uintptr_t)out_rt & 3)) == 0,
                "%s: out_mesh / out_xyz / out_rt / out_count must be aligned to 4 bytes, out_cost and out_trace to 8", fn);
-  if (faces_host)
-    for (int64_t i = 0; i < (int64_t)f * 3; ++i)
-      HN_CHECK_ARG(faces_host[i] >= 0 && faces_host[i] < v, "%s: face %lld uses vertex %d of %d", fn, (long long)(i / 3),
-                   faces_host[i], v);
+  if (int st = check_faces_host(fn, faces_host, f, v)) return st;
   const int s = n * k;
   unsigned char* base = static_cast<unsigned char*>(work);
   float* meshes[2] = {reinterpret_cast<float*>(base + lay.mesh[0]), reinterpret_cast<float*>(base + lay.mesh[1])};

@@ -99,6 +99,12 @@ def _fit_trace_views(kind):
     return collections.namedtuple(kind.__name__.replace("Views", "TraceViews"), kind._fields + ("fit_trace",))
 
 
+# What a cloud or fit step keeps on the device beside its copy buffer: the raster's nearest Z fp32 [n,h,w]; the cloud launches'
+# scratch, the fit launches' scratch and the iterated fit's work (each None in a step without them); a fit_draw step's geometry
+# depth fp32 [n,h,w] and slot byte uint8 [n,h,w] (else None)
+StepWork = collections.namedtuple("StepWork", "mesh_depth cloud_scratch fit_scratch fit_work geo_depth geo_who")
+
+
 @dataclass(frozen=True)
 class LiveLayout:
     """Byte layout of a live step's one copy buffer, in this order: the records (one-hand step: a wide record per frame + the
@@ -489,14 +495,23 @@ class _LiveStep:
                     owned = self._mirrored[key] = (torch.empty_like(images), torch.empty_like(depth))
         return ops.flip_w(images, depth, out=owned[0], out_other=owned[1])
 
-    def _draw(self, mesh, lifted, frames, k, out, depth=None, at=None, mesh_depth=None):
-        s = mesh.shape[0]
+    @property
+    def _camera(self):
+        """what the depth passes take as paras: the device table (row i for the k slots of frame i) of an engine built with a
+        camera per frame, else the one camera's four values"""
+        return self.paras if self.cams is None else self.cams
+
+    def _raster_scratch(self, s):
+        """the raster's scratch records of a step with s slots, allocated once"""
         scratch = self._render_scratch.get(s)
         if scratch is None:
             with torch.inference_mode(False):
                 scratch = self._render_scratch[s] = torch.empty(
                     (ops.mesh_render_scratch_bytes(s, self.faces.shape[0]),), dtype=torch.uint8, device=self.device)
-        paras = self.paras if self.cams is None else self.cams      # (the table: row i for the k slots of frame i)
+        return scratch
+
+    def _draw(self, mesh, lifted, frames, k, out, depth=None, at=None, mesh_depth=None):
+        paras, scratch = self._camera, self._raster_scratch(mesh.shape[0])
         if self.occlude is None:
             return ops.mesh_render(mesh, self.faces, paras, frames, lifted=lifted, k=k, out=out, scratch=scratch), None, None
         # (the depth map the step itself ran on: mirrored in a `left` step, channel 3 of an RGBD step's tensor)
@@ -507,43 +522,33 @@ class _LiveStep:
         """The cloud step's last two launches: the clouds of the slots from the raster's nearest Z, the silhouette and the
         depth map, camera table and extrinsics table the step itself used, straight into the copy buffer."""
         points, band, stride = self.cloud
-        paras = self.paras if self.cams is None else self.cams
-        return ops.hand_cloud(work[0], silhouette, depth, paras, k, points=points, band=band, stride=stride,
-                              extrinsics_table=self.extrinsics if self.cloud_frame == "rig" else None, out=at, scratch=work[1])
+        return ops.hand_cloud(work.mesh_depth, silhouette, depth, self._camera, k, points=points, band=band, stride=stride,
+                              extrinsics_table=self.extrinsics if self.cloud_frame == "rig" else None, out=at, scratch=work.cloud_scratch)
 
     def _fit(self, work, silhouette, depth, mesh, xyz_mm, k, at):
         """The fit step's last two launches: every slot's mesh and joints moved onto the depth pixels under its silhouette,
         from the raster's nearest Z, the silhouette, and the depth map, camera table, mesh and joints the step itself used,
         straight into the copy buffer."""
         band, stride, min_points, damp, max_shift, max_angle = self.fit
-        paras = self.paras if self.cams is None else self.cams
         mesh, xyz_mm = mesh.view(-1, self.vertices, 3), xyz_mm.view(-1, SMOOTH_JOINTS, 3)      # (a row per slot)
-        return ops.mesh_fit(work[0], silhouette, depth, paras, mesh, xyz_mm, k, band=band, stride=stride, min_points=min_points,
-                            damp=damp, max_shift=max_shift, max_angle=max_angle, out=at, scratch=work[2])
+        return ops.mesh_fit(work.mesh_depth, silhouette, depth, self._camera, mesh, xyz_mm, k, band=band, stride=stride, min_points=min_points,
+                            damp=damp, max_shift=max_shift, max_angle=max_angle, out=at, scratch=work.fit_scratch)
 
     def _fit_iters(self, work, best, who, depth, mesh, xyz_mm, drawn, k, at):
         """The iterated fit's launches (ops.mesh_fit_iters): fit_iters steps from the mesh depth `best` and the slot byte `who`
         that show `mesh`, the moved meshes drawn again into work buffers of their own before every further step; the results
         and the trace straight into the copy buffer."""
         band, stride, min_points, damp, max_shift, max_angle = self.fit
-        paras = self.paras if self.cams is None else self.cams
         mesh, xyz_mm = mesh.view(-1, self.vertices, 3), xyz_mm.view(-1, SMOOTH_JOINTS, 3)      # (a row per slot)
-        return ops.mesh_fit_iters(best, who, depth, paras, mesh, xyz_mm, self.faces, k, iters=self.fit_iters, lifted=drawn, band=band,
+        return ops.mesh_fit_iters(best, who, depth, self._camera, mesh, xyz_mm, self.faces, k, iters=self.fit_iters, lifted=drawn, band=band,
                                   stride=stride, min_points=min_points, damp=damp, max_shift=max_shift, max_angle=max_angle, out=at,
-                                  scratch=work[2], work=work[3])
+                                  scratch=work.fit_scratch, work=work.fit_work)
 
     def _geometry(self, work, mesh, drawn, k):
         """A fit_draw step's first two launches, in place of the raster: the nearest Z and the slot byte of the unfitted mesh,
         into work buffers of their own -- what the fit reads."""
-        s = mesh.shape[0]
-        scratch = self._render_scratch.get(s)
-        if scratch is None:
-            with torch.inference_mode(False):
-                scratch = self._render_scratch[s] = torch.empty(
-                    (ops.mesh_render_scratch_bytes(s, self.faces.shape[0]),), dtype=torch.uint8, device=self.device)
-        paras = self.paras if self.cams is None else self.cams
-        hw = tuple(work[4].shape[1:])
-        return ops.mesh_geometry(mesh, self.faces, paras, hw, lifted=drawn, k=k, out_depth=work[4], out_who=work[5], scratch=scratch)
+        return ops.mesh_geometry(mesh, self.faces, self._camera, tuple(work.geo_depth.shape[1:]), lifted=drawn, k=k,
+                                 out_depth=work.geo_depth, out_who=work.geo_who, scratch=self._raster_scratch(mesh.shape[0]))
 
     def _check_frames(self, n):
         if self.cams is not None and n != self.cams.shape[0]:
@@ -583,21 +588,19 @@ class _LiveStep:
                           cloud=self.cloud[0] if self.cloud and hw is not None else 0, rig=self.rig is not None)
 
     def _new_buffers(self, n, hw=None):
-        """A fresh (layout, device buffer, pinned host buffer, work) of a step over n frames; work: a cloud or fit step's (mesh
-        depth fp32 [n,h,w], the cloud launches' scratch or None, the fit launches' scratch or None, the iterated fit's work or
-        None, a fit_draw step's geometry depth fp32 [n,h,w] and slot byte uint8 [n,h,w] or None) on the device -- not part of
-        the copy --, else None."""
+        """A fresh (layout, device buffer, pinned host buffer, work) of a step over n frames; work: a cloud or fit step's
+        StepWork on the device -- not part of the copy --, else None."""
         layout = self._layout(n, hw)
         work = None
         if layout.cloud or layout.fit:
             scratch = lambda nbytes: torch.empty((nbytes,), dtype=torch.uint8, device=self.device)  # noqa: E731
-            work = (torch.zeros((n, *hw), dtype=torch.float32, device=self.device),
-                    scratch(ops.hand_cloud_scratch_bytes(n, self.hands or 1, hw[0])) if layout.cloud else None,
-                    scratch(ops.mesh_fit_scratch_bytes(n, self.hands or 1, hw[0])) if layout.fit else None,
-                    scratch(ops.mesh_fit_iters_scratch_bytes(n, self.hands or 1, hw[0], hw[1], self.vertices, self.faces.shape[0],
-                                                             SMOOTH_JOINTS, self.fit_iters)) if layout.fit_iters > 1 else None,
-                    torch.zeros((n, *hw), dtype=torch.float32, device=self.device) if layout.fit and self.fit_draw else None,
-                    torch.zeros((n, *hw), dtype=torch.uint8, device=self.device) if layout.fit and self.fit_draw else None)
+            work = StepWork(torch.zeros((n, *hw), dtype=torch.float32, device=self.device),
+                        scratch(ops.hand_cloud_scratch_bytes(n, self.hands or 1, hw[0])) if layout.cloud else None,
+                        scratch(ops.mesh_fit_scratch_bytes(n, self.hands or 1, hw[0])) if layout.fit else None,
+                        scratch(ops.mesh_fit_iters_scratch_bytes(n, self.hands or 1, hw[0], hw[1], self.vertices, self.faces.shape[0],
+                                                                 SMOOTH_JOINTS, self.fit_iters)) if layout.fit_iters > 1 else None,
+                        torch.zeros((n, *hw), dtype=torch.float32, device=self.device) if layout.fit and self.fit_draw else None,
+                        torch.zeros((n, *hw), dtype=torch.uint8, device=self.device) if layout.fit and self.fit_draw else None)
         return (layout, torch.zeros((layout.nbytes,), dtype=torch.uint8, device=self.device),
                 torch.zeros((layout.nbytes,), dtype=torch.uint8, pin_memory=True), work)
 
@@ -637,9 +640,9 @@ class _LiveStep:
             best, who = self._geometry(work, shown, drawn, k)
             more.update(self._fit_parts(work, best, who, depth, shown, at.smooth_xyz if layout.smoothed else out.xyz_mm, drawn, k,
                                         at, layout))
-            overlay, silhouette, coverage = self._draw(at.fit_mesh, drawn, frames, k, at.overlay, depth, at, work[0])
+            overlay, silhouette, coverage = self._draw(at.fit_mesh, drawn, frames, k, at.overlay, depth, at, work.mesh_depth)
         elif layout.overlay:
-            overlay, silhouette, coverage = self._draw(shown, drawn, frames, k, at.overlay, depth, at, work and work[0])
+            overlay, silhouette, coverage = self._draw(shown, drawn, frames, k, at.overlay, depth, at, work and work.mesh_depth)
         if layout.labels:
             box_label, pose_label = ops.draw_labels(out.keypoints, out.crop_box, frames, drawn=drawn, k=k, clamp=self.clamp,
                                                     out_box=at.box_label, out_pose=at.pose_label)
@@ -651,9 +654,9 @@ class _LiveStep:
                                        side=out.side if self.handed else None, out=at)
         if layout.cloud:    # (against the mesh the overlay drew and the depth map it was tested against)
             cloud = self._cloud(work, silhouette, depth, k, at)
-            more.update(cloud=cloud.cloud, cloud_count=cloud.count, cloud_resid=cloud.resid, mesh_depth=work[0])
+            more.update(cloud=cloud.cloud, cloud_count=cloud.count, cloud_resid=cloud.resid, mesh_depth=work.mesh_depth)
         if layout.fit and not redraw:      # (the mesh the overlay drew and the joints that go with it)
-            more.update(self._fit_parts(work, work[0], silhouette, depth, shown, at.smooth_xyz if layout.smoothed else out.xyz_mm,
+            more.update(self._fit_parts(work, work.mesh_depth, silhouette, depth, shown, at.smooth_xyz if layout.smoothed else out.xyz_mm,
                                         drawn, k, at, layout))
         host.copy_(dev, non_blocking=True)
         return self._output(out, at, layout, host, dict(pose2d=p2d, mesh=mesh, pose3d=pose3d, raw_mesh=raw, overlay=overlay,
@@ -663,12 +666,12 @@ class _LiveStep:
         """The fit's launches -- one iteration: ops.mesh_fit, today's two; more: ops.mesh_fit_iters -- on the mesh depth `best` and
         the slot byte `who`, and what the step hands out of them."""
         if layout.fit_iters == 1:
-            fit = self._fit((best,) + tuple(work[1:]), who, depth, mesh, xyz_mm, k, at)
+            fit = self._fit(work._replace(mesh_depth=best), who, depth, mesh, xyz_mm, k, at)
             trace = {}
         else:
             fit = self._fit_iters(work, best, who, depth, mesh, xyz_mm, drawn, k, at)
             trace = dict(fit_trace=fit.trace)
-        return dict(fit_mesh=fit.mesh, fit_xyz=fit.xyz, fit_rt=fit.rt, fit_count=fit.count, fit_cost=fit.cost, mesh_depth=work[0],
+        return dict(fit_mesh=fit.mesh, fit_xyz=fit.xyz, fit_rt=fit.rt, fit_count=fit.count, fit_cost=fit.cost, mesh_depth=work.mesh_depth,
                     **trace)
 
     def _key_options(self) -> tuple:

@@ -1953,6 +1953,124 @@ def check_occlude_margin(margin) -> float:
     return m
 
 
+# What the depth passes' wrappers (mesh_render, hand_cloud, mesh_fit, mesh_geometry, mesh_fit_iters) share.  `anchor` names the
+# tensor whose device the others must be on, in the words of the caller's message ("the mesh", "the silhouette").
+
+def _on_device(name, t, device, anchor):
+    if t.device != device:
+        raise ValueError(f"{name} on {t.device} but {anchor} on {device}")
+
+
+def _slot_meshes(mesh):
+    """mesh fp32 [S,V,3] or [N,K,V,3] -> (mesh [S,V,3], S, V)"""
+    _req(mesh, name="mesh")
+    if mesh.dim() == 4:
+        mesh = mesh.view(-1, mesh.shape[2], 3)
+    if mesh.dim() != 3 or mesh.shape[2] != 3:
+        raise ValueError(f"mesh: expected [S,V,3], got {tuple(mesh.shape)}")
+    return mesh, mesh.shape[0], mesh.shape[1]
+
+
+def _faces_arg(faces, device, nonempty=False):
+    """faces [F,3]: an int32 GPU tensor, or a host list, which the C entry checks index by index and this call uploads ->
+    (the GPU tensor, a pointer to the host list or None, F)"""
+    host = None
+    if not (torch.is_tensor(faces) and faces.is_cuda):
+        host = np.ascontiguousarray(np.asarray(faces.cpu() if torch.is_tensor(faces) else faces).astype(np.int32))
+        if host.ndim != 2 or host.shape[1] != 3:
+            raise ValueError(f"faces: expected [F,3], got {tuple(host.shape)}")
+        faces = torch.from_numpy(host).to(device)
+    _req(faces, torch.int32, "faces")
+    if faces.dim() != 2 or faces.shape[1] != 3 or (nonempty and faces.shape[0] < 1):
+        raise ValueError(f"faces: expected {'a non-empty ' if nonempty else ''}[F,3], got {tuple(faces.shape)}")
+    # (data_as: the pointer keeps the host array alive until the caller has made its call)
+    return faces, (host.ctypes.data_as(C.c_void_p) if host is not None else None), int(faces.shape[0])
+
+
+def _lifted_arg(lifted, s):
+    if lifted is not None:
+        _req(lifted, torch.int32, "lifted")
+        if lifted.numel() != s:
+            raise ValueError(f"lifted: expected {s} flags, got {lifted.numel()}")
+    return lifted
+
+
+def _camera_arg(paras, n, device, anchor):
+    """paras -> (the one camera's four values for a by-value argument, None), or -- a camera per frame: a device table fp32
+    [N,4] -- (None, the table's address)"""
+    if torch.is_tensor(paras) and paras.dim() != 1:
+        if paras.dtype != torch.float32 or tuple(paras.shape) != (n, 4):
+            raise ValueError(f"paras: a camera per frame is fp32 [{n},4] (fx, fy, cx, cy), got {paras.dtype} {tuple(paras.shape)}")
+        _on_device("paras", paras, device, anchor)
+        return None, ptr(_req(paras, torch.float32, "paras"))
+    return (C.c_float * 4)(*[float(x) for x in paras]), None
+
+
+def _scene_depth_arg(scene_depth, n, h, w, device, anchor):
+    """The camera's depth map, fp32 [N,1,H,W], [N,H,W] or RGBD [N,4,H,W] (channel 3 is read in place) -> (the address of frame
+    0's depth, the frame stride in elements)"""
+    _req(scene_depth, name="scene_depth")
+    _on_device("scene_depth", scene_depth, device, anchor)
+    shape = tuple(scene_depth.shape)
+    if shape not in ((n, 1, h, w), (n, h, w), (n, 4, h, w)):
+        raise ValueError(f"scene_depth: expected fp32 [{n},1,{h},{w}], [{n},{h},{w}] or RGBD [{n},4,{h},{w}], got {shape}")
+    rgbd = len(shape) == 4 and shape[1] == 4
+    return scene_depth.data_ptr() + (3 * h * w * 4 if rgbd else 0), (4 if rgbd else 1) * h * w
+
+
+def _depth_maps(mesh_depth, silhouette, k):
+    """What the occluded raster leaves, silhouette uint8 [N,H,W] and mesh_depth fp32 of as many values -> (N, H, W, int k)"""
+    if silhouette.dim() != 3:
+        raise ValueError(f"silhouette: expected uint8 [N,H,W], got {tuple(silhouette.shape)}")
+    n, h, w = (int(v) for v in silhouette.shape)
+    if mesh_depth.numel() != n * h * w:
+        raise ValueError(f"mesh_depth: expected fp32 [{n},{h},{w}], got {tuple(mesh_depth.shape)}")
+    k = int(k)
+    if not 1 <= k <= 16:
+        raise ValueError(f"the silhouette's byte holds at most 16 slots per frame (k = {k})")
+    return n, h, w, k
+
+
+def _fit_meshes(mesh, xyz_mm, s):
+    """mesh fp32 [s,V,3] and xyz_mm fp32 [s,J,3] -> (V, J)"""
+    if mesh.dim() != 3 or mesh.shape[0] != s or mesh.shape[2] != 3 or mesh.shape[1] < 1:
+        raise ValueError(f"mesh: expected fp32 [{s},V,3], got {tuple(mesh.shape)}")
+    if xyz_mm.dim() != 3 or xyz_mm.shape[0] != s or xyz_mm.shape[2] != 3 or xyz_mm.shape[1] < 1:
+        raise ValueError(f"xyz_mm: expected fp32 [{s},J,3], got {tuple(xyz_mm.shape)}")
+    return int(mesh.shape[1]), int(xyz_mm.shape[1])
+
+
+def _out_parts(out, specs, device):
+    """specs: (name, dtype, shape) per output -> the tensors, allocated, or `out`'s attributes of those names, viewed in shape"""
+    parts = []
+    for name, dtype, shp in specs:
+        t = torch.empty(shp, device=device, dtype=dtype) if out is None else getattr(out, name)
+        if _req(t, dtype, name).numel() != math.prod(shp):
+            raise ValueError(f"{name}: expected {dtype} {list(shp)}, got {tuple(t.shape)}")
+        parts.append(t.view(shp))
+    return parts
+
+
+def _scratch_arg(scratch, device, size, *dims, name="scratch"):
+    """the caller's byte buffer, or one of size(*dims) bytes"""
+    if scratch is None:
+        scratch = torch.empty((size(*dims),), device=device, dtype=torch.uint8)
+    return _req(scratch, torch.uint8, name)
+
+
+def _check_count(name, value):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= 2 ** 31 - 1:
+        raise ValueError(f"{name}: an integer >= 1 (got {value!r})")
+
+
+def _check_band(name, b, given, limit):
+    """b, `given` as a float (NaN: not a number): finite and in (0, limit] metres, also as the fp32 kernel argument it becomes"""
+    with np.errstate(over="ignore"):
+        g = float(np.float32(b))
+    if not (math.isfinite(b) and 0.0 < g <= limit and b <= limit):
+        raise ValueError(f"{name}: a finite number of metres in (0, {limit:g}] as fp32 (got {given!r})")
+
+
 def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out=None, scratch=None, *, scene_depth=None,
                 margin=OCCLUDE_MARGIN, silhouette_out=None, coverage_out=None):
     """The meshes drawn over their frames (hn_mesh_render_u8; render() of ros_demo.py:86-116 without a graphics pipeline):
@@ -1970,22 +2088,8 @@ def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out
     slot within the frame, k <= 16 --, coverage int32 [S,2]: per slot, the pixels where its mesh is the nearest and those of
     them that are shown), written into silhouette_out / coverage_out when given; depth_out holds the nearest mesh Z on every
     covered pixel, hidden or not.  Without scene_depth the call is the plain one and the three other keywords must stay unset."""
-    _req(mesh, name="mesh")
-    if mesh.dim() == 4:
-        mesh = mesh.view(-1, mesh.shape[2], 3)
-    if mesh.dim() != 3 or mesh.shape[2] != 3:
-        raise ValueError(f"mesh: expected [S,V,3], got {tuple(mesh.shape)}")
-    s, v, _ = mesh.shape
-    faces_host = None
-    if not (torch.is_tensor(faces) and faces.is_cuda):
-        faces_host = np.ascontiguousarray(np.asarray(faces.cpu() if torch.is_tensor(faces) else faces).astype(np.int32))
-        if faces_host.ndim != 2 or faces_host.shape[1] != 3:
-            raise ValueError(f"faces: expected [F,3], got {tuple(faces_host.shape)}")
-        faces = torch.from_numpy(faces_host).to(mesh.device)
-    _req(faces, torch.int32, "faces")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"faces: expected [F,3], got {tuple(faces.shape)}")
-    f = faces.shape[0]
+    mesh, s, v = _slot_meshes(mesh)
+    faces, fh, f = _faces_arg(faces, mesh.device)
     if frame.dtype == torch.uint8:
         _req(frame, torch.uint8, "frame")
         fmt, (n, h, w) = _lib.FRAME_U8_BGR_HWC, frame.shape[:3]
@@ -1998,10 +2102,7 @@ def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out
         raise ValueError(f"frame: expected fp32 [N,3,H,W] or uint8 [N,H,W,3], got {frame.dtype} {tuple(frame.shape)}")
     if k < 1 or n * k != s:
         raise ValueError(f"{s} mesh slots for {n} frames with k = {k} slots per frame")
-    if lifted is not None:
-        _req(lifted, torch.int32, "lifted")
-        if lifted.numel() != s:
-            raise ValueError(f"lifted: expected {s} flags, got {lifted.numel()}")
+    _lifted_arg(lifted, s)
     if out is None:
         out = torch.empty((n, h, w, 3), device=mesh.device, dtype=torch.uint8)
     _req(out, torch.uint8, "out")
@@ -2011,23 +2112,12 @@ def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out
         _req(depth_out, name="depth_out")
         if depth_out.numel() != n * h * w:
             raise ValueError(f"depth_out: expected fp32 [{n},{h},{w}], got {tuple(depth_out.shape)}")
-    need = mesh_render_scratch_bytes(s, f)
-    if scratch is None:
-        scratch = torch.empty((need,), device=mesh.device, dtype=torch.uint8)
-    _req(scratch, torch.uint8, "scratch")
+    scratch = _scratch_arg(scratch, mesh.device, mesh_render_scratch_bytes, s, f)
     # a camera per frame: a device table [N,4] (hn_mesh_render_cams_*); else the one camera's four values, passed by value
-    cams = torch.is_tensor(paras) and paras.dim() != 1
-    if cams:
-        if paras.dtype != torch.float32 or tuple(paras.shape) != (n, 4):
-            raise ValueError(f"paras: a camera per frame is fp32 [{n},4] (fx, fy, cx, cy), got {paras.dtype} {tuple(paras.shape)}")
-        if paras.device != mesh.device:
-            raise ValueError(f"paras on {paras.device} but the mesh on {mesh.device}")
-        p4 = ptr(_req(paras, torch.float32, "paras"))
-    else:
-        p4 = (C.c_float * 4)(*[float(x) for x in paras])
+    host4, cams = _camera_arg(paras, n, mesh.device, "the mesh")
+    p4 = host4 if cams is None else cams
     plain, occluded = ("hn_mesh_render_cams_u8", "hn_mesh_render_cams_occluded_u8") if cams else (
         "hn_mesh_render_u8", "hn_mesh_render_occluded_u8")
-    fh = faces_host.ctypes.data if faces_host is not None else None
     if scene_depth is None:
         if silhouette_out is not None or coverage_out is not None:
             raise ValueError("silhouette_out / coverage_out belong to the occluded call: give scene_depth")
@@ -2035,16 +2125,9 @@ def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out
                                           ptr(scratch), scratch.numel(), ptr(out), ptr(depth_out), _stream()), plain)
         return out.view(n, h, w, 3)
     margin = check_occlude_margin(margin)
-    _req(scene_depth, name="scene_depth")
-    if scene_depth.device != mesh.device:
-        raise ValueError(f"scene_depth on {scene_depth.device} but the mesh on {mesh.device}")
-    shape = tuple(scene_depth.shape)
-    if shape not in ((n, 1, h, w), (n, h, w), (n, 4, h, w)):
-        raise ValueError(f"scene_depth: expected fp32 [{n},1,{h},{w}], [{n},{h},{w}] or RGBD [{n},4,{h},{w}], got {shape}")
+    depth_ptr, depth_stride = _scene_depth_arg(scene_depth, n, h, w, mesh.device, "the mesh")
     if k > 16:
         raise ValueError(f"the silhouette's byte holds at most 16 slots per frame (k = {k})")
-    rgbd = len(shape) == 4 and shape[1] == 4
-    depth_ptr = scene_depth.data_ptr() + (3 * h * w * 4 if rgbd else 0)
     if silhouette_out is None:
         silhouette_out = torch.empty((n, h, w), device=mesh.device, dtype=torch.uint8)
     _req(silhouette_out, torch.uint8, "silhouette_out")
@@ -2056,7 +2139,7 @@ def mesh_render(mesh, faces, paras, frame, lifted=None, k=1, out=None, depth_out
     if coverage_out.numel() != s * 2:
         raise ValueError(f"coverage_out: expected int32 [{s},2], got {tuple(coverage_out.shape)}")
     check(getattr(_lib.load(), occluded)(ptr(mesh), ptr(faces), fh, ptr(lifted), s, v, f, k, p4, ptr(frame), fmt, h, w,
-                                         depth_ptr, (4 if rgbd else 1) * h * w, margin, ptr(scratch), scratch.numel(),
+                                         depth_ptr, depth_stride, margin, ptr(scratch), scratch.numel(),
                                          ptr(out), ptr(depth_out), ptr(silhouette_out), ptr(coverage_out), _stream()), occluded)
     return out.view(n, h, w, 3), silhouette_out.view(n, h, w), coverage_out.view(s, 2)
 
@@ -2176,17 +2259,13 @@ def check_cloud(points=CLOUD_POINTS, band=CLOUD_BAND, stride=CLOUD_STRIDE):
     """A hand cloud's three parameters as (int points >= 1, float band, int stride >= 1), the band finite and in (0, 100] metres
     also as the fp32 kernel argument it becomes; else ValueError.  The defaults (4096 rows, 0.03 m, every second row and column)
     are starting values, NOT tuned on this model."""
-    for name, value in (("cloud_points", points), ("cloud_stride", stride)):
-        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= 2 ** 31 - 1:
-            raise ValueError(f"{name}: an integer >= 1 (got {value!r})")
+    _check_count("cloud_points", points)
+    _check_count("cloud_stride", stride)
     try:
         b = float(band)
     except (TypeError, ValueError):
         b = math.nan
-    with np.errstate(over="ignore"):
-        g = float(np.float32(b))
-    if not (math.isfinite(b) and 0.0 < g <= CLOUD_MAX_BAND and b <= CLOUD_MAX_BAND):
-        raise ValueError(f"cloud_band: a finite number of metres in (0, {CLOUD_MAX_BAND:g}] as fp32 (got {band!r})")
+    _check_band("cloud_band", b, band, CLOUD_MAX_BAND)
     return int(points), b, int(stride)
 
 
@@ -2212,49 +2291,20 @@ def hand_cloud(mesh_depth, silhouette, scene_depth, paras, k, *, points=CLOUD_PO
     points = 4096, band = 0.03 m and stride = 2 are starting values, NOT tuned on this model."""
     points, band, stride = check_cloud(points, band, stride)
     _req(mesh_depth, name="mesh_depth"); _req(silhouette, torch.uint8, "silhouette"); _req(scene_depth, name="scene_depth")
-    if silhouette.dim() != 3:
-        raise ValueError(f"silhouette: expected uint8 [N,H,W], got {tuple(silhouette.shape)}")
-    n, h, w = (int(v) for v in silhouette.shape)
-    if mesh_depth.numel() != n * h * w:
-        raise ValueError(f"mesh_depth: expected fp32 [{n},{h},{w}], got {tuple(mesh_depth.shape)}")
-    k = int(k)
-    if not 1 <= k <= 16:
-        raise ValueError(f"the silhouette's byte holds at most 16 slots per frame (k = {k})")
-    for name, t in (("mesh_depth", mesh_depth), ("scene_depth", scene_depth)):
-        if t.device != silhouette.device:
-            raise ValueError(f"{name} on {t.device} but the silhouette on {silhouette.device}")
-    shape = tuple(scene_depth.shape)
-    if shape not in ((n, 1, h, w), (n, h, w), (n, 4, h, w)):
-        raise ValueError(f"scene_depth: expected fp32 [{n},1,{h},{w}], [{n},{h},{w}] or RGBD [{n},4,{h},{w}], got {shape}")
-    rgbd = len(shape) == 4 and shape[1] == 4
-    depth_ptr = scene_depth.data_ptr() + (3 * h * w * 4 if rgbd else 0)
-    host4 = table = None
-    if torch.is_tensor(paras) and paras.dim() != 1:
-        if paras.dtype != torch.float32 or tuple(paras.shape) != (n, 4):
-            raise ValueError(f"paras: a camera per frame is fp32 [{n},4] (fx, fy, cx, cy), got {paras.dtype} {tuple(paras.shape)}")
-        if paras.device != silhouette.device:
-            raise ValueError(f"paras on {paras.device} but the silhouette on {silhouette.device}")
-        table = ptr(_req(paras, torch.float32, "paras"))
-    else:
-        host4 = (C.c_float * 4)(*[float(x) for x in paras])
+    n, h, w, k = _depth_maps(mesh_depth, silhouette, k)
+    _on_device("mesh_depth", mesh_depth, silhouette.device, "the silhouette")
+    depth_ptr, depth_stride = _scene_depth_arg(scene_depth, n, h, w, silhouette.device, "the silhouette")
+    host4, table = _camera_arg(paras, n, silhouette.device, "the silhouette")
     if extrinsics_table is not None:
         _req(extrinsics_table, name="extrinsics_table")
         if tuple(extrinsics_table.shape) != (n, 12) or extrinsics_table.device != silhouette.device:
             raise ValueError(f"extrinsics_table: fp32 [{n},12] on {silhouette.device}, a row per frame, got "
                              f"{tuple(extrinsics_table.shape)} on {extrinsics_table.device}")
     s = n * k
-    parts = []
-    for name, dtype, shp in (("cloud", torch.float32, (s, points, 3)), ("cloud_count", torch.int32, (s, 2)),
-                             ("cloud_resid", torch.int64, (s,))):
-        t = torch.empty(shp, device=silhouette.device, dtype=dtype) if out is None else getattr(out, name)
-        if _req(t, dtype, name).numel() != math.prod(shp):
-            raise ValueError(f"{name}: expected {dtype} {list(shp)}, got {tuple(t.shape)}")
-        parts.append(t.view(shp))
-    need = hand_cloud_scratch_bytes(n, k, h)
-    if scratch is None:
-        scratch = torch.empty((need,), device=silhouette.device, dtype=torch.uint8)
-    _req(scratch, torch.uint8, "scratch")
-    check(_lib.load().hn_hand_cloud_f32(ptr(mesh_depth), ptr(silhouette), depth_ptr, (4 if rgbd else 1) * h * w, host4, table,
+    parts = _out_parts(out, (("cloud", torch.float32, (s, points, 3)), ("cloud_count", torch.int32, (s, 2)),
+                             ("cloud_resid", torch.int64, (s,))), silhouette.device)
+    scratch = _scratch_arg(scratch, silhouette.device, hand_cloud_scratch_bytes, n, k, h)
+    check(_lib.load().hn_hand_cloud_f32(ptr(mesh_depth), ptr(silhouette), depth_ptr, depth_stride, host4, table,
                                         ptr(extrinsics_table), n, k, h, w, points, stride, band, ptr(scratch), scratch.numel(),
                                         *(ptr(t) for t in parts), _stream()), "hn_hand_cloud_f32")
     return HandCloud(*parts)
@@ -2277,9 +2327,8 @@ def check_fit(band=FIT_BAND, stride=FIT_STRIDE, min_points=FIT_MIN_POINTS, damp=
     float max_angle in (0, pi)), the band finite and in (0, 100] metres also as the fp32 kernel argument it becomes; else
     ValueError.  The defaults (0.03 m, every second row and column, 200 matches, 1e-3, 0.05 m, 0.35 rad) are starting values,
     NOT tuned on this model."""
-    for name, value in (("fit_stride", stride), ("fit_min_points", min_points)):
-        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= 2 ** 31 - 1:
-            raise ValueError(f"{name}: an integer >= 1 (got {value!r})")
+    _check_count("fit_stride", stride)
+    _check_count("fit_min_points", min_points)
 
     def number(value):
         try:
@@ -2287,10 +2336,7 @@ def check_fit(band=FIT_BAND, stride=FIT_STRIDE, min_points=FIT_MIN_POINTS, damp=
         except (TypeError, ValueError):
             return math.nan
     b, lam, shift, angle = number(band), number(damp), number(max_shift), number(max_angle)
-    with np.errstate(over="ignore"):
-        g = float(np.float32(b))
-    if not (math.isfinite(b) and 0.0 < g <= FIT_MAX_BAND and b <= FIT_MAX_BAND):
-        raise ValueError(f"fit_band: a finite number of metres in (0, {FIT_MAX_BAND:g}] as fp32 (got {band!r})")
+    _check_band("fit_band", b, band, FIT_MAX_BAND)
     if not (math.isfinite(lam) and lam >= 0.0):
         raise ValueError(f"fit_damp: a finite number >= 0 (got {damp!r})")
     if not (math.isfinite(shift) and shift > 0.0 and math.isfinite(shift * shift) and shift * shift > 0.0):
@@ -2304,6 +2350,12 @@ def fit_caps(max_shift, max_angle):
     """the two caps as the doubles the kernel takes: max_shift^2 and tan^2(max_angle / 2)"""
     half = math.tan(max_angle / 2.0)
     return max_shift * max_shift, half * half
+
+
+def _fit_specs(s, v, joints):
+    """a fit's outputs as _out_parts takes them"""
+    return (("fit_mesh", torch.float32, (s, v, 3)), ("fit_xyz", torch.float32, (s, joints, 3)), ("fit_rt", torch.float32, (s, 12)),
+            ("fit_count", torch.int32, (s, 2)), ("fit_cost", torch.int64, (s,)))
 
 
 def mesh_fit_scratch_bytes(frames, k, h):
@@ -2332,50 +2384,17 @@ def mesh_fit(mesh_depth, silhouette, scene_depth, paras, mesh, xyz_mm, k, *, ban
     band, stride, min_points, damp, max_shift, max_angle = check_fit(band, stride, min_points, damp, max_shift, max_angle)
     _req(mesh_depth, name="mesh_depth"); _req(silhouette, torch.uint8, "silhouette"); _req(scene_depth, name="scene_depth")
     _req(mesh, name="mesh"); _req(xyz_mm, name="xyz_mm")
-    if silhouette.dim() != 3:
-        raise ValueError(f"silhouette: expected uint8 [N,H,W], got {tuple(silhouette.shape)}")
-    n, h, w = (int(v) for v in silhouette.shape)
-    if mesh_depth.numel() != n * h * w:
-        raise ValueError(f"mesh_depth: expected fp32 [{n},{h},{w}], got {tuple(mesh_depth.shape)}")
-    k = int(k)
-    if not 1 <= k <= 16:
-        raise ValueError(f"the silhouette's byte holds at most 16 slots per frame (k = {k})")
+    n, h, w, k = _depth_maps(mesh_depth, silhouette, k)
     s = n * k
-    if mesh.dim() != 3 or mesh.shape[0] != s or mesh.shape[2] != 3 or mesh.shape[1] < 1:
-        raise ValueError(f"mesh: expected fp32 [{s},V,3], got {tuple(mesh.shape)}")
-    if xyz_mm.dim() != 3 or xyz_mm.shape[0] != s or xyz_mm.shape[2] != 3 or xyz_mm.shape[1] < 1:
-        raise ValueError(f"xyz_mm: expected fp32 [{s},J,3], got {tuple(xyz_mm.shape)}")
-    v, joints = int(mesh.shape[1]), int(xyz_mm.shape[1])
-    for name, t in (("mesh_depth", mesh_depth), ("scene_depth", scene_depth), ("mesh", mesh), ("xyz_mm", xyz_mm)):
-        if t.device != silhouette.device:
-            raise ValueError(f"{name} on {t.device} but the silhouette on {silhouette.device}")
-    shape = tuple(scene_depth.shape)
-    if shape not in ((n, 1, h, w), (n, h, w), (n, 4, h, w)):
-        raise ValueError(f"scene_depth: expected fp32 [{n},1,{h},{w}], [{n},{h},{w}] or RGBD [{n},4,{h},{w}], got {shape}")
-    rgbd = len(shape) == 4 and shape[1] == 4
-    depth_ptr = scene_depth.data_ptr() + (3 * h * w * 4 if rgbd else 0)
-    host4 = table = None
-    if torch.is_tensor(paras) and paras.dim() != 1:
-        if paras.dtype != torch.float32 or tuple(paras.shape) != (n, 4):
-            raise ValueError(f"paras: a camera per frame is fp32 [{n},4] (fx, fy, cx, cy), got {paras.dtype} {tuple(paras.shape)}")
-        if paras.device != silhouette.device:
-            raise ValueError(f"paras on {paras.device} but the silhouette on {silhouette.device}")
-        table = ptr(_req(paras, torch.float32, "paras"))
-    else:
-        host4 = (C.c_float * 4)(*[float(x) for x in paras])
-    parts = []
-    for name, dtype, shp in (("fit_mesh", torch.float32, (s, v, 3)), ("fit_xyz", torch.float32, (s, joints, 3)),
-                             ("fit_rt", torch.float32, (s, 12)), ("fit_count", torch.int32, (s, 2)), ("fit_cost", torch.int64, (s,))):
-        t = torch.empty(shp, device=silhouette.device, dtype=dtype) if out is None else getattr(out, name)
-        if _req(t, dtype, name).numel() != math.prod(shp):
-            raise ValueError(f"{name}: expected {dtype} {list(shp)}, got {tuple(t.shape)}")
-        parts.append(t.view(shp))
-    need = mesh_fit_scratch_bytes(n, k, h)
-    if scratch is None:
-        scratch = torch.empty((need,), device=silhouette.device, dtype=torch.uint8)
-    _req(scratch, torch.uint8, "scratch")
+    v, joints = _fit_meshes(mesh, xyz_mm, s)
+    for name, t in (("mesh_depth", mesh_depth), ("mesh", mesh), ("xyz_mm", xyz_mm)):
+        _on_device(name, t, silhouette.device, "the silhouette")
+    depth_ptr, depth_stride = _scene_depth_arg(scene_depth, n, h, w, silhouette.device, "the silhouette")
+    host4, table = _camera_arg(paras, n, silhouette.device, "the silhouette")
+    parts = _out_parts(out, _fit_specs(s, v, joints), silhouette.device)
+    scratch = _scratch_arg(scratch, silhouette.device, mesh_fit_scratch_bytes, n, k, h)
     shift2, tan2 = fit_caps(max_shift, max_angle)
-    check(_lib.load().hn_mesh_fit_f32(ptr(mesh_depth), ptr(silhouette), depth_ptr, (4 if rgbd else 1) * h * w, host4, table,
+    check(_lib.load().hn_mesh_fit_f32(ptr(mesh_depth), ptr(silhouette), depth_ptr, depth_stride, host4, table,
                                       ptr(mesh), ptr(xyz_mm), n, k, h, w, v, joints, stride, band, min_points, damp, shift2, tan2,
                                       ptr(scratch), scratch.numel(), *(ptr(t) for t in parts), _stream()), "hn_mesh_fit_f32")
     return MeshFit(*parts)
@@ -2388,22 +2407,8 @@ def mesh_geometry(mesh, faces, paras, hw, lifted=None, k=1, *, out_depth=None, o
     takes them; hw = (h, w) of the frames.  Returns (depth fp32 [N,H,W]: the nearest Z, 0 where nothing was drawn; who uint8
     [N,H,W]: 0, or the nearest slot within the frame + 1) -- the occluded mesh_render's depth_out and silhouette & 0x7F, bit for
     bit --, allocated or out_depth / out_who, both fully written."""
-    _req(mesh, name="mesh")
-    if mesh.dim() == 4:
-        mesh = mesh.view(-1, mesh.shape[2], 3)
-    if mesh.dim() != 3 or mesh.shape[2] != 3:
-        raise ValueError(f"mesh: expected [S,V,3], got {tuple(mesh.shape)}")
-    s, v, _ = mesh.shape
-    faces_host = None
-    if not (torch.is_tensor(faces) and faces.is_cuda):
-        faces_host = np.ascontiguousarray(np.asarray(faces.cpu() if torch.is_tensor(faces) else faces).astype(np.int32))
-        if faces_host.ndim != 2 or faces_host.shape[1] != 3:
-            raise ValueError(f"faces: expected [F,3], got {tuple(faces_host.shape)}")
-        faces = torch.from_numpy(faces_host).to(mesh.device)
-    _req(faces, torch.int32, "faces")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"faces: expected [F,3], got {tuple(faces.shape)}")
-    f = faces.shape[0]
+    mesh, s, v = _slot_meshes(mesh)
+    faces, fh, f = _faces_arg(faces, mesh.device)
     h, w = (int(x) for x in hw)
     k = int(k)
     if not 1 <= k <= 16:
@@ -2411,10 +2416,7 @@ def mesh_geometry(mesh, faces, paras, hw, lifted=None, k=1, *, out_depth=None, o
     if s % k or s == 0:
         raise ValueError(f"{s} mesh slots with k = {k} slots per frame")
     n = s // k
-    if lifted is not None:
-        _req(lifted, torch.int32, "lifted")
-        if lifted.numel() != s:
-            raise ValueError(f"lifted: expected {s} flags, got {lifted.numel()}")
+    _lifted_arg(lifted, s)
     if out_depth is None:
         out_depth = torch.empty((n, h, w), device=mesh.device, dtype=torch.float32)
     if out_who is None:
@@ -2422,20 +2424,8 @@ def mesh_geometry(mesh, faces, paras, hw, lifted=None, k=1, *, out_depth=None, o
     _req(out_depth, name="out_depth"); _req(out_who, torch.uint8, "out_who")
     if out_depth.numel() != n * h * w or out_who.numel() != n * h * w:
         raise ValueError(f"out_depth fp32 and out_who uint8 [{n},{h},{w}], got {tuple(out_depth.shape)} and {tuple(out_who.shape)}")
-    need = mesh_render_scratch_bytes(s, f)
-    if scratch is None:
-        scratch = torch.empty((need,), device=mesh.device, dtype=torch.uint8)
-    _req(scratch, torch.uint8, "scratch")
-    host4 = table = None
-    if torch.is_tensor(paras) and paras.dim() != 1:
-        if paras.dtype != torch.float32 or tuple(paras.shape) != (n, 4):
-            raise ValueError(f"paras: a camera per frame is fp32 [{n},4] (fx, fy, cx, cy), got {paras.dtype} {tuple(paras.shape)}")
-        if paras.device != mesh.device:
-            raise ValueError(f"paras on {paras.device} but the mesh on {mesh.device}")
-        table = ptr(_req(paras, torch.float32, "paras"))
-    else:
-        host4 = (C.c_float * 4)(*[float(x) for x in paras])
-    fh = faces_host.ctypes.data if faces_host is not None else None
+    scratch = _scratch_arg(scratch, mesh.device, mesh_render_scratch_bytes, s, f)
+    host4, table = _camera_arg(paras, n, mesh.device, "the mesh")
     check(_lib.load().hn_mesh_geometry_f32(ptr(mesh), ptr(faces), fh, ptr(lifted), s, v, f, k, host4, table, h, w, ptr(scratch),
                                            scratch.numel(), ptr(out_depth), ptr(out_who), _stream()), "hn_mesh_geometry_f32")
     return out_depth.view(n, h, w), out_who.view(n, h, w)
@@ -2475,68 +2465,20 @@ def mesh_fit_iters(mesh_depth, silhouette, scene_depth, paras, mesh, xyz_mm, fac
     band, stride, min_points, damp, max_shift, max_angle = check_fit(band, stride, min_points, damp, max_shift, max_angle)
     _req(mesh_depth, name="mesh_depth"); _req(silhouette, torch.uint8, "silhouette"); _req(scene_depth, name="scene_depth")
     _req(mesh, name="mesh"); _req(xyz_mm, name="xyz_mm")
-    if silhouette.dim() != 3:
-        raise ValueError(f"silhouette: expected uint8 [N,H,W], got {tuple(silhouette.shape)}")
-    n, h, w = (int(x) for x in silhouette.shape)
-    if mesh_depth.numel() != n * h * w:
-        raise ValueError(f"mesh_depth: expected fp32 [{n},{h},{w}], got {tuple(mesh_depth.shape)}")
-    k = int(k)
-    if not 1 <= k <= 16:
-        raise ValueError(f"the silhouette's byte holds at most 16 slots per frame (k = {k})")
+    n, h, w, k = _depth_maps(mesh_depth, silhouette, k)
     s = n * k
-    if mesh.dim() != 3 or mesh.shape[0] != s or mesh.shape[2] != 3 or mesh.shape[1] < 1:
-        raise ValueError(f"mesh: expected fp32 [{s},V,3], got {tuple(mesh.shape)}")
-    if xyz_mm.dim() != 3 or xyz_mm.shape[0] != s or xyz_mm.shape[2] != 3 or xyz_mm.shape[1] < 1:
-        raise ValueError(f"xyz_mm: expected fp32 [{s},J,3], got {tuple(xyz_mm.shape)}")
-    v, joints = int(mesh.shape[1]), int(xyz_mm.shape[1])
-    faces_host = None
-    if not (torch.is_tensor(faces) and faces.is_cuda):
-        faces_host = np.ascontiguousarray(np.asarray(faces.cpu() if torch.is_tensor(faces) else faces).astype(np.int32))
-        if faces_host.ndim != 2 or faces_host.shape[1] != 3:
-            raise ValueError(f"faces: expected [F,3], got {tuple(faces_host.shape)}")
-        faces = torch.from_numpy(faces_host).to(mesh.device)
-    _req(faces, torch.int32, "faces")
-    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
-        raise ValueError(f"faces: expected a non-empty [F,3], got {tuple(faces.shape)}")
-    f = int(faces.shape[0])
-    if lifted is not None:
-        _req(lifted, torch.int32, "lifted")
-        if lifted.numel() != s:
-            raise ValueError(f"lifted: expected {s} flags, got {lifted.numel()}")
-    for name, t in (("mesh_depth", mesh_depth), ("scene_depth", scene_depth), ("mesh", mesh), ("xyz_mm", xyz_mm), ("faces", faces)):
-        if t.device != silhouette.device:
-            raise ValueError(f"{name} on {t.device} but the silhouette on {silhouette.device}")
-    shape = tuple(scene_depth.shape)
-    if shape not in ((n, 1, h, w), (n, h, w), (n, 4, h, w)):
-        raise ValueError(f"scene_depth: expected fp32 [{n},1,{h},{w}], [{n},{h},{w}] or RGBD [{n},4,{h},{w}], got {shape}")
-    rgbd = len(shape) == 4 and shape[1] == 4
-    depth_ptr = scene_depth.data_ptr() + (3 * h * w * 4 if rgbd else 0)
-    host4 = table = None
-    if torch.is_tensor(paras) and paras.dim() != 1:
-        if paras.dtype != torch.float32 or tuple(paras.shape) != (n, 4):
-            raise ValueError(f"paras: a camera per frame is fp32 [{n},4] (fx, fy, cx, cy), got {paras.dtype} {tuple(paras.shape)}")
-        if paras.device != silhouette.device:
-            raise ValueError(f"paras on {paras.device} but the silhouette on {silhouette.device}")
-        table = ptr(_req(paras, torch.float32, "paras"))
-    else:
-        host4 = (C.c_float * 4)(*[float(x) for x in paras])
-    parts = []
-    for name, dtype, shp in (("fit_mesh", torch.float32, (s, v, 3)), ("fit_xyz", torch.float32, (s, joints, 3)),
-                             ("fit_rt", torch.float32, (s, 12)), ("fit_count", torch.int32, (s, 2)), ("fit_cost", torch.int64, (s,)),
-                             ("fit_trace", torch.int64, (s, iters, 3))):
-        t = torch.empty(shp, device=silhouette.device, dtype=dtype) if out is None else getattr(out, name)
-        if _req(t, dtype, name).numel() != math.prod(shp):
-            raise ValueError(f"{name}: expected {dtype} {list(shp)}, got {tuple(t.shape)}")
-        parts.append(t.view(shp))
-    if scratch is None:
-        scratch = torch.empty((mesh_fit_scratch_bytes(n, k, h),), device=silhouette.device, dtype=torch.uint8)
-    if work is None:
-        work = torch.empty((mesh_fit_iters_scratch_bytes(n, k, h, w, v, f, joints, iters),), device=silhouette.device,
-                           dtype=torch.uint8)
-    _req(scratch, torch.uint8, "scratch"); _req(work, torch.uint8, "work")
+    v, joints = _fit_meshes(mesh, xyz_mm, s)
+    faces, fh, f = _faces_arg(faces, mesh.device, nonempty=True)
+    _lifted_arg(lifted, s)
+    for name, t in (("mesh_depth", mesh_depth), ("mesh", mesh), ("xyz_mm", xyz_mm), ("faces", faces)):
+        _on_device(name, t, silhouette.device, "the silhouette")
+    depth_ptr, depth_stride = _scene_depth_arg(scene_depth, n, h, w, silhouette.device, "the silhouette")
+    host4, table = _camera_arg(paras, n, silhouette.device, "the silhouette")
+    parts = _out_parts(out, _fit_specs(s, v, joints) + (("fit_trace", torch.int64, (s, iters, 3)),), silhouette.device)
+    scratch = _scratch_arg(scratch, silhouette.device, mesh_fit_scratch_bytes, n, k, h)
+    work = _scratch_arg(work, silhouette.device, mesh_fit_iters_scratch_bytes, n, k, h, w, v, f, joints, iters, name="work")
     shift2, tan2 = fit_caps(max_shift, max_angle)
-    fh = faces_host.ctypes.data if faces_host is not None else None
-    check(_lib.load().hn_mesh_fit_iters_f32(ptr(mesh_depth), ptr(silhouette), depth_ptr, (4 if rgbd else 1) * h * w, host4, table,
+    check(_lib.load().hn_mesh_fit_iters_f32(ptr(mesh_depth), ptr(silhouette), depth_ptr, depth_stride, host4, table,
                                             ptr(mesh), ptr(xyz_mm), ptr(faces), fh, ptr(lifted), n, k, h, w, v, f, joints, iters,
                                             stride, band, min_points, damp, shift2, tan2, ptr(scratch), scratch.numel(), ptr(work),
                                             work.numel(), *(ptr(t) for t in parts), _stream()), "hn_mesh_fit_iters_f32")

@@ -421,7 +421,10 @@ def test_the_entries_are_declared_exported_and_bound():
     for r in rows + geo:
         assert " vgpr_spill 0 " in r and r.endswith("sgpr_spill 0") and " scratch 0 " in r, r
     assert len(geo) == 1
-    src = (build.CSRC / "mesh_refit.hip").read_text() + (build.CSRC / "mesh_raster.hip").read_text().split("mesh_geometry_tiles(")[1].split("}  // namespace")[0]
+    raster = (build.CSRC / "mesh_raster.hip").read_text()
+    walk = raster.split("void walk_tile(")[1].split("\n}\n")[0]      # (the walk the geometry kernel shares with the raster's)
+    assert "on_hit(" in walk and "walk_tile(" in raster.split("mesh_geometry_tiles(")[1]
+    src = (build.CSRC / "mesh_refit.hip").read_text() + walk + raster.split("mesh_geometry_tiles(")[1].split("}  // namespace")[0]
     assert "atomic" not in src.replace("No atomic", "")
 
 

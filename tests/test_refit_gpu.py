@@ -165,6 +165,28 @@ def test_geometry_at_the_shapes(shape):
     assert covered >= h * w // 8
 
 
+def test_geometry_is_the_occluded_raster_walk():
+    """2 frames x 3 slots at 33 x 65 (no multiple of the 8 x 8 tile, an unlifted slot per frame), once with the host's four
+    values and once with a camera per frame in a device table [2,4]: ops.mesh_geometry returns exactly the occluded
+    ops.mesh_render's depth_out and silhouette & 0x7F -- both tile kernels make the one walk of csrc/mesh_raster.hip"""
+    from hn_amd import ops
+    n, k, h, w = 2, 3, 33, 65
+    meshes, faces, lifted, cams = _shape_scene(n, k, h, w)
+    mesh, fc_dev, lif, table = _device(meshes.reshape(n * k, -1, 3), faces, lifted.reshape(-1), cams)
+    frame = torch.zeros((n, h, w, 3), dtype=torch.uint8, device="cuda")
+    scene = torch.full((n, h, w), 0.5, device="cuda")
+    assert tuple(table.shape) == (2, 4) and not torch.equal(table[0], table[1])
+    for tag, paras in (("four host values", tuple(float(x) for x in cams[0])), ("device table", table)):
+        z = torch.full((n, h, w), -1.0, device="cuda")
+        _img, sil, _cov = ops.mesh_render(mesh, fc_dev, paras, frame, lifted=lif, k=k, depth_out=z, scene_depth=scene, margin=0.0)
+        depth, who = ops.mesh_geometry(mesh, fc_dev, paras, (h, w), lifted=lif, k=k)
+        torch.cuda.synchronize()
+        hidden = int((sil & 0x80).ne(0).sum())
+        print(f"{tag}: {int(who.ne(0).sum())} covered pixels, {hidden} of them hidden, slots {sorted(set(who.unique().tolist()) - {0})}")
+        assert int(who.ne(0).sum()) >= h * w // 8 and hidden > 0, tag      # (the hidden flag is there to be masked off)
+        assert _bytes(depth) == _bytes(z) and _bytes(who) == _bytes(sil & 0x7F), tag
+
+
 def test_geometry_refuses_bad_arguments():
     from hn_amd import ops
     mesh = torch.zeros((4, 5, 3), device="cuda")
