@@ -286,6 +286,11 @@ def test_conv_f16x3_groupnorm_partials_in_epilogue(n, h, w, cin, cout, groups, t
     sc_ref, sh_ref = ops.groupnorm_affine(y, gamma.cuda(), beta.cuda(), groups=groups)
     assert (sc - sc_ref).abs().max().item() <= 2e-6 * sc_ref.abs().max().item()
     assert (sh - sh_ref).abs().max().item() <= 2e-6 * max(1.0, sh_ref.abs().max().item())
+    # ... and against the float64 statistics of the conv's own output (tests/gn_ref.py): a record is a sum of 32 rows x 8
+    # channels in fp32, so in whatever order the epilogue adds them a value passes through fewer than 256 additions
+    import gn_ref
+    ratio = gn_ref.check(sc.cpu().numpy(), sh.cpu().numpy(), y.cpu().numpy(), gamma.numpy(), beta.numpy(), groups, 1e-5, chain=256)
+    print(f"gn partials in the conv epilogue {n}x{h}x{w}x{cout} / {groups}: max |err| / bound = {ratio:.4f}")
     with pytest.raises(ValueError):
         ops.conv2d_nhwc(x16, wt.cuda(), b.cuda(), pad=1, w16=w16, relu=True, gn_partial=part)
 
