@@ -6,8 +6,12 @@
 
 namespace {
 
+constexpr const char* kCarryRefused =
+    "the carried apply pass rides on the plain row-shared 128x128 grouped launch only (this shape takes another form): run the "
+    "separate pass";
+
 template <int BM, int BN, int WM, int WN, int NBUF, bool BUF, int TERMS = 3>
-int launch16_impl(const ConvParams16& p0, hipStream_t st) {
+int launch16_impl(const ConvParams16& p0, hipStream_t st, const hn::CarryHook* carry = nullptr) {
   ConvParams16 p = p0;
   p.tiles_m = hn::cdiv(p.M, BM);
   p.tiles_n = hn::cdiv(p.Cout, BN);
@@ -33,6 +37,7 @@ int launch16_impl(const ConvParams16& p0, hipStream_t st) {
     rs = rs_will_run(p, BM, BN, WM * WN, NBUF, BUF);
     if constexpr (BM == 128 && BN == 128 && WM == 2 && WN == 2 && TERMS == 3) {
       const int mask = rs ? mixed_small_mask(p, p.tiles_n) : 0;
+      if (mask && carry) return hn::fail(HN_ERR_ARG, "%s", kCarryRefused);
       if (mask) {   // members with their own tile shape: the small ones as 64 x 128 per-tap tiles (see the kernel's comment)
         p.small_mask = mask;
         grid_x = 0;
@@ -54,6 +59,15 @@ int launch16_impl(const ConvParams16& p0, hipStream_t st) {
         return HN_OK;
       }
     }
+    if (carry) {   // refused before anything is launched unless this is the plain row-shared 128 x 128 grouped launch
+      if constexpr (BM == 128 && BN == 128 && WM == 2 && WN == 2) {
+        if (!rs || p.groups <= 1 || p.splits != 1) return hn::fail(HN_ERR_ARG, "%s", kCarryRefused);
+        if (carry->dry) return HN_OK;
+        return hn::launch_conv_carry(&p, sizeof(p), grid_x, p.groups, TERMS, RS_LDS_BYTES, carry->job, st);
+      } else {
+        return hn::fail(HN_ERR_ARG, "%s", kCarryRefused);
+      }
+    }
     if (rs) {
       constexpr int LDS_BYTES = RS_LDS_BYTES;
       static bool attr_set[64] = {};  // per device: the attribute belongs to the function's image on the current device
@@ -68,6 +82,7 @@ int launch16_impl(const ConvParams16& p0, hipStream_t st) {
                          dim3(grid_x, 1, p.groups > 1 ? p.groups : 1), dim3(WM * WN * 64), LDS_BYTES, st, p);
     }
   }
+  if (carry) return hn::fail(HN_ERR_ARG, "%s", kCarryRefused);
   if (!rs)
     hipLaunchKernelGGL((conv_igemm_f16x3_kernel<BM, BN, WM, WN, NBUF, BUF, false, TERMS>),
                        dim3(grid_x, p.splits, p.groups > 1 ? p.groups : 1), dim3(WM * WN * 64), 0, st, p);
@@ -122,17 +137,17 @@ int launch16_deepk(const ConvParams16& p0, hipStream_t st) {
 }
 
 template <int BM, int BN, int WM, int WN, int NBUF, bool ALLOW_F16X1 = true>
-int launch16(const ConvParams16& p0, hipStream_t st) {
+int launch16(const ConvParams16& p0, hipStream_t st, const hn::CarryHook* carry = nullptr) {
   ConvParams16 p = p0;
   const bool ok = finish_params16(p);
   if (p.terms == 1) {   // throughput mode: descriptor-form kernels of the tiles the engines use
     if constexpr (ALLOW_F16X1) {
-      if (ok) return launch16_impl<BM, BN, WM, WN, NBUF, true, 1>(p, st);
+      if (ok) return launch16_impl<BM, BN, WM, WN, NBUF, true, 1>(p, st, carry);
     }
     return hn::fail(HN_ERR_ARG, "the f16x1 mode exists for the descriptor-form kernels of the engine tiles only");
   }
-  if (ok) return launch16_impl<BM, BN, WM, WN, NBUF, true>(p, st);
-  return launch16_impl<128, 128, 2, 2, 2, false>(p, st);
+  if (ok) return launch16_impl<BM, BN, WM, WN, NBUF, true>(p, st, carry);
+  return launch16_impl<128, 128, 2, 2, 2, false>(p, st, carry);
 }
 
 }  // namespace
@@ -254,6 +269,10 @@ extern "C" int hn_conv2d_nhwc_f16x3_gn(const hn_conv_desc* d, const void* x16, c
 // three A2J head layers, are independent and identical in shape; on their own each leaves CUs idle at small
 // batch and costs a launch.  (Side streams do not help on this platform: tools/probes/exp/streams.sh.)
 extern "C" int hn_conv2d_nhwc_f16x3_grouped(const hn_conv_desc* d, const hn_conv_group* group, void* stream) {
+  return hn::conv_grouped_run(d, group, stream, nullptr);
+}
+
+int hn::conv_grouped_run(const hn_conv_desc* d, const hn_conv_group* group, void* stream, const hn::CarryHook* carry) {
   HN_CHECK_ARG(d && group, "hn_conv2d_nhwc_f16x3_grouped: null pointer");
   HN_CHECK_ARG(group->count >= 1 && group->count <= HN_CONV_MAX_GROUP, "group count must be 1..%d", HN_CONV_MAX_GROUP);
   HN_CHECK_ARG(d->res_mode == 0, "grouped convolutions take no residual");
@@ -266,11 +285,12 @@ extern "C" int hn_conv2d_nhwc_f16x3_grouped(const hn_conv_desc* d, const hn_conv
   HN_CHECK_ARG(any_gn == all_gn, "gn_partial must be given for every group member or for none");
   HN_CHECK_ARG(group->gn_units == 0 || group->gn_units >= d->cout / 8, "gn_units smaller than cout/8");
   return hn_igemm_conv16_run(d, group->x16[0], group->w16[0], group->bias[0], nullptr, group->y[0], nullptr, nullptr, 0, stream,
-                    group);
+                    group, carry);
 }
 
 int hn_igemm_conv16_run(const hn_conv_desc* d, const void* x16, const void* w16, const float* bias, const void* residual, void* y,
-                        float* gn_partial, void* workspace, int64_t workspace_bytes, void* stream, const hn_conv_group* group) {
+                        float* gn_partial, void* workspace, int64_t workspace_bytes, void* stream, const hn_conv_group* group,
+                        const hn::CarryHook* carry) {
   ConvParams16 p;
   HN_TRY16(fill_params16(d, x16, w16, bias, residual, y, gn_partial, workspace, workspace_bytes, p));
   // 64-output-channel 3x3 / stride-1 layers with many tiles (ResNet-34 layer1): direct convolution from an LDS halo patch
@@ -322,8 +342,9 @@ int hn_igemm_conv16_run(const hn_conv_desc* d, const void* x16, const void* w16,
   }
   hipStream_t st = (hipStream_t)stream;
   int picked = hn_conv2d_f16x3_pick_tile(&tile_desc);
+  if (carry && (picked != HN_TILE_128x128 || !group)) return hn::fail(HN_ERR_ARG, "%s", kCarryRefused);
   switch (picked) {
-    case HN_TILE_128x128: return launch16<128, 128, 2, 2, 2>(p, st);
+    case HN_TILE_128x128: return launch16<128, 128, 2, 2, 2>(p, st, carry);
     // LDS stage counts from an in-pipeline sweep (round-1 commit 5dc48dd): extra stages only pay
     // where they do not cost occupancy
     case HN_TILE_128x64: return launch16<128, 64, 2, 2, 2>(p, st);

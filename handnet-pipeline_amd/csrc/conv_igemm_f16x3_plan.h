@@ -294,4 +294,4 @@ static int fill_params16(const hn_conv_desc* d, const void* x16, const void* w16
 // cannot share a grid
 int hn_igemm_conv16_run(const hn_conv_desc* d, const void* x16, const void* w16, const float* bias, const void* residual, void* y,
                         float* gn_partial, void* workspace, int64_t workspace_bytes, void* stream,
-                        const hn_conv_group* group = nullptr);
+                        const hn_conv_group* group = nullptr, const hn::CarryHook* carry = nullptr);

@@ -40,6 +40,19 @@ bool conv1x1_stream_operands_ok(const hn_conv_desc* d, const void* x16, const vo
 int conv1x1_stream(const hn_conv_desc* d, const void* x16, const void* w16, const float* bias, const void* residual, void* y,
                    hipStream_t st);
 
+// conv_igemm_f16x3_carry.hip: a grouped tower convolution whose workgroups, their tiles done, stream a slice of a GroupNorm apply
+// pass over another, already complete tensor (hn_conv2d_nhwc_f16x3_grouped_carry).  The planning stays the ordinary launcher's:
+// hn_igemm_conv16_run takes the hook through to the point where the plain row-shared 128 x 128 kernel would be launched and
+// hands its finished parameter block over (the block's type is private to each translation unit: same header, same layout).
+struct CarryHook {
+  const void* job;   // the carry TU's CarryJob
+  bool dry;          // planning only: HN_OK = this launch would carry (hn_conv2d_f16x3_grouped_carry_applies)
+};
+int launch_conv_carry(const void* conv_params, size_t conv_params_bytes, int grid_x, int groups, int terms, int lds_bytes,
+                      const void* job, hipStream_t st);
+// the grouped entry's argument checks + launch (conv_igemm_f16x3.hip); carry: nullptr = the plain grouped launch
+int conv_grouped_run(const hn_conv_desc* d, const hn_conv_group* group, void* stream, const CarryHook* carry);
+
 // hn_debug_tickets_nonzero: the split-K ticket arrays of the two translation units that hold one
 int tickets_nonzero_main(int64_t* count);
 int tickets_nonzero_multi(int64_t* count);

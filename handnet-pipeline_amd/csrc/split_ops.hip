@@ -8,25 +8,14 @@
 //   hn_unsplit_f32        S32 -> fp32 (hi + lo is exact in fp32)
 //   hn_maxpool3x3s2_s32   3x3/2 max pooling on S32 (the max element's (hi, lo) pair is copied,
 //                         so pooling commutes with the split exactly)
-#include "hn_common.h"
+#include "affine_split_body.h"   // the per-lane arithmetic, shared with the pass carried by a tower convolution
 
 #include <float.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, f16x8& hi, f16x8& lo) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const _Float16 h0 = (_Float16)a[e], h1 = (_Float16)b[e];
-    hi[e] = h0;
-    hi[4 + e] = h1;
-    lo[e] = (_Float16)(a[e] - (float)h0);
-    lo[4 + e] = (_Float16)(b[e] - (float)h1);
-  }
-}
+typedef hn::as_f32x4 f32x4;
+typedef hn::as_f16x8 f16x8;
 
 // one thread = one pixel x 8 channels: reads 32 B fp32, writes 16 B hi + 16 B lo
 __global__ __launch_bounds__(256) void affine_split_kernel(const float* __restrict__ x, const float* __restrict__ scale,
@@ -41,34 +30,13 @@ __global__ __launch_bounds__(256) void affine_split_kernel(const float* __restri
     const float* src = x + pix * xs + ch;
     f32x4 a = *reinterpret_cast<const f32x4*>(src);
     f32x4 b = *reinterpret_cast<const f32x4*>(src + 4);
+    f32x4 s0 = {1.f, 1.f, 1.f, 1.f}, s1 = s0, t0 = {0.f, 0.f, 0.f, 0.f}, t1 = t0;
     if (scale) {
       const long o = (pix / hw) * as + ch;
-      const f32x4 s0 = *reinterpret_cast<const f32x4*>(scale + o), s1 = *reinterpret_cast<const f32x4*>(scale + o + 4);
-      const f32x4 t0 = *reinterpret_cast<const f32x4*>(shift + o), t1 = *reinterpret_cast<const f32x4*>(shift + o + 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        a[e] = a[e] * s0[e] + t0[e];
-        b[e] = b[e] * s1[e] + t1[e];
-      }
+      s0 = *reinterpret_cast<const f32x4*>(scale + o), s1 = *reinterpret_cast<const f32x4*>(scale + o + 4);
+      t0 = *reinterpret_cast<const f32x4*>(shift + o), t1 = *reinterpret_cast<const f32x4*>(shift + o + 4);
     }
-    if (relu) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        a[e] = hn::relu(a[e]);
-        b[e] = hn::relu(b[e]);
-      }
-    }
-    if (range_flag) {
-      bool bad = false;   // (NaN-aware: this pass is HBM-bound, and its input may be any fp32 tensor)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) bad |= hn::range_bad(a[e]) | hn::range_bad(b[e]);
-      if (bad) *range_flag = 1;
-    }
-    f16x8 hi, lo;
-    split8(a, b, hi, lo);
-    _Float16* dst = y + pix * ys + (ch >> 5) * 64 + (ch & 31);
-    *reinterpret_cast<f16x8*>(dst) = hi;
-    *reinterpret_cast<f16x8*>(dst + 32) = lo;
+    hn::affine_split_store(a, b, s0, s1, t0, t1, scale != nullptr, relu, range_flag, y + pix * ys + (ch >> 5) * 64 + (ch & 31), false);
   }
 }
 
@@ -101,36 +69,7 @@ __global__ __launch_bounds__(256) void affine_split_pow2_kernel(const float* __r
     else return *reinterpret_cast<const f32x4*>(q);
   };
   auto one = [&](f32x4 a, f32x4 b, int pix) {
-    if constexpr (AFFINE) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        a[e] = a[e] * s0[e] + t0[e];
-        b[e] = b[e] * s1[e] + t1[e];
-      }
-    }
-    if (relu) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        a[e] = hn::relu(a[e]);
-        b[e] = hn::relu(b[e]);
-      }
-    }
-    if (range_flag) {
-      bool bad = false;   // (NaN-aware: this pass is HBM-bound, and its input may be any fp32 tensor)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) bad |= hn::range_bad(a[e]) | hn::range_bad(b[e]);
-      if (bad) *range_flag = 1;
-    }
-    f16x8 hi, lo;
-    split8(a, b, hi, lo);
-    _Float16* dst = yi + (long)pix * ys;
-    if constexpr (NT & 2) {
-      __builtin_nontemporal_store(hi, reinterpret_cast<f16x8*>(dst));
-      __builtin_nontemporal_store(lo, reinterpret_cast<f16x8*>(dst + 32));
-    } else {
-      *reinterpret_cast<f16x8*>(dst) = hi;
-      *reinterpret_cast<f16x8*>(dst + 32) = lo;
-    }
+    hn::affine_split_store(a, b, s0, s1, t0, t1, AFFINE, relu, range_flag, yi + (long)pix * ys, (NT & 2) != 0);
   };
   int pix = blockIdx.x * ppb + (threadIdx.x >> c8_log2);
   for (; pix + (UNR - 1) * step < hw; pix += UNR * step) {
@@ -189,29 +128,7 @@ __global__ __launch_bounds__(256) void affine_split_pow2_levels_kernel(const Spl
   _Float16* yi = y + (long)img * hw * ys + (ch >> 5) * 64 + (ch & 31);
   const int step = (b1 - b0) * ppb;
   auto one = [&](f32x4 a, f32x4 b, int pix) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      a[e] = a[e] * s0[e] + t0[e];
-      b[e] = b[e] * s1[e] + t1[e];
-    }
-    if (relu) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        a[e] = hn::relu(a[e]);
-        b[e] = hn::relu(b[e]);
-      }
-    }
-    if (range_flag) {
-      bool bad = false;   // (NaN-aware: this pass is HBM-bound, and its input may be any fp32 tensor)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) bad |= hn::range_bad(a[e]) | hn::range_bad(b[e]);
-      if (bad) *range_flag = 1;
-    }
-    f16x8 hi, lo;
-    split8(a, b, hi, lo);
-    _Float16* dst = yi + (long)pix * ys;
-    *reinterpret_cast<f16x8*>(dst) = hi;
-    *reinterpret_cast<f16x8*>(dst + 32) = lo;
+    hn::affine_split_store(a, b, s0, s1, t0, t1, true, relu, range_flag, yi + (long)pix * ys, false);
   };
   int pix = ((int)blockIdx.x - b0) * ppb + (threadIdx.x >> c8_log2);
   for (; pix + step < hw; pix += 2 * step) {
@@ -298,6 +215,10 @@ __global__ __launch_bounds__(256) void maxpool_s32_kernel(const _Float16* __rest
   }
 }
 
+// Is a level's apply pass an HBM stream?  Tensors that no cache level keeps (>= 128 MiB of fp32) take the streaming-store form
+// in launches of their own (hn_affine_split_f32); hn_affine_split_f32_levels_streams answers the same question for callers.
+bool level_streams(int64_t n, int64_t hw, int64_t c) { return n * hw * c * 4 >= ((int64_t)128 << 20); }
+
 int grid_for(long total) {
   const long g = (total + 255) / 256;
   return (int)(g < 16384 ? (g > 0 ? g : 1) : 16384);
@@ -330,7 +251,7 @@ extern "C" int hn_affine_split_f32(const float* x, const float* scale, const flo
     // 89 -> 73 us at batch 32); plain stores for small ones, which the next convolution finds in L2 / Infinity Cache
     // (sweep of NT bits x pixels in flight, profiles/r02_apply_pass_sweep.txt; streaming LOADS cost 8 % everywhere).  In the pipeline: +0.9 % at batch 32 over the
     // generic kernel, the same with either store form (tools/probes/exp/apply_ab.sh).
-    const bool big = (int64_t)npix * c * 4 >= ((int64_t)128 << 20);
+    const bool big = level_streams(n, hw, c);
 #define HN_SPLIT_LAUNCH(AFF, NTV, UNRV)                                                                                          \
   hipLaunchKernelGGL((affine_split_pow2_kernel<AFF, NTV, UNRV>), dim3(gx, n), dim3(256), 0, (hipStream_t)stream, x, scale, shift, \
                      relu, hw, lg, xs, as, (_Float16*)y16, ys, hn::range_flag_ptr())
@@ -363,7 +284,7 @@ extern "C" int hn_affine_split_f32_levels(const hn_split_levels* lv, int relu, i
   for (int l = 0; l < lv->count; ++l) {
     HN_CHECK_ARG(lv->x[l] && lv->y16[l] && lv->scale[l] && lv->shift[l] && lv->hw[l] > 0, "level %d: null pointer or hw <= 0", l);
     // tensors no cache keeps take the streaming-store form of the per-level launch (see hn_affine_split_f32)
-    if ((int64_t)n * lv->hw[l] * c * 4 >= ((int64_t)128 << 20)) merged = false;
+    if (level_streams(n, lv->hw[l], c)) merged = false;
   }
   if (!merged) {
     for (int l = 0; l < lv->count; ++l) {
@@ -396,6 +317,13 @@ extern "C" int hn_affine_split_f32_levels(const hn_split_levels* lv, int relu, i
                      relu, lg, xs, as, ys, hn::range_flag_ptr());
   HN_CHECK_LAUNCH("affine_split_pow2_levels_kernel");
   return HN_OK;
+}
+
+extern "C" int hn_affine_split_f32_levels_streams(const int32_t* hw, int count, int n, int c) {
+  if (!hw || count < 1 || n <= 0 || c <= 0) return 0;
+  for (int l = 0; l < count; ++l)
+    if (hw[l] > 0 && level_streams(n, hw[l], c)) return 1;
+  return 0;
 }
 
 extern "C" int hn_unsplit_f32(const void* x16, int n, int hw, int c, int in_pix_stride, float* y, int out_pix_stride,

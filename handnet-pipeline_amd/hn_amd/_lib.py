@@ -197,6 +197,10 @@ SIGNATURES = {
     "hn_destroy": (C.c_int, [VP]),
     "hn_groupnorm_finalize_rows32_levels": (C.c_int, [C.POINTER(GnLevels), VP, VP, C.c_int, C.c_int, C.c_int, C.c_float, VP]),
     "hn_affine_split_f32_levels": (C.c_int, [C.POINTER(SplitLevels)] + [C.c_int] * 6 + [VP]),
+    "hn_affine_split_f32_levels_streams": (C.c_int, [C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int]),
+    "hn_conv2d_nhwc_f16x3_grouped_carry": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvGroup), C.POINTER(SplitLevels)]
+                                           + [C.c_int] * 6 + [VP]),
+    "hn_conv2d_f16x3_grouped_carry_applies": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvGroup)]),
     "hn_pack_records": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP]),
     "hn_debug_tickets_nonzero": (C.c_int, [c_i64p]),
     "hn_pack_records_ex": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP, VP]),

@@ -68,6 +68,7 @@ def _check_resources(src: Path, remarks: str, objdir: Path) -> None:
     for name, res in rows:
         out.append(f"{name}: VGPRs {res.get('VGPRs')} AGPRs {res.get('AGPRs')} SGPRs {res.get('TotalSGPRs')} "
                    f"scratch {res.get('ScratchSize [bytes/lane]')} occupancy {res.get('Occupancy [waves/SIMD]')} "
+                   f"lds {res.get('LDS Size [bytes/block]')} "
                    f"vgpr_spill {res.get('VGPRs Spill')} sgpr_spill {res.get('SGPRs Spill')}")
         # (SGPR spills go to VGPR lanes, not to memory: harmless where no asm load is in flight -- the P-form kernel uses
         # plain loads only -- but they are refused in the hand-counted kernels all the same)

@@ -130,6 +130,11 @@ class FCOSEngine:
         self.thin_outputs = fm["thin_outputs"] and self.cls_out.cout <= 16   # (tap form bit-identical, P form to fp32 rounding)
         # conv1 of a downsampling block together with its 1x1 downsample (ops.conv2d_nhwc_multi)
         self.multi = fm["conv_multi_fcos"] and precision == "f16x3"
+        # the towers' apply passes in the tails of the other tower's convolutions, where those passes are HBM streams
+        # (heads_grouped; True = always, for tests of the schedule at small shapes; results are bit-identical either way)
+        self.tower_carry = fm["tower_carry"]
+        self.tower_carry_force = False
+        self.tower_tile = 0   # development / tests: HN_TILE_* id of the tower layers' launches in heads_grouped (0 = the heuristic)
 
     # -----------------------------------------------------------------------------------
     def _conv(self, x, cw: ConvW, relu=False, out_f32=False, **kw):
@@ -294,13 +299,62 @@ class FCOSEngine:
         # GroupNorm finalize and the affine + ReLU + split pass: ONE launch each over the levels (the library falls back
         # to per-level launches of the apply pass for tensors beyond the caches, where streaming stores win)
         aff = ops.groupnorm_finalize_rows32_levels(parts, self.gn0_gamma, self.gn0_beta, n, hw, 64)
+        if self.tower_carry and (self.tower_carry_force or ops.split_levels_stream(n, hw, 512)):
+            t, aff = self._towers_carried(t, aff, parts, new_t, n, hw)
+            if t is not None:
+                return self._head_outputs(t, aff, L)
+            t, aff = aff   # (the launches would not carry at this shape: nothing was issued)
         for cwc, cwr, (g2, b2) in zip(self.cls_tower, self.reg_tower, self.both_gn):
             a = ops.to_split_levels(t, aff, relu=True)                  # S32 [N,h,w,16,2,32]: cls blocks 0-7, reg 8-15
             t = new_t()
             ops.conv2d_nhwc_grouped([x[:, :, :, :8] for x in a] + [x[:, :, :, 8:] for x in a], [cwc] * L + [cwr] * L,
                                     pad=1, outs=t + t, out_channel_offsets=[0] * L + [256] * L,
-                                    gn=[(parts[l], 0) for l in range(L)] + [(parts[l], 32) for l in range(L)], gn_units=64)
+                                    gn=[(parts[l], 0) for l in range(L)] + [(parts[l], 32) for l in range(L)], gn_units=64,
+                                    tile=self.tower_tile)
             aff = ops.groupnorm_finalize_rows32_levels(parts, g2, b2, n, hw, 64)
+        return self._head_outputs(t, aff, L)
+
+    def _towers_carried(self, t, aff, parts, new_t, n, hw):
+        """Tower layers 1-3 as one launch per TOWER (cls, then reg) instead of one per layer: the two towers are independent
+        chains, so the launch of one carries the GroupNorm apply pass of the other's last output -- a pure HBM stream that
+        otherwise runs alone between two convolutions that leave HBM idle -- in the tails of its workgroups
+        (ops.conv2d_nhwc_grouped(carry=...)):
+            apply(y0 cls) alone;  C1 + apply(y0 reg);  R1 + apply(y1 cls);  C2 + apply(y1 reg);  ...  C3 + apply(y2 reg);  R3
+        Tensors, GroupNorm slabs and arithmetic are those of the lock-step schedule: same bits.  The finalize runs over the
+        whole slab after each launch; only the half that launch completed is read from its tables.
+        -> (stacked outputs of layer 3, their tables), or (None, (t, aff)) when the launches would not carry."""
+        L = len(t)
+        dev = t[0].device
+        half = lambda xs, k: [x[..., 256 * k:256 * (k + 1)] for x in xs]                        # noqa: E731
+        blocks = lambda xs, k: [x[:, :, :, 8 * k:8 * (k + 1)] for x in xs]                      # noqa: E731
+        tabs = lambda af, k: [(sc[:, 256 * k:256 * (k + 1)], sh[:, 256 * k:256 * (k + 1)]) for sc, sh in af]   # noqa: E731
+        new_a = lambda: [torch.empty(tuple(x.shape[:3]) + (16, 2, 32), device=dev, dtype=torch.float16) for x in t]  # noqa: E731
+
+        def tower(k, cw, a, y, carry=None, query=False):
+            return ops.conv2d_nhwc_grouped(blocks(a, k), [cw] * L, pad=1, outs=y, out_channel_offsets=[256 * k] * L,
+                                           gn=[(parts[l], 32 * k) for l in range(L)], gn_units=64, tile=self.tower_tile,
+                                           carry=carry, carry_query=query)
+
+        a = new_a()
+        if not tower(0, self.cls_tower[0], a, t, query=True):
+            return None, (t, aff)
+        ops.to_split_levels(half(t, 0), tabs(aff, 0), relu=True, outs=blocks(a, 0))      # needed at once: stays a pass of its own
+        layers = list(zip(self.cls_tower, self.reg_tower, self.both_gn))
+        for i, (cwc, cwr, (g2, b2)) in enumerate(layers):
+            y = new_t()
+            tower(0, cwc, a, y, carry=(half(t, 1), tabs(aff, 1), blocks(a, 1), True))      # C: reads a[cls], completes a[reg]
+            aff_c = ops.groupnorm_finalize_rows32_levels(parts, g2, b2, n, hw, 64)         # (cls half valid)
+            if i + 1 < len(layers):
+                a_next = new_a()
+                tower(1, cwr, a, y, carry=(half(y, 0), tabs(aff_c, 0), blocks(a_next, 0), True))   # R: completes a_next[cls]
+            else:
+                a_next = None
+                tower(1, cwr, a, y)                                     # the last layer's pass stays in the head-output kernels
+            t, a = y, a_next
+            aff = ops.groupnorm_finalize_rows32_levels(parts, g2, b2, n, hw, 64)           # both halves valid
+        return t, aff
+
+    def _head_outputs(self, t, aff, L):
         ops.PROFILE_STAGE = "head_outputs"
         if (self.thin_outputs and self.fuse_last_gn and self.terms == 3 and not self.ext
                 and ops.thin_affine_applies(t, self.cls_out) and ops.thin_affine_applies(t, self.reg_out)):

@@ -21,6 +21,7 @@ ENGINE_DEFAULTS = dict(
     thin_outputs=True,      # thin-N kernels for the <= 16-channel head outputs
     conv_multi=True,        # heterogeneous launches in the A2J engine (<= MULTI_MAX_CROPS crops)
     conv_multi_fcos=True,   # ... for the downsample blocks of the FCOS trunk
+    tower_carry=True,       # large batch: each tower's conv launch carries the other tower's GroupNorm apply pass (bit-identical)
 )
 ACTIVE = dict(ENGINE_DEFAULTS)
 
@@ -68,7 +69,7 @@ def apply_env(environ=None) -> dict:
         ops.set_form("thin_form_tap" if env["HN_THIN_FORM"][0] == "t" else "thin_form_flat", True)
         done["HN_THIN_FORM"] = env["HN_THIN_FORM"]
     for var, key in (("HN_GROUP_CONVS", "group_convs"), ("HN_FUSE_STEM_POOL", "fuse_stem_pool"), ("HN_CONV_MULTI", "conv_multi"),
-                     ("HN_CONV_MULTI_FCOS", "conv_multi_fcos")):
+                     ("HN_CONV_MULTI_FCOS", "conv_multi_fcos"), ("HN_TOWER_CARRY", "tower_carry")):
         if var in env:
             ACTIVE[key] = env[var] != "0"
             done[var] = env[var]

@@ -540,7 +540,7 @@ def conv2d_nhwc_multi(items, fused=None):
 
 
 def conv2d_nhwc_grouped(xs, ws, *, pad=0, relu=False, relu_cols=None, out_split=False, tile=0, gn_partials=None,
-                        outs=None, out_channel_offsets=None, gn=None, gn_units=0):
+                        outs=None, out_channel_offsets=None, gn=None, gn_units=0, carry=None, carry_query=False):
     """Independent stride-1 f16x3 convolutions with identical channels / filter / batch as ONE launch
     (gridDim.z = member); the members may differ in spatial size (the FPN levels of one layer).
       xs            S32 inputs (same N, channels and pixel stride); ws: ConvW-like objects (.w [Cout,R,S,Cin], .bias,
@@ -550,11 +550,15 @@ def conv2d_nhwc_grouped(xs, ws, *, pad=0, relu=False, relu_cols=None, out_split=
                     e.g. the cls / reg towers of a level together.  Default: fresh dense outputs.
       gn_partials   one GroupNorm-sum buffer per member (each Cout/8 units wide), or
       gn, gn_units  [(buffer, unit offset)] per member into slabs that are gn_units units wide (stacked members).
+      carry         (xs, affines, outs, relu) as to_split_levels takes them: the launch also runs that apply pass, every
+                    workgroup a slice of it once its output tile is stored (hn_conv2d_nhwc_f16x3_grouped_carry) -- on a
+                    tensor this convolution neither reads nor writes; only where grouped_carry_applies() says so.
+      carry_query   plan only: returns True / False, would this launch carry? (launches nothing)
     Returns the list of outputs.  A single plain member falls through to conv2d_nhwc."""
     k = len(xs)
     if k != len(ws) or k == 0 or k > _lib.CONV_MAX_GROUP:
         raise ValueError(f"need 1..{_lib.CONV_MAX_GROUP} inputs and as many weight sets")
-    if k == 1 and outs is None and gn is None:
+    if k == 1 and outs is None and gn is None and carry is None and not carry_query:
         return [conv2d_nhwc(xs[0], ws[0].w, ws[0].bias, pad=pad, relu=relu, relu_cols=relu_cols, w16=ws[0].w16,
                             out_split=out_split, tile=tile, gn_partial=None if gn_partials is None else gn_partials[0])]
     lib = _lib.load()
@@ -608,11 +612,19 @@ def conv2d_nhwc_grouped(xs, ws, *, pad=0, relu=False, relu_cols=None, out_split=
             if buf.numel() < need or buf.dtype != torch.float32 or not buf.is_cuda or uoff * 8 + cout > units * 8:
                 raise ValueError(f"member {i}: GroupNorm slab must be an fp32 GPU buffer of >= {need} floats")
             grp.gn_partial[i] = buf.data_ptr() + 16 * uoff
+    if carry_query:
+        return bool(lib.hn_conv2d_f16x3_grouped_carry_applies(C.byref(d), C.byref(grp)))
     prof = CONV_PROFILE
     if prof is not None:
         timer = HipTimer()
         timer.start()
-    check(lib.hn_conv2d_nhwc_f16x3_grouped(C.byref(d), C.byref(grp), _stream()), "hn_conv2d_nhwc_f16x3_grouped")
+    if carry is not None:
+        cxs, caff, couts, crelu = carry
+        lv, cn, cc, cxstride, ca_stride, cystride, _ = _split_levels_arg(cxs, caff, couts)
+        check(lib.hn_conv2d_nhwc_f16x3_grouped_carry(C.byref(d), C.byref(grp), C.byref(lv), 1 if crelu else 0, cn, cc, cxstride,
+                                                     ca_stride, cystride, _stream()), "hn_conv2d_nhwc_f16x3_grouped_carry")
+    else:
+        check(lib.hn_conv2d_nhwc_f16x3_grouped(C.byref(d), C.byref(grp), _stream()), "hn_conv2d_nhwc_f16x3_grouped")
     if prof is not None:
         timer.stop()
         rows = sum(n * oh * ow for oh, ow in sizes)
@@ -844,30 +856,58 @@ def groupnorm_finalize_rows32_levels(partials, gamma, beta, n, hws, groups=32, e
     return [(tables[i, 0], tables[i, 1]) for i in range(len(partials))]
 
 
-def to_split_levels(xs, affines, relu=True):
-    """to_split(x, scale, shift, relu) for the FPN levels of one tower layer in ONE launch (per-level launches when a
-    level is too large for the caches, decided by the library).  xs: fp32 [N,h_l,w_l,C]; affines: [(scale, shift)]."""
-    lib = _lib.load()
+def _split_levels_arg(xs, affines, outs=None):
+    """The levels of one apply pass as the library takes them -> (hn_split_levels, n, c, x stride, table stride, out stride, outs).
+    xs: fp32 [N,h_l,w_l,C] (channel slices of wider tensors are fine); affines: [(scale, shift)] [N,C] tables; outs: S32
+    [N,h_l,w_l,C/32,2,32] destinations (block slices of wider tensors are fine), default fresh dense ones."""
     n, _, _, c = xs[0].shape
     xstride = _pixel_stride(xs[0], "x")
     a_stride = affines[0][0].stride(0)
+    if len(xs) > _lib.HN_FCOS_MAX_LEVELS or len(affines) != len(xs) or (outs is not None and len(outs) != len(xs)):
+        raise ValueError(f"need 1..{_lib.HN_FCOS_MAX_LEVELS} levels with one (scale, shift) pair (and one output) each")
     lv = _lib.SplitLevels()
     lv.count = len(xs)
-    outs = []
+    made = []
+    ystride = None
     for i, (x, (scale, shift)) in enumerate(zip(xs, affines)):
-        if x.shape[0] != n or x.shape[3] != c or _pixel_stride(x, "x") != xstride or is_split(x):
+        if x.shape[0] != n or x.shape[3] != c or _pixel_stride(x, "x") != xstride or is_split(x) or x.dtype != torch.float32:
             raise ValueError("levels must be fp32 NHWC tensors of one batch size, channel count and pixel stride")
         for t in (scale, shift):
             if (not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (n, c) or t.stride(1) != 1
                     or t.stride(0) != a_stride):
                 raise ValueError("scale / shift must be fp32 GPU [N, C] tables with equal row stride")
-        out = torch.empty((n, x.shape[1], x.shape[2], c // 32, 2, 32), device=x.device, dtype=torch.float16)
+        if outs is None:
+            out = torch.empty((n, x.shape[1], x.shape[2], c // 32, 2, 32), device=x.device, dtype=torch.float16)
+        else:
+            out = outs[i]
+            if not is_split(out) or tuple(out.shape) != (n, x.shape[1], x.shape[2], c // 32, 2, 32) or out.device != x.device:
+                raise ValueError("outputs must be S32 tensors [N,h,w,C/32,2,32] of their level's size")
+        ys = _pixel_stride(out, "out")
+        if ystride is not None and ys != ystride:
+            raise ValueError("outputs must share one pixel stride")
+        ystride = ys
         lv.hw[i] = x.shape[1] * x.shape[2]
         lv.x[i], lv.scale[i], lv.shift[i], lv.y16[i] = x.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.data_ptr()
-        outs.append(out)
-    check(lib.hn_affine_split_f32_levels(C.byref(lv), 1 if relu else 0, n, c, xstride, a_stride, 2 * c, _stream()),
+        made.append(out)
+    return lv, n, c, xstride, a_stride, ystride, made
+
+
+def to_split_levels(xs, affines, relu=True, outs=None):
+    """to_split(x, scale, shift, relu) for the FPN levels of one tower layer in ONE launch (per-level launches when a
+    level is too large for the caches, decided by the library).  xs: fp32 [N,h_l,w_l,C]; affines: [(scale, shift)];
+    outs: optional preallocated S32 destinations (e.g. one tower's blocks of the stacked operand)."""
+    lib = _lib.load()
+    lv, n, c, xstride, a_stride, ystride, outs = _split_levels_arg(xs, affines, outs)
+    check(lib.hn_affine_split_f32_levels(C.byref(lv), 1 if relu else 0, n, c, xstride, a_stride, ystride, _stream()),
           "hn_affine_split_f32_levels")
     return outs
+
+
+def split_levels_stream(n, hws, c) -> bool:
+    """Is the apply pass of these levels an HBM stream (a level beyond the caches: the library runs per-level launches with
+    streaming stores)?  The threshold at which FCOSEngine.heads_grouped lets the tower convolutions carry the pass."""
+    arr = (C.c_int32 * len(hws))(*[int(v) for v in hws])
+    return bool(_lib.load().hn_affine_split_f32_levels_streams(arr, len(hws), int(n), int(c)))
 
 
 def _device_readable(t: torch.Tensor, name: str):

@@ -39,7 +39,8 @@ extern "C" {
  * hn_track_state_bytes, the smoothed step's hn_mesh_finish_smooth_f32 and hn_smooth_state_bytes, the per-frame cameras'
  * hn_mesh_render_cams_u8 and hn_mesh_render_cams_occluded_u8, the rig frame's hn_rig_fuse_f32, the hand cloud's
  * hn_hand_cloud_f32 and hn_hand_cloud_scratch_bytes, the mesh fit's hn_mesh_fit_f32 and hn_mesh_fit_scratch_bytes, and the
- * iterated fit's hn_mesh_geometry_f32, hn_mesh_fit_iters_f32 and hn_mesh_fit_iters_scratch_bytes). */
+ * iterated fit's hn_mesh_geometry_f32, hn_mesh_fit_iters_f32 and hn_mesh_fit_iters_scratch_bytes, and the carried apply pass's
+ * hn_conv2d_nhwc_f16x3_grouped_carry, hn_conv2d_f16x3_grouped_carry_applies and hn_affine_split_f32_levels_streams). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -326,6 +327,21 @@ typedef struct hn_split_levels {
 } hn_split_levels;
 int hn_affine_split_f32_levels(const hn_split_levels* lv, int relu, int n, int c, int in_pix_stride,
                                int affine_stride, int out_pix_stride, void* stream);
+/* 1 when a level of this size makes the call above an HBM stream (per-level launches with streaming stores); host-only. */
+int hn_affine_split_f32_levels_streams(const int32_t* hw, int count, int n, int c);
+
+/* hn_conv2d_nhwc_f16x3_grouped that CARRIES hn_affine_split_f32_levels(lv, relu, n, c, ...) in ONE launch: every convolution
+ * workgroup, its output tile stored, streams a slice of the apply pass and leaves -- the pass (an HBM stream) runs under the
+ * matrix work of the other workgroups instead of after it.  The levels' tensors must be complete before the call and must not
+ * be read or written by the convolution (the cls tower's launch carries the reg tower's pass and the other way round); their
+ * n / c / levels are their own (c = 32 .. 2048, a power of two; 16-byte aligned pointers).  Same bits as the two calls one after
+ * the other.  Only the plain row-shared 128 x 128 form of the grouped launch carries: for any other shape the call fails with
+ * HN_ERR_ARG before it launches anything (hn_conv2d_f16x3_grouped_carry_applies() == 0, host-only) and the caller runs the
+ * separate pass. */
+int hn_conv2d_nhwc_f16x3_grouped_carry(const hn_conv_desc* desc, const hn_conv_group* group, const hn_split_levels* lv,
+                                       int relu, int n, int c, int in_pix_stride, int affine_stride, int out_pix_stride,
+                                       void* stream);
+int hn_conv2d_f16x3_grouped_carry_applies(const hn_conv_desc* desc, const hn_conv_group* group);
 
 /* The FCOS head OUTPUT convolutions (cls_logits + hand_lr, bbox_reg + bbox_ctrness, the ext heads: fcos_utils/fcos.py:
  * 247-264,299-320,362-363): 3x3 / stride 1 / pad 1, cin % 32 == 0, 1 <= cout <= 16, the same filter on every FPN level,
