@@ -180,8 +180,9 @@ __global__ __launch_bounds__(256) void fcos_preprocess_split_tiled_kernel(const 
   }
   __syncthreads();
   const long total = (long)n * hb * wb;
-  // a lane owns TWO adjacent canvas columns (one 16-byte store per plane and row; wb is even: pw % 32 == 0) of rows
-  // (tid >> 6) + 4 k
+  // a lane owns TWO adjacent canvas columns of rows (tid >> 6) + 4 k: one 16-byte store per plane and row.  wb is EVEN here
+  // (preprocess_run sends an odd pw + 2 b to the per-pixel kernel), so cxa < wb implies cxa + 1 < wb, and with n * hb * wb
+  // even too every such store is 16-byte aligned in both planes
   const int cxa = cx0 + (tid & 63) * 2;
   int x0[2] = {0, 0}, x1[2] = {0, 0};
   float wx0[2] = {0.f, 0.f}, wx1[2] = {0.f, 0.f};
@@ -223,13 +224,8 @@ __global__ __launch_bounds__(256) void fcos_preprocess_split_tiled_kernel(const 
       hi[j * 4 + 3] = lo[j * 4 + 3] = (_Float16)0.f;
     }
     const long i = ((long)img * hb + cy) * wb + cxa;
-    if (cxa + 1 < wb) {
-      *reinterpret_cast<f16x8_*>(dst + i * 4) = hi;
-      *reinterpret_cast<f16x8_*>(dst + (total + i) * 4) = lo;
-    } else {   // (odd canvas width: the last column alone)
-      *reinterpret_cast<f16x4*>(dst + i * 4) = f16x4{hi[0], hi[1], hi[2], hi[3]};
-      *reinterpret_cast<f16x4*>(dst + (total + i) * 4) = f16x4{lo[0], lo[1], lo[2], lo[3]};
-    }
+    *reinterpret_cast<f16x8_*>(dst + i * 4) = hi;
+    *reinterpret_cast<f16x8_*>(dst + (total + i) * 4) = lo;
   }
 }
 
@@ -1264,8 +1260,10 @@ static int preprocess_run(const float* src, const float* const* srcs, const int3
   g.geom = geom;
   const float scale_h = geom ? 1.f : (float)h / (float)oh, scale_w = geom ? 1.f : (float)w / (float)ow;
   const float need_r = (kPreTH - 1) * scale_h + 3.f, need_c = (kPreTW - 1) * scale_w + 3.f;   // source rows / columns under a tile
-  if (split && !geom && n <= 65535 && !hn::env_flags().pre_generic && need_r <= 16.f && need_c <= 160.f) {
-    // dense batch, source rectangle of a tile fits an LDS patch: the tiled kernel (HN_PREPROCESS_GENERIC=1: A/B)
+  if (split && !geom && n <= 65535 && !hn::env_flags().pre_generic && need_r <= 16.f && need_c <= 160.f &&
+      (pw + 2 * border) % 2 == 0) {
+    // dense batch, source rectangle of a tile fits an LDS patch, even bordered width (the tiled kernel's 16-byte stores of
+    // two columns need it; the engines' canvases are multiples of 32 wide): the tiled kernel (HN_PREPROCESS_GENERIC=1: A/B)
     const int hb = ph + 2 * border, wb = pw + 2 * border;
     const dim3 grid(hn::cdiv(wb, kPreTW), hn::cdiv(hb, kPreTH), n);
     if (need_r <= 8.f && need_c <= 96.f)

@@ -537,13 +537,15 @@ def test_chunked_candidates_equal_the_single_workgroup_form(n, sizes, thresh):
     assert lib.hn_fcos_candidates_ws_bytes(2, 17850) == 2 * 18 * 4 and lib.hn_fcos_candidates_ws_bytes(0, 5) == 0
 
 
-@pytest.mark.parametrize("n,h,w", [(2, 480, 640), (1, 720, 1280), (3, 300, 333), (1, 1200, 1600)])
+@pytest.mark.parametrize("n,h,w", [(2, 480, 640), (1, 720, 1280), (3, 300, 333), (1, 1200, 1600), (1, 900, 1200)])
 def test_tiled_preprocess_is_bit_identical_to_the_per_pixel_kernel(n, h, w, monkeypatch):
     """fcos_preprocess_split_tiled_kernel normalises the source rectangle of an 8 x 128 output tile once into LDS and
     interpolates from there: the same divisions on the same values and the same interpolation expressions as the per-pixel
     kernel (tv GeneralizedRCNNTransform: normalize, then bilinear resize, fcos.py:702-709) -> torch.equal on the stem image,
-    for up- and down-scaling frames (the 1200 x 1600 frame is DOWNscaled: its tiles need more source rows than the patch
-    holds only beyond scale 1.85, so it still takes the tiled kernel)."""
+    for up- and down-scaling frames.  The 900 x 1200 frame is DOWNscaled by 1.125 (a tile needs 127 * 1.125 + 3 = 145.9
+    source columns) and takes the <16, 160> instantiation.  The 1200 x 1600 frame does NOT take the tiled kernel: at scale
+    1.5 a tile needs 127 * 1.5 + 3 = 193.5 > 160 source columns, so both runs are the per-pixel kernel there (the case only
+    shows that the dispatch falls back; tests/test_pre_gpu.py checks either kernel against a float64 rule)."""
     from hn_amd import ops, synth
     from hn_amd.fcos_engine import FCOSEngine, IMAGE_MEAN, IMAGE_STD, resized_size
     x = synth.make_rgb(n, h, w, seed=7).cuda()
