@@ -418,7 +418,8 @@ static int stem16_run(const void* x16, int n, int ph, int pw, int pad, int r, in
     HN_CHECK_ARG(cout == 64 && relu && out_split && bias, "the fused stem + max-pool kernel needs cout = 64, bias, ReLU and an S32 output");
     HN_CHECK_ARG((uintptr_t)y % 16 == 0 && (uintptr_t)bias % 16 == 0, "unaligned output / bias");
     // the ResNet stem shape, the only one this path has: direct convolution from an LDS-resident image patch
-    // (conv_stem_direct.hip; bit-identical to hn_conv_stem_f16x3 + hn_maxpool3x3s2_s32)
+    // (conv_stem_direct.hip; the values of hn_conv_stem_f16x3 + hn_maxpool3x3s2_s32 bit for bit, the planes too except for
+    // equal-sum pairs: see that file's header)
     HN_CHECK_ARG(r == 7 && stride == 2 && pad == 3 && (uintptr_t)w16 % 16 == 0,
                  "the fused stem + max-pool kernel is written for the 7x7 / stride-2 / pad-3 ResNet stem");
     return hn::stem_pool_direct(x16, n, ph, pw, w16, bias, y, terms == 1 ? 1 : 3, st);
@@ -441,7 +442,9 @@ extern "C" int hn_conv_stem_f16x3(const void* x16, int n, int ph, int pw, int pa
 
 // The same stem with the 3x3 / stride-2 / pad-1 max pooling that follows it in a ResNet (conv1 -> bn1 -> relu -> maxpool,
 // torchvision resnet34 at fcos_utils/fcos.py:737) fused into the epilogue: y is the POOLED S32 map
-// [n][(oh+1)/2][(ow+1)/2][64]; bit-identical to hn_conv_stem_f16x3 + hn_maxpool3x3s2_s32.
+// [n][(oh+1)/2][(ow+1)/2][64]; its values (hi + lo) are those of hn_conv_stem_f16x3 + hn_maxpool3x3s2_s32 bit for bit, and
+// its planes too unless a pooling window holds two values either side of an fp16 rounding midpoint whose pairs recombine to
+// the same sum (this kernel splits the maximum, the unfused pooling copies the first such pair: conv_stem_direct.hip).
 extern "C" int hn_conv_stem_pool_f16x3(const void* x16, int n, int ph, int pw, int pad, int r, int stride, int cout,
                                        const void* w16, const float* bias, void* y, void* stream) {
   return stem16_run(x16, n, ph, pw, pad, r, stride, cout, w16, bias, 1, y, 1, true, stream);

@@ -11,9 +11,14 @@
 //   * A fragment of conv pixel (oy, ox), filter row ky, lane group g: the 16 bytes at patch[(2 oy + ky)][2 ox + 2 g]
 //     (k = kx * 4 + c, two pixels per 8-half chunk) -- a plain ds_read_b128 at a per-lane address,
 //   * W fragments from the resident bank; MFMA operands swapped (lane = pixel, registers = channels) and the three
-//     terms per k tile in the order of the implicit-GEMM kernel (lo*hi, hi*lo, hi*hi), so results are BIT-IDENTICAL to
-//     hn_conv_stem_f16x3 + hn_maxpool3x3s2_s32,
+//     terms per k tile in the order of the implicit-GEMM kernel (lo*hi, hi*lo, hi*hi), so the fp32 conv values are those of
+//     hn_conv_stem_f16x3 bit for bit and the pooled VALUES (hi + lo) those of hn_conv_stem_f16x3 + hn_maxpool3x3s2_s32,
 //   * epilogue: bias + ReLU patch -> LDS (fp32), 3x3 / stride-2 max over the patch, S32 (hi | lo) store of the pooled map.
+//     This splits max(v), while hn_maxpool3x3s2_s32 keeps the pair of the window's first element with the largest hi + lo.
+//     The PLANES are the same too unless two fp32 values of one window lie either side of an fp16 rounding midpoint, within
+//     an ulp or two of it: their pairs (a, +u/2) and (b, -u/2) differ and recombine to the same sum, and when the smaller
+//     value comes first the unfused form stores the first pair, this kernel the second (tests/test_stem_cpu.py,
+//     tests/test_stem_gpu.py: equal-sum pairs).  The next convolution then differs by one dropped lo*lo-sized product.
 // Conv pixels outside the map (the pooling's padding ring, partial patches at the bottom / right edge) read clamped
 // image rows / pieces and are zeroed before pooling (every pooling window holds a real pixel and ReLU >= 0).
 #include "hn_common.h"

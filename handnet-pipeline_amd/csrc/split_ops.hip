@@ -6,8 +6,11 @@
 //                         first: this is the GroupNorm(32,256)+ReLU of the FCOS towers
 //                         (fcos_utils/fcos.py:232-239,352-359) applied between two convs
 //   hn_unsplit_f32        S32 -> fp32 (hi + lo is exact in fp32)
-//   hn_maxpool3x3s2_s32   3x3/2 max pooling on S32 (the max element's (hi, lo) pair is copied,
-//                         so pooling commutes with the split exactly)
+//   hn_maxpool3x3s2_s32   3x3/2 max pooling on S32 (the (hi, lo) pair of the window's first element with the
+//                         largest hi + lo is copied, so pooling commutes with the split exactly in VALUE;
+//                         two values either side of an fp16 rounding midpoint can have different pairs with
+//                         equal sums, and then the copied pair need not be the split of the fp32 maximum:
+//                         conv_stem_direct.hip)
 #include "affine_split_body.h"   // the per-lane arithmetic, shared with the pass carried by a tower convolution
 
 #include <float.h>

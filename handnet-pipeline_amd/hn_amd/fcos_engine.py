@@ -125,7 +125,7 @@ class FCOSEngine:
         fm = engine_forms(forms)
         self.head_streams = fm["head_streams"] if head_streams is None else head_streams
         self.group_towers = fm["group_convs"]
-        self.fuse_stem_pool = fm["fuse_stem_pool"]   # (results are bit-identical either way)
+        self.fuse_stem_pool = fm["fuse_stem_pool"]   # (the pooled values are bit-identical either way: ops.conv_stem_pool_split)
         self.fuse_last_gn = fm["fuse_last_gn"]       # bit-identical
         self.thin_outputs = fm["thin_outputs"] and self.cls_out.cout <= 16   # (tap form bit-identical, P form to fp32 rounding)
         # conv1 of a downsampling block together with its 1x1 downsample (ops.conv2d_nhwc_multi)

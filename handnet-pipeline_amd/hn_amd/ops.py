@@ -1092,7 +1092,10 @@ def conv_stem_split(x16, w16, bias, cout, r=7, stride=2, relu=True, out_split=Tr
 
 def conv_stem_pool_split(x16, w16, bias, cout=64, r=7, stride=2, algo_cin=3, out=None):
     """Stem conv + ReLU + 3x3/2 max pooling in ONE kernel (hn_conv_stem_pool_f16x3): stem image -> pooled S32 map
-    [N, (oh+1)//2, (ow+1)//2, cout/32, 2, 32]; bit-identical to conv_stem_split(...) followed by maxpool3x3s2_nhwc."""
+    [N, (oh+1)//2, (ow+1)//2, cout/32, 2, 32].  from_split of it is bit-identical to from_split of conv_stem_split(...) followed
+    by maxpool3x3s2_nhwc; the planes are identical too, except where a pooling window holds two fp32 values either side of an
+    fp16 rounding midpoint whose (hi, lo) pairs recombine to the same sum: this kernel splits the maximum, the unfused pooling
+    copies the first such pair (tests/test_stem_gpu.py, equal-sum pairs)."""
     lib = _lib.load()
     pad = r // 2
     if x16.dim() != 5 or x16.shape[0] != 2 or x16.shape[4] != 4 or x16.dtype != torch.float16 or not x16.is_cuda \
