@@ -23,7 +23,14 @@ def crop_box(box, width, height, percent=0.4):
 
 
 def crop_depth(depth_img, box, size=176):
-    """handnet_pipeline.py:101: inclusive slice + nearest resize.  depth_img [C,H,W]."""
+    """handnet_pipeline.py:101: inclusive slice + nearest resize.  depth_img [C,H,W].
+
+    Deviation from the reference: a stop that is not above its start is an empty slice, a NEGATIVE stop included.  (Python
+    counts a negative stop from the far end, so a detection wholly above or left of the frame, or an inverted one -- padded
+    x2 or y2 below zero -- would be cut as almost the whole frame.)
+    """
+    if int(box[3]) + 1 <= int(box[1]) or int(box[2]) + 1 <= int(box[0]):
+        return None
     sl = depth_img[:, box[1]:box[3] + 1, box[0]:box[2] + 1]
     if sl.shape[1] == 0 or sl.shape[2] == 0:
         return None
