@@ -91,6 +91,10 @@ class A2JModel(EngineOwner):
           paras  None, one camera (fx, fy, cx, cy), or [K,4] float32 per sample (a2jdataset.py:279)
         -> (crop uvd [K,J,3], image uvd [K,J,3], camera xyz in mm [K,J,3] or None): CPU tensors from ONE device -> host copy,
         under the same range contract as forward()."""
+        return self._xyz_to_host(*self._forward_xyz_device(x, box, paras))
+
+    def _forward_xyz_device(self, x, box, paras=None):
+        """forward_xyz up to its copy: ((crop uvd, image uvd, camera xyz or None) on the device, the range words or None, x)."""
         eng = self.engine()
         dev = eng.device
         x = x.to(dev)
@@ -107,7 +111,13 @@ class A2JModel(EngineOwner):
                 conv["paras"] = [float(v) for v in p.reshape(4)]
             else:
                 conv["sample_paras"] = p.reshape(k, 4).to(dev).contiguous()
-        (kp, img, xyz), flags = eng.forward_flags(x, convert=conv)
+        outs, flags = eng.forward_flags(x, convert=conv)
+        return outs, flags, x
+
+    @staticmethod
+    def _xyz_to_host(outs, flags, x):
+        """forward_xyz's one device -> host copy and its range contract."""
+        kp, img, xyz = outs
         parts = [t.contiguous().reshape(-1).view(torch.int32) for t in (kp, img) + ((xyz,) if xyz is not None else ())]
         if flags is not None:
             parts.append(flags[:3])
@@ -192,6 +202,25 @@ class A2JModelLightning(EngineOwner):
         """Lightning's self.log, reduced to what the evaluation loop needs: values per name, in call order (`logged`)."""
         self.__dict__.setdefault("logged", {}).setdefault(name, []).append(float(value))
 
+    _hpe_metrics = None    # None: off (the default).  False: on, not yet built.  Else the module's hn_amd.metrics.HPEMetrics.
+    hpe_results = None     # the last epoch's results dict (device_metrics(True) only)
+
+    def device_metrics(self, enable: bool = True):
+        """Opt in to (or out of) the evaluator's numbers computed on the device (hn_amd.metrics.HPEMetrics):
+        `test_step` then also feeds its prediction and its converted ground truth, both still on the device, to an accumulator,
+        and `test_epoch_end` returns MPJPE and AUC for the absolute, root-relative and Procrustes-aligned error (and the PCK
+        curves) instead of asking for the DexYCB toolkit.  Off, every call does what it does without this method.
+        Deviation from the toolkit: its ground truth is its own annotation file's joint_3d * 1000; this path uses the loop's
+        converted ground truth, the values `test_rmse` is computed from."""
+        self._hpe_metrics = (self._hpe_metrics or False) if enable else None
+        return self
+
+    def _hpe(self, device, joints):
+        if self._hpe_metrics is False:
+            from hn_amd.metrics import HPEMetrics
+            self._hpe_metrics = HPEMetrics(device, joints=joints)
+        return self._hpe_metrics
+
     def test_step(self, batch, batch_idx):
         """a2j/a2j.py:333-359, the evaluation caller of the path: forward -> convert_joints (prediction AND ground truth, the
         dataset's float32 box and the sample's intrinsics) -> RMSE in mm -> one text line per sample for the HPE evaluator.
@@ -203,12 +232,16 @@ class A2JModelLightning(EngineOwner):
         im, jt_uvd_gt, dexycb_id, _color_im, box, paras, combined_im = batch
         x = combined_im if self.rgbd else im
         k = x.shape[0]
-        _kp, _img, pred_xyz = self.a2j.forward_xyz(x, torch.as_tensor(box, dtype=torch.float32), torch.as_tensor(paras, dtype=torch.float32).reshape(k, 4))
+        on_device = self.a2j._forward_xyz_device(x, torch.as_tensor(box, dtype=torch.float32), torch.as_tensor(paras, dtype=torch.float32).reshape(k, 4))
+        _kp, _img, pred_xyz = self.a2j._xyz_to_host(*on_device)
         dev = self.a2j.engine().device
         gt = torch.as_tensor(jt_uvd_gt, dtype=torch.float32).reshape(k, -1, 3).to(dev).contiguous()
         _, gt_xyz = ops.convert_joints_samples(gt, torch.as_tensor(box, dtype=torch.float32).reshape(k, 4).to(dev).contiguous(),
                                                torch.as_tensor(paras, dtype=torch.float32).reshape(k, 4).to(dev).contiguous(),
                                                want_image=False)
+        if self._hpe_metrics is not None:
+            # device_metrics(True): the same two tensors, still on the device, into the evaluator's tables (one launch, no copy)
+            self._hpe(dev, gt.shape[1]).update(on_device[0][2].contiguous(), gt_xyz)
         jt_xyz_pred, jt_xyz_gt = pred_xyz.numpy().reshape(-1, 3), gt_xyz.cpu().numpy().reshape(-1, 3)
         rmse = np.sqrt(np.mean(np.square(jt_xyz_gt - jt_xyz_pred)))
         self.log("test_rmse", rmse)
@@ -227,7 +260,19 @@ class A2JModelLightning(EngineOwner):
 
     def test_epoch_end(self, outputs):
         """a2j/a2j.py:361-363: hands the epoch's file to dex_ycb_toolkit's HPEEvaluator (not part of this image: raises a clear
-        ImportError when the toolkit is absent; the file `test_step` wrote is complete either way)."""
+        ImportError when the toolkit is absent; the file `test_step` wrote is complete either way).
+        After device_metrics(True): no toolkit -- the evaluator's `results` dict (absolute / root-relative / procrustes -> mpjpe,
+        auc; plus pck, thresholds, fed, skipped) from the tables `test_step` accumulated on the device, kept in `self.hpe_results`,
+        logged as six scalars and returned; the accumulator then starts the next epoch from zero."""
+        if self._hpe_metrics is not None:
+            from hn_amd.metrics import NAMES
+            results = self._hpe(self.a2j.engine().device, self.a2j.num_classes).compute()
+            self.hpe_results = results
+            for name in NAMES:
+                for key in ("mpjpe", "auc"):
+                    self.log(f"test_{name}_{key}", results[name][key])
+            self._hpe_metrics.reset()
+            return results
         try:
             from dex_ycb_toolkit.hpe_eval import HPEEvaluator
         except ImportError as e:

@@ -257,6 +257,8 @@ SIGNATURES = {
     "hn_mesh_fit_iters_scratch_bytes": (C.c_int64, [C.c_int] * 8),
     "hn_mesh_fit_iters_f32": (C.c_int, [VP] * 3 + [C.c_int64] + [VP] * 7 + [C.c_int] * 9 + [C.c_float, C.c_int] + [C.c_double] * 3
                               + [VP, C.c_int64, VP, C.c_int64] + [VP] * 7),
+    # the evaluation loop's MPJPE / PCK / AUC tables, accumulated as integers (a new function under ABI 36)
+    "hn_hpe_accumulate_f32": (C.c_int, [VP] * 3 + [C.c_int, C.c_int, VP, C.c_int] + [VP] * 6),
 }
 
 _lock = threading.Lock()

@@ -1602,6 +1602,66 @@ def convert_joints_samples(kp, box_f32, sample_paras=None, valid=None, crop=176,
     return img, xyz
 
 
+HPE_MAX_JOINTS = 64        # one lane per joint
+HPE_MAX_STEPS = 1024       # thresholds of a PCK curve
+HPE_WAVES_PER_GROUP = 4    # samples per workgroup of hn_hpe_accumulate_f32 (csrc/hpe_metrics.hip kWaves)
+
+HPEState = collections.namedtuple("HPEState", "hist sum n flat")
+# hist int64 [3,J,T+1], sum int64 [3,J], n int64 [2]: views of `flat`, ONE int64 buffer (a single copy moves the whole state)
+HPEBatch = collections.namedtuple("HPEBatch", "state dist aligned")
+
+
+def hpe_state(joints, steps, device) -> HPEState:
+    """A zeroed state of the evaluator's tables for `joints` joints and `steps` thresholds."""
+    joints, steps = int(joints), int(steps)
+    if not 1 <= joints <= HPE_MAX_JOINTS or not 1 <= steps <= HPE_MAX_STEPS:
+        raise ValueError(f"joints 1..{HPE_MAX_JOINTS} and thresholds 1..{HPE_MAX_STEPS}, got {joints} and {steps}")
+    a, b = 3 * joints * (steps + 1), 3 * joints
+    flat = torch.zeros((a + b + 2,), device=device, dtype=torch.int64)
+    return HPEState(flat[:a].view(3, joints, steps + 1), flat[a:a + b].view(3, joints), flat[a + b:], flat)
+
+
+def hpe_accumulate(pred, gt, thresholds, state=None, valid=None, want_dist=False, want_aligned=False) -> HPEBatch:
+    """One batch into the evaluator's tables (hn_hpe_accumulate_f32: one launch, no synchronisation; tests/hpe_ref.py is the rule
+    and every output equals it bit for bit).  pred, gt fp32 [S,J,3] camera millimetres, J <= 64; thresholds fp64 [T] non-decreasing,
+    T <= 1024; valid int32 [S] (0: the sample is skipped) or None, all on one device.  state: an HPEState to add to (hpe_state), or
+    None for a new zeroed one.  Returns HPEBatch(state, dist fp64 [S,3,J] or None, aligned fp64 [S,J,3] or None): the absolute,
+    root-relative and Procrustes-aligned distances and align_w_scale(gt, pred); rows of skipped samples are NaN."""
+    _req(pred, name="pred"); _req(gt, name="gt"); _req(thresholds, torch.float64, "thresholds")
+    if pred.dim() != 3 or pred.shape[2] != 3 or tuple(gt.shape) != tuple(pred.shape):
+        raise ValueError(f"pred and gt must be fp32 [S,J,3] of one shape, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    s, j, _ = pred.shape
+    if not 1 <= j <= HPE_MAX_JOINTS:
+        raise ValueError(f"{j} joints: 1..{HPE_MAX_JOINTS} (one lane per joint)")
+    if thresholds.dim() != 1 or not 1 <= thresholds.shape[0] <= HPE_MAX_STEPS:
+        raise ValueError(f"thresholds must be fp64 [T], T in 1..{HPE_MAX_STEPS}, got {tuple(thresholds.shape)}")
+    t = thresholds.shape[0]
+    if valid is not None and _req(valid, torch.int32, "valid").numel() != s:
+        raise ValueError(f"valid must hold one value per sample ({s}), got {valid.numel()}")
+    if state is None:
+        state = hpe_state(j, t, pred.device)
+    else:
+        for name, part, shape in (("hist", state.hist, (3, j, t + 1)), ("sum", state.sum, (3, j)), ("n", state.n, (2,))):
+            if tuple(_req(part, torch.int64, f"state.{name}").shape) != shape:
+                raise ValueError(f"state.{name}: expected int64 {list(shape)}, got {tuple(part.shape)}")
+    for name, other in (("gt", gt), ("thresholds", thresholds), ("valid", valid), ("state", state.hist)):
+        if other is not None and other.device != pred.device:
+            raise ValueError(f"{name} lives on {other.device}, pred on {pred.device}")
+    dist = torch.empty((s, 3, j), device=pred.device, dtype=torch.float64) if want_dist else None
+    aligned = torch.empty((s, j, 3), device=pred.device, dtype=torch.float64) if want_aligned else None
+    check(_lib.load().hn_hpe_accumulate_f32(ptr(pred), ptr(gt), ptr(valid), s, j, ptr(thresholds), t, ptr(state.hist), ptr(state.sum),
+                                            ptr(state.n), ptr(dist), ptr(aligned), _stream()), "hn_hpe_accumulate_f32")
+    return HPEBatch(state, dist, aligned)
+
+
+def procrustes_align(gt, pred):
+    """align_w_scale (freihand/eval.py:72-95) for a batch on the device: gt, pred fp32 [S,J,3] -> fp64 [S,J,3], the prediction
+    moved, turned (reflections allowed, as scipy's orthogonal_procrustes leaves them) and scaled onto the ground truth; rows of
+    samples with a non-finite value or one of 2^20 and beyond are NaN.  The rule's own kernel (hpe_accumulate's `aligned`)."""
+    _req(pred, name="pred")
+    return hpe_accumulate(pred, gt, torch.zeros((1,), device=pred.device, dtype=torch.float64), want_aligned=True).aligned
+
+
 def pack_records(kp, crop_box, has_hand, rows, rec_bytes, out=None, extras=()):
     """One step's per-frame results -> [rows, rec_bytes] uint8 records (rows >= frames: shard padding is zero rows).
     extras: up to two more [N,J,3] fp32 fields behind the keypoints (image uvd, camera xyz: the wide record)."""

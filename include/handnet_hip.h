@@ -40,7 +40,7 @@ extern "C" {
  * hn_mesh_render_cams_u8 and hn_mesh_render_cams_occluded_u8, the rig frame's hn_rig_fuse_f32, the hand cloud's
  * hn_hand_cloud_f32 and hn_hand_cloud_scratch_bytes, the mesh fit's hn_mesh_fit_f32 and hn_mesh_fit_scratch_bytes, and the
  * iterated fit's hn_mesh_geometry_f32, hn_mesh_fit_iters_f32 and hn_mesh_fit_iters_scratch_bytes, and the carried apply pass's
- * hn_conv2d_nhwc_f16x3_grouped_carry, hn_conv2d_f16x3_grouped_carry_applies and hn_affine_split_f32_levels_streams). */
+ * hn_conv2d_nhwc_f16x3_grouped_carry, hn_conv2d_f16x3_grouped_carry_applies and hn_affine_split_f32_levels_streams, and the evaluator's hn_hpe_accumulate_f32). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -954,6 +954,24 @@ int hn_mesh_fit_iters_f32(const float* mesh_depth, const uint8_t* silhouette, co
                           int stride, float band, int min_points, double damp, double max_shift2, double tan2_half_angle,
                           void* scratch, int64_t scratch_bytes, void* work, int64_t work_bytes, float* out_mesh, float* out_xyz,
                           float* out_rt, int32_t* out_count, int64_t* out_cost, int64_t* out_trace, void* stream);
+/* The hand-pose evaluator's tables for the evaluation loop (tests/hpe_ref.py is the rule in numpy fp64, and
+ * every output equals it bit for bit): what HPEEvaluator.evaluate feeds its three EvalUtil accumulators -- the absolute, the
+ * root-relative and the Procrustes-aligned (align_w_scale, reflections allowed) distance of every joint -- added into an integer
+ * state.  pred, gt DEVICE fp32 [s][j][3] in millimetres; valid DEVICE int32 [s] or NULL; thresholds DEVICE fp64 [t], non-decreasing.
+ * A sample is fed when valid != 0 (or NULL) and all its values are finite and below 2^20 in magnitude; any other sample is counted
+ * as skipped and adds nothing else.
+ *   hist [3][j][t+1]  int64 += 1 at bin #{i : thresholds[i] < d} per alignment (ab, rr, pa), joint and fed sample
+ *   sum  [3][j]       int64 += rint(d * 2^20), ties to even
+ *   n    [2]          int64 += (fed, skipped)
+ *   dist_out [s][3][j], aligned_out [s][j][3]   fp64, or NULL (not written): the distances and align_w_scale(gt, pred); every
+ *                     row is written, NaN for a skipped sample
+ * The state is ADDED to (the caller zeroes it once); integer adds only, so any order of samples and any split into calls gives
+ * the same bytes.  One launch on `stream`, no allocation, no synchronisation.  Refused before the launch: s < 0, j outside 1..64
+ * (one lane per joint), t outside 1..1024, a null required pointer, a misaligned one; s == 0 is a successful no-op.  Added under
+ * ABI 36: a new function only. */
+int hn_hpe_accumulate_f32(const float* pred, const float* gt, const int32_t* valid /* or NULL */, int s, int j,
+                          const double* thresholds, int t, int64_t* hist, int64_t* sum, int64_t* n, double* dist_out /* or NULL */,
+                          double* aligned_out /* or NULL */, void* stream);
 /* A Linear layer on 1..4 rows as a matrix-vector product on the vector ALU (PoseNet at the live caller's batch, posenet.py:24-41,
  * 78-88: 67 MB of filter bank per 17 M MACs): y[m][:] = act(W (pre(x[m])) + bias (+ residual[m])), pre = relu(x * scale + shift)
  * when scale / shift ([k_real] fp32: the pre-activation BatchNorm) are given.  x fp32 [batch][x_stride] (k_real columns used), w16 =
