@@ -54,6 +54,53 @@ class FCOS(EngineOwner):
                                       image_std=self.image_std)
         return self._engine
 
+    _detection_ap = None   # the module's hn_amd.metrics.DetectionAP once device_metrics() was called
+
+    def device_metrics(self, annotations, image_index, **options):
+        """Opt in to the evaluation's numbers computed on the device (hn_amd.metrics.DetectionAP): the six
+        AP tables `evaluate()` of trainval_net_fcos.py gets from the VOC text files and voc_eval.py.  annotations: the reference's
+        annotation cache dict (image name -> records) or its flattened form; image_index: the image names, position = the id a
+        batch carries; options: max_dets, hand_label, object_label, score_min, ovthresh.  Returns the accumulator and keeps it
+        for `eval_step` / `eval_results`.  `forward` is untouched."""
+        if not self.ext:
+            raise RuntimeError("the evaluation needs the ext heads (contacts, dxdymags): FCOS(ext=True)")
+        from hn_amd.metrics import DetectionAP
+        self._detection_ap = DetectionAP(self._require_gpu(), annotations, image_index, **options)
+        return self._detection_ap
+
+    def _require_metrics(self):
+        if self._detection_ap is None:
+            raise RuntimeError("call device_metrics(annotations, image_index) before eval_step / eval_results")
+        return self._detection_ap
+
+    def eval_step(self, images: List[torch.Tensor], image_ids) -> None:
+        """One batch of the evaluation loop (trainval_net_fcos.py:121-169) without its host side: the detector, then ONE more
+        launch that files the batch's records under their image ids.  No dicts are built, no count is copied to the host and
+        nothing waits.  image_ids: int32 [N] on the device (anything else is converted and uploaded)."""
+        ap = self._require_metrics()
+        if self.training:
+            raise NotImplementedError("training (fcos.py:543-570 losses) is outside the inference hot path")
+        det, _, contacts, dxdymags = self.engine().detect_ext(self._batch(images))
+        if not (torch.is_tensor(image_ids) and image_ids.is_cuda and image_ids.dtype == torch.int32):
+            image_ids = torch.as_tensor(image_ids).to(dtype=torch.int32).reshape(-1).to(det.scores.device)
+        ap.update(det, contacts, dxdymags, image_ids.contiguous())
+
+    def eval_results(self, use_07_metric: bool = False):
+        """The epoch's end: {name: {'ap', 'rec', 'prec'}} for targetobject, hand and hand + handstate / handside / objectbbox /
+        all, plus mean_ap, npos and fed (one device -> host copy); the accumulator then starts the next epoch from zero."""
+        ap = self._require_metrics()
+        results = ap.compute(use_07_metric)
+        ap.reset()
+        return results
+
+    @staticmethod
+    def _batch(images):
+        if len({tuple(i.shape) for i in images}) != 1:
+            # torchvision batch_images (fcos.py:702-709): every image is resized on its own, padded to the common
+            # canvas, and its boxes are scaled back by its own ratios
+            return [i.float() for i in images]
+        return torch.stack([i.float() for i in images])
+
     def forward(self, images: List[torch.Tensor], targets=None) -> List[Dict[str, torch.Tensor]]:
         if self.training or targets is not None:
             raise NotImplementedError("training (fcos.py:543-570 losses) is outside the inference hot path")

@@ -259,6 +259,9 @@ SIGNATURES = {
                               + [VP, C.c_int64, VP, C.c_int64] + [VP] * 7),
     # the evaluation loop's MPJPE / PCK / AUC tables, accumulated as integers (a new function under ABI 36)
     "hn_hpe_accumulate_f32": (C.c_int, [VP] * 3 + [C.c_int, C.c_int, VP, C.c_int] + [VP] * 6),
+    # the detector evaluation's record tables (hand and object AP), also a new function under ABI 36
+    "hn_det_ap_accumulate_f32": (C.c_int, [VP] * 8 + [C.c_int, C.c_int] + [VP] * 4 + [C.c_int] + [VP] * 3 + [C.c_int] * 4
+                                 + [C.c_float, C.c_double] + [VP] * 4 + [C.c_int, VP]),
 }
 
 _lock = threading.Lock()

@@ -38,12 +38,13 @@ ARCH = "gfx950"
 # without the SLP vectoriser too: it packed the rigid motion's products into v_pk_mul_f32 with op_sel (the build refused it).
 # mesh_refit.hip: mesh_fit.hip's flags, for the fp64 composition of the iterations' motions (tests/refit_ref.py).
 # hpe_metrics.hip: the same for the evaluator's fp64 distances, Procrustes alignment and Jacobi SVD (tests/hpe_ref.py).
+# det_ap.hip: the same for the detector evaluation's fp64 overlaps, association distances and file round trip (tests/ap_ref.py).
 EXTRA_FLAGS = {"fcos_post.hip": ["-ffp-contract=off", "-fno-slp-vectorize"], "graph_ops.hip": ["-fno-slp-vectorize"],
                "mesh_raster.hip": ["-ffp-contract=off"], "label_draw.hip": ["-ffp-contract=off"],
                "rig_ops.hip": ["-ffp-contract=off"], "hand_cloud.hip": ["-ffp-contract=off"],
                "mesh_fit.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
                "mesh_refit.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
-               "hpe_metrics.hip": ["-ffp-contract=off"]}
+               "hpe_metrics.hip": ["-ffp-contract=off"], "det_ap.hip": ["-ffp-contract=off"]}
 
 # Kernels that request operands with `asm volatile` loads / LDS-DMA and retire them with hand-counted s_waitcnt: the
 # compiler cannot see that such a register is still in flight, so a SPILL of it stores garbage (profiles/NOTEBOOK.md, round

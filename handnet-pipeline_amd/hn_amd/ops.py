@@ -1662,6 +1662,106 @@ def procrustes_align(gt, pred):
     return hpe_accumulate(pred, gt, torch.zeros((1,), device=pred.device, dtype=torch.float64), want_aligned=True).aligned
 
 
+DET_AP_MAX_GT = 64                 # ground-truth boxes per image and class: one lane each (csrc/det_ap.hip)
+DET_AP_MAX_RECORDS = 1 << 27       # images * max_dets of one record table: 512 MiB of int32, and the state holds two
+DET_AP_SCORE_BITS, DET_AP_TP_SHIFT, DET_AP_FP_SHIFT, DET_AP_VALID = 10, 10, 15, 1 << 20
+
+DetAPTable = collections.namedtuple("DetAPTable", "hand_off hand_box hand_meta hand_obj obj_off obj_box obj_diff num_images "
+                                                  "npos_hand npos_obj")
+DetAPState = collections.namedtuple("DetAPState", "hand obj fed overflow flat")
+# hand, obj int32 [I,max_dets], fed int32 [I], overflow int32 [1]: views of `flat`, ONE int32 buffer
+
+
+def det_ap_table(hand_off, hand_box, hand_meta, hand_obj, obj_off, obj_box, obj_diff, device) -> DetAPTable:
+    """The annotation cache, flattened, on the device (uploaded once).  Host arrays: hand_off int [I+1]
+    into hand_box int [H,4], hand_meta int [H,4] (difficult, handstate, leftright, objectbbox present), hand_obj float64 [H,4];
+    obj_off int [I+1] into obj_box int [O,4], obj_diff int [O].  Refused: offsets that do not partition their rows, more than
+    64 boxes of a class in one image."""
+    hand_off, obj_off = (np.asarray(x, np.int64).reshape(-1) for x in (hand_off, obj_off))
+    hand_box, hand_meta, obj_box = (np.asarray(x, np.int64).reshape(-1, 4) for x in (hand_box, hand_meta, obj_box))
+    hand_obj, obj_diff = np.asarray(hand_obj, np.float64).reshape(-1, 4), np.asarray(obj_diff, np.int64).reshape(-1)
+    num_images = hand_off.shape[0] - 1
+    if num_images < 1 or obj_off.shape[0] != num_images + 1:
+        raise ValueError(f"hand_off and obj_off must hold images + 1 >= 2 offsets, got {hand_off.shape[0]} and {obj_off.shape[0]}")
+    for name, off, rows in (("hand", hand_off, hand_box.shape[0]), ("obj", obj_off, obj_box.shape[0])):
+        per = np.diff(off)
+        if off[0] != 0 or off[-1] != rows or (per < 0).any():
+            raise ValueError(f"{name}_off must rise from 0 to the {rows} rows of {name}_box")
+        if (per > DET_AP_MAX_GT).any():
+            raise ValueError(f"image {int(np.argmax(per))} has {int(per.max())} {name} boxes: at most {DET_AP_MAX_GT} (one lane each)")
+    if hand_meta.shape[0] != hand_box.shape[0] or hand_obj.shape[0] != hand_box.shape[0] or obj_diff.shape[0] != obj_box.shape[0]:
+        raise ValueError("hand_meta, hand_obj and obj_diff must hold one row per box")
+    if max(np.abs(hand_box).max(initial=0), np.abs(obj_box).max(initial=0), np.abs(hand_meta).max(initial=0)) >= 1 << 24:
+        raise ValueError("box coordinates and hand fields must be integers below 2^24")
+    dev = torch.device(device)
+    up = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x.astype(dt))).to(dev)
+    return DetAPTable(up(hand_off, np.int32), up(hand_box, np.int32), up(hand_meta, np.int32), up(hand_obj, np.float64),
+                      up(obj_off, np.int32), up(obj_box, np.int32), up(obj_diff, np.int32), num_images,
+                      int((hand_meta[:, 0] == 0).sum()), int((obj_diff == 0).sum()))
+
+
+def det_ap_state(num_images, max_dets, device) -> DetAPState:
+    """A zeroed state of the detector evaluation: one record word per (image, rank) and class, the per-image feed counts and the
+    overflow counter.  num_images * max_dets is bounded by DET_AP_MAX_RECORDS (2^27 words: 512 MiB per table)."""
+    num_images, max_dets = int(num_images), int(max_dets)
+    if num_images < 1 or max_dets < 1 or num_images * max_dets > DET_AP_MAX_RECORDS:
+        raise ValueError(f"num_images >= 1, max_dets >= 1 and num_images * max_dets <= {DET_AP_MAX_RECORDS}, got {num_images} and {max_dets}")
+    a = num_images * max_dets
+    flat = torch.zeros((2 * a + num_images + 1,), device=device, dtype=torch.int32)
+    return DetAPState(flat[:a].view(num_images, max_dets), flat[a:2 * a].view(num_images, max_dets), flat[2 * a:2 * a + num_images],
+                      flat[2 * a + num_images:], flat)
+
+
+def det_ap_accumulate(det, contacts, dxdymags, image_ids, table: DetAPTable, state: DetAPState | None = None, max_dets=100,
+                      hand_label=2, object_label=1, score_min=0.1, ovthresh=0.5) -> DetAPState:
+    """One batch of detections into the evaluation's record tables (hn_det_ap_accumulate_f32: one launch, no synchronisation;
+    tests/ap_ref.py is the rule and the state equals it byte for byte).  det: the detector's `Detections` (boxes fp32 [N,cap,4],
+    scores fp32 [N,cap], labels / sides int32 [N,cap], count int32 [N]); contacts int32 [N,cap], dxdymags fp32 [N,cap,3] (ext
+    heads); image_ids int32 [N]: the row of `table` each image is matched against -- an id outside it writes nothing and counts
+    into `overflow`, on the device.  state: a DetAPState to write into (det_ap_state), or None for a new one of `max_dets`."""
+    _req(det.boxes, name="det.boxes"); _req(det.scores, name="det.scores")
+    if det.scores.dim() != 2 or tuple(det.boxes.shape) != tuple(det.scores.shape) + (4,):
+        raise ValueError(f"det.scores must be fp32 [N,cap] and det.boxes [N,cap,4], got {tuple(det.scores.shape)} and {tuple(det.boxes.shape)}")
+    n, cap = det.scores.shape
+    for name, t, shape in (("det.labels", det.labels, (n, cap)), ("det.sides", det.sides, (n, cap)), ("det.count", det.count, (n,)),
+                           ("contacts", contacts, (n, cap)), ("image_ids", image_ids, (n,))):
+        if tuple(_req(t, torch.int32, name).shape) != shape:
+            raise ValueError(f"{name}: expected int32 {list(shape)}, got {tuple(t.shape)}")
+    if tuple(_req(dxdymags, name="dxdymags").shape) != (n, cap, 3):
+        raise ValueError(f"dxdymags: expected fp32 {[n, cap, 3]}, got {tuple(dxdymags.shape)}")
+    if not isinstance(table, DetAPTable):
+        raise TypeError("table must come from det_ap_table")
+    if int(hand_label) == int(object_label):
+        raise ValueError(f"hand_label and object_label are both {hand_label}")
+    if not 0.0 <= float(score_min) < 1.0 or math.isnan(float(ovthresh)):
+        raise ValueError(f"score_min in [0, 1) and a threshold that is a number, got {score_min} and {ovthresh}")
+    if n * cap > 1 << 28:
+        raise ValueError(f"{n} x {cap} detections: at most 2^28 a batch")
+    images = table.num_images
+    if state is None:
+        state = det_ap_state(images, max_dets, det.scores.device)
+    else:
+        if state.hand.dim() != 2 or state.hand.shape[0] != images:
+            raise ValueError(f"state.hand: expected int32 [{images}, max_dets], got {tuple(state.hand.shape)}")
+        m = state.hand.shape[1]
+        for name, part, shape in (("hand", state.hand, (images, m)), ("obj", state.obj, (images, m)), ("fed", state.fed, (images,)),
+                                  ("overflow", state.overflow, (1,))):
+            if tuple(_req(part, torch.int32, f"state.{name}").shape) != shape:
+                raise ValueError(f"state.{name}: expected int32 {list(shape)}, got {tuple(part.shape)}")
+    for name, other in (("det.boxes", det.boxes), ("det.labels", det.labels), ("det.sides", det.sides), ("det.count", det.count),
+                        ("contacts", contacts), ("dxdymags", dxdymags), ("image_ids", image_ids), ("table", table.hand_off),
+                        ("state", state.hand)):
+        if other.device != det.scores.device:
+            raise ValueError(f"{name} lives on {other.device}, det.scores on {det.scores.device}")
+    check(_lib.load().hn_det_ap_accumulate_f32(
+        ptr(det.boxes), ptr(det.scores), ptr(det.labels), ptr(det.sides), ptr(det.count), ptr(contacts), ptr(dxdymags), ptr(image_ids),
+        n, cap, ptr(table.hand_off), ptr(table.hand_box), ptr(table.hand_meta), ptr(table.hand_obj), table.hand_box.shape[0],
+        ptr(table.obj_off), ptr(table.obj_box), ptr(table.obj_diff), table.obj_box.shape[0], images, int(hand_label),
+        int(object_label), float(score_min), float(ovthresh), ptr(state.hand), ptr(state.obj), ptr(state.fed), ptr(state.overflow),
+        state.hand.shape[1], _stream()), "hn_det_ap_accumulate_f32")
+    return state
+
+
 def pack_records(kp, crop_box, has_hand, rows, rec_bytes, out=None, extras=()):
     """One step's per-frame results -> [rows, rec_bytes] uint8 records (rows >= frames: shard padding is zero rows).
     extras: up to two more [N,J,3] fp32 fields behind the keypoints (image uvd, camera xyz: the wide record)."""

@@ -40,7 +40,8 @@ extern "C" {
  * hn_mesh_render_cams_u8 and hn_mesh_render_cams_occluded_u8, the rig frame's hn_rig_fuse_f32, the hand cloud's
  * hn_hand_cloud_f32 and hn_hand_cloud_scratch_bytes, the mesh fit's hn_mesh_fit_f32 and hn_mesh_fit_scratch_bytes, and the
  * iterated fit's hn_mesh_geometry_f32, hn_mesh_fit_iters_f32 and hn_mesh_fit_iters_scratch_bytes, and the carried apply pass's
- * hn_conv2d_nhwc_f16x3_grouped_carry, hn_conv2d_f16x3_grouped_carry_applies and hn_affine_split_f32_levels_streams, and the evaluator's hn_hpe_accumulate_f32). */
+ * hn_conv2d_nhwc_f16x3_grouped_carry, hn_conv2d_f16x3_grouped_carry_applies and hn_affine_split_f32_levels_streams, the evaluator's hn_hpe_accumulate_f32, and the
+ * detector evaluation's hn_det_ap_accumulate_f32). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -972,6 +973,31 @@ int hn_mesh_fit_iters_f32(const float* mesh_depth, const uint8_t* silhouette, co
 int hn_hpe_accumulate_f32(const float* pred, const float* gt, const int32_t* valid /* or NULL */, int s, int j,
                           const double* thresholds, int t, int64_t* hist, int64_t* sum, int64_t* n, double* dist_out /* or NULL */,
                           double* aligned_out /* or NULL */, void* stream);
+/* The detector evaluation's per-image part (tests/ap_ref.py is the rule in numpy fp64, and every output
+ * equals it byte for byte): the records trainval_net_fcos.py:132-169 selects from a batch of detections (score > score_min and
+ * label == hand_label / object_label, in the detector's order; an image without hand records keeps no object records), passed
+ * through the VOC text files' rounding (pascal_voc.py:339-343), associated (voc_eval.py:662-704) and matched against the image's
+ * ground truth (voc_eval.py:191-225,386-496) for the object class and the five hand tables.
+ *   the batch, DEVICE: boxes fp32 [n][cap][4], scores fp32 [n][cap], labels / sides / contacts int32 [n][cap], dxdymags fp32
+ *   [n][cap][3], count int32 [n] (rows at or beyond it are not read), image_ids int32 [n]
+ *   the ground truth, DEVICE, indexed by image id: hand_off int32 [images+1] into hand_box int32 [hand_total][4], hand_meta int32
+ *   [hand_total][4] (difficult, handstate, leftright, objectbbox present) and hand_obj fp64 [hand_total][4]; obj_off int32
+ *   [images+1] into obj_box int32 [obj_total][4] and obj_diff int32 [obj_total].  At most 64 boxes per image and class: an image
+ *   with more (or with offsets outside the table) is matched as if it had none -- hn_amd.ops.det_ap_table refuses such a table.
+ *   the state: hand, obj int32 [images][max_dets], one word per record at [image id][rank]: bits 0..9 the score in thousandths,
+ *   bits 10..14 TP and 15..19 FP of the tables '', handstate, handside, objectbbox, all (obj: bits 10 and 15), bit 20 valid;
+ *   fed int32 [images] += 1 per image of the batch; overflow int32 [1] += the records that do not fit (rank >= max_dets, or a
+ *   score above 1) + the image ids outside 0..images-1 (nothing else is written for those).
+ * Records are plain stores, the counts integer atomic adds.  One launch on `stream`, no allocation, no synchronisation.  Refused
+ * before the launch: negative sizes, images * max_dets above 2^27, n * cap above 2^28, equal labels, score_min outside [0, 1),
+ * a null required pointer, a misaligned one; n == 0 is a successful no-op.  Added under ABI 36: a new function only. */
+int hn_det_ap_accumulate_f32(const float* boxes, const float* scores, const int32_t* labels, const int32_t* sides,
+                             const int32_t* count, const int32_t* contacts, const float* dxdymags, const int32_t* image_ids, int n,
+                             int cap, const int32_t* hand_off, const int32_t* hand_box, const int32_t* hand_meta,
+                             const double* hand_obj, int hand_total, const int32_t* obj_off, const int32_t* obj_box,
+                             const int32_t* obj_diff, int obj_total, int images, int hand_label, int object_label, float score_min,
+                             double ovthresh, int32_t* hand, int32_t* obj, int32_t* fed, int32_t* overflow, int max_dets,
+                             void* stream);
 /* A Linear layer on 1..4 rows as a matrix-vector product on the vector ALU (PoseNet at the live caller's batch, posenet.py:24-41,
  * 78-88: 67 MB of filter bank per 17 M MACs): y[m][:] = act(W (pre(x[m])) + bias (+ residual[m])), pre = relu(x * scale + shift)
  * when scale / shift ([k_real] fp32: the pre-activation BatchNorm) are given.  x fp32 [batch][x_stride] (k_real columns used), w16 =
