@@ -13,8 +13,10 @@ of a Lightning `.ckpt` (handnet_pipeline.py:28-29; commented alternative in a2j_
 `forward` -- so that `from a2j.a2j import A2JModelLightning` (a2j_infer.py:12, a2j_mesh.py:15,
 handnet_pipeline/handnet_pipeline.py:8) resolves -- and its evaluation hook `test_step` (a2j/a2j.py:333-359: forward ->
 convert_joints on prediction and ground truth -> RMSE in mm -> the HPE evaluator's text file), the second caller SURVEY 8f #1
-names, with the conversion in the aggregation's epilogue.  The training-side hooks raise.
-Training (`gt is not None`) is out of scope and raises.
+names, with the conversion in the aggregation's epilogue.
+`model(x, gt)` returns `(losses, output)` like the reference (a2j/a2j.py:231-239): the criterion (a2j/anchor.py:99-153) is
+evaluated in the aggregation's sweep over the heads, forward only -- nothing here can back-propagate, so `training_step` and
+`configure_optimizers` raise, and `validation_step` runs after `device_loss()`.
 """
 from __future__ import annotations
 
@@ -37,6 +39,7 @@ class A2JModel(EngineOwner):
         self.is_RGBD = is_RGBD
         self.num_classes = num_classes
         self.crop_height, self.crop_width = crop_height, crop_width
+        self.spatial_factor = float(spatial_factor)   # the criterion's spatialFactor (a2j/a2j.py:221-222)
         # The reference starts from ImageNet weights fetched over the network
         # (a2j/a2j.py:188); offline, the state starts from the deterministic synthetic
         # checkpoint and is normally overwritten by load_state_dict().
@@ -63,9 +66,32 @@ class A2JModel(EngineOwner):
         """Same as forward() but leaves the [K,J,3] result on the GPU (no forced sync)."""
         return self.engine().forward(x, valid)
 
+    last_loss_host = None   # forward(x, gt): the call's five batch scalars as floats, from its one device -> host copy
+
+    def _forward_loss(self, x, gt):
+        """forward(x, gt) (a2j/a2j.py:231-239, eager_outputs with gt): the criterion rides in the aggregation's sweep
+        (ops.a2j_loss), forward only.  -> (losses, output): losses = {"classification", "regression" (already times
+        reg_loss_factor = 3), "total_loss"}, fp32 tensors of shape [1] on the device; output = forward(x)'s, bit for bit.
+        The keypoints, the range words and the five batch scalars (self.last_loss_host: classification, regression_mean,
+        regression, total_loss, rmse) come back in ONE device -> host copy, under forward(x)'s range contract."""
+        eng = self.engine()
+        g = torch.as_tensor(gt)
+        if not g.is_floating_point() or g.dim() != 3 or tuple(g.shape[1:]) != (self.num_classes, 3) or g.shape[0] != x.shape[0]:
+            raise ValueError(f"gt must be a float tensor or array of shape [K,{self.num_classes},3], one row per crop")
+        g = g.detach().to(device=eng.device, dtype=torch.float32).contiguous()
+        (kp, _terms, _sample, batch), flags = eng.forward_flags(x, gt=g, spatial_factor=self.spatial_factor)
+        parts = [kp.contiguous().reshape(-1).view(torch.int32), batch.view(torch.int32)] + ([flags[:3]] if flags is not None else [])
+        flat = torch.cat(parts).cpu()
+        n = kp.numel()
+        out = flat[:n].contiguous().view(torch.float32).reshape(kp.shape)
+        check_range_contract(out, flat[n + 5:].tolist() if flags is not None else None, x)
+        host = flat[n:n + 5].contiguous().view(torch.float32).tolist()
+        self.last_loss_host = dict(zip(("classification", "regression_mean", "regression", "total_loss", "rmse"), host))
+        return {"classification": batch[0:1], "regression": batch[2:3], "total_loss": batch[3:4]}, out
+
     def forward(self, x, gt=None):
         if gt is not None:
-            raise NotImplementedError("training losses (a2j/anchor.py:84-152) are outside the inference hot path")
+            return self._forward_loss(x, gt)
         # keypoints and the step's range-contract words in ONE device -> host copy (the reference's .data.cpu(), a2j.py:229);
         # an overflowing activation or a finite input beyond the fp16 range raises instead of returning inf / NaN or silently
         # wrong keypoints, a crop with NaN / inf pixels gives NaN keypoints like the reference (hn_amd.pipeline)
@@ -286,7 +312,28 @@ class A2JModelLightning(EngineOwner):
         raise NotImplementedError("the training-side hooks of A2JModelLightning (training_step / validation_step need the A2J "
                                   "loss, a2j/a2j.py:283-331; configure_optimizers) are outside the inference hot path")
 
-    training_step = validation_step = configure_optimizers = _no_training
+    training_step = configure_optimizers = _no_training
+
+    _device_loss = False   # off (the default): validation_step raises like the other training-side hooks
+
+    def device_loss(self, enable: bool = True):
+        """Opt in to (or out of) `validation_step` on the device: the A2J criterion evaluated in the
+        aggregation's sweep, forward only.  Off, validation_step raises NotImplementedError as before.  training_step and
+        configure_optimizers raise either way: nothing here can back-propagate through the HIP convolutions."""
+        self._device_loss = bool(enable)
+        return self
+
+    def validation_step(self, batch, batch_idx):
+        """a2j/a2j.py:309-332 without the vis_minibatch image: forward with the ground truth, `val_loss` = total_loss and
+        `test_rmse` = sqrt(mean((gt - output)^2)) over the batch's K * J * 3 crop-uvd values (the reduction launch's, read
+        from the forward's one copy), returns total_loss."""
+        if not self._device_loss:
+            return self._no_training()
+        im, jt_uvd_gt, _dexycb_id, _color_im, _, _, combined_im = batch
+        losses, _outputs = self.a2j(combined_im if self.rgbd else im, jt_uvd_gt)
+        self.log("val_loss", self.a2j.last_loss_host["total_loss"])
+        self.log("test_rmse", self.a2j.last_loss_host["rmse"])
+        return losses["total_loss"]
 
 
 def convert_joints(jt_uvd_pred, jt_uvd_gt, box, paras, cropWidth, cropHeight):

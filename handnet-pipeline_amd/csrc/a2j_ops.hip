@@ -117,129 +117,98 @@ constexpr int kMaxGroups = 9;   // (round 4: 3 -> 9 cell groups: on an 11 x 11 m
                                 // same for every batch size)
 constexpr int kJointSplit = 3;
 
-__global__ __launch_bounds__(1024) void a2j_aggregate_kernel(const float* __restrict__ cls,
-                                                             const float* __restrict__ reg,
-                                                             const float* __restrict__ dep,
-                                                             const int* __restrict__ valid, int fh, int fw,
-                                                             int J, int Jw, int stride, int G, float* __restrict__ out,
-                                                             const ConvertSpec cs) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];  // [G][4][A*Jw]
-  const int k = blockIdx.x;
-  const int j0 = blockIdx.y * Jw;
-  const int jn = min(Jw, J - j0);      // joints of this workgroup (the last one may have fewer, or none)
-  if (jn <= 0) return;
-  const int AJ = kAnchorsPerCell * J;   // channels per cell in memory
-  const int AW = kAnchorsPerCell * Jw;  // thread slots per cell group
-  const int g = threadIdx.x / AW, cl = threadIdx.x - g * AW;
-  const int a = cl / Jw, jl = cl - a * Jw;
-  const bool active = g < G && jl < jn;
-  const int c = a * J + j0 + jl;        // channel in memory
-  if (valid && valid[k] != 1) {  // uniform per workgroup: 0 = no crop (zero row), 2 = non-finite crop (NaN row, as the
-    // reference's network returns for it: every cell of the 11 x 11 maps sees every pixel of the crop)
-    if ((int)threadIdx.x < jn * 3) {
-      const float fill = valid[k] == 0 ? 0.f : __builtin_nanf("");
-      const long at = ((long)k * J + j0) * 3 + threadIdx.x;
-      out[at] = fill;
-      if ((cs.box || cs.box_f32) && cs.image_uvd) cs.image_uvd[at] = fill;
-      if ((cs.box || cs.box_f32) && cs.xyz_mm && cs.has_paras) cs.xyz_mm[at] = fill;
-    }
-    return;
-  }
-  const int cells = fh * fw;
-  const float* clsk = cls + (long)k * cells * AJ;
-  const float* depk = dep + (long)k * cells * AJ;
-  const float* regk = reg + (long)k * cells * AJ * 2;
+// what the loss form (hn_a2j_aggregate_loss_f32; DESIGN.md section 9o, tests/loss_ref.py) adds to the kernel's arguments
+struct LossSpec {
+  const float* gt;   // [n,J,3] ground truth in crop (coord0, coord1, depth), the coordinates of the output row
+  float* terms;      // [n,J,8]: (La_h, La_w, Lr_h, Lr_w, d, (gt - out)^2 x 3)
+};
+constexpr int kLossTerms = 8;
 
-  // Both cell loops fetch kBatch (14: three rounds for the 41 cells a thread owns on an 11 x 11 map) cells' operands before they use any (same operations in the same order): written as
-  // load -> use per cell, each of the 2 x 41 iterations waited for its own L2 round trip -- 27 us per launch.
-  constexpr int kBatch = 14;
-  float mx = -FLT_MAX;
-  if (active)
-    for (int pb = g; pb < cells; pb += kBatch * G) {
-      float v[kBatch];
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) {
-        const int p = pb + u * G;
-        v[u] = p < cells ? clsk[(long)p * AJ + c] : -FLT_MAX;
-      }
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) mx = fmaxf(mx, v[u]);
-    }
-  if (g < G) lds[g * AW + cl] = mx;
-  __syncthreads();
-  if ((int)threadIdx.x < AW) {   // (group 0's threads: slot cl = threadIdx.x) maximum over the groups, then over the anchors below
-    float m = lds[threadIdx.x];
-    for (int gg = 1; gg < G; ++gg) m = fmaxf(m, lds[gg * AW + threadIdx.x]);
-    lds[threadIdx.x] = m;
-  }
-  __syncthreads();
-  float mj = -FLT_MAX;
-  if (active)
-    for (int aa = 0; aa < kAnchorsPerCell; ++aa) mj = fmaxf(mj, lds[aa * Jw + jl]);
-  __syncthreads();
+// a2j/anchor.py:125-129,135-139: where(diff <= 1, 0.5 * diff^2, diff - 0.5); a NaN takes the second branch and stays NaN
+__device__ __forceinline__ float smooth_l1(float a) {
+#pragma clang fp contract(off)
+  return a <= 1.f ? 0.5f * (a * a) : a - 0.5f;
+}
 
-  if (active) {
-    float s = 0.f, s0 = 0.f, s1 = 0.f, sd = 0.f;
-    const float p0 = 2.f + 4.f * (float)(a >> 2), p1 = 2.f + 4.f * (float)(a & 3);
-    for (int pb = g; pb < cells; pb += kBatch * G) {
-      float vc[kBatch], vd[kBatch];
-      float2 vr[kBatch];
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) {
-        const int p = pb + u * G;
-        const long q = (long)(p < cells ? p : g) * AJ + c;   // (clamped: the tail batch's extra cells are not used)
-        vc[u] = clsk[q];
-        vr[u] = *reinterpret_cast<const float2*>(regk + q * 2);
-        vd[u] = depk[q];
+// the criterion's terms of one joint (a2j/anchor.py:123-150), one rounding per operation: e0, e1 = sum w anchor; (ku, kv, kd) =
+// the keypoint the caller gets.  The depth term is the plain |difference| (the smooth-L1 with knee 3 of lines 145-149 is never used)
+__device__ __forceinline__ void loss_terms_one(const LossSpec& ls, long joint_row, float e0, float e1, float ku, float kv, float kd) {
+#pragma clang fp contract(off)
+  const float* g = ls.gt + joint_row * 3;
+  const float g0 = g[0], g1 = g[1], g2 = g[2];
+  const float du = g0 - ku, dv = g1 - kv, dd = g2 - kd;
+  f32x4* o = reinterpret_cast<f32x4*>(ls.terms + joint_row * kLossTerms);
+  const f32x4 lo = {smooth_l1(fabsf(g0 - e0)), smooth_l1(fabsf(g1 - e1)), smooth_l1(fabsf(du)), smooth_l1(fabsf(dv))};
+  const f32x4 hi = {fabsf(dd), du * du, dv * dv, dd * dd};
+  o[0] = lo;
+  o[1] = hi;
+}
+
+// a2j_aggregate_kernel and a2j_loss_aggregate_kernel: ONE body (a2j_aggregate_body.h) with a compile-time switch, the same flags
+#define A2J_AGG_LOSS 0
+#include "a2j_aggregate_body.h"
+#define A2J_AGG_LOSS 1
+#include "a2j_aggregate_body.h"
+
+// The criterion's reductions (a2j/anchor.py:130,140,150,153; a2j/a2j.py:233-238,318) in ONE workgroup and a fixed order, no
+// atomics: thread i of a round of 256 samples adds its own sample's joints in joint order (a sample row depends on its own
+// crop only), then thread 0 adds the round's samples in sample order.  valid == 0 rows are left out of the batch values
+// (divisor = rows with valid != 0; none: 0 / 0 = NaN, like torch.mean of nothing), valid == 2 rows carry NaN terms.
+// batch [5] = (classification, the criterion's regression mean, regression * reg_loss_factor, total, rmse over n * J * 3 values)
+__global__ __launch_bounds__(256) void a2j_loss_reduce_kernel(const float* __restrict__ terms, const int* __restrict__ valid, int n,
+                                                              int J, float spatial_factor, float reg_loss_factor,
+                                                              float* __restrict__ sample, float* __restrict__ batch) {
+#pragma clang fp contract(off)
+  __shared__ float sh[3][256];
+  __shared__ int use[256];
+  float ba = 0.f, br = 0.f, bq = 0.f;   // (thread 0) running batch sums
+  int rows = 0;
+  for (int base = 0; base < n; base += 256) {
+    const int i = base + (int)threadIdx.x;
+    if (i < n) {
+      const f32x4* t = reinterpret_cast<const f32x4*>(terms + (long)i * J * kLossTerms);
+      float la = 0.f, lr = 0.f, ld = 0.f, sq = 0.f;
+      for (int j = 0; j < J; ++j) {
+        const f32x4 lo = t[2 * j], hi = t[2 * j + 1];
+        la += lo[0];
+        la += lo[1];
+        lr += lo[2];
+        lr += lo[3];
+        ld += hi[0];
+        sq += hi[1];
+        sq += hi[2];
+        sq += hi[3];
       }
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) {
-        const int p = pb + u * G;
-        if (p < cells) {
-          const int hh = p / fw, ww = p - hh * fw;
-          const float e = expf(vc[u] - mj);
-          const float a0 = (float)(hh * stride) + p0, a1 = (float)(ww * stride) + p1;
-          s += e;
-          s0 += e * (a0 + vr[u].x);
-          s1 += e * (a1 + vr[u].y);
-          sd += e * vd[u];
+      const float anchor_loss = la / (float)(2 * J);
+      const float regression_loss = lr / (float)(2 * J) * spatial_factor + ld / (float)J;
+      sample[(long)i * 2 + 0] = anchor_loss;
+      sample[(long)i * 2 + 1] = regression_loss;
+      sh[0][threadIdx.x] = anchor_loss;
+      sh[1][threadIdx.x] = regression_loss;
+      sh[2][threadIdx.x] = sq;
+      use[threadIdx.x] = !valid || valid[i] != 0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int m = min(256, n - base);
+      for (int r = 0; r < m; ++r)
+        if (use[r]) {
+          ba += sh[0][r];
+          br += sh[1][r];
+          bq += sh[2][r];
+          ++rows;
         }
-      }
     }
-    float* o = lds + (long)g * 4 * AW;
-    o[cl] = s;
-    o[AW + cl] = s0;
-    o[2 * AW + cl] = s1;
-    o[3 * AW + cl] = sd;
+    __syncthreads();
   }
-  __syncthreads();
-  // fixed-order combination in two steps: thread (quantity q, anchor a, joint jl) of the first 4 * AW sums its slot over the
-  // groups 0 .. G-1, then thread jj sums the 16 anchors of its joint (G + 16 dependent additions instead of 16 G)
-  for (int s4 = threadIdx.x; s4 < 4 * AW; s4 += blockDim.x) {
-    float acc = lds[s4];
-    for (int gg = 1; gg < G; ++gg) acc += lds[(long)gg * 4 * AW + s4];
-    lds[s4] = acc;   // (group 0's slot: only this thread reads or writes it here)
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < jn) {
-    const int jj = threadIdx.x;
-    float t = 0.f, t0 = 0.f, t1 = 0.f, td = 0.f;
-    for (int aa = 0; aa < kAnchorsPerCell; ++aa) {
-      t += lds[aa * Jw + jj];
-      t0 += lds[AW + aa * Jw + jj];
-      t1 += lds[2 * AW + aa * Jw + jj];
-      td += lds[3 * AW + aa * Jw + jj];
-    }
-    float* o = out + ((long)k * J + j0 + jj) * 3;
-    float ku = t0 / t;
-    const float kv = t1 / t, kd = td / t;
-    if (cs.mirror && cs.mirror[k]) ku = cs.crop_w - ku;   // (one fp32 subtraction, before anything else sees the value)
-    o[0] = ku;
-    o[1] = kv;
-    o[2] = kd;
-    // convert_joints + uvd2xyz in the aggregation's epilogue (what every caller does next: ros_demo.py:289,
-    // 329-330, a2j/a2j.py:341-348) -- from the registers that hold the joint, no second launch
-    if (cs.box || cs.box_f32) convert_one(cs, k, (long)k * J + j0 + jj, ku, kv, kd);
+  if (threadIdx.x == 0) {
+    const float cls_loss = ba / (float)rows, reg_mean = br / (float)rows;
+    const float reg_loss = reg_mean * reg_loss_factor;
+    batch[0] = cls_loss;
+    batch[1] = reg_mean;
+    batch[2] = reg_loss;
+    batch[3] = cls_loss + reg_loss;
+    batch[4] = sqrtf(bq / ((float)rows * (float)(J * 3)));
   }
 }
 
@@ -328,8 +297,11 @@ extern "C" int hn_pack_depth_nhwc(const float* src, float* dst, int n, int hw, i
   return HN_OK;
 }
 
+template <class... Loss>
 static int launch_aggregate(const float* cls, const float* reg, const float* dep, const int32_t* valid, int k, int fh, int fw,
-                            int joints, int stride, float* out, const ConvertSpec& cs, void* stream) {
+                            int joints, int stride, float* out, const ConvertSpec& cs, void* stream, const Loss... loss) {
+  constexpr bool kLoss = sizeof...(Loss) != 0;
+  constexpr int nq = kLoss ? 6 : 4;
   // the cell-group count depends on the joint count only (it fixes the summation order): min(9, 1024 / (16 * joints per workgroup))
   const int split = joints >= 2 * kJointSplit ? kJointSplit : 1;
   const int jw = (joints + split - 1) / split;
@@ -338,9 +310,15 @@ static int launch_aggregate(const float* cls, const float* reg, const float* dep
   groups = groups > kMaxGroups ? kMaxGroups : groups;
   groups = groups < 1 ? 1 : groups;
   const int threads = ((groups * aw + 63) / 64) * 64;
-  hipLaunchKernelGGL(a2j_aggregate_kernel, dim3(k, split), dim3(threads), groups * 4 * aw * sizeof(float),
-                     (hipStream_t)stream, cls, reg, dep, valid, fh, fw, joints, jw, stride, groups, out, cs);
-  HN_CHECK_LAUNCH("a2j_aggregate_kernel");
+  if constexpr (kLoss) {
+    hipLaunchKernelGGL(a2j_loss_aggregate_kernel, dim3(k, split), dim3(threads), groups * nq * aw * sizeof(float),
+                       (hipStream_t)stream, cls, reg, dep, valid, fh, fw, joints, jw, stride, groups, out, cs, loss...);
+    HN_CHECK_LAUNCH("a2j_loss_aggregate_kernel");
+  } else {
+    hipLaunchKernelGGL(a2j_aggregate_kernel, dim3(k, split), dim3(threads), groups * nq * aw * sizeof(float),
+                       (hipStream_t)stream, cls, reg, dep, valid, fh, fw, joints, jw, stride, groups, out, cs);
+    HN_CHECK_LAUNCH("a2j_aggregate_kernel");
+  }
   return HN_OK;
 }
 
@@ -384,6 +362,52 @@ static int aggregate_convert_run(const float* cls, const float* reg, const float
   cs.xyz_mm = out_xyz_mm;
   cs.mirror = mirror;
   return launch_aggregate(cls, reg, dep, valid, k, fh, fw, joints, stride, out_uvd, cs, stream);
+}
+
+extern "C" int hn_a2j_aggregate_loss_f32(const float* cls, const float* reg, const float* dep, const int32_t* valid, const float* gt,
+                                         int k, int fh, int fw, int joints, int stride, float spatial_factor,
+                                         float reg_loss_factor, const int64_t* crop_box, float crop_w, float crop_h,
+                                         const float* paras, const hn_convert_opts* opts, float* out_uvd, float* out_image_uvd,
+                                         float* out_xyz_mm, float* out_terms, float* out_sample, float* out_batch, void* stream) {
+  HN_CHECK_ARG(cls && reg && dep && gt && out_uvd && out_terms && out_sample && out_batch,
+               "hn_a2j_aggregate_loss_f32: null pointer");
+  HN_CHECK_ARG(joints > 0 && joints * kAnchorsPerCell <= 1024, "hn_a2j_aggregate_loss_f32: joints must be in [1, 64]");
+  HN_CHECK_ARG(fh > 0 && fw > 0, "hn_a2j_aggregate_loss_f32: fh * fw must not be 0");
+  HN_CHECK_ARG(k >= 0 && stride > 0, "hn_a2j_aggregate_loss_f32: bad dims");
+  HN_CHECK_ARG((uintptr_t)out_terms % 16 == 0, "hn_a2j_aggregate_loss_f32: out_terms must be 16-byte aligned");
+  ConvertSpec cs{};
+  if (crop_box || (opts && opts->sample_box)) {   // the conversion, as hn_a2j_aggregate_convert_f32 takes it; absent: none
+    HN_CHECK_ARG(out_image_uvd || out_xyz_mm, "hn_a2j_aggregate_loss_f32: boxes given but no converted output requested");
+    HN_CHECK_ARG(!out_xyz_mm || paras || (opts && opts->sample_paras),
+                 "hn_a2j_aggregate_loss_f32: camera xyz needs the intrinsics (fx, fy, cx, cy)");
+    HN_CHECK_ARG(crop_w > 0.f && crop_h > 0.f, "hn_a2j_aggregate_loss_f32: bad crop size");
+    cs.box = (const long long*)crop_box;
+    cs.crop_w = crop_w;
+    cs.crop_h = crop_h;
+    cs.box_f32 = opts ? opts->sample_box : nullptr;
+    cs.sample_paras = opts ? opts->sample_paras : nullptr;
+    cs.has_paras = (paras || cs.sample_paras) ? 1 : 0;
+    cs.fx = paras ? paras[0] : 1.f;
+    cs.fy = paras ? paras[1] : 1.f;
+    cs.cx = paras ? paras[2] : 0.f;
+    cs.cy = paras ? paras[3] : 0.f;
+    cs.clamp_kp = opts ? opts->clamp_keypoints : 0;
+    cs.clamp_h = opts ? opts->clamp_box_h : 0;
+    cs.clamp_w = opts ? opts->clamp_box_w : 0;
+    HN_CHECK_ARG((cs.clamp_h > 0) == (cs.clamp_w > 0), "clamp_box_h and clamp_box_w are given together");
+    cs.image_uvd = out_image_uvd;
+    cs.xyz_mm = out_xyz_mm;
+  } else {
+    HN_CHECK_ARG(!out_image_uvd && !out_xyz_mm, "hn_a2j_aggregate_loss_f32: converted outputs need boxes (crop_box or opts->sample_box)");
+  }
+  if (k == 0) return HN_OK;
+  const LossSpec ls{gt, out_terms};
+  const int st = launch_aggregate(cls, reg, dep, valid, k, fh, fw, joints, stride, out_uvd, cs, stream, ls);
+  if (st != HN_OK) return st;
+  hipLaunchKernelGGL(a2j_loss_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)out_terms, valid, k, joints,
+                     spatial_factor, reg_loss_factor, out_sample, out_batch);
+  HN_CHECK_LAUNCH("a2j_loss_reduce_kernel");
+  return HN_OK;
 }
 
 extern "C" int hn_a2j_aggregate_convert_f32(const float* cls, const float* reg, const float* dep, const int32_t* valid, int k,

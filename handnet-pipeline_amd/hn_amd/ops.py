@@ -1516,6 +1516,72 @@ def a2j_aggregate(cls, reg, dep, joints=21, stride=16, valid=None, out=None, con
     return out
 
 
+def a2j_loss(cls, reg, dep, gt, joints=21, stride=16, spatial_factor=0.5, reg_loss_factor=3.0, valid=None, convert=None, out=None):
+    """The aggregation with the A2J criterion in its sweep (hn_a2j_aggregate_loss_f32; a2j/anchor.py:99-153, DESIGN.md section
+    9o): heads as a2j_aggregate takes them, gt [K,J,3] fp32 in crop (coord0, coord1, depth)
+      -> (uvd [K,J,3] -- or, with convert, a2j_aggregate's triple (crop_uvd, image_uvd, xyz_mm or None) --,
+          terms [K,J,8] = (La_h, La_w, Lr_h, Lr_w, d, squared uvd differences x 3),
+          sample [K,2] = (anchor_loss, regression_loss) per sample,
+          batch [5] = (classification, the criterion's regression mean, regression * reg_loss_factor, total, rmse)),
+    all on the device.  uvd and the converted outputs are a2j_aggregate's on the same heads bit for bit.
+    valid: rows with 0 are left out of the batch values, rows with 2 make them NaN.  convert: a2j_aggregate's dict without
+    mirror.  out: a preallocated uvd."""
+    lib = _lib.load()
+    _req(cls, name="cls"); _req(reg, name="reg"); _req(dep, name="dep"); _req(gt, name="gt")
+    if cls.dim() != 4 or reg.dim() != 4:
+        raise ValueError("bad head shapes")
+    k, fh, fw, aj = cls.shape
+    if joints < 1 or aj != 16 * joints or reg.shape[3] != 2 * aj or dep.shape != cls.shape or reg.shape[:3] != cls.shape[:3]:
+        raise ValueError("bad head shapes")
+    if tuple(gt.shape) != (k, joints, 3):
+        raise ValueError("gt must be [K,J,3]")
+    dev = cls.device
+    if out is None:
+        out = torch.empty((k, joints, 3), device=dev, dtype=torch.float32)
+    elif tuple(_req(out, name="out").shape) != (k, joints, 3):
+        raise ValueError("out must be [K,J,3]")
+    if valid is not None and _req(valid, torch.int32, "valid").numel() != k:
+        raise ValueError("valid must hold one flag per crop")
+    terms = torch.empty((k, joints, 8), device=dev, dtype=torch.float32)
+    sample = torch.empty((k, 2), device=dev, dtype=torch.float32)
+    # (no crop at all: nothing is launched, and the batch values are the mean of nothing)
+    batch = torch.empty((5,), device=dev, dtype=torch.float32) if k else torch.full((5,), float("nan"), device=dev)
+    box = sbox = sparas = img = xyz = pp = opts = None
+    crop = 0.0
+    if convert is not None:
+        if convert.get("mirror") is not None:
+            raise ValueError("a2j_loss: convert takes no mirror flags")
+        sbox, sparas = convert.get("sample_box"), convert.get("sample_paras")
+        box = convert.get("crop_box")
+        if (box is None) == (sbox is None):
+            raise ValueError("convert needs crop_box (int64, the detector's) or sample_box (fp32, the dataset's), one of them")
+        for t, dt, nm in ((box, torch.int64, "crop_box"), (sbox, torch.float32, "sample_box"), (sparas, torch.float32, "sample_paras")):
+            if t is not None and tuple(_req(t, dt, nm).shape) != (k, 4):
+                raise ValueError(f"{nm} must be [K,4]")
+        paras = convert.get("paras")
+        if paras is not None and sparas is not None:
+            raise ValueError("convert: paras (one camera) or sample_paras (one per sample), not both")
+        img, xyz = convert.get("image_uvd"), convert.get("xyz_mm")
+        if img is None:
+            img = torch.empty((k, joints, 3), device=dev, dtype=torch.float32)
+        if xyz is None and (paras is not None or sparas is not None):
+            xyz = torch.empty((k, joints, 3), device=dev, dtype=torch.float32)
+        pp = (C.c_float * 4)(*[float(v) for v in paras]) if paras is not None else None
+        cb = convert.get("clamp_box")
+        if convert.get("clamp_keypoints") or cb or sbox is not None or sparas is not None:
+            opts = _lib.ConvertOpts(1 if convert.get("clamp_keypoints") else 0, int(cb[0]) if cb else 0, int(cb[1]) if cb else 0, 0,
+                                    ptr(sbox), ptr(sparas))
+        crop = float(convert.get("crop", 176))
+    res = out if convert is None else (out, img, xyz)
+    if k == 0:
+        return res, terms, sample, batch
+    check(lib.hn_a2j_aggregate_loss_f32(ptr(cls), ptr(reg), ptr(dep), ptr(valid), ptr(gt), k, fh, fw, joints, stride,
+                                        float(spatial_factor), float(reg_loss_factor), ptr(box), crop, crop, pp,
+                                        C.byref(opts) if opts is not None else None, ptr(out), ptr(img), ptr(xyz), ptr(terms),
+                                        ptr(sample), ptr(batch), _stream()), "hn_a2j_aggregate_loss_f32")
+    return res, terms, sample, batch
+
+
 def joints2d_standardize(image_uvd, valid=None, out=None):
     """image (u,v,d) joints [N,J,3] -> the lifter's input [N,J,2]: per frame and axis (x - mean) / std over the joints
     (hn_joints2d_standardize_f32 = the live caller's bbox / affine / normalisation chain, ros_demo.py:148-157, which reduces

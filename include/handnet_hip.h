@@ -40,8 +40,8 @@ extern "C" {
  * hn_mesh_render_cams_u8 and hn_mesh_render_cams_occluded_u8, the rig frame's hn_rig_fuse_f32, the hand cloud's
  * hn_hand_cloud_f32 and hn_hand_cloud_scratch_bytes, the mesh fit's hn_mesh_fit_f32 and hn_mesh_fit_scratch_bytes, and the
  * iterated fit's hn_mesh_geometry_f32, hn_mesh_fit_iters_f32 and hn_mesh_fit_iters_scratch_bytes, and the carried apply pass's
- * hn_conv2d_nhwc_f16x3_grouped_carry, hn_conv2d_f16x3_grouped_carry_applies and hn_affine_split_f32_levels_streams, the evaluator's hn_hpe_accumulate_f32, and the
- * detector evaluation's hn_det_ap_accumulate_f32). */
+ * hn_conv2d_nhwc_f16x3_grouped_carry, hn_conv2d_f16x3_grouped_carry_applies and hn_affine_split_f32_levels_streams, the evaluator's hn_hpe_accumulate_f32, the
+ * detector evaluation's hn_det_ap_accumulate_f32, and the A2J criterion's hn_a2j_aggregate_loss_f32). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -669,6 +669,29 @@ int hn_a2j_aggregate_convert_mirror_f32(const float* cls, const float* reg, cons
                                         const int64_t* crop_box, float crop_w, float crop_h, const float* paras,
                                         const hn_convert_opts* opts, float* out_uvd, float* out_image_uvd, float* out_xyz_mm,
                                         void* stream);
+
+/* The aggregation with the A2J criterion (a2j/anchor.py:99-153 A2J_loss.forward, a2j/a2j.py:231-238) in the SAME sweep over the
+ * heads: out_uvd (and the conversion's outputs) are hn_a2j_aggregate_convert_f32's bit for bit, and the thread that holds a joint
+ * also writes the joint's terms against gt [k][J][3] (crop (coord0, coord1, depth), the coordinates of an out_uvd row):
+ *   out_terms [k][J][8] (16-byte aligned) = (La_h, La_w, Lr_h, Lr_w, d, (gt - out_uvd)^2 x 3)
+ *     La = smooth-L1 (knee 1) of |gt - sum w anchor|, Lr the same of |gt - out_uvd| (first two columns), d = |gt_depth - out_depth|
+ *     (a plain L1: the reference computes a smooth-L1 with knee 3 for the depth and never uses it).
+ * A second, small launch reduces them in a fixed order (no atomics):
+ *   out_sample [k][2] = (mean of La over 2J values, mean of Lr over 2J values * spatial_factor + mean of d over J values);
+ *     row i depends on crop i only (bit-identical to the k = 1 call on that crop)
+ *   out_batch [5] = (classification = mean over the samples of column 0, the criterion's regression = mean of column 1,
+ *     regression * reg_loss_factor, total = classification + regression * reg_loss_factor,
+ *     rmse = sqrt(mean (gt - out_uvd)^2 over all samples * J * 3 values), a2j/a2j.py:318)
+ * valid (or NULL) as in hn_a2j_aggregate_f32; rows with valid == 0 are left out of every out_batch value (the divisor is the
+ * number of rows with valid != 0; none gives 0 / 0 = NaN), rows with valid == 2 have NaN terms and make out_batch NaN.
+ * The conversion's arguments (crop_box .. opts, out_image_uvd, out_xyz_mm) are those of hn_a2j_aggregate_convert_f32 and may all
+ * be absent (NULL / 0): then nothing is converted.  k == 0 launches nothing. */
+int hn_a2j_aggregate_loss_f32(const float* cls, const float* reg, const float* dep, const int32_t* valid /* or NULL */,
+                              const float* gt, int k, int fh, int fw, int joints, int stride, float spatial_factor,
+                              float reg_loss_factor, const int64_t* crop_box /* or NULL */, float crop_w, float crop_h,
+                              const float* paras /* host, 4 floats, or NULL */, const hn_convert_opts* opts /* host or NULL */,
+                              float* out_uvd, float* out_image_uvd /* or NULL */, float* out_xyz_mm /* or NULL */,
+                              float* out_terms, float* out_sample, float* out_batch, void* stream);
 
 /* The lifter's input from a step's image-(u,v) joints (the live caller's glue between the path and Pose2Mesh,
  * ros_demo.py:148-157: get_bbox -> process_bbox -> j2d_processing (rot 0, no flip) -> / input_shape -> (x - mean) / std):
