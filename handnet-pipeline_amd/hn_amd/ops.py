@@ -120,8 +120,21 @@ def _pixel_stride(t: torch.Tensor, name: str) -> int:
 
 
 _DESC_TEMPLATES = {}
-_MULTI_PLANS = {}
-_CONV_PLANS = {}
+# Launch plans of conv2d_nhwc / conv2d_nhwc_multi: a call whose tensors have the shapes / strides / flags of an earlier call
+# reuses that call's validated struct (the checks cost more host time than the launch at batch 1).
+_PLANS = {}
+
+
+def _plan_get(*parts):
+    """-> (key, plan or None).  The key is the front end's own parts (its struct type first) and the development switches
+    that every plan depends on."""
+    key = (SPLITK, SPLITK_EAGER, F16_TERMS, parts)
+    return key, _PLANS.get(key)
+
+
+def _plan_put(key, struct, out_specs, use_ws):
+    """plan = (the stamped struct, what the outputs are, does the launch take the split-K workspace?)"""
+    _PLANS[key] = (type(struct).from_buffer_copy(struct), out_specs, bool(use_ws))
 
 
 def make_conv_desc(n, h, w, cin, cout, r, s, stride=1, pad=0, dil=1, relu_cols=0, res_mode=0,
@@ -141,6 +154,73 @@ def make_conv_desc(n, h, w, cin, cout, r, s, stride=1, pad=0, dil=1, relu_cols=0
     return ConvDesc.from_buffer_copy(tpl)
 
 
+# ---- the argument checks and descriptor stamps that the convolution front ends share ----
+def _table_stride(scale, shift, n, c, stride=None, names="scale / shift", width="C"):
+    """The (scale, shift) tables of a per-(image, channel) affine, possibly column slices of wider tables -> their row
+    stride (which must be `stride` where the caller's other tables fixed it)."""
+    if stride is None:
+        stride = scale.stride(0)
+    for t in (scale, shift):
+        if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (n, c) or t.stride(1) != 1 or t.stride(0) != stride:
+            raise ValueError(f"{names} must be fp32 GPU [N, {width}] tables with equal row stride")
+    return stride
+
+
+def _s32_levels(xs, cin, what="levels"):
+    """The S32 maps of one launch -> (batch size, pixel stride), the same for all of them."""
+    n, xstride = xs[0].shape[0], _pixel_stride(xs[0], "x")
+    for x in xs:
+        if not is_split(x) or x.shape[0] != n or channels(x) != cin or _pixel_stride(x, "x") != xstride:
+            raise ValueError(f"{what} must be S32 tensors of one batch size, channel count and pixel stride")
+    return n, xstride
+
+
+def _f32_levels(ts, c):
+    """The fp32 maps of one launch (channel slices of wider tensors are fine) -> (batch size, pixel stride)."""
+    n, xstride = ts[0].shape[0], _pixel_stride(ts[0], "x")
+    for t in ts:
+        if t.dtype != torch.float32 or is_split(t) or t.shape[0] != n or t.shape[3] != c or _pixel_stride(t, "x") != xstride:
+            raise ValueError("levels must be fp32 NHWC tensors of one batch size, channel count and pixel stride")
+    return n, xstride
+
+
+def _rows(xs) -> int:
+    """Pixels of all the maps together: the GEMM rows of a level launch."""
+    return sum(x.shape[0] * x.shape[1] * x.shape[2] for x in xs)
+
+
+def _alloc_out(n, oh, ow, cout, split, device):
+    """A fresh dense output: S32 when split, else fp32."""
+    if split:
+        if cout % 32:
+            raise ValueError("out_split needs Cout % 32 == 0")
+        return torch.empty((n, oh, ow, cout // 32, 2, 32), device=device, dtype=torch.float16)
+    return torch.empty((n, oh, ow, cout), device=device, dtype=torch.float32)
+
+
+def _relu_cols(cout, relu, relu_cols):
+    """Output columns that get the ReLU: relu_cols where given, else all of them or none."""
+    return (cout if relu else 0) if relu_cols is None else relu_cols
+
+
+def _stamp_out(d, out, cout, f16=True, splitk=None):
+    """Into the descriptor: the format and pixel stride of `out`, the term count, and (splitk = is it allowed? None: leave the
+    field alone) the split-K rule -> out's pixel stride."""
+    ys = _pixel_stride(out, "out")
+    d.out_split = 1 if is_split(out) else 0
+    d.out_pix_stride = 0 if ys == (2 * cout if d.out_split else cout) else ys
+    d.terms = 1 if (f16 and F16_TERMS == 1) else 0
+    if splitk is not None:
+        d.splitk = (1 if SPLITK_EAGER else 0) if splitk else -1
+    return ys
+
+
+def _stamp_residual(d, residual):
+    """Into an f16x3 descriptor: the format and pixel stride of the residual."""
+    d.res_split = 1 if is_split(residual) else 0
+    d.res_pix_stride = _pixel_stride(residual, "residual")
+
+
 def to_split(x, scale=None, shift=None, relu=False, out=None):
     """fp32 [N,H,W,C] -> S32 [N,H,W,C/32,2,32]; optional per-(image, channel) affine (+ReLU) first
     (GroupNorm-apply of the FCOS towers)."""
@@ -154,13 +234,7 @@ def to_split(x, scale=None, shift=None, relu=False, out=None):
     if out is None:
         out = torch.empty((n, h, w, c // 32, 2, 32), device=x.device, dtype=torch.float16)
     ys = _pixel_stride(out, "out")
-    a_stride = 0
-    if scale is not None:
-        for t in (scale, shift):
-            if (not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (n, c) or t.stride(1) != 1
-                    or t.stride(0) != scale.stride(0)):
-                raise ValueError("scale / shift must be fp32 GPU [N, C] tables with equal row stride")
-        a_stride = scale.stride(0)
+    a_stride = 0 if scale is None else _table_stride(scale, shift, n, c)
     check(lib.hn_affine_split_f32(ptr(x), ptr(scale), ptr(shift), 1 if relu else 0, n, h * w, c, xs, a_stride,
                                   ptr(out), ys, _stream()), "hn_affine_split_f32")
     return out
@@ -204,6 +278,24 @@ def tile_name(tile) -> str:
         ("+multi" if isinstance(tile, int) and tile & TILE_MULTI else "")
 
 
+def _profile_start():
+    """Before a conv launch: a started HipTimer when CONV_PROFILE is a list, else None (and nothing is created)."""
+    if CONV_PROFILE is None:
+        return None
+    timer = HipTimer()
+    timer.start()
+    return timer
+
+
+def _profile_stop(timer, describe):
+    """After the launch, where _profile_start gave a timer: close the bracket and append the record.  describe() -> ((precision,
+    tile or form), algorithmic MACs, shape tuple); it runs after the closing event is on the stream, so the library queries it
+    makes stay outside the bracket."""
+    timer.stop()
+    kind, macs, shape = describe()
+    CONV_PROFILE.append((kind, macs, timer, shape, PROFILE_STAGE))
+
+
 # Term count of the f16x3 kernels for the launches issued from now on: 3 = the split-precision product (default),
 # 1 = hi*hi only (the engines' precision="f16x1" throughput mode, reported beside the headline by bench.py).
 F16_TERMS = 3
@@ -227,9 +319,8 @@ class f16_terms:
 def clear_plan_caches():
     """Drop the cached conv descriptors / launch plans (they are keyed by weight addresses: engines call this when
     they are rebuilt, so that a recycled address can never meet a stale plan and the caches stay bounded)."""
-    _CONV_PLANS.clear()
+    _PLANS.clear()
     _DESC_TEMPLATES.clear()
-    _MULTI_PLANS.clear()
 
 
 # split-K workspace: one fp32 buffer per (device, stream) -- a convolution only uses it between its own two
@@ -309,22 +400,20 @@ def conv2d_nhwc(x, w, bias=None, *, stride=1, pad=0, dil=1, relu=False, relu_col
     gn_partial -> (f16x3, fp32 output, no residual / ReLU) fp32 scratch of gn_rows32_scratch_floats(rows, Cout)
                   floats: the epilogue also writes GroupNorm partial sums for groupnorm_finalize_rows32()."""
     lib = _lib.load()
-    # Plan cache: a call whose tensors have the shapes / strides / flags of an earlier call reuses that call's
-    # validated descriptor (the checks below cost more host time than the launch at batch 1).
     plan_key = None
     if (out is None and in_scale is None and w16 is not None and gn_partial is None and CONV_PROFILE is None
             and x.dtype == torch.float16 and x.is_cuda):
         _check_device(x, "x")
-        plan_key = (x.device.index, x.shape, x.stride(), w.data_ptr(), tuple(w.shape), w16.data_ptr(),
-                    None if bias is None else bias.data_ptr(),
-                    stride, pad, dil, relu, relu_cols, tile, out_split, res_upsample, splitk, SPLITK, SPLITK_EAGER, F16_TERMS,
-                    None if residual is None else (residual.shape, residual.stride(), residual.dtype))
-        plan = _CONV_PLANS.get(plan_key)
+        dev = x.device
+        plan_key, plan = _plan_get(
+            ConvDesc, dev.index, x.shape, x.stride(), w.data_ptr(), tuple(w.shape), w16.data_ptr(),
+            None if bias is None else bias.data_ptr(), stride, pad, dil, relu, relu_cols, tile, out_split, res_upsample, splitk,
+            None if residual is None else (residual.shape, residual.stride(), residual.dtype))
         if plan is not None:
-            tpl, out_shape, out_dtype, use_ws = plan
+            tpl, (out_shape, out_dtype), use_ws = plan
             d = ConvDesc.from_buffer_copy(tpl)
-            out = torch.empty(out_shape, device=x.device, dtype=out_dtype)
-            ws = _conv_workspace(x.device) if use_ws else None
+            out = torch.empty(out_shape, device=dev, dtype=out_dtype)
+            ws = _conv_workspace(dev) if use_ws else None
             check(lib.hn_conv2d_nhwc_f16x3_ws(C.byref(d), ptr(x), ptr(w16), ptr(bias), ptr(residual), ptr(out),
                                               ptr(ws), ws.numel() * 4 if use_ws else 0, _stream()),
                   "hn_conv2d_nhwc_f16x3_ws")
@@ -345,9 +434,7 @@ def conv2d_nhwc(x, w, bias=None, *, stride=1, pad=0, dil=1, relu=False, relu_col
     n, h, wd = x.shape[:3]
     if channels(x) != cin:
         raise ValueError(f"weight Cin {cin} != input channels {channels(x)}")
-    rc = cout if relu else 0
-    if relu_cols is not None:
-        rc = relu_cols
+    rc = _relu_cols(cout, relu, relu_cols)
     res_mode, rh, rw = 0, 0, 0
     if residual is not None:
         if channels(residual) != cout or residual.shape[0] != n:
@@ -362,40 +449,25 @@ def conv2d_nhwc(x, w, bias=None, *, stride=1, pad=0, dil=1, relu=False, relu_col
     d = make_conv_desc(n, h, wd, cin, cout, r, s, stride, pad, dil, rc, res_mode, rh, rw,
                        1 if in_scale is not None else 0, tile, in_pix_stride=0 if dense_in else xs)
     if out is None:
-        if out_split:
-            if cout % 32:
-                raise ValueError("out_split needs Cout % 32 == 0")
-            out = torch.empty((n, d.oh, d.ow, cout // 32, 2, 32), device=x.device, dtype=torch.float16)
-        else:
-            out = torch.empty((n, d.oh, d.ow, cout), device=x.device, dtype=torch.float32)
+        out = _alloc_out(n, d.oh, d.ow, cout, out_split, x.device)
     if tuple(out.shape[:3]) != (n, d.oh, d.ow) or channels(out) != cout:
         raise ValueError("out has the wrong shape")
-    ys = _pixel_stride(out, "out")
-    d.out_split = 1 if is_split(out) else 0
-    d.out_pix_stride = 0 if ys == (2 * cout if d.out_split else cout) else ys
-    d.terms = 1 if (use16 and F16_TERMS == 1) else 0
+    # split-K is a matter of the plain f16x3 launch only (None: the field keeps the template's 0)
+    splitk = bool(splitk and SPLITK) if use16 and gn_partial is None else None
+    _stamp_out(d, out, cout, use16, splitk)
     if residual is not None:
-        rs = _pixel_stride(residual, "residual")
-        d.res_split = 1 if is_split(residual) else 0
         if res_mode == 1 and tuple(residual.shape[:3]) != (n, d.oh, d.ow):
             raise ValueError("residual shape mismatch")
         if use16:
-            d.res_pix_stride = rs
-        elif rs != cout:
+            _stamp_residual(d, residual)
+        elif _pixel_stride(residual, "residual") != cout:
             raise ValueError("the f32 kernel needs a dense residual")
     if bias is not None:
         _req(bias, name="bias")
     if in_scale is not None:
-        # [N, Cin] tables, possibly column slices of a wider [N, C] table
-        for t in (in_scale, in_shift):
-            if (not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (n, cin) or t.stride(1) != 1
-                    or t.stride(0) != in_scale.stride(0)):
-                raise ValueError("in_scale / in_shift must be fp32 GPU [N, Cin] tables with equal row stride")
-        d.in_affine_stride = 0 if in_scale.stride(0) == cin else in_scale.stride(0)
-    prof = CONV_PROFILE
-    if prof is not None:
-        timer = HipTimer()
-        timer.start()
+        a_stride = _table_stride(in_scale, in_shift, n, cin, names="in_scale / in_shift", width="Cin")
+        d.in_affine_stride = 0 if a_stride == cin else a_stride
+    timer = _profile_start()
     if use16:
         if (not w16.is_cuda or w16.dtype != torch.float16 or not w16.is_contiguous()
                 or w16.numel() != 2 * w.numel()):
@@ -409,17 +481,12 @@ def conv2d_nhwc(x, w, bias=None, *, stride=1, pad=0, dil=1, relu=False, relu_col
             check(lib.hn_conv2d_nhwc_f16x3_gn(C.byref(d), ptr(x), ptr(w16), ptr(bias), ptr(out), ptr(gn_partial),
                                               _stream()), "hn_conv2d_nhwc_f16x3_gn")
         else:
-            splitk = splitk and SPLITK
-            d.splitk = (1 if SPLITK_EAGER else 0) if splitk else -1
             if force_splits is not None:      # sweeps only: exactly this many splits (1 = none)
                 d.splitk = int(force_splits) if force_splits >= 2 else -1
                 plan_key = None
             ws = _conv_workspace(x.device) if splitk else None
-            if plan_key is not None:
-                if bias is not None and not bias.is_contiguous():
-                    plan_key = None
-                else:
-                    _CONV_PLANS[plan_key] = (ConvDesc.from_buffer_copy(d), tuple(out.shape), out.dtype, bool(splitk))
+            if plan_key is not None and (bias is None or bias.is_contiguous()):
+                _plan_put(plan_key, d, (tuple(out.shape), out.dtype), splitk)
             check(lib.hn_conv2d_nhwc_f16x3_ws(C.byref(d), ptr(x), ptr(w16), ptr(bias), ptr(residual), ptr(out),
                                               ptr(ws), ws.numel() * 4 if splitk else 0, _stream()),
                   "hn_conv2d_nhwc_f16x3_ws")
@@ -428,17 +495,17 @@ def conv2d_nhwc(x, w, bias=None, *, stride=1, pad=0, dil=1, relu=False, relu_col
             raise ValueError("gn_partial is an f16x3-kernel feature")
         check(lib.hn_conv2d_nhwc_f32(C.byref(d), ptr(x), ptr(w), ptr(bias), ptr(residual), ptr(in_scale),
                                      ptr(in_shift), ptr(out), _stream()), "hn_conv2d_nhwc_f32")
-    if prof is not None:
-        timer.stop()
-        macs = n * d.oh * d.ow * cout * r * s * (algo_cin or cin)
-        if use16:
-            flags = TILE_HALO if lib.hn_conv2d_f16x3_uses_halo(C.byref(d), 1 if residual is not None else 0) else \
-                (TILE_STREAM if lib.hn_conv2d_f16x3_uses_stream(C.byref(d)) else
-                 TILE_RS if lib.hn_conv2d_f16x3_uses_rs(C.byref(d)) else 0)
-            kind = ("f16x3", lib.hn_conv2d_f16x3_pick_tile(C.byref(d)) | flags)
-        else:
-            kind = ("f32", lib.hn_conv2d_pick_tile(C.byref(d)))
-        prof.append((kind, macs, timer, (n, h, wd, cin, cout, r, stride, dil), PROFILE_STAGE))
+    if timer is not None:
+        def describe():
+            if use16:
+                flags = TILE_HALO if lib.hn_conv2d_f16x3_uses_halo(C.byref(d), 1 if residual is not None else 0) else \
+                    (TILE_STREAM if lib.hn_conv2d_f16x3_uses_stream(C.byref(d)) else
+                     TILE_RS if lib.hn_conv2d_f16x3_uses_rs(C.byref(d)) else 0)
+                kind = ("f16x3", lib.hn_conv2d_f16x3_pick_tile(C.byref(d)) | flags)
+            else:
+                kind = ("f32", lib.hn_conv2d_pick_tile(C.byref(d)))
+            return kind, n * d.oh * d.ow * cout * r * s * (algo_cin or cin), (n, h, wd, cin, cout, r, stride, dil)
+        _profile_stop(timer, describe)
     return out
 
 
@@ -454,18 +521,17 @@ def conv2d_nhwc_multi(items, fused=None):
     if k == 0 or k > _lib.CONV_MULTI_MAX:
         raise ValueError(f"need 1..{_lib.CONV_MULTI_MAX} members")
     splitk = SPLITK
-    # Plan cache (like conv2d_nhwc's): the validated descriptor table of an earlier call with the same shapes / strides /
-    # weights is stamped out again; only the activation pointers change.
-    key = [splitk, SPLITK_EAGER, F16_TERMS]
+    # Plan (like conv2d_nhwc's): the validated descriptor table of an earlier call with the same shapes / strides / weights
+    # is stamped out again; only the activation pointers change.
+    key = [_lib.ConvMulti]
     for x, cw, opts in items:
         res = opts.get("residual")
         key.append((x.device.index, x.shape, x.stride(), x.dtype, cw.w16.data_ptr() if cw.w16 is not None else None,
                     None if cw.bias is None else cw.bias.data_ptr(), cw.stride, cw.pad, cw.dil, opts.get("relu", False),
                     opts.get("relu_cols"), opts.get("out_split", True),
                     None if res is None else (res.shape, res.stride(), res.dtype)))
-    key = tuple(key)
-    plan = _MULTI_PLANS.get(key) if CONV_PROFILE is None and fused is None else None
-    if plan is not None:
+    key, plan = _plan_get(*key)
+    if plan is not None and CONV_PROFILE is None and fused is None:
         tpl, out_specs, use_ws = plan
         mm = _lib.ConvMulti.from_buffer_copy(tpl)
         outs = []
@@ -495,23 +561,14 @@ def conv2d_nhwc_multi(items, fused=None):
         if channels(x) != cin:
             raise ValueError(f"member {i}: weight Cin {cin} != input channels {channels(x)}")
         xs = _pixel_stride(x, "x")
-        rc = (cout if relu else 0) if relu_cols is None else relu_cols
-        d = make_conv_desc(n, h, wd, cin, cout, r, s_, cw.stride, cw.pad, cw.dil, rc, 1 if residual is not None else 0, 0, 0,
-                           0, 0, in_pix_stride=0 if xs == 2 * cin else xs)
-        if out_split:
-            if cout % 32:
-                raise ValueError("out_split needs Cout % 32 == 0")
-            y = torch.empty((n, d.oh, d.ow, cout // 32, 2, 32), device=x.device, dtype=torch.float16)
-        else:
-            y = torch.empty((n, d.oh, d.ow, cout), device=x.device, dtype=torch.float32)
-        d.out_split = 1 if out_split else 0
-        d.terms = 1 if F16_TERMS == 1 else 0
-        d.splitk = (1 if SPLITK_EAGER else 0) if splitk else -1
+        d = make_conv_desc(n, h, wd, cin, cout, r, s_, cw.stride, cw.pad, cw.dil, _relu_cols(cout, relu, relu_cols),
+                           1 if residual is not None else 0, 0, 0, 0, 0, in_pix_stride=0 if xs == 2 * cin else xs)
+        y = _alloc_out(n, d.oh, d.ow, cout, out_split, x.device)
+        _stamp_out(d, y, cout, splitk=bool(splitk))
         if residual is not None:
             if tuple(residual.shape[:3]) != (n, d.oh, d.ow) or channels(residual) != cout:
                 raise ValueError(f"member {i}: residual shape mismatch")
-            d.res_split = 1 if is_split(residual) else 0
-            d.res_pix_stride = _pixel_stride(residual, "residual")
+            _stamp_residual(d, residual)
         if cw.bias is not None:
             _req(cw.bias, name="bias")
         mm.desc[i] = d
@@ -523,19 +580,16 @@ def conv2d_nhwc_multi(items, fused=None):
     ws = _conv_workspace(items[0][0].device) if splitk else None
     if fused is not None:
         fused.append(bool(lib.hn_conv2d_f16x3_multi_fuses(C.byref(mm), ws.numel() * 4 if splitk else 0)))
-    prof = CONV_PROFILE
-    if prof is not None:
-        timer = HipTimer()
-        timer.start()
+    timer = _profile_start()
     check(lib.hn_conv2d_nhwc_f16x3_multi(C.byref(mm), ptr(ws), ws.numel() * 4 if splitk else 0, _stream()),
           "hn_conv2d_nhwc_f16x3_multi")
-    if prof is not None:
-        timer.stop()
-        big = max(range(k), key=lambda i: shapes[i][0] * shapes[i][1] * shapes[i][2] * shapes[i][3] * shapes[i][4] * shapes[i][5] ** 2)
-        prof.append((("f16x3", lib.hn_conv2d_f16x3_pick_tile(C.byref(mm.desc[big])) | TILE_MULTI), macs, timer, shapes[big],
-                     PROFILE_STAGE))
+    if timer is not None:
+        def describe():     # one record: the largest member's tile and shape, the MACs of all
+            big = max(range(k), key=lambda i: shapes[i][0] * shapes[i][1] * shapes[i][2] * shapes[i][3] * shapes[i][4] * shapes[i][5] ** 2)
+            return ("f16x3", lib.hn_conv2d_f16x3_pick_tile(C.byref(mm.desc[big])) | TILE_MULTI), macs, shapes[big]
+        _profile_stop(timer, describe)
     else:
-        _MULTI_PLANS[key] = (_lib.ConvMulti.from_buffer_copy(mm), [(tuple(y.shape), y.dtype) for y in outs], bool(splitk))
+        _plan_put(key, mm, [(tuple(y.shape), y.dtype) for y in outs], splitk)
     return outs
 
 
@@ -564,19 +618,14 @@ def conv2d_nhwc_grouped(xs, ws, *, pad=0, relu=False, relu_cols=None, out_split=
     lib = _lib.load()
     cout, r, s, cin = ws[0].w.shape
     x0 = xs[0]
-    xstride = _pixel_stride(x0, "x")
-    n = x0.shape[0]
-    for x, cw in zip(xs, ws):
-        if not is_split(x) or x.shape[0] != n or channels(x) != cin or _pixel_stride(x, "x") != xstride:
-            raise ValueError("grouped inputs must be S32 tensors of one batch size, channel count and pixel stride")
+    n, xstride = _s32_levels(xs, cin, "grouped inputs")
+    for cw in ws:
         if tuple(cw.w.shape) != (cout, r, s, cin) or cw.w16 is None or (cw.bias is None) != (ws[0].bias is None):
             raise ValueError("grouped weights must share one shape (and all or none have a bias)")
-    rc = (cout if relu else 0) if relu_cols is None else relu_cols
+    rc = _relu_cols(cout, relu, relu_cols)
     h0, w0 = x0.shape[1:3]
     d = make_conv_desc(n, h0, w0, cin, cout, r, s, 1, pad, 1, rc, 0, 0, 0, 0, tile,
                        in_pix_stride=0 if xstride == 2 * cin else xstride)
-    d.splitk = -1
-    d.terms = 1 if F16_TERMS == 1 else 0
     if gn_partials is not None:
         if gn is not None or len(gn_partials) != k:
             raise ValueError("give gn_partials (one per member) or gn, not both")
@@ -585,14 +634,9 @@ def conv2d_nhwc_grouped(xs, ws, *, pad=0, relu=False, relu_cols=None, out_split=
         raise ValueError("GroupNorm sums need fp32 outputs without ReLU")
     sizes = [conv_out_size(x.shape[1], x.shape[2], r, s, 1, pad, 1) for x in xs]
     if outs is None:
-        if out_split:
-            outs = [torch.empty((n, oh, ow, cout // 32, 2, 32), device=x0.device, dtype=torch.float16) for oh, ow in sizes]
-        else:
-            outs = [torch.empty((n, oh, ow, cout), device=x0.device, dtype=torch.float32) for oh, ow in sizes]
+        outs = [_alloc_out(n, oh, ow, cout, out_split, x0.device) for oh, ow in sizes]
     offs = [0] * k if out_channel_offsets is None else list(out_channel_offsets)
-    ystride = _pixel_stride(outs[0], "out")
-    d.out_split = 1 if is_split(outs[0]) else 0
-    d.out_pix_stride = 0 if ystride == (2 * cout if d.out_split else cout) else ystride
+    ystride = _stamp_out(d, outs[0], cout, splitk=False)
     grp = ConvGroup()
     grp.count = k
     grp.gn_units = int(gn_units)
@@ -614,10 +658,7 @@ def conv2d_nhwc_grouped(xs, ws, *, pad=0, relu=False, relu_cols=None, out_split=
             grp.gn_partial[i] = buf.data_ptr() + 16 * uoff
     if carry_query:
         return bool(lib.hn_conv2d_f16x3_grouped_carry_applies(C.byref(d), C.byref(grp)))
-    prof = CONV_PROFILE
-    if prof is not None:
-        timer = HipTimer()
-        timer.start()
+    timer = _profile_start()
     if carry is not None:
         cxs, caff, couts, crelu = carry
         lv, cn, cc, cxstride, ca_stride, cystride, _ = _split_levels_arg(cxs, caff, couts)
@@ -625,15 +666,16 @@ def conv2d_nhwc_grouped(xs, ws, *, pad=0, relu=False, relu_cols=None, out_split=
                                                      ca_stride, cystride, _stream()), "hn_conv2d_nhwc_f16x3_grouped_carry")
     else:
         check(lib.hn_conv2d_nhwc_f16x3_grouped(C.byref(d), C.byref(grp), _stream()), "hn_conv2d_nhwc_f16x3_grouped")
-    if prof is not None:
-        timer.stop()
-        rows = sum(n * oh * ow for oh, ow in sizes)
-        tot = make_conv_desc(1, rows, 1, cin, cout, 1, 1)          # what the tile heuristic saw: all rows together
-        tile = lib.hn_conv2d_f16x3_pick_tile(C.byref(tot))
-        q = ConvDesc.from_buffer_copy(d)                           # geometry of the launch, picked tile, narrowest member
-        q.tile, q.w = tile, min(ow for _, ow in sizes)
-        prof.append((("f16x3", tile | (TILE_RS if lib.hn_conv2d_f16x3_uses_rs(C.byref(q)) else 0)), rows * cout * r * s * cin,
-                     timer, (1, rows, 1, cin, cout, r, 1, 1), PROFILE_STAGE))
+    if timer is not None:
+        def describe():
+            rows = sum(n * oh * ow for oh, ow in sizes)
+            tot = make_conv_desc(1, rows, 1, cin, cout, 1, 1)          # what the tile heuristic saw: all rows together
+            picked = lib.hn_conv2d_f16x3_pick_tile(C.byref(tot))
+            q = ConvDesc.from_buffer_copy(d)                           # geometry of the launch, picked tile, narrowest member
+            q.tile, q.w = picked, min(ow for _, ow in sizes)
+            return (("f16x3", picked | (TILE_RS if lib.hn_conv2d_f16x3_uses_rs(C.byref(q)) else 0)), rows * cout * r * s * cin,
+                    (1, rows, 1, cin, cout, r, 1, 1))
+        _profile_stop(timer, describe)
     return outs
 
 
@@ -646,28 +688,18 @@ def conv3x3_thin_levels(xs, cw, relu_cols=0):
     cout, r, s, cin = cw.w.shape
     if (r, s) != (3, 3) or cout > 16 or cw.w16 is None or len(xs) > _lib.HN_FCOS_MAX_LEVELS:
         raise ValueError("conv3x3_thin_levels needs a 3x3 filter bank with <= 16 output channels and a split bank")
-    n = xs[0].shape[0]
-    xstride = _pixel_stride(xs[0], "x")
-    lv = _lib.ThinLevels()
-    lv.count = len(xs)
-    outs = []
-    for i, x in enumerate(xs):
-        if not is_split(x) or x.shape[0] != n or channels(x) != cin or _pixel_stride(x, "x") != xstride:
-            raise ValueError("levels must be S32 tensors of one batch size, channel count and pixel stride")
-        y = torch.empty((n, x.shape[1], x.shape[2], cout), device=x.device, dtype=torch.float32)
-        lv.x16[i], lv.y[i], lv.h[i], lv.w[i] = x.data_ptr(), y.data_ptr(), x.shape[1], x.shape[2]
-        outs.append(y)
-    prof = CONV_PROFILE
-    if prof is not None:
-        timer = HipTimer()
-        timer.start()
+    n, xstride = _s32_levels(xs, cin)
+    lv = _thin_levels_of(xs, inputs=True)
+    outs = _thin_outs(lv, xs, cout)
+    timer = _profile_start()
     check(lib.hn_conv3x3_thin_f16x3_levels(C.byref(lv), n, cin, cout, ptr(cw.w16), ptr(cw.bias), int(relu_cols),
                                            0 if xstride == 2 * cin else xstride, _stream()), "hn_conv3x3_thin_f16x3_levels")
-    if prof is not None:
-        timer.stop()
-        rows = sum(n * x.shape[1] * x.shape[2] for x in xs)
-        form = "thin-P" if lib.hn_conv3x3_thin_uses_flat(C.byref(lv), n, cin, cout) else "thin16x16"
-        prof.append((("f16x3", form), rows * cout * 9 * cin, timer, (1, rows, 1, cin, cout, 3, 1, 1), PROFILE_STAGE))
+    if timer is not None:
+        def describe():
+            rows = _rows(xs)
+            form = "thin-P" if lib.hn_conv3x3_thin_uses_flat(C.byref(lv), n, cin, cout) else "thin16x16"
+            return ("f16x3", form), rows * cout * 9 * cin, (1, rows, 1, cin, cout, 3, 1, 1)
+        _profile_stop(timer, describe)
     return outs
 
 
@@ -679,56 +711,54 @@ def conv3x3_thin_levels_group(members):
     lib = _lib.load()
     if not 1 <= len(members) <= 3:
         raise ValueError("1..3 members")
-    n = members[0][0][0].shape[0]
     cin = members[0][1].w.shape[3]
-    xstride = _pixel_stride(members[0][0][0], "x")
+    n, xstride = _s32_levels([x for xs, _, _ in members for x in xs], cin)
     arr = (_lib.ThinMember * len(members))()
     results = []
-    rows = 0
     for m, (xs, cw, relu_cols) in enumerate(members):
         cout, r, s_, c = cw.w.shape
         if (r, s_) != (3, 3) or cout > 16 or cw.w16 is None or len(xs) > _lib.HN_FCOS_MAX_LEVELS or c != cin:
             raise ValueError("members need 3x3 filter banks with <= 16 output channels, a split bank and one input channel count")
         mm = arr[m]
-        mm.lv.count = len(xs)
-        outs = []
-        for i, x in enumerate(xs):
-            if not is_split(x) or x.shape[0] != n or channels(x) != cin or _pixel_stride(x, "x") != xstride:
-                raise ValueError("levels must be S32 tensors of one batch size, channel count and pixel stride")
-            y = torch.empty((n, x.shape[1], x.shape[2], cout), device=x.device, dtype=torch.float32)
-            mm.lv.x16[i], mm.lv.y[i], mm.lv.h[i], mm.lv.w[i] = x.data_ptr(), y.data_ptr(), x.shape[1], x.shape[2]
-            outs.append(y)
+        mm.lv = _thin_levels_of(xs, inputs=True)
+        results.append(_thin_outs(mm.lv, xs, cout))
         mm.cout, mm.relu_cols, mm.w16, mm.bias = cout, int(relu_cols), ptr(cw.w16), ptr(cw.bias)
-        results.append(outs)
-        rows += sum(n * x.shape[1] * x.shape[2] for x in xs) * cout
-    prof = CONV_PROFILE
-    if prof is not None:
-        timer = HipTimer()
-        timer.start()
+    timer = _profile_start()
     check(lib.hn_conv3x3_thin_f16x3_levels_group(arr, len(members), n, cin, 0 if xstride == 2 * cin else xstride, _stream()),
           "hn_conv3x3_thin_f16x3_levels_group")
-    if prof is not None:
-        timer.stop()
-        flat = any(lib.hn_conv3x3_thin_uses_flat(C.byref(arr[m].lv), n, cin, arr[m].cout) for m in range(len(members)))
-        px = sum(n * x.shape[1] * x.shape[2] for x in members[0][0])
-        couts = sum(mm[1].w.shape[0] for mm in members)
-        prof.append((("f16x3", "thin-P" if flat else f"thin16x16x{len(members)}"), rows * 9 * cin, timer,
-                     (1, px, 1, cin, couts, 3, 1, 1), PROFILE_STAGE))
+    if timer is not None:
+        def describe():     # the shape: member 0's pixels by the output channels of all members
+            flat = any(lib.hn_conv3x3_thin_uses_flat(C.byref(arr[m].lv), n, cin, arr[m].cout) for m in range(len(members)))
+            macs = sum(_rows(xs) * cw.w.shape[0] for xs, cw, _ in members) * 9 * cin
+            couts = sum(cw.w.shape[0] for _, cw, _ in members)
+            return ("f16x3", "thin-P" if flat else f"thin16x16x{len(members)}"), macs, (1, _rows(members[0][0]), 1, cin, couts, 3, 1, 1)
+        _profile_stop(timer, describe)
     return results
 
 
-def _thin_levels_of(shapes):
+def _thin_levels_of(ts, inputs=False):
+    """hn_thin_levels with the sizes of the maps ts (and, for a launch on S32 maps, their addresses as its inputs)."""
     lv = _lib.ThinLevels()
-    lv.count = len(shapes)
-    for i, (h, w) in enumerate(shapes):
-        lv.h[i], lv.w[i] = h, w
+    lv.count = len(ts)
+    for i, t in enumerate(ts):
+        lv.h[i], lv.w[i] = t.shape[1], t.shape[2]
+        if inputs:
+            lv.x16[i] = t.data_ptr()
     return lv
+
+
+def _thin_outs(lv, ts, cout):
+    """Fresh fp32 [N,h_l,w_l,Cout] outputs of a thin launch on the maps ts, their addresses stamped into lv."""
+    outs = [torch.empty((t.shape[0], t.shape[1], t.shape[2], cout), device=t.device, dtype=torch.float32) for t in ts]
+    for i, y in enumerate(outs):
+        lv.y[i] = y.data_ptr()
+    return outs
 
 
 def thin_affine_applies(ts, cw) -> bool:
     """Would conv3x3_thin_affine_levels take these raw tower outputs ts (fp32 [N,h_l,w_l,C]) with filter bank cw?"""
     cout, _, _, cin = cw.w.shape
-    lv = _thin_levels_of([t.shape[1:3] for t in ts])
+    lv = _thin_levels_of(ts)
     return len(ts) <= _lib.HN_FCOS_MAX_LEVELS and bool(_lib.load().hn_conv3x3_thin_affine_applies(C.byref(lv), ts[0].shape[0], cin, cout))
 
 
@@ -739,45 +769,32 @@ def conv3x3_thin_affine_levels(ts, affines, ch0, cw, relu_cols=0):
     conv3x3_thin_levels(to_split_levels(ts, affines)[..., ch0 // 32 : (ch0 + cin) // 32], cw) bit for bit, without the pass."""
     lib = _lib.load()
     cout, r, s, cin = cw.w.shape
-    n, c = ts[0].shape[0], ts[0].shape[3]
+    c = ts[0].shape[3]
     if (r, s) != (3, 3) or cw.w16 is None or ch0 % 32 or ch0 + cin > c:
         raise ValueError("conv3x3_thin_affine_levels needs a split 3x3 filter bank and a 32-aligned channel range")
-    xstride = _pixel_stride(ts[0], "x")
+    n, xstride = _f32_levels(ts, c)
     a_stride = affines[0][0].stride(0)
-    lv, aff = _thin_levels_of([t.shape[1:3] for t in ts]), _lib.ThinAffine()
+    lv, aff = _thin_levels_of(ts), _lib.ThinAffine()
     aff.in_pix_stride, aff.affine_stride = xstride, a_stride
-    outs = []
     for i, (t, (scale, shift)) in enumerate(zip(ts, affines)):
-        if t.dtype != torch.float32 or is_split(t) or t.shape[0] != n or t.shape[3] != c or _pixel_stride(t, "x") != xstride:
-            raise ValueError("levels must be fp32 NHWC tensors of one batch size, channel count and pixel stride")
-        for q in (scale, shift):
-            if not q.is_cuda or q.dtype != torch.float32 or tuple(q.shape) != (n, c) or q.stride(1) != 1 or q.stride(0) != a_stride:
-                raise ValueError("scale / shift must be fp32 GPU [N, C] tables with equal row stride")
-        y = torch.empty((n, t.shape[1], t.shape[2], cout), device=t.device, dtype=torch.float32)
+        _table_stride(scale, shift, n, c, a_stride)
         aff.x[i], aff.scale[i], aff.shift[i] = t.data_ptr() + 4 * ch0, scale.data_ptr() + 4 * ch0, shift.data_ptr() + 4 * ch0
-        lv.y[i] = y.data_ptr()
-        outs.append(y)
-    prof = CONV_PROFILE
-    if prof is not None:
-        timer = HipTimer()
-        timer.start()
+    outs = _thin_outs(lv, ts, cout)
+    timer = _profile_start()
     check(lib.hn_conv3x3_thin_affine_f16x3_levels(C.byref(lv), C.byref(aff), n, cin, cout, ptr(cw.w16), ptr(cw.bias),
                                                   int(relu_cols), _stream()), "hn_conv3x3_thin_affine_f16x3_levels")
-    if prof is not None:
-        timer.stop()
-        rows = sum(n * t.shape[1] * t.shape[2] for t in ts)
-        prof.append((("f16x3", "thin-P+gn"), rows * cout * 9 * cin, timer, (1, rows, 1, cin, cout, 3, 1, 1), PROFILE_STAGE))
+    if timer is not None:
+        def describe():
+            rows = _rows(ts)
+            return ("f16x3", "thin-P+gn"), rows * cout * 9 * cin, (1, rows, 1, cin, cout, 3, 1, 1)
+        _profile_stop(timer, describe)
     return outs
 
 
 def thin_uses_flat(xs, cw) -> bool:
     """Would conv3x3_thin_levels(xs, cw) run the P-form kernel (True) or the tap kernel (False)?"""
-    lv = _lib.ThinLevels()
-    lv.count = len(xs)
-    for i, x in enumerate(xs):
-        lv.h[i], lv.w[i] = x.shape[1], x.shape[2]
     cout, _, _, cin = cw.w.shape
-    return bool(_lib.load().hn_conv3x3_thin_uses_flat(C.byref(lv), xs[0].shape[0], cin, cout))
+    return bool(_lib.load().hn_conv3x3_thin_uses_flat(C.byref(_thin_levels_of(xs)), xs[0].shape[0], cin, cout))
 
 
 def maxpool3x3s2_nhwc(x, out=None):
@@ -860,24 +877,19 @@ def _split_levels_arg(xs, affines, outs=None):
     """The levels of one apply pass as the library takes them -> (hn_split_levels, n, c, x stride, table stride, out stride, outs).
     xs: fp32 [N,h_l,w_l,C] (channel slices of wider tensors are fine); affines: [(scale, shift)] [N,C] tables; outs: S32
     [N,h_l,w_l,C/32,2,32] destinations (block slices of wider tensors are fine), default fresh dense ones."""
-    n, _, _, c = xs[0].shape
-    xstride = _pixel_stride(xs[0], "x")
+    c = xs[0].shape[3]
     a_stride = affines[0][0].stride(0)
     if len(xs) > _lib.HN_FCOS_MAX_LEVELS or len(affines) != len(xs) or (outs is not None and len(outs) != len(xs)):
         raise ValueError(f"need 1..{_lib.HN_FCOS_MAX_LEVELS} levels with one (scale, shift) pair (and one output) each")
+    n, xstride = _f32_levels(xs, c)
     lv = _lib.SplitLevels()
     lv.count = len(xs)
     made = []
     ystride = None
     for i, (x, (scale, shift)) in enumerate(zip(xs, affines)):
-        if x.shape[0] != n or x.shape[3] != c or _pixel_stride(x, "x") != xstride or is_split(x) or x.dtype != torch.float32:
-            raise ValueError("levels must be fp32 NHWC tensors of one batch size, channel count and pixel stride")
-        for t in (scale, shift):
-            if (not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (n, c) or t.stride(1) != 1
-                    or t.stride(0) != a_stride):
-                raise ValueError("scale / shift must be fp32 GPU [N, C] tables with equal row stride")
+        _table_stride(scale, shift, n, c, a_stride)
         if outs is None:
-            out = torch.empty((n, x.shape[1], x.shape[2], c // 32, 2, 32), device=x.device, dtype=torch.float16)
+            out = _alloc_out(n, x.shape[1], x.shape[2], c, True, x.device)
         else:
             out = outs[i]
             if not is_split(out) or tuple(out.shape) != (n, x.shape[1], x.shape[2], c // 32, 2, 32) or out.device != x.device:
@@ -1058,35 +1070,31 @@ def fcos_preprocess_list(images, geom, ph, pw, mean, std, split=True, border=3):
     return out
 
 
-def conv_stem_split(x16, w16, bias, cout, r=7, stride=2, relu=True, out_split=True, algo_cin=3, out=None):
-    """Stem conv on the f16x3 kernel.  x16: stem image from fcos_preprocess_split (border = r // 2);
-    w16: weights.pack_stem_split(...).w16.  -> [N, oh, ow, cout] fp32 or S32."""
-    lib = _lib.load()
+def _stem_sizes(x16, w16, cout, r, stride):
+    """Stem image and packed filter bank of a stem launch -> (N, image height, image width, border, conv output height, width)."""
     pad = r // 2
     if x16.dim() != 5 or x16.shape[0] != 2 or x16.shape[4] != 4 or x16.dtype != torch.float16 or not x16.is_cuda \
             or not x16.is_contiguous():
         raise ValueError("x16 must be the contiguous fp16 GPU stem image [2, N, H+2p, W+2p, 4]")
     n, hb, wb = x16.shape[1:4]
-    ph, pw = hb - 2 * pad, wb - 2 * pad
-    oh, ow = (hb - r) // stride + 1, (wb - r) // stride + 1
     if tuple(w16.shape) != (cout, r, 2, 32) or w16.dtype != torch.float16 or not w16.is_cuda or not w16.is_contiguous():
         raise ValueError("w16 must be the fp16 GPU tensor [cout, r, 2, 32] from weights.pack_stem_split")
+    return n, hb - 2 * pad, wb - 2 * pad, pad, (hb - r) // stride + 1, (wb - r) // stride + 1
+
+
+def conv_stem_split(x16, w16, bias, cout, r=7, stride=2, relu=True, out_split=True, algo_cin=3, out=None):
+    """Stem conv on the f16x3 kernel.  x16: stem image from fcos_preprocess_split (border = r // 2);
+    w16: weights.pack_stem_split(...).w16.  -> [N, oh, ow, cout] fp32 or S32."""
+    lib = _lib.load()
+    n, ph, pw, pad, oh, ow = _stem_sizes(x16, w16, cout, r, stride)
     if out is None:
-        if out_split:
-            out = torch.empty((n, oh, ow, cout // 32, 2, 32), device=x16.device, dtype=torch.float16)
-        else:
-            out = torch.empty((n, oh, ow, cout), device=x16.device, dtype=torch.float32)
-    prof = CONV_PROFILE
-    if prof is not None:
-        timer = HipTimer()
-        timer.start()
+        out = _alloc_out(n, oh, ow, cout, out_split, x16.device)
+    timer = _profile_start()
     check(lib.hn_conv_stem_f16x3(ptr(x16), n, ph, pw, pad, r, stride, cout, ptr(w16), ptr(bias), 1 if relu else 0,
                                  ptr(out), 1 if is_split(out) else 0, _stream()), "hn_conv_stem_f16x3")
-    if prof is not None:
-        timer.stop()
+    if timer is not None:
         tile = 4 if cout <= 32 else (2 if cout <= 64 else 1)  # HN_TILE_128x32 / 128x64 / 128x128
-        prof.append((("f16x3", tile), n * oh * ow * cout * r * r * algo_cin, timer, (n, ph, pw, 4, cout, r, stride, 1),
-                     PROFILE_STAGE))
+        _profile_stop(timer, lambda: (("f16x3", tile), n * oh * ow * cout * r * r * algo_cin, (n, ph, pw, 4, cout, r, stride, 1)))
     return out
 
 
@@ -1097,29 +1105,16 @@ def conv_stem_pool_split(x16, w16, bias, cout=64, r=7, stride=2, algo_cin=3, out
     fp16 rounding midpoint whose (hi, lo) pairs recombine to the same sum: this kernel splits the maximum, the unfused pooling
     copies the first such pair (tests/test_stem_gpu.py, equal-sum pairs)."""
     lib = _lib.load()
-    pad = r // 2
-    if x16.dim() != 5 or x16.shape[0] != 2 or x16.shape[4] != 4 or x16.dtype != torch.float16 or not x16.is_cuda \
-            or not x16.is_contiguous():
-        raise ValueError("x16 must be the contiguous fp16 GPU stem image [2, N, H+2p, W+2p, 4]")
+    n, ph, pw, pad, oh, ow = _stem_sizes(x16, w16, cout, r, stride)
     _check_device(x16, "x16")
-    n, hb, wb = x16.shape[1:4]
-    ph, pw = hb - 2 * pad, wb - 2 * pad
-    oh, ow = (hb - r) // stride + 1, (wb - r) // stride + 1
-    poh, pow_ = (oh + 2 - 3) // 2 + 1, (ow + 2 - 3) // 2 + 1
-    if tuple(w16.shape) != (cout, r, 2, 32) or w16.dtype != torch.float16 or not w16.is_cuda or not w16.is_contiguous():
-        raise ValueError("w16 must be the fp16 GPU tensor [cout, r, 2, 32] from weights.pack_stem_split")
     if out is None:
-        out = torch.empty((n, poh, pow_, cout // 32, 2, 32), device=x16.device, dtype=torch.float16)
-    prof = CONV_PROFILE
-    if prof is not None:
-        timer = HipTimer()
-        timer.start()
+        out = _alloc_out(n, (oh + 2 - 3) // 2 + 1, (ow + 2 - 3) // 2 + 1, cout, True, x16.device)
+    timer = _profile_start()
     check(lib.hn_conv_stem_pool_f16x3_terms(ptr(x16), n, ph, pw, pad, r, stride, cout, ptr(w16), ptr(bias), ptr(out),
                                             1 if F16_TERMS == 1 else 3, _stream()), "hn_conv_stem_pool_f16x3_terms")
-    if prof is not None:
-        timer.stop()
+    if timer is not None:
         # algorithmic work = the stem convolution as the reference executes it (the patch halo is overhead, not work)
-        prof.append((("f16x3", 8), n * oh * ow * cout * r * r * algo_cin, timer, (n, ph, pw, 4, cout, r, stride, 1), PROFILE_STAGE))
+        _profile_stop(timer, lambda: (("f16x3", 8), n * oh * ow * cout * r * r * algo_cin, (n, ph, pw, 4, cout, r, stride, 1)))
     return out
 
 
@@ -1453,6 +1448,34 @@ def pack_depth_nhwc(depth, cpad=4, out=None):
     return out
 
 
+def _convert_arg(convert, k, joints, device):
+    """The `convert` dict of a2j_aggregate / a2j_loss as the library takes it -> (crop_box or None, crop side, paras array or
+    None, ConvertOpts or None, image_uvd, xyz_mm or None); the two outputs are fresh where the dict brings none."""
+    # the evaluation caller's operands (a2j/a2j.py:339-346): the dataset's fp32 boxes / per-sample intrinsics on the device
+    sbox, sparas = convert.get("sample_box"), convert.get("sample_paras")
+    box = convert.get("crop_box")
+    if (box is None) == (sbox is None):
+        raise ValueError("convert needs crop_box (int64, the detector's) or sample_box (fp32, the dataset's), one of them")
+    for t, dt, nm in ((box, torch.int64, "crop_box"), (sbox, torch.float32, "sample_box"), (sparas, torch.float32, "sample_paras")):
+        if t is not None and tuple(_req(t, dt, nm).shape) != (k, 4):
+            raise ValueError(f"{nm} must be [K,4]")
+    paras = convert.get("paras")
+    if paras is not None and sparas is not None:
+        raise ValueError("convert: paras (one camera) or sample_paras (one per sample), not both")
+    img, xyz = convert.get("image_uvd"), convert.get("xyz_mm")
+    if img is None:
+        img = torch.empty((k, joints, 3), device=device, dtype=torch.float32)
+    if xyz is None and (paras is not None or sparas is not None):
+        xyz = torch.empty((k, joints, 3), device=device, dtype=torch.float32)
+    pp = (C.c_float * 4)(*[float(v) for v in paras]) if paras is not None else None
+    opts = None
+    cb = convert.get("clamp_box")
+    if convert.get("clamp_keypoints") or cb or sbox is not None or sparas is not None:
+        opts = _lib.ConvertOpts(1 if convert.get("clamp_keypoints") else 0, int(cb[0]) if cb else 0, int(cb[1]) if cb else 0, 0,
+                                ptr(sbox), ptr(sparas))
+    return box, float(convert.get("crop", 176)), pp, opts, img, xyz
+
+
 def a2j_aggregate(cls, reg, dep, joints=21, stride=16, valid=None, out=None, convert=None):
     """cls/dep [K,fh,fw,16*J], reg [K,fh,fw,16*J*2] -> [K,J,3].
     convert: optional dict -- convert_joints + uvd2xyz in the SAME launch (hn_a2j_aggregate_convert_f32):
@@ -1474,30 +1497,7 @@ def a2j_aggregate(cls, reg, dep, joints=21, stride=16, valid=None, out=None, con
     if valid is not None:
         _req(valid, torch.int32, "valid")
     if convert is not None:
-        # the evaluation caller's operands (a2j/a2j.py:339-346): the dataset's fp32 boxes / per-sample intrinsics on the device
-        sbox, sparas = convert.get("sample_box"), convert.get("sample_paras")
-        box = convert.get("crop_box")
-        if (box is None) == (sbox is None):
-            raise ValueError("convert needs crop_box (int64, the detector's) or sample_box (fp32, the dataset's), one of them")
-        for t, dt, nm in ((box, torch.int64, "crop_box"), (sbox, torch.float32, "sample_box"), (sparas, torch.float32, "sample_paras")):
-            if t is not None and tuple(_req(t, dt, nm).shape) != (k, 4):
-                raise ValueError(f"{nm} must be [K,4]")
-        paras = convert.get("paras")
-        if paras is not None and sparas is not None:
-            raise ValueError("convert: paras (one camera) or sample_paras (one per sample), not both")
-        img = convert.get("image_uvd")
-        xyz = convert.get("xyz_mm")
-        if img is None:
-            img = torch.empty((k, joints, 3), device=cls.device, dtype=torch.float32)
-        if xyz is None and (paras is not None or sparas is not None):
-            xyz = torch.empty((k, joints, 3), device=cls.device, dtype=torch.float32)
-        pp = (C.c_float * 4)(*[float(v) for v in paras]) if paras is not None else None
-        opts = None
-        cb = convert.get("clamp_box")
-        if convert.get("clamp_keypoints") or cb or sbox is not None or sparas is not None:
-            opts = _lib.ConvertOpts(1 if convert.get("clamp_keypoints") else 0, int(cb[0]) if cb else 0, int(cb[1]) if cb else 0, 0,
-                                    ptr(sbox), ptr(sparas))
-        crop = float(convert.get("crop", 176))
+        box, crop, pp, opts, img, xyz = _convert_arg(convert, k, joints, cls.device)
         mirror = convert.get("mirror")
         if mirror is not None:
             if _req(mirror, torch.int32, "mirror").numel() != k:
@@ -1546,32 +1546,12 @@ def a2j_loss(cls, reg, dep, gt, joints=21, stride=16, spatial_factor=0.5, reg_lo
     sample = torch.empty((k, 2), device=dev, dtype=torch.float32)
     # (no crop at all: nothing is launched, and the batch values are the mean of nothing)
     batch = torch.empty((5,), device=dev, dtype=torch.float32) if k else torch.full((5,), float("nan"), device=dev)
-    box = sbox = sparas = img = xyz = pp = opts = None
+    box = img = xyz = pp = opts = None
     crop = 0.0
     if convert is not None:
         if convert.get("mirror") is not None:
             raise ValueError("a2j_loss: convert takes no mirror flags")
-        sbox, sparas = convert.get("sample_box"), convert.get("sample_paras")
-        box = convert.get("crop_box")
-        if (box is None) == (sbox is None):
-            raise ValueError("convert needs crop_box (int64, the detector's) or sample_box (fp32, the dataset's), one of them")
-        for t, dt, nm in ((box, torch.int64, "crop_box"), (sbox, torch.float32, "sample_box"), (sparas, torch.float32, "sample_paras")):
-            if t is not None and tuple(_req(t, dt, nm).shape) != (k, 4):
-                raise ValueError(f"{nm} must be [K,4]")
-        paras = convert.get("paras")
-        if paras is not None and sparas is not None:
-            raise ValueError("convert: paras (one camera) or sample_paras (one per sample), not both")
-        img, xyz = convert.get("image_uvd"), convert.get("xyz_mm")
-        if img is None:
-            img = torch.empty((k, joints, 3), device=dev, dtype=torch.float32)
-        if xyz is None and (paras is not None or sparas is not None):
-            xyz = torch.empty((k, joints, 3), device=dev, dtype=torch.float32)
-        pp = (C.c_float * 4)(*[float(v) for v in paras]) if paras is not None else None
-        cb = convert.get("clamp_box")
-        if convert.get("clamp_keypoints") or cb or sbox is not None or sparas is not None:
-            opts = _lib.ConvertOpts(1 if convert.get("clamp_keypoints") else 0, int(cb[0]) if cb else 0, int(cb[1]) if cb else 0, 0,
-                                    ptr(sbox), ptr(sparas))
-        crop = float(convert.get("crop", 176))
+        box, crop, pp, opts, img, xyz = _convert_arg(convert, k, joints, dev)
     res = out if convert is None else (out, img, xyz)
     if k == 0:
         return res, terms, sample, batch
