@@ -10,6 +10,7 @@
 //   hn_crop_resize         : handnet_pipeline/handnet_pipeline.py:74-105
 //   hn_crop_resize_hands   : the same rule for the first K hand detections of each frame (K crops per frame)
 #include "hn_common.h"
+#include "fcos_points.h"
 
 #pragma clang fp contract(off)
 
@@ -232,13 +233,7 @@ __global__ __launch_bounds__(256) void fcos_preprocess_split_tiled_kernel(const 
 // ---------------------------------------------------------------------------------------
 // candidates: score / argmax / threshold / decode / ordered compaction
 // ---------------------------------------------------------------------------------------
-struct LevelTable {
-  int num_levels;
-  int h[HN_FCOS_MAX_LEVELS], w[HN_FCOS_MAX_LEVELS], stride[HN_FCOS_MAX_LEVELS];
-  int start[HN_FCOS_MAX_LEVELS + 1];  // first point index of each level
-  const float* cls_lr[HN_FCOS_MAX_LEVELS];
-  const float* reg_ctr[HN_FCOS_MAX_LEVELS];
-};
+using hn_fcos::LevelTable;   // fcos_points.h: the level table, a point's level and anchor (shared with fcos_loss.hip)
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
@@ -252,8 +247,7 @@ struct CandPoint {
 };
 __device__ __forceinline__ bool eval_point(const LevelTable& lt, int img, int i, int num_classes, int cw, float thresh,
                                            CandPoint& o) {
-  int lv = 0;
-  while (lv + 1 < lt.num_levels && i >= lt.start[lv + 1]) ++lv;
+  const int lv = hn_fcos::point_level(lt, i);
   o.lvl = lv;
   const int q = i - lt.start[lv];
   const int hw = lt.h[lv] * lt.w[lv];
@@ -277,17 +271,11 @@ __device__ __forceinline__ bool eval_point(const LevelTable& lt, int img, int i,
   if (pass) {
     const float s0 = sigmoidf_(pc[num_classes]), s1 = sigmoidf_(pc[num_classes + 1]);
     o.side = s1 > s0 ? 1 : 0;
-    const int gy = q / lt.w[lv], gx = q - gy * lt.w[lv];
-    const float st = (float)lt.stride[lv];
-    const float half = rintf(st * 0.5f);  // base anchor [-s/2, -s/2, s/2, s/2].round()
-    const float ax0 = (float)(gx * lt.stride[lv]) - half, ay0 = (float)(gy * lt.stride[lv]) - half;
-    const float ax1 = (float)(gx * lt.stride[lv]) + half, ay1 = (float)(gy * lt.stride[lv]) + half;
-    const float cx = 0.5f * (ax0 + ax1), cy = 0.5f * (ay0 + ay1);
-    const float bw = ax1 - ax0, bh = ay1 - ay0;
-    o.x0 = cx - pr[0] * bw;
-    o.y0 = cy - pr[1] * bh;
-    o.x1 = cx + pr[2] * bw;
-    o.y1 = cy + pr[3] * bh;
+    const hn_fcos::PointAnchor a = hn_fcos::point_anchor(lt, lv, q);
+    o.x0 = a.cx - pr[0] * a.bw;
+    o.y0 = a.cy - pr[1] * a.bh;
+    o.x1 = a.cx + pr[2] * a.bw;
+    o.y1 = a.cy + pr[3] * a.bh;
   }
   return pass;
 }
@@ -470,11 +458,11 @@ __global__ __launch_bounds__(256) void fcos_ext_gather_kernel(const ExtTable et,
     int lvl = 0;
     while (lvl + 1 < et.num_levels && pt >= et.start[lvl + 1]) ++lvl;
     const float* e = et.ext[lvl] + ((long)img * et.hw[lvl] + (pt - et.start[lvl])) * 8;
-    const float dx = e[1], dy = e[2];
-    const float denom = fmaxf(sqrtf(dx * dx + dy * dy), 1e-12f);
-    dxdymags[i * 3 + 0] = e[0];
-    dxdymags[i * 3 + 1] = 0.1f * (dx / denom);
-    dxdymags[i * 3 + 2] = 0.1f * (dy / denom);
+    float m3[3];
+    hn_fcos::ext_dxdymag(e, m3);
+    dxdymags[i * 3 + 0] = m3[0];
+    dxdymags[i * 3 + 1] = m3[1];
+    dxdymags[i * 3 + 2] = m3[2];
     int best = 0;
     float bs = sigmoidf_(e[3]);
     for (int c = 1; c < 5; ++c) {
@@ -1352,22 +1340,7 @@ static int candidates_run(const hn_fcos_levels* lv, int n, int num_classes, floa
   HN_CHECK_ARG(lv->num_levels > 0 && lv->num_levels <= HN_FCOS_MAX_LEVELS, "bad level count");
   HN_CHECK_ARG(n > 0 && num_classes > 0 && num_classes <= 64 && cap > 0, "bad dims");
   LevelTable lt;
-  lt.num_levels = lv->num_levels;
-  lt.start[0] = 0;
-  for (int l = 0; l < lv->num_levels; ++l) {
-    HN_CHECK_ARG(lv->h[l] > 0 && lv->w[l] > 0 && lv->stride[l] > 0 && lv->cls_lr[l] && lv->reg_ctr[l], "bad level %d", l);
-    lt.h[l] = lv->h[l];
-    lt.w[l] = lv->w[l];
-    lt.stride[l] = lv->stride[l];
-    lt.cls_lr[l] = lv->cls_lr[l];
-    lt.reg_ctr[l] = lv->reg_ctr[l];
-    lt.start[l + 1] = lt.start[l] + lv->h[l] * lv->w[l];
-  }
-  for (int l = lv->num_levels; l < HN_FCOS_MAX_LEVELS; ++l) {
-    lt.h[l] = lt.w[l] = lt.stride[l] = 0;
-    lt.cls_lr[l] = lt.reg_ctr[l] = nullptr;
-    lt.start[l + 1] = lt.start[lv->num_levels];
-  }
+  if (const int rc = hn_fcos::level_table_fill(lv, lt)) return rc;
   if (workspace) {
     const int P = lt.start[lv->num_levels], chunks = (P + 1023) / 1024;
     HN_CHECK_ARG(workspace_bytes >= hn_fcos_candidates_ws_bytes(n, P), "workspace too small: %lld < %lld bytes",

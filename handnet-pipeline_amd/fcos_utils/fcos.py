@@ -7,7 +7,12 @@ returns one dict per image with `boxes [k,4]` (original-image pixels, unclipped)
 descending score; with `ext=True` (the class default, used by trainval_net_fcos.py --test-only) the dicts hold
 `dxdymags [k,3]`, `contacts [k] int64` and `sides` instead of `feature_idx` (fcos.py:637-647).  As in the reference, `score_thresh / nms_thresh / topk_candidates /
 detections_per_img` are accepted and IGNORED: post-processing hard-codes score > 0.7 and
-NMS IoU 0.3 (fcos.py:600,635).  Training (targets / losses) is out of scope.
+NMS IoU 0.3 (fcos.py:600,635).
+
+The criterion is available forward only, as an opt-in: after `device_loss()`, `model.train(); model(images, targets)` returns the
+reference's loss dict (fcos.py:523-570 the matching, :44-178 the six terms) computed on the device from the detector's own head
+tensors, and `loss_step` is the same for a validation loop in either mode (hn_amd.ops.fcos_loss).  There
+is no backward pass and no optimizer; without the opt-in, train mode and targets raise as before.
 """
 from __future__ import annotations
 
@@ -15,7 +20,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from hn_amd import synth
+from hn_amd import ops, synth
 from hn_amd.fcos_engine import FCOSEngine
 from hn_amd.state import EngineOwner, build_state_tree
 
@@ -37,7 +42,8 @@ class FCOS(EngineOwner):
         self.ext = ext
         self.num_classes = num_classes
         self.min_size, self.max_size = min_size, max_size
-        # stored-and-ignored, exactly like the reference (fcos.py:507-511)
+        # the criterion's centre sampling radius (fcos.py:545); the four below are stored and ignored, exactly like the reference
+        # (fcos.py:507-511)
         self.center_sampling_radius = center_sampling_radius
         self.score_thresh, self.nms_thresh = score_thresh, nms_thresh
         self.detections_per_img, self.topk_candidates = detections_per_img, topk_candidates
@@ -93,6 +99,45 @@ class FCOS(EngineOwner):
         ap.reset()
         return results
 
+    _device_loss = False   # device_loss(): train-mode forward(images, targets) returns the loss dict
+
+    def device_loss(self, on: bool = True):
+        """Opt in to (or out of) the criterion on the device.  On and in train mode, `forward(images, targets)` returns the
+        reference's loss dict; off (the default) every path behaves as before.  Returns self."""
+        self._device_loss = bool(on)
+        return self
+
+    def loss_step(self, images: List[torch.Tensor], targets, want_terms: bool = False):
+        """The detector's heads plus the criterion's two launches, in either mode: -> (losses, fg) with losses the reference's
+        dict (classification, bbox_regression, bbox_ctrness, hand_lr and, with ext, hand_contact_state, hand_dxdy: 0-d fp32
+        tensors on the device) and fg int32 [N], the foreground points per image.  Nothing is copied to the host and nothing
+        waits.  targets: the reference's list of dicts ('boxes' in image pixels, 'labels', 'box_info'), scaled per image like
+        torchvision's transform scales them, or an ops.FcosTargets already on the canvas's scale.  Equal-size batches and lists
+        of differently sized images (per-image ratios, anchors on the common canvas) both work; a list of different sizes runs
+        the network image by image (FCOSEngine.forward_heads_each), so that an image's terms and fg are the bytes of that
+        image alone on the same canvas, whatever else the list holds.  want_terms: also return the per-image sums [N, 6] before
+        any factor or division."""
+        dev = self._require_gpu()
+        eng = self.engine()
+        batch = self._batch(images)
+        heads = eng.forward_heads if torch.is_tensor(batch) else eng.forward_heads_each
+        cls_lr, reg_ctr, strides, (oh, ow, _, _) = heads(batch)
+        if not isinstance(targets, ops.FcosTargets):
+            if len(targets) != len(images):
+                raise ValueError("one target dict per image")
+            if torch.is_tensor(batch):
+                new = [(oh, ow)] * len(images)
+            else:
+                new = list(zip(oh, ow))
+            ratios = ops.fcos_target_ratios([tuple(i.shape[-2:]) for i in images], new)
+            targets = ops.pack_fcos_targets(targets, ratios, num_classes=self.num_classes, ext=self.ext, device=dev)
+        with ops.on_device(dev):
+            res = ops.fcos_loss(cls_lr, reg_ctr, strides, self.num_classes, targets, ext=eng._ext_levels if self.ext else None,
+                                radius=self.center_sampling_radius)
+        keys = ops.FCOS_LOSS_KEYS if self.ext else ops.FCOS_LOSS_KEYS[:4]
+        losses = {k: res.losses[i] for i, k in enumerate(keys)}
+        return (losses, res.fg, res.terms) if want_terms else (losses, res.fg)
+
     @staticmethod
     def _batch(images):
         if len({tuple(i.shape) for i in images}) != 1:
@@ -102,6 +147,10 @@ class FCOS(EngineOwner):
         return torch.stack([i.float() for i in images])
 
     def forward(self, images: List[torch.Tensor], targets=None) -> List[Dict[str, torch.Tensor]]:
+        if self._device_loss and self.training:
+            if targets is None:
+                raise ValueError("In training mode, targets should be passed")
+            return self.loss_step(images, targets)[0]
         if self.training or targets is not None:
             raise NotImplementedError("training (fcos.py:543-570 losses) is outside the inference hot path")
         if len({tuple(i.shape) for i in images}) != 1:

@@ -39,12 +39,15 @@ ARCH = "gfx950"
 # mesh_refit.hip: mesh_fit.hip's flags, for the fp64 composition of the iterations' motions (tests/refit_ref.py).
 # hpe_metrics.hip: the same for the evaluator's fp64 distances, Procrustes alignment and Jacobi SVD (tests/hpe_ref.py).
 # det_ap.hip: the same for the detector evaluation's fp64 overlaps, association distances and file round trip (tests/ap_ref.py).
+# fcos_loss.hip: the same for the criterion's float32 matching (compared bit for bit) and its terms (tests/fcos_loss_ref.py);
+# without the SLP vectoriser too: it packed the box differences into v_pk_add_f32 with op_sel (the build refused it).
 EXTRA_FLAGS = {"fcos_post.hip": ["-ffp-contract=off", "-fno-slp-vectorize"], "graph_ops.hip": ["-fno-slp-vectorize"],
                "mesh_raster.hip": ["-ffp-contract=off"], "label_draw.hip": ["-ffp-contract=off"],
                "rig_ops.hip": ["-ffp-contract=off"], "hand_cloud.hip": ["-ffp-contract=off"],
                "mesh_fit.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
                "mesh_refit.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
-               "hpe_metrics.hip": ["-ffp-contract=off"], "det_ap.hip": ["-ffp-contract=off"]}
+               "hpe_metrics.hip": ["-ffp-contract=off"], "det_ap.hip": ["-ffp-contract=off"],
+               "fcos_loss.hip": ["-ffp-contract=off", "-fno-slp-vectorize"]}
 
 # Kernels that request operands with `asm volatile` loads / LDS-DMA and retire them with hand-counted s_waitcnt: the
 # compiler cannot see that such a register is still in flight, so a SPILL of it stores garbage (profiles/NOTEBOOK.md, round

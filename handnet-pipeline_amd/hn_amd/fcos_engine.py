@@ -455,6 +455,29 @@ class FCOSEngine:
         return [o[0] for o in outs], [o[1] for o in outs], strides, (oh, ow, ph, pw)
 
     @ops.device_guarded
+    def forward_heads_each(self, images):
+        """forward_heads for a list of [3,h_i,w_i] images with the network run image by image on the list's common canvas.
+        The convolutions pick their forms by problem size (split-K by workgroup count), so an image's head tensors in a batch
+        of two differ in their last bits from those of the image alone; here every image's rows are the bytes of that image
+        alone on this canvas, whatever else the list holds -- what a per-image validation number needs (FCOS.loss_step).
+        One preprocess launch for the list; the price is the batch-1 convolution forms once per image."""
+        with ops.f16_terms(self.terms):
+            geom, ph, pw = self.list_geometry(images)
+            split = self.precision == "f16x3"
+            x = ops.fcos_preprocess_list(images, geom, ph, pw, self.image_mean, self.image_std, split=split)
+            per = []
+            for i in range(len(images)):
+                xi = x[:, i:i + 1].contiguous() if split else x[i:i + 1]
+                feats = self.backbone(xi)
+                # (copies: the engine may hand the same buffers out again on the next image)
+                per.append([tuple(None if t is None else t.clone() for t in o) for o in self.heads(feats)])
+            strides = [ph // o[0].shape[1] for o in per[0]]
+            cat = lambda l, k: torch.cat([p[l][k] for p in per])
+            levels = range(len(per[0]))
+            self._ext_levels = [cat(l, 2) for l in levels] if self.ext else None
+            return [cat(l, 0) for l in levels], [cat(l, 1) for l in levels], strides, ([g[2] for g in geom], [g[3] for g in geom], ph, pw)
+
+    @ops.device_guarded
     def detect(self, images, cand=None, det=None, nms_scratch=None):
         """Full detector on the device -> ops.Detections (fixed capacity, score-ordered).  images: [N,3,H,W], or a
         list of [3,h_i,w_i] tensors of different sizes (each resized on its own, boxes rescaled per image)."""

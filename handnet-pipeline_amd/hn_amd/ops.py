@@ -1231,6 +1231,147 @@ def fcos_ext_gather(ext, det: "Detections", cand: Candidates):
     return contacts, dxdymags
 
 
+FCOS_MAX_GT = 64            # HN_FCOS_MAX_GT: ground-truth rows per image
+FCOS_LOSS_KEYS = ("classification", "bbox_regression", "bbox_ctrness", "hand_lr", "hand_contact_state", "hand_dxdy")
+
+
+@dataclass
+class FcosTargets:
+    """The criterion's ground truth as padded device tables (pack_fcos_targets)."""
+    boxes: torch.Tensor     # [N, G, 4] fp32, scaled to the canvas
+    labels: torch.Tensor    # [N, G] int32
+    info: torch.Tensor      # [N, G, 5] fp32 = (contactstate, handside, mag, dx, dy)
+    count: torch.Tensor     # [N] int32
+
+
+@dataclass
+class FcosLoss:
+    terms: torch.Tensor     # [N, 6] fp32: per-image sums before any factor or division, FCOS_LOSS_KEYS order
+    fg: torch.Tensor        # [N] int32: foreground points
+    losses: torch.Tensor    # [6] fp32: the dict values of the batch
+    matched: torch.Tensor = None   # [N, P] int32: each point's ground-truth row or -1 (want_matched)
+
+
+def fcos_target_ratios(original_sizes, new_sizes):
+    """per image (ratio_h, ratio_w) = float32(new) / float32(original), the float32 division of torchvision's resize_boxes
+    (FCOSEngine.detect divides the other way round for the detections)"""
+    f = np.float32
+    return [(f(nh) / f(oh), f(nw) / f(ow)) for (oh, ow), (nh, nw) in zip(original_sizes, new_sizes)]
+
+
+def pack_fcos_targets(targets, ratios, G=None, *, num_classes=None, ext=False, device=None) -> FcosTargets:
+    """The reference's list of target dicts ('boxes' [M,4] in image pixels, 'labels' [M], 'box_info' [M,5]) -> FcosTargets.
+    ratios: one (ratio_h, ratio_w) pair for every image or one pair per image (fcos_target_ratios); the boxes are scaled in
+    float32 on the host, box * ratio per axis, as torchvision's transform scales them.  Refused here, before anything reaches
+    the device: a box that is degenerate after scaling (the reference drops the box and keeps its label, which misaligns the
+    two), a label outside [0, num_classes) (when num_classes is given), more than FCOS_MAX_GT boxes in an image, and, with ext,
+    an image without boxes (the reference raises KeyError('hand_contact_state') there, fcos.py:75)."""
+    f = np.float32
+    n = len(targets)
+    if n == 0:
+        raise ValueError("pack_fcos_targets: no images")
+    if len(ratios) == 2 and not isinstance(ratios[0], (tuple, list, np.ndarray)):
+        ratios = [ratios] * n
+    if len(ratios) != n:
+        raise ValueError("pack_fcos_targets: one (ratio_h, ratio_w) pair per image")
+    host = lambda t, dt: (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)).astype(dt)
+    rows = []
+    for i, (t, (rh, rw)) in enumerate(zip(targets, ratios)):
+        boxes, labels = host(t["boxes"], f).reshape(-1, 4), host(t["labels"], np.int64).reshape(-1)
+        info = host(t["box_info"], f).reshape(-1, 5) if "box_info" in t else np.zeros((len(labels), 5), f)
+        if not (len(boxes) == len(labels) == len(info)):
+            raise ValueError(f"image {i}: boxes, labels and box_info differ in length")
+        if len(labels) > FCOS_MAX_GT:
+            raise ValueError(f"image {i}: {len(labels)} boxes, more than {FCOS_MAX_GT}")
+        if ext and len(labels) == 0:
+            raise KeyError("hand_contact_state")
+        boxes = (boxes * np.array([rw, rh, rw, rh], f)[None, :]).astype(f)
+        if len(boxes) and ((boxes[:, 2] <= boxes[:, 0]) | (boxes[:, 3] <= boxes[:, 1])).any():
+            raise ValueError(f"image {i}: a degenerate box (x1 <= x0 or y1 <= y0 after scaling)")
+        if num_classes is not None and len(labels) and (labels.min() < 0 or labels.max() >= num_classes):
+            raise ValueError(f"image {i}: a label outside [0, {num_classes})")
+        rows.append((boxes, labels.astype(np.int32), info))
+    most = max(len(r[1]) for r in rows)
+    G = max(1, most) if G is None else int(G)
+    if G < max(1, most) or G > FCOS_MAX_GT:
+        raise ValueError(f"G = {G} outside {max(1, most)}..{FCOS_MAX_GT}")
+    tb, tl, ti, tc = np.zeros((n, G, 4), f), np.zeros((n, G), np.int32), np.zeros((n, G, 5), f), np.zeros((n,), np.int32)
+    for i, (b, l, info) in enumerate(rows):
+        k = len(l)
+        tb[i, :k], tl[i, :k], ti[i, :k], tc[i] = b, l, info, k
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    up = lambda a: torch.from_numpy(a).to(dev, non_blocking=True)
+    return FcosTargets(up(tb), up(tl), up(ti), up(tc))
+
+
+def alloc_fcos_loss(n, points, device, want_matched=False) -> FcosLoss:
+    return FcosLoss(torch.empty((n, 6), device=device, dtype=torch.float32), torch.empty((n,), device=device, dtype=torch.int32),
+                    torch.empty((6,), device=device, dtype=torch.float32),
+                    torch.empty((n, points), device=device, dtype=torch.int32) if want_matched else None)
+
+
+def fcos_loss(cls_lr, reg_ctr, strides, num_classes, targets: FcosTargets, ext=None, radius=1.5, want_matched=False,
+              out: FcosLoss | None = None) -> FcosLoss:
+    """The FCOS criterion, forward only, on the detector's head tensors (hn_fcos_loss_f32; fcos_utils/fcos.py:44-178,523-570,
+    DESIGN.md section 9p): cls_lr[l] [N,h,w,C+2], reg_ctr[l] [N,h,w,5] and, for the ext terms, ext[l] [N,h,w,8] per level;
+    targets as pack_fcos_targets builds them (boxes already on the canvas's scale) -> FcosLoss, everything on the device and
+    nothing waited for.  Two launches with a fixed summation order: the same bytes on every run, and row i of a batch is the
+    row of image i alone.  Every refusal happens before a launch."""
+    lib = _lib.load()
+    nl = len(cls_lr)
+    if nl == 0 or len(reg_ctr) != nl or len(strides) != nl or (ext is not None and len(ext) != nl):
+        raise ValueError("fcos_loss: cls_lr, reg_ctr, strides and ext must have one entry per level")
+    if not 1 <= int(num_classes) <= 8:
+        raise ValueError(f"fcos_loss: num_classes = {num_classes} outside 1..8")
+    lv = FcosLevels()
+    lv.num_levels = nl
+    n = cls_lr[0].shape[0]
+    points = 0
+    arr = (C.c_void_p * nl)() if ext is not None else None
+    for i, (a, b, st) in enumerate(zip(cls_lr, reg_ctr, strides)):
+        _req(a, name="cls_lr"); _req(b, name="reg_ctr")
+        if a.dim() != 4 or a.shape[0] != n or a.shape[3] != num_classes + 2 or b.shape[3] != 5 or a.shape[:3] != b.shape[:3]:
+            raise ValueError("bad head tensor shapes")
+        if ext is not None:
+            if tuple(_req(ext[i], name="ext").shape) != tuple(a.shape[:3]) + (8,):
+                raise ValueError("ext tensors must be [N,h,w,8] on the levels of cls_lr")
+            arr[i] = ext[i].data_ptr()
+        lv.h[i], lv.w[i], lv.stride[i] = a.shape[1], a.shape[2], int(st)
+        lv.cls_lr[i], lv.reg_ctr[i] = a.data_ptr(), b.data_ptr()
+        points += a.shape[1] * a.shape[2]
+    _req(targets.boxes, name="targets.boxes"); _req(targets.info, name="targets.info")
+    _req(targets.labels, torch.int32, "targets.labels"); _req(targets.count, torch.int32, "targets.count")
+    g = targets.boxes.shape[1] if targets.boxes.dim() == 3 else 0
+    if not 1 <= g <= FCOS_MAX_GT:
+        raise ValueError(f"fcos_loss: G = {g} outside 1..{FCOS_MAX_GT}")
+    if (tuple(targets.boxes.shape) != (n, g, 4) or tuple(targets.labels.shape) != (n, g) or tuple(targets.info.shape) != (n, g, 5)
+            or tuple(targets.count.shape) != (n,)):
+        raise ValueError("fcos_loss: targets must be boxes [N,G,4], labels [N,G], info [N,G,5], count [N]")
+    dev = cls_lr[0].device
+    if out is None:
+        out = alloc_fcos_loss(n, points, dev, want_matched)
+    else:
+        _req(out.terms, name="out.terms"); _req(out.fg, torch.int32, "out.fg"); _req(out.losses, name="out.losses")
+        if tuple(out.terms.shape) != (n, 6) or tuple(out.fg.shape) != (n,) or tuple(out.losses.shape) != (6,):
+            raise ValueError("out must be terms [N,6], fg [N], losses [6]")
+        if want_matched and (out.matched is None or tuple(_req(out.matched, torch.int32, "out.matched").shape) != (n, points)):
+            raise ValueError("out.matched must be int32 [N,P]")
+    nbytes = lib.hn_fcos_loss_ws_bytes(n, points)
+    ws = torch.empty((nbytes // 8,), device=dev, dtype=torch.float64)
+    global PROFILE_STAGE
+    prev, PROFILE_STAGE = PROFILE_STAGE, "fcos_loss"
+    try:
+        timer = _profile_start()
+        check(lib.hn_fcos_loss_f32(C.byref(lv), arr, n, int(num_classes), ptr(targets.boxes), ptr(targets.labels), ptr(targets.info),
+                                   ptr(targets.count), g, float(radius), ptr(out.terms), ptr(out.fg), ptr(out.losses),
+                                   ptr(out.matched) if want_matched else None, ptr(ws), nbytes, _stream()), "hn_fcos_loss_f32")
+        if timer is not None:
+            _profile_stop(timer, lambda: (("f32", "fcos_loss"), 0, (n, points, int(num_classes), g)))
+    finally:
+        PROFILE_STAGE = prev
+    return out
+
+
 def fcos_nms(cand: Candidates, iou_thresh, ratio_h, ratio_w, scratch=None, out: Detections | None = None,
              ratios=None):
     """ratios: optional fp32 GPU [N,2] = (ratio_h, ratio_w) per image (batches of differently sized images);

@@ -41,7 +41,8 @@ extern "C" {
  * hn_hand_cloud_f32 and hn_hand_cloud_scratch_bytes, the mesh fit's hn_mesh_fit_f32 and hn_mesh_fit_scratch_bytes, and the
  * iterated fit's hn_mesh_geometry_f32, hn_mesh_fit_iters_f32 and hn_mesh_fit_iters_scratch_bytes, and the carried apply pass's
  * hn_conv2d_nhwc_f16x3_grouped_carry, hn_conv2d_f16x3_grouped_carry_applies and hn_affine_split_f32_levels_streams, the evaluator's hn_hpe_accumulate_f32, the
- * detector evaluation's hn_det_ap_accumulate_f32, and the A2J criterion's hn_a2j_aggregate_loss_f32). */
+ * detector evaluation's hn_det_ap_accumulate_f32, the A2J criterion's hn_a2j_aggregate_loss_f32, and the FCOS criterion's
+ * hn_fcos_loss_f32 and hn_fcos_loss_ws_bytes). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -504,6 +505,25 @@ int hn_fcos_ext_gather(const hn_fcos_levels* lv, const float* const* ext, const 
                        const int32_t* cand_point, const int32_t* det_count, int n, int cap,
                        int32_t* det_contacts /* [n][cap] */, float* det_dxdymags /* [n][cap][3] */,
                        void* stream);
+
+/* The FCOS criterion, forward only (fcos_utils/fcos.py:523-570 the matching, :44-178 the six terms), on
+ * the head tensors of hn_fcos_candidates plus, with the ext heads, ext[l] as hn_fcos_ext_gather takes it (NULL: no ext terms).
+ * Ground truth per image, padded to G rows (device memory): gt_boxes ALREADY SCALED to the canvas, gt_info = (contactstate,
+ * handside, mag, dx, dy), gt_count clamped to [0, G] by the kernel (a count of 0: all background, zero dxdy targets).
+ * Outputs (device): terms [n][6] = the per-image sums before any factor or division, in the order classification (focal),
+ * bbox_regression (GIoU), bbox_ctrness (BCE), hand_lr (focal), hand_contact_state (focal), hand_dxdy (squared differences; the
+ * last two zero without ext); fg [n] = foreground points; losses [6] = the reference's dict values over max(1, sum fg);
+ * matched [n][points] = each point's ground-truth row or -1 (NULL skips the store).  Two launches, no atomics, a fixed
+ * order: the same bytes on every run, and image i of a batch gives the bytes of that image alone.  Null pointers, G outside
+ * 1..HN_FCOS_MAX_GT and num_classes outside 1..8 are refused before any launch.
+ * workspace = hn_fcos_loss_ws_bytes(n, total points) bytes, 8-byte aligned, contents irrelevant before and after. */
+#define HN_FCOS_MAX_GT 64
+int64_t hn_fcos_loss_ws_bytes(int n, int total_points);
+int hn_fcos_loss_f32(const hn_fcos_levels* lv, const float* const* ext /* or NULL */, int n, int num_classes,
+                     const float* gt_boxes /* [n][G][4], scaled */, const int32_t* gt_labels /* [n][G] */,
+                     const float* gt_info /* [n][G][5] */, const int32_t* gt_count /* [n] */, int G, float radius,
+                     float* terms, int32_t* fg, float* losses, int32_t* matched /* or NULL */, void* ws, int64_t ws_bytes,
+                     void* stream);
 
 int64_t hn_fcos_nms_scratch_bytes(int n, int cap);
 int hn_fcos_nms(const float* cand_boxes, const float* cand_scores, const int32_t* cand_labels,
