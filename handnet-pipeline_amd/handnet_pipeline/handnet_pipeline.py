@@ -155,6 +155,7 @@ class HandNet(EngineOwner):
     def live_hands(self, lifter, paras, max_hands: int = 2, clamp: bool = True, perm_reverse=None, faces=None,
                    labels: bool = False, left: bool = False, handed: bool = False, left_side: int = 0, track: bool = False,
                    track_iou: float = 0.3, track_hold: int = 5, occlude: bool = False, occlude_margin: float = 0.03,
+                   objects: bool = False, object_band: float = 0.15, object_stride: int = 2, object_min_points: int = 50,
                    extrinsics=None, rig_radius: float = 0.08, fit_iters: int = 1, fit_draw: bool = False, cloud: bool = False,
                    cloud_points: int = 4096,
                    cloud_band: float = 0.03, cloud_stride: int = 2, cloud_frame: str = "camera", fit: bool = False,
@@ -200,9 +201,20 @@ class HandNet(EngineOwner):
         fit (needs occlude): as live()'s, per slot: read() ends with fit_mesh [N,K,V,3], fit_xyz
         [N,K,21,3], fit_rt [N,K,12], fit_count [N,K,2] and fit_cost [N,K]; fit_iters / fit_draw as
         live()'s, fit_trace [N,K,I,3].  fit_band = 0.03 m, fit_stride = 2, fit_min_points =
-        200, fit_damp = 1e-3, fit_max_shift = 0.05 m and fit_max_angle = 0.35 rad are starting values, NOT tuned on this model."""
+        200, fit_damp = 1e-3, fit_max_shift = 0.05 m and fit_max_angle = 0.35 rad are starting values, NOT tuned on this model.
+        objects (needs paras and a detector built with ext=True): the step also says what every hand holds
+        -- read() ends with contact and object_index [N,K], object_box [N,K,4], object_score [N,K], object_point [N,K,2],
+        object_xyz [N,K,3], object_extent [N,K,6] and object_count [N,K,2]: each slot's contact state, the detector's object its
+        offset vector points at (the reference's evaluation rule, voc_eval.py:687-699) and the centroid and extent of that
+        object's depth pixels in the camera frame, inside the captured step and its one copy; with labels, box_label also shows
+        the object's rectangle and the link line.  object_band = 0.15 m, object_stride = 2 and object_min_points = 50 are
+        starting values, NOT tuned on any model; contact state > 0 = in contact is 100DOH's numbering, to be checked against the
+        checkpoint.  A detector without the ext heads: ValueError."""
         from hn_amd.live import LiveHandsEngine
         k = ops.check_max_hands(max_hands)
+        if objects and not getattr(self.detector, "ext", False):
+            raise ValueError("live_hands(objects=True) needs the detector's contact heads: assign a FCOS(num_classes=..., ext=True, "
+                             "nms_thresh=0.5) to net.detector and load its weights")
         if left and handed:
             raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
         paras = ops.camera_paras(paras)
@@ -215,7 +227,9 @@ class HandNet(EngineOwner):
                                fit_min_points=fit_min_points, fit_damp=fit_damp, fit_max_shift=fit_max_shift,
                                fit_max_angle=fit_max_angle,
                                smooth=smooth, smooth_min_cutoff=smooth_min_cutoff,
-                               smooth_beta=smooth_beta, smooth_d_cutoff=smooth_d_cutoff, smooth_rate=smooth_rate)
+                               smooth_beta=smooth_beta, smooth_d_cutoff=smooth_d_cutoff, smooth_rate=smooth_rate,
+                               objects=objects, object_band=object_band, object_stride=object_stride,
+                               object_min_points=object_min_points)
 
     # forward() switches ITSELF to hipGraph replay once the same input shapes have come in a few times in a row -- the live
     # caller's case (ros_demo.py:270-273: one 640x480 frame per call, ~150 dependent launches whose host cost is 8 % of the

@@ -254,6 +254,11 @@ SIGNATURES = {
     # each hand's depth pixels as a point cloud: count + write (new functions under ABI 36)
     "hn_hand_cloud_scratch_bytes": (C.c_int64, [C.c_int] * 3),
     "hn_hand_cloud_f32": (C.c_int, [VP] * 3 + [C.c_int64] + [VP] * 3 + [C.c_int] * 6 + [C.c_float, VP, C.c_int64] + [VP] * 4),
+    # the object each hand holds: associate + walk + finish, and its label launch (new functions under ABI 36)
+    "hn_hand_objects_scratch_bytes": (C.c_int64, [C.c_int] * 3),
+    "hn_hand_objects_f32": (C.c_int, [VP] * 7 + [C.c_int] * 2 + [VP, C.c_int64, VP, VP, C.c_int, VP, VP] + [C.c_int] * 5
+                            + [C.c_float, C.c_int, VP, C.c_int64] + [VP] * 9),
+    "hn_draw_object_labels_u8": (C.c_int, [VP] * 3 + [C.c_int] * 5 + [VP, VP]),
     # each hand's mesh fitted to its measured depth: accumulate + apply (new functions under ABI 36)
     "hn_mesh_fit_scratch_bytes": (C.c_int64, [C.c_int] * 3),
     "hn_mesh_fit_f32": (C.c_int, [VP] * 3 + [C.c_int64] + [VP] * 4 + [C.c_int] * 7 + [C.c_float, C.c_int] + [C.c_double] * 3

@@ -34,6 +34,7 @@ ARCH = "gfx950"
 # label_draw.hip: the same for the resize's sample positions (tests/draw_ref.py).
 # rig_ops.hip: the same for the rig frame's transform, distances and weighted means (tests/rig_ref.py).
 # hand_cloud.hip: the same for the cloud's residual, back-projection and transform (tests/cloud_ref.py).
+# hand_object.hip: the same for the association's centres, points and distances and the object's back-projection (tests/object_ref.py).
 # mesh_fit.hip: the same for the fit's normals, levers, residuals, fp64 solve and rigid motion (tests/fit_ref.py);
 # without the SLP vectoriser too: it packed the rigid motion's products into v_pk_mul_f32 with op_sel (the build refused it).
 # mesh_refit.hip: mesh_fit.hip's flags, for the fp64 composition of the iterations' motions (tests/refit_ref.py).
@@ -44,6 +45,7 @@ ARCH = "gfx950"
 EXTRA_FLAGS = {"fcos_post.hip": ["-ffp-contract=off", "-fno-slp-vectorize"], "graph_ops.hip": ["-fno-slp-vectorize"],
                "mesh_raster.hip": ["-ffp-contract=off"], "label_draw.hip": ["-ffp-contract=off"],
                "rig_ops.hip": ["-ffp-contract=off"], "hand_cloud.hip": ["-ffp-contract=off"],
+               "hand_object.hip": ["-ffp-contract=off"],
                "mesh_fit.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
                "mesh_refit.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
                "hpe_metrics.hip": ["-ffp-contract=off"], "det_ap.hip": ["-ffp-contract=off"],

@@ -498,12 +498,19 @@ class FCOSEngine:
         return det, cand
 
     @ops.device_guarded
-    def detect_ext(self, images):
-        """ext=True detector: (Detections, Candidates, contacts [N,cap] int32, dxdymags [N,cap,3])."""
+    def detect_ext(self, images, zero=True):
+        """ext=True detector: (Detections, Candidates, contacts [N,cap] int32, dxdymags [N,cap,3]).  zero=False: no fill
+        launches -- the two tensors' rows at or beyond count[i] are then undefined, like the detections' (the engines' steps,
+        which only ever read the rows below it, ask for this)."""
         if not self.ext:
             raise RuntimeError("engine was built without the ext heads")
         det, cand = self.detect(images)
-        contacts, dxdymags = ops.fcos_ext_gather(self._ext_levels, det, cand)
+        out = None
+        if not zero:
+            n, cap = det.scores.shape
+            out = (torch.empty((n, cap), device=det.scores.device, dtype=torch.int32),
+                   torch.empty((n, cap, 3), device=det.scores.device, dtype=torch.float32))
+        contacts, dxdymags = ops.fcos_ext_gather(self._ext_levels, det, cand, out=out)
         return det, cand, contacts, dxdymags
 
     # -----------------------------------------------------------------------------------

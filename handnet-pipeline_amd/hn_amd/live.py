@@ -99,6 +99,15 @@ def _fit_trace_views(kind):
     return collections.namedtuple(kind.__name__.replace("Views", "TraceViews"), kind._fields + ("fit_trace",))
 
 
+OBJECT_FIELDS = ops.OBJECT_FIELDS
+
+
+@functools.lru_cache(maxsize=None)
+def _objects_views(kind):
+    """... and of an objects step: the fields of its step without the option, then the eight parts of the held objects"""
+    return collections.namedtuple(kind.__name__.replace("Views", "ObjectsViews"), kind._fields + OBJECT_FIELDS)
+
+
 # What a cloud or fit step keeps on the device beside its copy buffer: the raster's nearest Z fp32 [n,h,w]; the cloud launches'
 # scratch, the fit launches' scratch and the iterated fit's work (each None in a step without them); a fit_draw step's geometry
 # depth fp32 [n,h,w] and slot byte uint8 [n,h,w] (else None)
@@ -122,7 +131,10 @@ class LiveLayout:
     and `fit_count` int32 [slots,2], each on a dword, and `fit_cost` int64 [slots] on 8 bytes, as the last parts (fit_mesh_at,
     fit_xyz_at, fit_rt_at, fit_count_at, fit_cost_at: properties too), and -- fit steps of I = 2..8 iterations, for
     which `fit` holds the integer I where a step of one iteration holds True -- `fit_trace` int64 [slots,I,3] on 8 bytes as the
-    last part (fit_trace_at: a property).
+    last part (fit_trace_at: a property), and -- objects steps (LiveObjectsLayout, the same class with `objects` on:
+    a class attribute, not a field) -- `contact` and `object_index` int32 [slots], `object_box` fp32 [slots,4], `object_score` fp32
+    [slots], `object_point` fp32 [slots,2], `object_xyz` fp32 [slots,3], `object_extent` fp32 [slots,6] and `object_count` int32
+    [slots,2], each on a dword, behind every other part (contact_at, object_index_at, ...: properties).
     slots = frames for the one-hand step (hands None), frames * hands for the K-hand step.  A part the step does not have takes
     no bytes and its offset is None; every part in front of it stays where a step without the option has it."""
     frames: int
@@ -162,6 +174,7 @@ class LiveLayout:
     fused_xyz_at: int = field(init=False)
     fused_mesh_at: int = field(init=False)
     nbytes: int = field(init=False)
+    objects = False              # (no field: LiveObjectsLayout switches the held objects' eight parts on)
 
     def __post_init__(self):
         if ((self.overlay or self.labels) and self.hw is None) or ((self.handed or self.tracked) and self.hands is None):
@@ -179,6 +192,8 @@ class LiveLayout:
         if not isinstance(self.fit, bool) and (not isinstance(self.fit, (int, np.integer)) or not 2 <= self.fit <= ops.FIT_MAX_ITERS):
             raise ValueError(f"fit: False, True (one iteration) or the iterations as an integer 2..{ops.FIT_MAX_ITERS} "
                              f"(got {self.fit!r})")
+        if self.objects and self.hands is None:
+            raise ValueError("objects is a K-hand step's option: the slots' detection rows are what the objects are associated with")
         if self.rig:
             if self.hands is None:
                 raise ValueError("rig is a K-hand step's option: the rig frame puts the slots of several frames together")
@@ -217,13 +232,21 @@ class LiveLayout:
                                                    ("fit_rt", self.fit, torch.float32, (s, 12), 4),
                                                    ("fit_count", self.fit, torch.int32, (s, 2), 4),
                                                    ("fit_cost", self.fit, torch.int64, (s,), 8),
-                                                   ("fit_trace", self.fit_iters > 1, torch.int64, (s, self.fit_iters, 3), 8)):
+                                                   ("fit_trace", self.fit_iters > 1, torch.int64, (s, self.fit_iters, 3), 8),
+                                                   ("contact", self.objects, torch.int32, (s,), 4),
+                                                   ("object_index", self.objects, torch.int32, (s,), 4),
+                                                   ("object_box", self.objects, torch.float32, (s, 4), 4),
+                                                   ("object_score", self.objects, torch.float32, (s,), 4),
+                                                   ("object_point", self.objects, torch.float32, (s, 2), 4),
+                                                   ("object_xyz", self.objects, torch.float32, (s, 3), 4),
+                                                   ("object_extent", self.objects, torch.float32, (s, 6), 4),
+                                                   ("object_count", self.objects, torch.int32, (s, 2), 4)):
             start = None
             if present:
                 start = (end + align - 1) // align * align
                 end = start + math.prod(shape) * dtype.itemsize
                 spans[name] = (start, end, dtype, shape)
-            if name != "records" and name not in CLOUD_FIELDS + FIT_FIELDS + ("fit_trace",):
+            if name != "records" and name not in CLOUD_FIELDS + FIT_FIELDS + ("fit_trace",) + OBJECT_FIELDS:
                 put(name + "_at", start)
         put("record_rows", rows)
         put("record_bytes", rb)
@@ -252,6 +275,14 @@ class LiveLayout:
     fit_count_at = property(lambda self: self._part_at("fit_count"))
     fit_cost_at = property(lambda self: self._part_at("fit_cost"))
     fit_trace_at = property(lambda self: self._part_at("fit_trace"))
+    contact_at = property(lambda self: self._part_at("contact"))
+    object_index_at = property(lambda self: self._part_at("object_index"))
+    object_box_at = property(lambda self: self._part_at("object_box"))
+    object_score_at = property(lambda self: self._part_at("object_score"))
+    object_point_at = property(lambda self: self._part_at("object_point"))
+    object_xyz_at = property(lambda self: self._part_at("object_xyz"))
+    object_extent_at = property(lambda self: self._part_at("object_extent"))
+    object_count_at = property(lambda self: self._part_at("object_count"))
 
     def views(self, buf) -> LiveViews:
         """The parts of a step's flat uint8 buffer (the device buffer or its pinned copy), typed and shaped; None: not there."""
@@ -267,7 +298,16 @@ class LiveLayout:
             kind = _fit_views(kind)
         if self.fit_iters > 1:
             kind = _fit_trace_views(kind)
+        if self.objects:
+            kind = _objects_views(kind)
         return kind(*(cut.get(name) for name in kind._fields))
+
+
+@dataclass(frozen=True)
+class LiveObjectsLayout(LiveLayout):
+    """LiveLayout of a K-hand step with objects=True: the same fields and the same offsets for every part a step
+    without the option has, and the held objects' eight parts behind them."""
+    objects = True
 
 
 @functools.lru_cache(maxsize=None)
@@ -306,6 +346,15 @@ def _fit_trace_read_type(kind):
     return type(name, (collections.namedtuple(name, kind._fields + ("fit_trace",)),), dict(absent, __slots__=(), __doc__=doc))
 
 
+@functools.lru_cache(maxsize=None)
+def _objects_read_type(kind):
+    """The read type of an objects step: the fields of `kind` -- the read type of its step without the option --, then the eight."""
+    name = kind.__name__[:-len("Read")] + "ObjectsRead"
+    absent = {f: None for f in ("overlay", "box_label", "pose_label") if f not in kind._fields}
+    doc = kind.__doc__.rstrip(".") + "".join(f" + {f}" for f in OBJECT_FIELDS) + "."
+    return type(name, (collections.namedtuple(name, kind._fields + OBJECT_FIELDS),), dict(absent, __slots__=(), __doc__=doc))
+
+
 def _read(step, base, values, layout, v, per_slot=lambda t: t):
     """read()'s result: `values` + fresh copies of the images and the sides the step has, as the step's read type."""
     if layout.overlay:
@@ -338,6 +387,9 @@ def _read(step, base, values, layout, v, per_slot=lambda t: t):
         if layout.fit_iters > 1:      # (per slot: [N,K,I,3]; the one-hand step: [N,I,3])
             values += (per_slot(v.fit_trace).clone(),)
             kind = _fit_trace_read_type(kind)
+    if layout.objects:  # (per slot: [N,K], [N,K], [N,K,4], [N,K], [N,K,2], [N,K,3], [N,K,6], [N,K,2])
+        values += tuple(per_slot(getattr(v, f)).clone() for f in OBJECT_FIELDS)
+        kind = _objects_read_type(kind)
     return kind(*values)
 
 
@@ -399,6 +451,7 @@ class _LiveStep:
     rig = None                   # the rig K-hand step: its radius (metres); `extrinsics` is the device table [N,12]
     extrinsics = None
     cloud_frame = "camera"       # the frame of a cloud step's points ("rig": a K-hand step's with extrinsics)
+    objects = None               # the objects K-hand step: (band, stride, min_points)
 
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, clamp: bool = True, perm_reverse=None, faces=None,
                  labels: bool = False, left: bool = False, occlude: bool = False, occlude_margin: float = ops.OCCLUDE_MARGIN,
@@ -581,7 +634,8 @@ class _LiveStep:
 
     def _layout(self, n, hw=None) -> LiveLayout:
         """The buffer of a step over n frames (hw: of a step that draws, the frames' size)."""
-        return LiveLayout(n, self.hands, self.vertices, hw, hw is not None and self.faces is not None,
+        return (LiveLayout if self.objects is None else LiveObjectsLayout)(
+                          n, self.hands, self.vertices, hw, hw is not None and self.faces is not None,
                           hw is not None and self.labels, self.handed, self.track is not None, self.smooth is not None,
                           occluded=self.occlude is not None,
                           fit=(True if self.fit_iters == 1 else self.fit_iters) if self.fit is not None and hw is not None else False,
@@ -658,6 +712,13 @@ class _LiveStep:
         if layout.fit and not redraw:      # (the mesh the overlay drew and the joints that go with it)
             more.update(self._fit_parts(work, work.mesh_depth, silhouette, depth, shown, at.smooth_xyz if layout.smoothed else out.xyz_mm,
                                         drawn, k, at, layout))
+        if layout.objects:  # (against the depth map the step ran on -- mirrored in a `left` step -- and the unsmoothed root joint)
+            band, stride, min_points = self.objects
+            held = ops.hand_objects(out.detections, out.contacts, out.dxdymags, out.det_index.view(n, k), depth.float().contiguous(), out.xyz_mm,
+                                    self._camera, k, band=band, stride=stride, min_points=min_points, silhouette=silhouette, out=at)
+            if layout.labels:
+                ops.draw_object_labels(out.detections, out.det_index.view(n, k), held.object_index, box_label)
+            more.update({f: getattr(held, f) for f in OBJECT_FIELDS})
         host.copy_(dev, non_blocking=True)
         return self._output(out, at, layout, host, dict(pose2d=p2d, mesh=mesh, pose3d=pose3d, raw_mesh=raw, overlay=overlay,
                                                         box_label=box_label, pose_label=pose_label, **more))
@@ -681,7 +742,8 @@ class _LiveStep:
                 + (() if self.cloud is None else ("cloud",) + self.cloud + (self.cloud_frame,))
                 + (() if self.fit is None else ("fit",) + self.fit)
                 + (() if self.fit_iters == 1 and not self.fit_draw else ("fit_iters", self.fit_iters, self.fit_draw))
-                + (() if self.rig is None else ("rig", self.rig)))
+                + (() if self.rig is None else ("rig", self.rig))
+                + (() if self.objects is None else ("objects",) + self.objects))
 
     def _smooth_untouched(self, n):
         return contextlib.nullcontext()
@@ -847,6 +909,14 @@ class LiveHandsOutput:
     fit_count: torch.Tensor = None   # [N,K,2] int32 (matching pixels, status: 0 fitted, 1 too few, 2 no solution, 3 beyond the caps)
     fit_cost: torch.Tensor = None    # [N,K] int64 the summed squared residual along the normals, 2^-30 m^2
     fit_trace: torch.Tensor = None   # fit steps of I >= 2 iterations: [N,K,I,3] int64 (matches, status, cost) of each
+    contact: torch.Tensor = None     # objects steps, on the device: [N,K] int32 the slot's contact state (-1: empty slot)
+    object_index: torch.Tensor = None  # [N,K] int32 the held object's row in hands.detections, or -1
+    object_box: torch.Tensor = None    # [N,K,4] fp32 its box (zeros: no object)
+    object_score: torch.Tensor = None  # [N,K] fp32 its score
+    object_point: torch.Tensor = None  # [N,K,2] fp32 the point the hand's offset vector names (zeros: empty slot)
+    object_xyz: torch.Tensor = None    # [N,K,3] fp32 the centroid of the object's depth pixels, camera frame, metres (zeros unless status 0)
+    object_extent: torch.Tensor = None  # [N,K,6] fp32 (min x y z, max x y z) of those pixels (zeros: no match)
+    object_count: torch.Tensor = None  # [N,K,2] int32 (matches, status: 0 ok, 1 no object, 2 too few matches, -1 empty slot)
     smooth_xyz: torch.Tensor = None  # smoothed steps: [N,K,21,3] on the device, xyz_mm filtered over time (zeros: has_hand != 1)
     smooth_mesh: torch.Tensor = None  # smoothed steps: [N,K,V,3] on the device, `mesh` filtered over time (zeros: not lifted)
 
@@ -860,7 +930,10 @@ class LiveHandsOutput:
         [N,K,21,3], rig_mesh [N,K,V,3], rig_hand [N,K] int32, rig_count (a Python int), rig_views and rig_seed [N*K] int32,
         fused_xyz [N*K,21,3] and fused_mesh [N*K,V,3]; a cloud step: behind those, cloud [N,K,P,3] fp32, cloud_count [N,K,2]
         int32 and cloud_resid [N,K] int64; a fit step: behind those, fit_mesh [N,K,V,3], fit_xyz [N,K,21,3], fit_rt [N,K,12]
-        fp32, fit_count [N,K,2] int32 and fit_cost [N,K] int64, and -- fit_iters >= 2 -- fit_trace [N,K,I,3] int64)."""
+        fp32, fit_count [N,K,2] int32 and fit_cost [N,K] int64, and -- fit_iters >= 2 -- fit_trace [N,K,I,3] int64; an objects
+        step: behind those, contact and object_index [N,K] int32, object_box [N,K,4], object_score [N,K], object_point [N,K,2],
+        object_xyz [N,K,3] and object_extent [N,K,6] fp32 and object_count [N,K,2] int32 -- a read type whose name ends in
+        ObjectsRead)."""
         v, s = self.layout.views(self.host), self.layout.slots
         per = lambda t: t.reshape((self.layout.frames, self.layout.hands) + tuple(t.shape[1:]))
         kp, has, box, words, (img, xyz) = read_host_record(v.records, s, extras=True)
@@ -881,7 +954,9 @@ class LiveHandsEngine(_LiveStep):
     def __init__(self, hand: HandNetEngine, lifter: Pose2MeshEngine, paras, max_hands: int = 2, clamp: bool = True,
                  perm_reverse=None, faces=None, labels: bool = False, left: bool = False, handed: bool = False,
                  left_side: int = 0, track: bool = False, track_iou: float = 0.3, track_hold: int = 5, occlude: bool = False,
-                 occlude_margin: float = ops.OCCLUDE_MARGIN, extrinsics=None, rig_radius: float = ops.RIG_RADIUS,
+                 occlude_margin: float = ops.OCCLUDE_MARGIN, objects: bool = False, object_band: float = ops.OBJECT_BAND,
+                 object_stride: int = ops.OBJECT_STRIDE, object_min_points: int = ops.OBJECT_MIN_POINTS, extrinsics=None,
+                 rig_radius: float = ops.RIG_RADIUS,
                  fit_iters: int = 1, fit_draw: bool = False, cloud: bool = False, cloud_points: int = ops.CLOUD_POINTS, cloud_band: float = ops.CLOUD_BAND,
                  cloud_stride: int = ops.CLOUD_STRIDE, cloud_frame: str = "camera", fit: bool = False,
                  fit_band: float = ops.FIT_BAND, fit_stride: int = ops.FIT_STRIDE, fit_min_points: int = ops.FIT_MIN_POINTS,
@@ -953,7 +1028,24 @@ class LiveHandsEngine(_LiveStep):
         overlay and the cloud stay what they are.  fit_iters / fit_draw: as LiveHandEngine's, .fit_trace
         [N,K,I,3]; every slot that is lifted is drawn again before a further iteration, fitted or not, because it may cover
         another slot's pixels; labels, rig outputs and the smoothing state are not touched.  fit_band = 0.03 m, fit_stride = 2, fit_min_points = 200, fit_damp = 1e-3,
-        fit_max_shift = 0.05 m and fit_max_angle = 0.35 rad are starting values, NOT tuned on this model."""
+        fit_max_shift = 0.05 m and fit_max_angle = 0.35 rad are starting values, NOT tuned on this model.
+        objects (needs paras and a detector with the ext heads): the step also says what every hand holds.  The
+        detector pass goes through detect_ext (one more launch) and the step ends with three more launches (ops.hand_objects)
+        whose results ride in the same copy, behind every other field: LiveHandsOutput.contact [N,K] int32 (the slot's contact
+        state; -1: empty slot), .object_index [N,K] int32 (the held object's row in hands.detections, -1: none), .object_box
+        [N,K,4], .object_score [N,K] and .object_point [N,K,2] (the point the hand's offset vector names) -- the association
+        of the reference's evaluation (voc_eval.py:687-699) on the detections as they are, without its file round trip --,
+        .object_xyz [N,K,3] and .object_extent [N,K,6] (the centroid and the min / max corner, camera frame, metres, of the
+        candidates -- every object_stride-th row and column -- inside the object's box whose depth is finite and > 0, lies
+        within object_band metres of the depth of the slot's root joint and -- occlude=True -- is under no hand's mesh) and
+        .object_count [N,K,2] (matches, status: 0 ok, 1 no object, 2 fewer than object_min_points matches, -1 empty slot);
+        read() likewise, a read type whose name ends in ObjectsRead.  labels=True: box_label also carries the object's
+        rectangle and the line from the hand box's centre to the object's, in (0, 0, 255) (one more launch); pose_label is
+        untouched.  A `left` step works in the mirrored frame; handed, track, smooth, fit, cloud and extrinsics change nothing
+        here: the root joint is the unsmoothed xyz_mm's and the object stays in the camera frame.  That a contact state > 0
+        means "in contact" (3 / 4: a portable / stationary object) is 100DOH's numbering, which the reference's live code never
+        reads: check it against your checkpoint.  object_band = 0.15 m, object_stride = 2 and object_min_points = 50 are
+        starting values, NOT tuned on any model."""
         self.hands = self.max_hands = ops.check_max_hands(max_hands)
         if left and handed:
             raise ValueError("left=True mirrors the whole frame and handed=True mirrors the left-hand slots: give one of them")
@@ -984,6 +1076,14 @@ class LiveHandsEngine(_LiveStep):
         if cloud_frame == "rig" and extrinsics is None:
             raise ValueError('cloud_frame="rig" needs extrinsics=: the camera -> rig transforms the points go through')
         self.cloud_frame = cloud_frame
+        if objects:
+            if paras is None:
+                raise ValueError("objects=True needs paras=: the object's depth pixels are back-projected with the camera, around "
+                                 "the depth of xyz_mm's root joint")
+            if not hand.fcos.ext:
+                raise ValueError("objects=True needs a detector with the ext heads (contact state and offset vector): build the "
+                                 "FCOS engine with ext=True")
+            self.objects = ops.check_objects(object_band, object_stride, object_min_points)
         super().__init__(hand, lifter, paras, clamp, perm_reverse, faces, labels, left, occlude, occlude_margin, fit_iters,
                          fit_draw, cloud, cloud_points, cloud_band, cloud_stride, fit, fit_band, fit_stride, fit_min_points, fit_damp,
                          fit_max_shift, fit_max_angle)
@@ -999,7 +1099,7 @@ class LiveHandsEngine(_LiveStep):
         more = {} if self.track is None else dict(track=True, track_iou=self.track[0], track_hold=self.track[1],
                                                   _track_out=(at.track_id, at.track_age))      # (at: LiveTrackedViews)
         return self.hand.forward_hands(images, depth, self.hands, _record=(None, at.records), _tail=lift, handed=self.handed,
-                                       left_side=self.left_side, _side=at.side, **more)
+                                       left_side=self.left_side, _side=at.side, objects=self.objects is not None, **more)
 
     def track_reset(self):
         """Empty the hand engine's trackers (HandNetEngine.track_reset; also between replays of a captured step) and, on a
@@ -1094,6 +1194,8 @@ class LiveHandsEngine(_LiveStep):
                          fit_cost=parts["fit_cost"].view(n, k))
         if "fit_trace" in parts:
             parts["fit_trace"] = parts["fit_trace"].view(n, k, -1, 3)
+        if "contact" in parts:
+            parts.update({f: parts[f].view((n, k) + tuple(parts[f].shape[1:])) for f in OBJECT_FIELDS})
         return LiveHandsOutput(hands=out, lifted=at.lifted.view(n, k), host=host, n=n, k=k, side=out.side, mirror=out.mirror,
                                layout=layout, track_id=out.track_id, track_age=out.track_age,
                                smooth_xyz=None if self.smooth is None else at.smooth_xyz.view(n, k, SMOOTH_JOINTS, 3),

@@ -1206,9 +1206,11 @@ def fcos_candidates(cls_lr, reg_ctr, strides, num_classes, score_thresh=0.7, out
     return out
 
 
-def fcos_ext_gather(ext, det: "Detections", cand: Candidates):
+def fcos_ext_gather(ext, det: "Detections", cand: Candidates, *, out=None):
     """ext[l] [N,h,w,8] raw (relu(dxdy)[3], contact[5]) per level -> (contacts [N,cap] int32,
-    dxdymags [N,cap,3] fp32) for the kept detections (fcos.py:299-320,605-607,631-647)."""
+    dxdymags [N,cap,3] fp32) for the kept detections (fcos.py:299-320,605-607,631-647).  out: the caller's (contacts, dxdymags)
+    to write into -- no allocation and no zero fill here, so rows at and beyond count[i] keep what they held (a captured step
+    passes its own buffers); without it both are allocated and zero-filled, as ever."""
     lib = _lib.load()
     if cand.point is None:
         raise ValueError("candidates were produced without anchor-point indices")
@@ -1224,8 +1226,16 @@ def fcos_ext_gather(ext, det: "Detections", cand: Candidates):
     n, cap = det.scores.shape
     if sum(e.shape[1] * e.shape[2] for e in ext) != cand.scores.shape[1] or cand.scores.shape[1] != cap:
         raise ValueError("ext levels do not match the candidate capacity")
-    contacts = torch.zeros((n, cap), device=det.scores.device, dtype=torch.int32)
-    dxdymags = torch.zeros((n, cap, 3), device=det.scores.device, dtype=torch.float32)
+    if out is None:
+        contacts = torch.zeros((n, cap), device=det.scores.device, dtype=torch.int32)
+        dxdymags = torch.zeros((n, cap, 3), device=det.scores.device, dtype=torch.float32)
+    else:
+        contacts, dxdymags = out
+        _req(contacts, torch.int32, "out contacts"); _req(dxdymags, name="out dxdymags")
+        if tuple(contacts.shape) != (n, cap) or tuple(dxdymags.shape) != (n, cap, 3) or contacts.device != det.scores.device \
+                or dxdymags.device != det.scores.device:
+            raise ValueError(f"out: (contacts int32 [{n},{cap}], dxdymags fp32 [{n},{cap},3]) on {det.scores.device}, got "
+                             f"{tuple(contacts.shape)} on {contacts.device} and {tuple(dxdymags.shape)} on {dxdymags.device}")
     check(lib.hn_fcos_ext_gather(C.byref(lv), arr, ptr(det.keep), ptr(cand.point), ptr(det.count), n, cap,
                                  ptr(contacts), ptr(dxdymags), _stream()), "hn_fcos_ext_gather")
     return contacts, dxdymags
@@ -2873,6 +2883,131 @@ def mesh_fit_iters(mesh_depth, silhouette, scene_depth, paras, mesh, xyz_mm, fac
                                             stride, band, min_points, damp, shift2, tan2, ptr(scratch), scratch.numel(), ptr(work),
                                             work.numel(), *(ptr(t) for t in parts), _stream()), "hn_mesh_fit_iters_f32")
     return MeshFitIters(*parts)
+
+
+OBJECT_BAND = 0.15         # metres around the depth of the hand's root joint; a starting value, NOT tuned on any model
+OBJECT_STRIDE = 2          # every second row and column is a candidate; a starting value, NOT tuned on any model
+OBJECT_MIN_POINTS = 50     # fewer matches: no centroid is handed out; a starting value, NOT tuned on any model
+OBJECT_MAX_BAND = 100.0    # metres
+OBJECT_FIELDS = ("contact", "object_index", "object_box", "object_score", "object_point", "object_xyz", "object_extent", "object_count")
+
+
+@dataclass
+class HandObjects:
+    """ops.hand_objects: per hand slot s = i * k + j"""
+    contact: torch.Tensor        # [S] int32: the slot's contact state (100DOH: 0 none, 1 self, 2 other person, 3 portable, 4 stationary; -1: empty slot)
+    object_index: torch.Tensor   # [S] int32: the held object's detection row, or -1
+    object_box: torch.Tensor     # [S,4] fp32: its box (zeros: no object)
+    object_score: torch.Tensor   # [S] fp32: its score (0: no object)
+    object_point: torch.Tensor   # [S,2] fp32: the point the hand's offset vector names (zeros: empty slot)
+    object_xyz: torch.Tensor     # [S,3] fp32: the centroid of the object's depth pixels, camera frame, metres (zeros unless status 0)
+    object_extent: torch.Tensor  # [S,6] fp32: (min x y z, max x y z) of those pixels (zeros: no match)
+    object_count: torch.Tensor   # [S,2] int32: (matches, status: 0 ok, 1 no object, 2 fewer than min_points matches, -1 empty slot)
+
+
+def check_objects(band=OBJECT_BAND, stride=OBJECT_STRIDE, min_points=OBJECT_MIN_POINTS):
+    """The held objects' three parameters as (float band, int stride >= 1, int min_points >= 1), the band finite and in (0, 100]
+    metres also as the fp32 kernel argument it becomes; else ValueError.  The defaults (0.15 m, every second row and column, 50
+    matches) are starting values, NOT tuned on any model."""
+    _check_count("object_stride", stride)
+    _check_count("object_min_points", min_points)
+    try:
+        b = math.nan if isinstance(band, bool) else float(band)
+    except (TypeError, ValueError):
+        b = math.nan
+    _check_band("object_band", b, band, OBJECT_MAX_BAND)
+    return b, int(stride), int(min_points)
+
+
+def hand_objects_scratch_bytes(frames, k, h):
+    return int(_lib.load().hn_hand_objects_scratch_bytes(frames, k, h))
+
+
+def hand_objects(det: Detections, contacts, dxdymags, det_index, depth, xyz_mm, paras, k, *, object_label=1, band=OBJECT_BAND,
+                 stride=OBJECT_STRIDE, min_points=OBJECT_MIN_POINTS, silhouette=None, scratch=None, out=None) -> HandObjects:
+    """The object each hand holds (hn_hand_objects_f32: three launches, csrc/hand_object.hip; DESIGN.md section 9q,
+    tests/object_ref.py is the rule and the outputs equal it bit for bit).  det: the detector's Detections of N frames (boxes
+    [N,cap,4], scores, labels, count); contacts int32 [N,cap] and dxdymags fp32 [N,cap,3]: what fcos_ext_gather /
+    FCOSEngine.detect_ext leave; det_index int32 [N,k]: each slot's detection row (-1: empty slot), as forward_hands hands it
+    out; depth: the camera's depth map, fp32 [N,1,H,W], [N,H,W] or an RGB-D [N,4,H,W] (channel 3 is read in place); xyz_mm fp32
+    [N*k,J,3] or [N,k,J,3]: camera millimetres, joint 0 the root; paras (fx, fy, cx, cy) on the host, or an fp32 tensor [N,4] on
+    the device, a camera per frame; k slots per frame (1..16).
+    A slot whose contact state is > 0 is given, among the frame's rows of `object_label` (1: the targetobject of num_classes =
+    3), the one whose centre lies nearest to hand centre + (magnitude * 10000) * (x, y) -- the association of the reference's
+    evaluation (voc_eval.py:687-699) on the detections AS THEY ARE: its %.1f / %.3f file round trip and its + 1 are left out on
+    purpose; ties go to the earlier rank.  The candidates (every stride-th row and column) whose centre (c + 0.5, r + 0.5) lies
+    in that box, whose depth D is finite and > 0, whose silhouette byte -- silhouette uint8 [N,H,W], the occluded raster's, or
+    None -- names no hand ((byte & 0x7F) == 0) and |D - z of the slot's root joint| <= band metres are back-projected as
+    hand_cloud does and reduced to a centroid (integer sums of micrometres) and an extent.  Returns HandObjects, a row per
+    slot; allocated, or `out`'s attributes of the same names (the live step's buffer views), every one fully written.
+    That contact states > 0 mean "in contact" (3 / 4: a portable / stationary object) is 100DOH's numbering, which the
+    reference's live code never reads: check it against the checkpoint in use.  band = 0.15 m, stride = 2 and min_points = 50
+    are starting values, NOT tuned on any model."""
+    band, stride, min_points = check_objects(band, stride, min_points)
+    for name, t, dtype in (("det.boxes", det.boxes, torch.float32), ("det.scores", det.scores, torch.float32),
+                           ("det.labels", det.labels, torch.int32), ("det.count", det.count, torch.int32),
+                           ("contacts", contacts, torch.int32), ("dxdymags", dxdymags, torch.float32),
+                           ("det_index", det_index, torch.int32), ("xyz_mm", xyz_mm, torch.float32)):
+        _req(t, dtype, name)
+    dev = det.scores.device
+    if det.scores.dim() != 2:
+        raise ValueError(f"det.scores: expected [N,cap], got {tuple(det.scores.shape)}")
+    n, cap = (int(v) for v in det.scores.shape)
+    k = int(k)
+    if not 1 <= k <= 16:
+        raise ValueError(f"k = {k} slots per frame (1..16)")
+    for name, t, shape in (("det.boxes", det.boxes, (n, cap, 4)), ("det.labels", det.labels, (n, cap)), ("det.count", det.count, (n,)),
+                           ("contacts", contacts, (n, cap)), ("dxdymags", dxdymags, (n, cap, 3)), ("det_index", det_index, (n, k))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected {list(shape)}, got {tuple(t.shape)}")
+        _on_device(name, t, dev, "the detections")
+    s = n * k
+    if xyz_mm.dim() < 3 or xyz_mm.shape[-1] != 3 or xyz_mm.numel() != s * xyz_mm.shape[-2] * 3 or xyz_mm.shape[-2] < 1:
+        raise ValueError(f"xyz_mm: expected fp32 [{s},J,3] or [{n},{k},J,3], got {tuple(xyz_mm.shape)}")
+    _on_device("xyz_mm", xyz_mm, dev, "the detections")
+    joints = int(xyz_mm.shape[-2])
+    if not torch.is_tensor(depth) or depth.dim() < 3:
+        raise ValueError("depth: expected fp32 [N,1,H,W], [N,H,W] or RGBD [N,4,H,W]")
+    h, w = (int(v) for v in depth.shape[-2:])
+    depth_ptr, depth_stride = _scene_depth_arg(depth, n, h, w, dev, "the detections")
+    if silhouette is not None:
+        _req(silhouette, torch.uint8, "silhouette")
+        if tuple(silhouette.shape) != (n, h, w):
+            raise ValueError(f"silhouette: expected uint8 [{n},{h},{w}], got {tuple(silhouette.shape)}")
+        _on_device("silhouette", silhouette, dev, "the detections")
+    host4, table = _camera_arg(paras, n, dev, "the detections")
+    parts = _out_parts(out, (("contact", torch.int32, (s,)), ("object_index", torch.int32, (s,)), ("object_box", torch.float32, (s, 4)),
+                             ("object_score", torch.float32, (s,)), ("object_point", torch.float32, (s, 2)),
+                             ("object_xyz", torch.float32, (s, 3)), ("object_extent", torch.float32, (s, 6)),
+                             ("object_count", torch.int32, (s, 2))), dev)
+    scratch = _scratch_arg(scratch, dev, hand_objects_scratch_bytes, n, k, h)
+    check(_lib.load().hn_hand_objects_f32(ptr(det.boxes), ptr(det.scores), ptr(det.labels), ptr(det.count), ptr(contacts), ptr(dxdymags),
+                                          ptr(det_index), cap, int(object_label), depth_ptr, depth_stride, ptr(silhouette), ptr(xyz_mm),
+                                          joints, host4, table, n, k, h, w, stride, band, min_points, ptr(scratch), scratch.numel(),
+                                          *(ptr(t) for t in parts), _stream()), "hn_hand_objects_f32")
+    return HandObjects(*parts)
+
+
+def draw_object_labels(det: Detections, det_index, object_index, box_label):
+    """The held objects on the box label image, IN PLACE (hn_draw_object_labels_u8: one launch, csrc/hand_object.hip;
+    tests/object_ref.py draw_object_labels is the rule): box_label uint8 [N,H,W,3] as draw_labels leaves it; for every slot with
+    object_index >= 0 (int32 [N,k] or [N*k], as hand_objects hands it out) the object's rectangle and the line from the hand
+    box's centre (det.boxes of det_index) to the object box's centre, both in (0, 0, 255); corners and centres are rounded to
+    the nearest integer and saturated at 2^20, as the crop boxes are.  Every other pixel keeps its bytes.  Returns box_label."""
+    _req(det.boxes, name="det.boxes"); _req(det_index, torch.int32, "det_index"); _req(object_index, torch.int32, "object_index")
+    _req(box_label, torch.uint8, "box_label")
+    if det.boxes.dim() != 3 or det.boxes.shape[2] != 4 or box_label.dim() != 4 or box_label.shape[3] != 3 \
+            or box_label.shape[0] != det.boxes.shape[0]:
+        raise ValueError(f"det.boxes [N,cap,4] and box_label uint8 [N,H,W,3], got {tuple(det.boxes.shape)} and {tuple(box_label.shape)}")
+    n, cap = (int(v) for v in det.boxes.shape[:2])
+    h, w = (int(v) for v in box_label.shape[1:3])
+    if det_index.numel() % n or det_index.numel() != object_index.numel() or not 1 <= det_index.numel() // n <= 16:
+        raise ValueError(f"det_index / object_index: int32 [{n},k] each, k 1..16, got {tuple(det_index.shape)} and {tuple(object_index.shape)}")
+    for name, t in (("det_index", det_index), ("object_index", object_index), ("box_label", box_label)):
+        _on_device(name, t, det.boxes.device, "the detections")
+    check(_lib.load().hn_draw_object_labels_u8(ptr(det.boxes), ptr(det_index), ptr(object_index), cap, n, det_index.numel() // n, h, w,
+                                               ptr(box_label), _stream()), "hn_draw_object_labels_u8")
+    return box_label
 
 
 LABEL_CROP = 176      # side of a pose_label image

@@ -94,6 +94,8 @@ class HandsOutput:
     tail: object = None                # what forward_hands' `_tail` callable returned (the multi-hand live step, hn_amd/live.py)
     side: torch.Tensor = None          # handed steps: [N,K] int32 device, detections.sides of the slot's detection (-1 when empty)
     mirror: torch.Tensor = None        # handed steps: [N,K] int32 device, 1 where the slot went through A2J mirrored (a left hand)
+    contacts: torch.Tensor = None      # objects steps: [N,cap] int32 device, the contact state of every detection row below count
+    dxdymags: torch.Tensor = None      # objects steps: [N,cap,3] fp32 device, (magnitude, x, y) of every such row's offset vector
     track_id: torch.Tensor = None      # tracked steps: [N,K] int32 device, the slot's track id (held slots included; 0: free)
     track_age: torch.Tensor = None     # tracked steps: [N,K] int32 device, the steps on which the slot's track was seen again
 
@@ -299,7 +301,7 @@ class HandNetEngine:
     @ops.device_guarded
     def forward_hands(self, images, depth: torch.Tensor, max_hands: int = 2, to_host: bool = False, _record=None,
                       _tail=None, handed: bool = False, left_side: int = 0, _side=None, track: bool = False,
-                      track_iou: float = 0.3, track_hold: int = 5, _track_out=None) -> HandsOutput:
+                      track_iou: float = 0.3, track_hold: int = 5, _track_out=None, objects: bool = False) -> HandsOutput:
         """forward_device for up to max_hands (1..16) hands per frame: slot k of frame i is the k-th hand-label detection of
         frame i in the detector's score order, cropped as forward_device crops the first (max_hands = 1 IS forward_device's
         crop); A2J runs on the N * max_hands crops with the slots' has_hand mask (capturable), or -- eager, when the previous
@@ -319,10 +321,16 @@ class HandNetEngine:
         its score rank; a slot whose hand is missing is held EMPTY (has_hand 0) for track_hold steps, then freed; new hands
         take the free slots, lowest first, in score order.  The engine owns one state per (N, K), shared by eager steps and
         captures of that shape (track_reset() empties it).  to_host records carry track_id and track_age last
-        (read_hands_tail(..., tracked=True)).  Frames of at most 32767 x 32767 pixels."""
+        (read_hands_tail(..., tracked=True)).  Frames of at most 32767 x 32767 pixels.
+        objects: the detector pass goes through FCOSEngine.detect_ext (one more launch) and the step also hands out what the
+        contact heads say about every detection row: HandsOutput.contacts [N,cap] and .dxdymags [N,cap,3] -- with det_index,
+        what ops.hand_objects takes (the live step's objects=True).  An engine whose detector has no ext heads: RuntimeError,
+        before any launch."""
+        if objects and not self.fcos.ext:
+            raise RuntimeError("forward_hands(objects=True) needs a detector with the ext heads: build the FCOS engine with ext=True")
         return self._step(images, depth, ops.check_max_hands(max_hands), to_host, _record, _tail,
                           (int(left_side), _side) if handed else None,
-                          ops.check_track_options(track_iou, track_hold) + (_track_out,) if track else None)
+                          ops.check_track_options(track_iou, track_hold) + (_track_out,) if track else None, bool(objects))
 
     def _track_state(self, n, hands):
         st = self._track_states.get((n, hands))
@@ -338,7 +346,7 @@ class HandNetEngine:
             st.zero_()
         return self
 
-    def _step(self, images, depth, hands, to_host, _record, _tail, handed=None, track=None):
+    def _step(self, images, depth, hands, to_host, _record, _tail, handed=None, track=None, objects=False):
         """The body of forward_device (hands None: the top-1 crop, HandNetOutput) and forward_hands (hands = K; handed =
         (left_side, where the sides go or None): the handed step; track = (thr_milli, hold, (where the ids go, the ages) or
         None): the tracked step)."""
@@ -358,7 +366,11 @@ class HandNetEngine:
                                                                                    track is not None)
         # (the scope is this host thread's: another engine on another thread keeps its own switch and block)
         with ops.range_scope(self._range_block, on=noting):
-            det, cand = self.fcos.detect(images)
+            contacts = dxdymags = None
+            if objects:      # (the K-hand step's option: the contact heads' rows ride along)
+                det, cand, contacts, dxdymags = self.fcos.detect_ext(images, zero=False)
+            else:
+                det, cand = self.fcos.detect(images)
             if hands is None:
                 crop_box, has_hand, crops = ops.crop_resize(det, self.num_classes - 1, depth.float().contiguous(), CROP, 4,
                                                             reorder_bgr=self.a2j.rgbd)
@@ -445,7 +457,7 @@ class HandNetEngine:
         per_slot = (n, hands) + tuple(kp.shape[1:])
         return HandsOutput(kp.view(per_slot), crops, crop_box, has_hand, score, det_index, det, cand, flags,
                            None if img_uvd is None else img_uvd.view(per_slot), None if xyz is None else xyz.view(per_slot),
-                           host_rec, tail, side, mirror, track_id, track_age)
+                           host_rec, tail, side, mirror, contacts, dxdymags, track_id, track_age)
 
     # -------------------------------------------------------------------------------
     # sparse streams: A2J on the frames with a hand only

@@ -42,7 +42,8 @@ extern "C" {
  * iterated fit's hn_mesh_geometry_f32, hn_mesh_fit_iters_f32 and hn_mesh_fit_iters_scratch_bytes, and the carried apply pass's
  * hn_conv2d_nhwc_f16x3_grouped_carry, hn_conv2d_f16x3_grouped_carry_applies and hn_affine_split_f32_levels_streams, the evaluator's hn_hpe_accumulate_f32, the
  * detector evaluation's hn_det_ap_accumulate_f32, the A2J criterion's hn_a2j_aggregate_loss_f32, and the FCOS criterion's
- * hn_fcos_loss_f32 and hn_fcos_loss_ws_bytes). */
+ * hn_fcos_loss_f32 and hn_fcos_loss_ws_bytes, and the held objects' hn_hand_objects_f32, hn_hand_objects_scratch_bytes and
+ * hn_draw_object_labels_u8). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -998,6 +999,44 @@ int hn_mesh_fit_iters_f32(const float* mesh_depth, const uint8_t* silhouette, co
                           int stride, float band, int min_points, double damp, double max_shift2, double tan2_half_angle,
                           void* scratch, int64_t scratch_bytes, void* work, int64_t work_bytes, float* out_mesh, float* out_xyz,
                           float* out_rt, int32_t* out_count, int64_t* out_cost, int64_t* out_trace, void* stream);
+/* The object each hand holds (tests/object_ref.py is the rule in numpy float32, and the outputs equal it bit
+ * for bit: one rounding per operation, integer sums, no atomics).  det_* DEVICE: the detector's rows of n frames, `cap` rows each
+ * (boxes [n][cap][4] x1 y1 x2 y2, scores, labels, count [n] -- clamped to 0..cap); contacts [n][cap] and dxdymags [n][cap][3]
+ * (magnitude, x, y): what hn_fcos_ext_gather leaves; det_index [n][k]: each hand slot's detection row (< 0, or >= cap: an empty
+ * slot).  scene_depth / depth_frame_stride, paras / cams: as hn_hand_cloud_f32 takes them (exactly one of paras -- HOST, 4 floats --
+ * and cams -- DEVICE [n][4]); silhouette DEVICE [n][h][w] or NULL; xyz_mm DEVICE [n*k][joints][3], joint 0 the root.
+ * Association (voc_eval.py:687-699 on the detections as they are): a slot whose contact state is > 0 takes, among the frame's rows
+ * of `object_label`, the one whose centre is nearest to hand centre + (magnitude * 10000) * (x, y); the sequential scan's ties (the
+ * earlier rank) and NaN behaviour (a NaN distance only stays when it is the first object's).  Then the candidates (r % stride == 0,
+ * c % stride == 0) whose centre (c + 0.5, r + 0.5) lies in the object's box [x1, x2) x [y1, y2), whose depth D is finite and > 0,
+ * whose silhouette byte names no slot ((byte & 0x7F) == 0; NULL: not tested) and |D - xyz_mm[s][0][2] * 0.001| <= band are
+ * back-projected as hn_hand_cloud_f32 does and reduced.
+ *   out_contact [n*k]     the slot's contact state (-1: empty slot)
+ *   out_index   [n*k]     the object's detection row, or -1
+ *   out_box     [n*k][4]  its box, out_score [n*k] its score (zeros: no object)
+ *   out_point   [n*k][2]  the point the hand's vector names (zeros: empty slot)
+ *   out_xyz     [n*k][3]  (float)((double)sum of rint(coordinate * 1e6) / (matches * 1e6)), metres; zeros unless the status is 0
+ *   out_extent  [n*k][6]  minimum x y z, maximum x y z over the matches; zeros without a match
+ *   out_count   [n*k][2]  (matches, status: 0 ok, 1 no object, 2 fewer than min_points matches, -1 empty slot)
+ * Every output is fully written.  Three launches on `stream`; every argument is checked before the first (k 1..16, h and w
+ * 1..16384, cap 1..2^24, stride and min_points >= 1, 0 < band <= 100, scratch of hn_hand_objects_scratch_bytes(n, k, h) bytes,
+ * 8-byte aligned). */
+int64_t hn_hand_objects_scratch_bytes(int n, int k, int h);
+int hn_hand_objects_f32(const float* det_boxes, const float* det_scores, const int32_t* det_labels, const int32_t* det_count,
+                        const int32_t* contacts, const float* dxdymags, const int32_t* det_index, int cap, int object_label,
+                        const float* scene_depth, int64_t depth_frame_stride, const uint8_t* silhouette /* or NULL */,
+                        const float* xyz_mm, int joints, const float* paras /* host, or NULL */,
+                        const float* cams /* device [n][4], or NULL */, int n, int k, int h, int w, int stride, float band,
+                        int min_points, void* scratch, int64_t scratch_bytes, int32_t* out_contact, int32_t* out_index,
+                        float* out_box, float* out_score, float* out_point, float* out_xyz, float* out_extent, int32_t* out_count,
+                        void* stream);
+/* The held objects on the box label image, IN PLACE on box_label DEVICE uint8 [n][h][w][3] (tests/object_ref.py draw_object_labels
+ * is the rule): for every slot with object_index >= 0, the object's rectangle (thickness 1, inclusive corners) and the line
+ * (8-connected Bresenham, tests/draw_ref.py line_points) from the hand box's centre to the object box's centre, both in (0, 0, 255);
+ * corners and centres ((a + b) * 0.5 in fp32) are rounded to the nearest integer, ties to even, and saturated at +-2^20 (NaN: 0).
+ * Every other pixel is left as it is.  One launch. */
+int hn_draw_object_labels_u8(const float* det_boxes, const int32_t* det_index, const int32_t* object_index, int cap, int n, int k,
+                             int h, int w, uint8_t* box_label, void* stream);
 /* The hand-pose evaluator's tables for the evaluation loop (tests/hpe_ref.py is the rule in numpy fp64, and
  * every output equals it bit for bit): what HPEEvaluator.evaluate feeds its three EvalUtil accumulators -- the absolute, the
  * root-relative and the Procrustes-aligned (align_w_scale, reflections allowed) distance of every joint -- added into an integer
