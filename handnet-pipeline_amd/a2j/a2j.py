@@ -15,8 +15,9 @@ handnet_pipeline/handnet_pipeline.py:8) resolves -- and its evaluation hook `tes
 convert_joints on prediction and ground truth -> RMSE in mm -> the HPE evaluator's text file), the second caller SURVEY 8f #1
 names, with the conversion in the aggregation's epilogue.
 `model(x, gt)` returns `(losses, output)` like the reference (a2j/a2j.py:231-239): the criterion (a2j/anchor.py:99-153) is
-evaluated in the aggregation's sweep over the heads, forward only -- nothing here can back-propagate, so `training_step` and
-`configure_optimizers` raise, and `validation_step` runs after `device_loss()`.
+evaluated in the aggregation's sweep over the heads, forward only -- nothing here can back-propagate through the HIP
+convolutions; the gradient at the heads is `head_grads` --, so `training_step` and `configure_optimizers` raise, and
+`validation_step` runs after `device_loss()`.
 """
 from __future__ import annotations
 
@@ -68,7 +69,14 @@ class A2JModel(EngineOwner):
 
     last_loss_host = None   # forward(x, gt): the call's five batch scalars as floats, from its one device -> host copy
 
-    def _forward_loss(self, x, gt):
+    def head_grads(self, x, gt):
+        """forward(x, gt) and the criterion's backward at the engine's own heads in one more launch (ops.a2j_loss_grad;
+        DESIGN.md section 9r) -> (losses, output, (d_cls, d_reg, d_dep)): losses and output are forward(x, gt)'s bytes, the
+        gradients are total_loss's with respect to the three head tensors, in their layouts ([K,11,11,16 J] / [K,11,11,32 J])
+        and on the device."""
+        return self._forward_loss(x, gt, head_grads=True)
+
+    def _forward_loss(self, x, gt, head_grads=False):
         """forward(x, gt) (a2j/a2j.py:231-239, eager_outputs with gt): the criterion rides in the aggregation's sweep
         (ops.a2j_loss), forward only.  -> (losses, output): losses = {"classification", "regression" (already times
         reg_loss_factor = 3), "total_loss"}, fp32 tensors of shape [1] on the device; output = forward(x)'s, bit for bit.
@@ -79,7 +87,8 @@ class A2JModel(EngineOwner):
         if not g.is_floating_point() or g.dim() != 3 or tuple(g.shape[1:]) != (self.num_classes, 3) or g.shape[0] != x.shape[0]:
             raise ValueError(f"gt must be a float tensor or array of shape [K,{self.num_classes},3], one row per crop")
         g = g.detach().to(device=eng.device, dtype=torch.float32).contiguous()
-        (kp, _terms, _sample, batch), flags = eng.forward_flags(x, gt=g, spatial_factor=self.spatial_factor)
+        res, flags = eng.forward_flags(x, gt=g, spatial_factor=self.spatial_factor, head_grads=head_grads)
+        (kp, _terms, _sample, batch), grads = res if head_grads else (res, None)
         parts = [kp.contiguous().reshape(-1).view(torch.int32), batch.view(torch.int32)] + ([flags[:3]] if flags is not None else [])
         flat = torch.cat(parts).cpu()
         n = kp.numel()
@@ -87,7 +96,8 @@ class A2JModel(EngineOwner):
         check_range_contract(out, flat[n + 5:].tolist() if flags is not None else None, x)
         host = flat[n:n + 5].contiguous().view(torch.float32).tolist()
         self.last_loss_host = dict(zip(("classification", "regression_mean", "regression", "total_loss", "rmse"), host))
-        return {"classification": batch[0:1], "regression": batch[2:3], "total_loss": batch[3:4]}, out
+        losses = {"classification": batch[0:1], "regression": batch[2:3], "total_loss": batch[3:4]}
+        return (losses, out, grads) if head_grads else (losses, out)
 
     def forward(self, x, gt=None):
         if gt is not None:
@@ -319,7 +329,8 @@ class A2JModelLightning(EngineOwner):
     def device_loss(self, enable: bool = True):
         """Opt in to (or out of) `validation_step` on the device: the A2J criterion evaluated in the
         aggregation's sweep, forward only.  Off, validation_step raises NotImplementedError as before.  training_step and
-        configure_optimizers raise either way: nothing here can back-propagate through the HIP convolutions."""
+        configure_optimizers raise either way: nothing here can back-propagate through the HIP convolutions; the gradient at
+        the heads is `head_grads`."""
         self._device_loss = bool(enable)
         return self
 

@@ -150,6 +150,244 @@ __device__ __forceinline__ void loss_terms_one(const LossSpec& ls, long joint_ro
 #define A2J_AGG_LOSS 1
 #include "a2j_aggregate_body.h"
 
+// what the criterion's backward (hn_a2j_loss_grad_f32; DESIGN.md section 9r, tests/loss_grad_ref.py) adds to the kernel's arguments
+struct GradSpec {
+  const float* gt;         // [n,J,3]
+  const float* upstream;   // device (wa, wr): the weights of classification and regression in the differentiated scalar; nullptr: (1, 1)
+  float spatial_factor, reg_loss_factor;
+  float* d_cls;            // [n,fh,fw,16 J]
+  float* d_reg;            // [n,fh,fw,16 J,2]
+  float* d_dep;            // [n,fh,fw,16 J]
+  float* uvd;              // [n,J,3] or nullptr: the loss entry's keypoints
+  float* terms;            // [n,J,8] or nullptr: the loss entry's terms
+};
+constexpr int kGradJoint = 12;   // per-joint values of the third sweep: mj, t, Ea x 2, Er x 2, Ed, ga x 2, gr x 2, gd
+
+// the derivative of smooth_l1(|x|) in x (C1: the knee needs no guard); a NaN stays NaN (fminf / fmaxf would drop it)
+__device__ __forceinline__ float clip1(float x) { return x != x ? x : fminf(fmaxf(x, -1.f), 1.f); }
+// the derivative of |x|: sign(0) = 0 as torch's, a NaN stays NaN
+__device__ __forceinline__ float sign1(float x) { return x > 0.f ? 1.f : x < 0.f ? -1.f : x; }
+
+// The criterion's backward in the aggregation's sweep: grid, thread <-> (group, anchor, joint) map, cell batches and LDS
+// combination of a2j_loss_aggregate_kernel (phases one and two below are its lines: the same maximum and six sums through the same
+// chains in the same order, so the divided uvd and the eight terms are the loss entry's bytes), then
+//   the thread that owns a joint: n = rows with valid != 0 (counted here, per workgroup), the coefficients
+//     ga_c = wa / n / (2J) clip(Ea_c - g_c),  gr_c = wr R sf / n / (2J) clip(Er_c - g_c),  gd = wr R / n / J sign(Ed - g_d)
+//     and t, Ea, Er, Ed into LDS (mj is there since the first phase);
+//   a third sweep over the workgroup's own cells: e = expf(cls - mj) (the same expression), w = e / t,
+//     d_reg = w gr_c,  d_dep = w gd,  d_cls = w (sum_c ga_c (anchor_c - Ea_c) + sum_c gr_c (anchor_c + reg_c - Er_c) + gd (dep - Ed)).
+// Every gradient element is written by exactly one thread (the one that summed it): no atomics, no second launch.  Rows with
+// valid == 0 get zero gradients, rows with valid == 2 NaN.  Dynamic LDS: [G][6][AW] floats + kGradJoint * Jw.
+__global__ __launch_bounds__(1024) void a2j_loss_grad_kernel(const float* __restrict__ cls, const float* __restrict__ reg,
+                                                             const float* __restrict__ dep, const int* __restrict__ valid, int fh,
+                                                             int fw, int J, int Jw, int stride, int G, const GradSpec gs) {
+  constexpr int NQ = 6;
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // [G][NQ][A*Jw], then [kGradJoint][Jw]
+  __shared__ int wave_rows[16];
+  const int k = blockIdx.x;
+  const int j0 = blockIdx.y * Jw;
+  const int jn = min(Jw, J - j0);
+  if (jn <= 0) return;
+  const int AJ = kAnchorsPerCell * J;
+  const int AW = kAnchorsPerCell * Jw;
+  const int g = threadIdx.x / AW, cl = threadIdx.x - g * AW;
+  const int a = cl / Jw, jl = cl - a * Jw;
+  const bool active = g < G && jl < jn;
+  const int c = a * J + j0 + jl;
+  const int cells = fh * fw;
+  if (valid && valid[k] != 1) {  // uniform per workgroup: the row's slice of the gradients (and of the forward outputs) is 0 or NaN
+    const float fill = valid[k] == 0 ? 0.f : __builtin_nanf("");
+    if (active)
+      for (int p = g; p < cells; p += G) {
+        const long q = ((long)k * cells + p) * AJ + c;
+        gs.d_cls[q] = fill;
+        *reinterpret_cast<float2*>(gs.d_reg + q * 2) = make_float2(fill, fill);
+        gs.d_dep[q] = fill;
+      }
+    if (gs.uvd && (int)threadIdx.x < jn * 3) gs.uvd[((long)k * J + j0) * 3 + threadIdx.x] = fill;
+    if (gs.terms && (int)threadIdx.x < jn * kLossTerms) gs.terms[((long)k * J + j0) * kLossTerms + threadIdx.x] = fill;
+    return;
+  }
+  {  // rows that count in the batch means: this thread's share, then its wave's (read behind the barriers below)
+    int rows = 0;
+    if (valid)
+      for (int i = threadIdx.x; i < (int)gridDim.x; i += blockDim.x) rows += valid[i] != 0 ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) rows += __shfl_xor(rows, o);
+    if ((threadIdx.x & 63) == 0) wave_rows[threadIdx.x >> 6] = rows;
+  }
+  const float* clsk = cls + (long)k * cells * AJ;
+  const float* depk = dep + (long)k * cells * AJ;
+  const float* regk = reg + (long)k * cells * AJ * 2;
+
+  constexpr int kBatch = 14;
+  float mx = -FLT_MAX;
+  if (active)
+    for (int pb = g; pb < cells; pb += kBatch * G) {
+      float v[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int p = pb + u * G;
+        v[u] = p < cells ? clsk[(long)p * AJ + c] : -FLT_MAX;
+      }
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) mx = fmaxf(mx, v[u]);
+    }
+  if (g < G) lds[g * AW + cl] = mx;
+  __syncthreads();
+  if ((int)threadIdx.x < AW) {
+    float m = lds[threadIdx.x];
+    for (int gg = 1; gg < G; ++gg) m = fmaxf(m, lds[gg * AW + threadIdx.x]);
+    lds[threadIdx.x] = m;
+  }
+  __syncthreads();
+  float mj = -FLT_MAX;
+  if (active)
+    for (int aa = 0; aa < kAnchorsPerCell; ++aa) mj = fmaxf(mj, lds[aa * Jw + jl]);
+  float* jv = lds + (long)G * NQ * AW;   // [kGradJoint][Jw]: behind the planes
+  if ((int)threadIdx.x < jn) jv[threadIdx.x] = mj;   // (thread jl = group 0, anchor 0 of its joint; read in the third sweep)
+  __syncthreads();
+
+  if (active) {
+    const float p0 = 2.f + 4.f * (float)(a >> 2), p1 = 2.f + 4.f * (float)(a & 3);
+    float s = 0.f, s0 = 0.f, s1 = 0.f, sd = 0.f;
+    float sa0 = 0.f, sa1 = 0.f;   // e * anchor
+    for (int pb = g; pb < cells; pb += kBatch * G) {
+      float vc[kBatch], vd[kBatch];
+      float2 vr[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int p = pb + u * G;
+        const long q = (long)(p < cells ? p : g) * AJ + c;   // (clamped: the tail batch's extra cells are not used)
+        vc[u] = clsk[q];
+        vr[u] = *reinterpret_cast<const float2*>(regk + q * 2);
+        vd[u] = depk[q];
+      }
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int p = pb + u * G;
+        if (p < cells) {
+          const int hh = p / fw, ww = p - hh * fw;
+          const float e = expf(vc[u] - mj);
+          const float a0 = (float)(hh * stride) + p0, a1 = (float)(ww * stride) + p1;
+          s += e;
+          s0 += e * (a0 + vr[u].x);
+          s1 += e * (a1 + vr[u].y);
+          sd += e * vd[u];
+          sa0 += e * a0;
+          sa1 += e * a1;
+        }
+      }
+    }
+    float* o = lds + (long)g * NQ * AW;
+    o[cl] = s;
+    o[AW + cl] = s0;
+    o[2 * AW + cl] = s1;
+    o[3 * AW + cl] = sd;
+    o[4 * AW + cl] = sa0;
+    o[5 * AW + cl] = sa1;
+  }
+  __syncthreads();
+  for (int s4 = threadIdx.x; s4 < NQ * AW; s4 += blockDim.x) {
+    float acc = lds[s4];
+    for (int gg = 1; gg < G; ++gg) acc += lds[(long)gg * NQ * AW + s4];
+    lds[s4] = acc;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < jn) {
+    const int jj = threadIdx.x;
+    float t = 0.f, t0 = 0.f, t1 = 0.f, td = 0.f;
+    float ta0 = 0.f, ta1 = 0.f;
+    for (int aa = 0; aa < kAnchorsPerCell; ++aa) {
+      t += lds[aa * Jw + jj];
+      t0 += lds[AW + aa * Jw + jj];
+      t1 += lds[2 * AW + aa * Jw + jj];
+      td += lds[3 * AW + aa * Jw + jj];
+      ta0 += lds[4 * AW + aa * Jw + jj];
+      ta1 += lds[5 * AW + aa * Jw + jj];
+    }
+    const long joint_row = (long)k * J + j0 + jj;
+    const float ku = t0 / t, kv = t1 / t, kd = td / t;
+    const float e0 = ta0 / t, e1 = ta1 / t;
+    if (gs.uvd) {
+      float* o = gs.uvd + joint_row * 3;
+      o[0] = ku;
+      o[1] = kv;
+      o[2] = kd;
+    }
+    if (gs.terms) loss_terms_one(LossSpec{gs.gt, gs.terms}, joint_row, e0, e1, ku, kv, kd);
+    {
+#pragma clang fp contract(off)
+      int rows = (int)gridDim.x;
+      if (valid) {
+        rows = 0;
+        for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) rows += wave_rows[wv];
+      }
+      const float wa = gs.upstream ? gs.upstream[0] : 1.f, wr = gs.upstream ? gs.upstream[1] : 1.f;
+      const float n = (float)rows, wrr = wr * gs.reg_loss_factor;
+      const float ca = wa / n / (float)(2 * J);
+      const float cr = wrr * gs.spatial_factor / n / (float)(2 * J);
+      const float cd = wrr / n / (float)J;
+      const float* gj = gs.gt + joint_row * 3;
+      const float g0 = gj[0], g1 = gj[1], g2 = gj[2];
+      jv[1 * Jw + jj] = t;
+      jv[2 * Jw + jj] = e0;
+      jv[3 * Jw + jj] = e1;
+      jv[4 * Jw + jj] = ku;
+      jv[5 * Jw + jj] = kv;
+      jv[6 * Jw + jj] = kd;
+      jv[7 * Jw + jj] = ca * clip1(e0 - g0);
+      jv[8 * Jw + jj] = ca * clip1(e1 - g1);
+      jv[9 * Jw + jj] = cr * clip1(ku - g0);
+      jv[10 * Jw + jj] = cr * clip1(kv - g1);
+      jv[11 * Jw + jj] = cd * sign1(kd - g2);
+    }
+  }
+  __syncthreads();
+  if (active) {
+#pragma clang fp contract(off)
+    const float p0 = 2.f + 4.f * (float)(a >> 2), p1 = 2.f + 4.f * (float)(a & 3);
+    const float mjj = jv[0 * Jw + jl], t = jv[1 * Jw + jl];
+    const float ea0 = jv[2 * Jw + jl], ea1 = jv[3 * Jw + jl], er0 = jv[4 * Jw + jl], er1 = jv[5 * Jw + jl], ed = jv[6 * Jw + jl];
+    const float ga0 = jv[7 * Jw + jl], ga1 = jv[8 * Jw + jl], gr0 = jv[9 * Jw + jl], gr1 = jv[10 * Jw + jl], gd = jv[11 * Jw + jl];
+    // (offsets inside the crop's slice in 32 bits -- the entry refuses a slice of 2^31 elements --: the batch's addresses
+    // would not fit the registers beside its operands otherwise)
+    float* dck = gs.d_cls + (long)k * cells * AJ;
+    float* ddk = gs.d_dep + (long)k * cells * AJ;
+    float* drk = gs.d_reg + (long)k * cells * AJ * 2;
+    for (int pb = g; pb < cells; pb += kBatch * G) {
+      float vc[kBatch], vd[kBatch];
+      float2 vr[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int p = pb + u * G;
+        const int q = (p < cells ? p : g) * AJ + c;   // (clamped, as above)
+        vc[u] = clsk[q];
+        vr[u] = *reinterpret_cast<const float2*>(regk + q * 2);
+        vd[u] = depk[q];
+      }
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int p = pb + u * G;
+        if (p < cells) {
+          const int hh = p / fw, ww = p - hh * fw;
+          const float e = expf(vc[u] - mjj);
+          const float w = e / t;
+          const float a0 = (float)(hh * stride) + p0, a1 = (float)(ww * stride) + p1;
+          float b = ga0 * (a0 - ea0);
+          b += ga1 * (a1 - ea1);
+          b += gr0 * ((a0 + vr[u].x) - er0);
+          b += gr1 * ((a1 + vr[u].y) - er1);
+          b += gd * (vd[u] - ed);
+          const int q = p * AJ + c;
+          dck[q] = w * b;
+          *reinterpret_cast<float2*>(drk + q * 2) = make_float2(w * gr0, w * gr1);
+          ddk[q] = w * gd;
+        }
+      }
+    }
+  }
+}
+
 // The criterion's reductions (a2j/anchor.py:130,140,150,153; a2j/a2j.py:233-238,318) in ONE workgroup and a fixed order, no
 // atomics: thread i of a round of 256 samples adds its own sample's joints in joint order (a sample row depends on its own
 // crop only), then thread 0 adds the round's samples in sample order.  valid == 0 rows are left out of the batch values
@@ -297,19 +535,28 @@ extern "C" int hn_pack_depth_nhwc(const float* src, float* dst, int n, int hw, i
   return HN_OK;
 }
 
+// the launch geometry of the three aggregation kernels, from the joint count alone (tests/agg_ref.py geometry())
+struct AggGeometry {
+  int split, jw, aw, groups, threads;
+  explicit AggGeometry(int joints) {
+    // the cell-group count depends on the joint count only (it fixes the summation order): min(9, 1024 / (16 * joints per workgroup))
+    split = joints >= 2 * kJointSplit ? kJointSplit : 1;
+    jw = (joints + split - 1) / split;
+    aw = kAnchorsPerCell * jw;
+    groups = 1024 / aw;            // cell groups of a workgroup (16 * jw thread slots each)
+    groups = groups > kMaxGroups ? kMaxGroups : groups;
+    groups = groups < 1 ? 1 : groups;
+    threads = ((groups * aw + 63) / 64) * 64;
+  }
+};
+
 template <class... Loss>
 static int launch_aggregate(const float* cls, const float* reg, const float* dep, const int32_t* valid, int k, int fh, int fw,
                             int joints, int stride, float* out, const ConvertSpec& cs, void* stream, const Loss... loss) {
   constexpr bool kLoss = sizeof...(Loss) != 0;
   constexpr int nq = kLoss ? 6 : 4;
-  // the cell-group count depends on the joint count only (it fixes the summation order): min(9, 1024 / (16 * joints per workgroup))
-  const int split = joints >= 2 * kJointSplit ? kJointSplit : 1;
-  const int jw = (joints + split - 1) / split;
-  const int aw = kAnchorsPerCell * jw;
-  int groups = 1024 / aw;            // cell groups of a workgroup (16 * jw thread slots each)
-  groups = groups > kMaxGroups ? kMaxGroups : groups;
-  groups = groups < 1 ? 1 : groups;
-  const int threads = ((groups * aw + 63) / 64) * 64;
+  const AggGeometry geo(joints);
+  const int split = geo.split, jw = geo.jw, aw = geo.aw, groups = geo.groups, threads = geo.threads;
   if constexpr (kLoss) {
     hipLaunchKernelGGL(a2j_loss_aggregate_kernel, dim3(k, split), dim3(threads), groups * nq * aw * sizeof(float),
                        (hipStream_t)stream, cls, reg, dep, valid, fh, fw, joints, jw, stride, groups, out, cs, loss...);
@@ -407,6 +654,28 @@ extern "C" int hn_a2j_aggregate_loss_f32(const float* cls, const float* reg, con
   hipLaunchKernelGGL(a2j_loss_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)out_terms, valid, k, joints,
                      spatial_factor, reg_loss_factor, out_sample, out_batch);
   HN_CHECK_LAUNCH("a2j_loss_reduce_kernel");
+  return HN_OK;
+}
+
+extern "C" int hn_a2j_loss_grad_f32(const float* cls, const float* reg, const float* dep, const int32_t* valid, const float* gt,
+                                    int k, int fh, int fw, int joints, int stride, float spatial_factor, float reg_loss_factor,
+                                    const float* upstream, float* d_cls, float* d_reg, float* d_dep, float* out_uvd,
+                                    float* out_terms, void* stream) {
+  HN_CHECK_ARG(cls && reg && dep && gt && d_cls && d_reg && d_dep, "hn_a2j_loss_grad_f32: null pointer");
+  HN_CHECK_ARG(joints > 0 && joints * kAnchorsPerCell <= 1024, "hn_a2j_loss_grad_f32: joints must be in [1, 64]");
+  HN_CHECK_ARG(fh > 0 && fw > 0, "hn_a2j_loss_grad_f32: fh * fw must not be 0");
+  HN_CHECK_ARG(k >= 0 && stride > 0, "hn_a2j_loss_grad_f32: bad dims");
+  HN_CHECK_ARG((long)fh * fw * kAnchorsPerCell * joints * 2 < (1L << 31),
+               "hn_a2j_loss_grad_f32: one crop's reg slice (fh * fw * 32 * joints) must be below 2^31 elements");
+  HN_CHECK_ARG((uintptr_t)reg % 8 == 0 && (uintptr_t)d_reg % 8 == 0, "hn_a2j_loss_grad_f32: reg and d_reg must be 8-byte aligned");
+  HN_CHECK_ARG((uintptr_t)out_terms % 16 == 0, "hn_a2j_loss_grad_f32: out_terms must be 16-byte aligned");
+  if (k == 0) return HN_OK;
+  const AggGeometry geo(joints);
+  const GradSpec gs{gt, upstream, spatial_factor, reg_loss_factor, d_cls, d_reg, d_dep, out_uvd, out_terms};
+  hipLaunchKernelGGL(a2j_loss_grad_kernel, dim3(k, geo.split), dim3(geo.threads),
+                     (geo.groups * 6 * geo.aw + kGradJoint * geo.jw) * sizeof(float), (hipStream_t)stream, cls, reg, dep, valid, fh,
+                     fw, joints, geo.jw, stride, geo.groups, gs);
+  HN_CHECK_LAUNCH("a2j_loss_grad_kernel");
   return HN_OK;
 }
 

@@ -222,6 +222,8 @@ SIGNATURES = {
     # the aggregation with the A2J criterion in its sweep (a new function under ABI 36)
     "hn_a2j_aggregate_loss_f32": (C.c_int, [VP] * 5 + [C.c_int] * 5 + [C.c_float, C.c_float, VP, C.c_float, C.c_float, c_f32p,
                                             C.POINTER(ConvertOpts)] + [VP] * 7),
+    # the A2J criterion's backward at the heads (a new function under ABI 36)
+    "hn_a2j_loss_grad_f32": (C.c_int, [VP] * 5 + [C.c_int] * 5 + [C.c_float, C.c_float] + [VP] * 7),
     "hn_joints2d_standardize_f32": (C.c_int, [VP, VP, C.c_int, C.c_int, VP, VP]),
     "hn_lifter_input_gated_f32": (C.c_int, [VP, VP, C.c_int, C.c_int, VP, VP, VP]),
     "hn_handnet_forward_xyz": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_int, c_f32p, C.POINTER(ConvertOpts),

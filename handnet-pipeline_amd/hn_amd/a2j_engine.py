@@ -231,18 +231,23 @@ class A2JEngine:
         return cls, reg, dep
 
     @ops.device_guarded
-    def forward_nhwc(self, x, valid=None, return_heads=False, convert=None, gt=None, spatial_factor=0.5):
+    def forward_nhwc(self, x, valid=None, return_heads=False, convert=None, gt=None, spatial_factor=0.5, head_grads=False):
         """convert (ops.a2j_aggregate's dict: crop_box, paras, clamps): the aggregation's epilogue also writes image (u,v,d)
         and camera xyz in mm -> returns (crop_uvd, image_uvd, xyz_mm or None) instead of crop_uvd alone.
         gt [K,J,3] fp32 on the device (crop uvd): the aggregation also evaluates the A2J criterion in its sweep (ops.a2j_loss,
         a2j/anchor.py:99-153; reg_loss_factor = 3, a2j/a2j.py:224) -> returns (that result, terms, sample, batch) in its place;
-        the keypoints are the same bytes either way."""
+        the keypoints are the same bytes either way.
+        head_grads (with gt): one more launch (ops.a2j_loss_grad) -> returns (that tuple, (d_cls, d_reg,
+        d_dep)): the gradient of total_loss at this engine's own heads, on the device."""
         with ops.f16_terms(self.terms):
             x3, x4 = self.trunk(x, valid)
             cls, reg, dep = self.heads(x3, x4)
         if gt is not None:
             out = ops.a2j_loss(cls, reg, dep, gt, joints=self.joints, stride=16, spatial_factor=spatial_factor,
                                reg_loss_factor=self.REG_LOSS_FACTOR, valid=valid, convert=convert)
+            if head_grads:
+                out = out, ops.a2j_loss_grad(cls, reg, dep, gt, joints=self.joints, stride=16, spatial_factor=spatial_factor,
+                                             reg_loss_factor=self.REG_LOSS_FACTOR, valid=valid)
         else:
             out = ops.a2j_aggregate(cls, reg, dep, joints=self.joints, stride=16, valid=valid, convert=convert)
         if return_heads:
@@ -254,23 +259,24 @@ class A2JEngine:
     REG_LOSS_FACTOR = 3.0   # a2j/a2j.py:224
 
     @ops.device_guarded
-    def forward_flags(self, depth, convert=None, gt=None, spatial_factor=0.5):
+    def forward_flags(self, depth, convert=None, gt=None, spatial_factor=0.5, head_grads=False):
         """The A2J-only entry with the f16x3 range contract: -> (keypoints [K,J,3] on the GPU, flag words [4] int32 on the GPU
         or None in the f32 mode / with HN_CHECK_RANGE=0).  No sync; the drop-in reads the words with the keypoints.
-        convert, gt: as forward()."""
+        convert, gt, head_grads: as forward()."""
         if self.precision != "f16x3" or not self.note_range:
-            return self.forward(depth, convert=convert, gt=gt, spatial_factor=spatial_factor), None
+            return self.forward(depth, convert=convert, gt=gt, spatial_factor=spatial_factor, head_grads=head_grads), None
         if getattr(self, "_range_block", None) is None:
             self._range_block = torch.zeros((4,), device=self.device, dtype=torch.int32)
         with ops.range_scope(self._range_block):
-            kp = self.forward(depth, convert=convert, gt=gt, spatial_factor=spatial_factor)
+            kp = self.forward(depth, convert=convert, gt=gt, spatial_factor=spatial_factor, head_grads=head_grads)
             flags = ops.range_check_collect(self._range_block)
         return kp, flags
 
     @ops.device_guarded
-    def forward(self, depth, valid=None, convert=None, gt=None, spatial_factor=0.5):
+    def forward(self, depth, valid=None, convert=None, gt=None, spatial_factor=0.5, head_grads=False):
         """depth [K,1,H,W] (or [K,4,H,W] for RGBD) fp32 on the GPU -> [K,J,3] on the GPU; with convert (forward_nhwc) the
-        triple (crop uvd, image uvd, camera xyz in mm or None); with gt (forward_nhwc) that result, terms, sample and batch."""
+        triple (crop uvd, image uvd, camera xyz in mm or None); with gt (forward_nhwc) that result, terms, sample and batch;
+        with head_grads too (forward_nhwc) that tuple and the gradients at the heads."""
         if depth.dim() != 4:
             raise ValueError("expected [K,C,H,W]")
         if not depth.is_cuda:
@@ -284,7 +290,16 @@ class A2JEngine:
             # (the A2J-only entry: flags of its own, so that a crop with NaN / inf pixels gives NaN keypoints like
             # a2j/a2j.py:243-250 does)
             valid = torch.ones((depth.shape[0],), device=depth.device, dtype=torch.int32)
-        return self.forward_nhwc(x, valid, convert=convert, gt=gt, spatial_factor=spatial_factor)
+        return self.forward_nhwc(x, valid, convert=convert, gt=gt, spatial_factor=spatial_factor, head_grads=head_grads)
+
+    def head_grads(self, depth, gt, valid=None, spatial_factor=0.5):
+        """forward(depth, gt=gt) and the criterion's backward at this engine's own heads
+        -> (losses, crop uvd [K,J,3], (d_cls, d_reg, d_dep)), all on the device: losses = {"classification", "regression"
+        (times reg_loss_factor), "total_loss"} are the bytes forward(depth, gt=gt) gives, the gradients are total_loss's in the
+        heads' layouts [K,11,11,16 J] / [K,11,11,32 J].  This is where a backward pass through the convolutions would start;
+        there is none here."""
+        (uvd, _terms, _sample, batch), grads = self.forward(depth, valid, gt=gt, spatial_factor=spatial_factor, head_grads=True)
+        return {"classification": batch[0:1], "regression": batch[2:3], "total_loss": batch[3:4]}, uvd, grads
 
     # -----------------------------------------------------------------------------------
     def macs_per_crop(self, h=176, w=176) -> int:

@@ -58,6 +58,9 @@ EXTRA_FLAGS = {"fcos_post.hip": ["-ffp-contract=off", "-fno-slp-vectorize"], "gr
 # (plain, deep-k, multi, mixed -- the deep-k kernel's name once slipped through per-kernel entries), the others are the
 # remaining files with LDS-DMA / counted waits (tests/test_build_cpu.py keeps this list in step with the sources).
 NO_SPILL_KERNELS = ("conv_igemm_f16x3_", "conv3x3_halo_kernel", "conv_stem_pool_direct_kernel", "conv3x3_thin", "conv1x1_stream_kernel")
+# Plain compiler-scheduled loads, but batches of 14 cells' operands under 1024 threads' 128 registers: a VGPR spill or scratch
+# would put memory traffic where the batching removed it, so the build refuses either (SGPR spills go to VGPR lanes: allowed).
+NO_SCRATCH_KERNELS = ("a2j_loss_grad_kernel",)
 
 
 def _check_resources(src: Path, remarks: str, objdir: Path) -> None:
@@ -90,6 +93,10 @@ def _check_resources(src: Path, remarks: str, objdir: Path) -> None:
         if any(k in name for k in NO_SPILL_KERNELS) and res.get("ScratchSize [bytes/lane]", "0") != "0":
             raise RuntimeError(f"{src.name}: {name} uses {res.get('ScratchSize [bytes/lane]')} bytes of scratch per lane "
                                "(a kernel argument copied to private memory?): these kernels are written to run from registers")
+        if any(k in name for k in NO_SCRATCH_KERNELS) and (res.get("VGPRs Spill", "0") != "0"
+                                                            or res.get("ScratchSize [bytes/lane]", "0") != "0"):
+            raise RuntimeError(f"{src.name}: {name} spills {res.get('VGPRs Spill')} VGPRs / uses "
+                               f"{res.get('ScratchSize [bytes/lane]')} bytes of scratch per lane: it is written to run from registers")
     (objdir / (src.stem + ".resources.txt")).write_text("\n".join(out) + "\n")
 
 

@@ -1713,6 +1713,39 @@ def a2j_loss(cls, reg, dep, gt, joints=21, stride=16, spatial_factor=0.5, reg_lo
     return res, terms, sample, batch
 
 
+def a2j_loss_grad(cls, reg, dep, gt, joints=21, stride=16, spatial_factor=0.5, reg_loss_factor=3.0, valid=None, upstream=None,
+                  want_forward=False):
+    """The A2J criterion's backward at the three heads in one launch (hn_a2j_loss_grad_f32): heads, gt
+    and valid as a2j_loss takes them -> (d_cls, d_reg, d_dep), the gradients of
+    wa * classification + wr * regression (a2j_loss's batch [0] and [2]) in the layouts of the heads, on the device.
+    upstream: fp32 [2] on the device = (wa, wr), or None for (1, 1), the gradient of total_loss; it is read by the kernel, so
+    nothing here synchronises.  Rows with valid == 0 get zero gradients and are not counted in the batch mean, rows with
+    valid == 2 get NaN.  want_forward: also return a2j_loss's uvd [K,J,3] and terms [K,J,8] of the same heads, bit for bit."""
+    lib = _lib.load()
+    _req(cls, name="cls"); _req(reg, name="reg"); _req(dep, name="dep"); _req(gt, name="gt")
+    if cls.dim() != 4 or reg.dim() != 4:
+        raise ValueError("bad head shapes")
+    k, fh, fw, aj = cls.shape
+    if joints < 1 or aj != 16 * joints or reg.shape[3] != 2 * aj or dep.shape != cls.shape or reg.shape[:3] != cls.shape[:3]:
+        raise ValueError("bad head shapes")
+    if tuple(gt.shape) != (k, joints, 3):
+        raise ValueError("gt must be [K,J,3]")
+    if valid is not None and _req(valid, torch.int32, "valid").numel() != k:
+        raise ValueError("valid must hold one flag per crop")
+    if upstream is not None and _req(upstream, name="upstream").numel() != 2:
+        raise ValueError("upstream must hold (wa, wr)")
+    d_cls, d_reg, d_dep = torch.empty_like(cls), torch.empty_like(reg), torch.empty_like(dep)
+    uvd = terms = None
+    if want_forward:
+        uvd = torch.empty((k, joints, 3), device=cls.device, dtype=torch.float32)
+        terms = torch.empty((k, joints, 8), device=cls.device, dtype=torch.float32)
+    if k:
+        check(lib.hn_a2j_loss_grad_f32(ptr(cls), ptr(reg), ptr(dep), ptr(valid), ptr(gt), k, fh, fw, joints, stride,
+                                       float(spatial_factor), float(reg_loss_factor), ptr(upstream), ptr(d_cls), ptr(d_reg),
+                                       ptr(d_dep), ptr(uvd), ptr(terms), _stream()), "hn_a2j_loss_grad_f32")
+    return (d_cls, d_reg, d_dep, uvd, terms) if want_forward else (d_cls, d_reg, d_dep)
+
+
 def joints2d_standardize(image_uvd, valid=None, out=None):
     """image (u,v,d) joints [N,J,3] -> the lifter's input [N,J,2]: per frame and axis (x - mean) / std over the joints
     (hn_joints2d_standardize_f32 = the live caller's bbox / affine / normalisation chain, ros_demo.py:148-157, which reduces

@@ -43,7 +43,7 @@ extern "C" {
  * hn_conv2d_nhwc_f16x3_grouped_carry, hn_conv2d_f16x3_grouped_carry_applies and hn_affine_split_f32_levels_streams, the evaluator's hn_hpe_accumulate_f32, the
  * detector evaluation's hn_det_ap_accumulate_f32, the A2J criterion's hn_a2j_aggregate_loss_f32, and the FCOS criterion's
  * hn_fcos_loss_f32 and hn_fcos_loss_ws_bytes, and the held objects' hn_hand_objects_f32, hn_hand_objects_scratch_bytes and
- * hn_draw_object_labels_u8). */
+ * hn_draw_object_labels_u8, and the A2J criterion's backward hn_a2j_loss_grad_f32). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -713,6 +713,24 @@ int hn_a2j_aggregate_loss_f32(const float* cls, const float* reg, const float* d
                               const float* paras /* host, 4 floats, or NULL */, const hn_convert_opts* opts /* host or NULL */,
                               float* out_uvd, float* out_image_uvd /* or NULL */, float* out_xyz_mm /* or NULL */,
                               float* out_terms, float* out_sample, float* out_batch, void* stream);
+
+/* The A2J criterion's backward at the three heads, in ONE launch with the aggregation's grid and summation order (DESIGN.md
+ * section 9r): the gradient of  wa * classification + wr * (reg_loss_factor * the criterion's regression mean)  -- out_batch [0]
+ * and [2] of hn_a2j_aggregate_loss_f32 -- with respect to cls, reg and dep, written to d_cls, d_dep [k][fh][fw][16 J] and
+ * d_reg [k][fh][fw][16 J][2] (8-byte aligned), the layouts of the heads.  upstream: DEVICE (wa, wr), or NULL for (1, 1), the
+ * gradient of out_batch [3].  Per joint, with w the softmax weights, Ea = sum w anchor, Er = sum w (anchor + reg), Ed = sum w dep,
+ * g = gt and n = the number of rows with valid != 0 (counted on the device):
+ *   ga_c = wa / n / (2J) clip(Ea_c - g_c, -1, 1), gr_c = wr reg_loss_factor spatial_factor / n / (2J) clip(Er_c - g_c, -1, 1),
+ *   gd = wr reg_loss_factor / n / J sign(Ed - g_d);
+ *   d_reg = w gr_c, d_dep = w gd, d_cls = w (sum_c ga_c (anchor_c - Ea_c) + sum_c gr_c (anchor_c + reg_c - Er_c) + gd (dep - Ed)).
+ * Every element is written once, in a fixed order (bitwise reproducible); rows with valid == 0 get zeros, rows with valid == 2
+ * NaN; a NaN coordinate of gt makes that joint's d_cls and that coordinate's d_reg NaN, as the reference's autograd does.
+ * out_uvd [k][J][3] and out_terms [k][J][8] (16-byte aligned), each or NULL: hn_a2j_aggregate_loss_f32's outputs of those names,
+ * bit for bit.  k == 0 launches nothing.  Added under ABI 36: a new function only. */
+int hn_a2j_loss_grad_f32(const float* cls, const float* reg, const float* dep, const int32_t* valid /* or NULL */,
+                         const float* gt, int k, int fh, int fw, int joints, int stride, float spatial_factor,
+                         float reg_loss_factor, const float* upstream /* device, 2 floats, or NULL */, float* d_cls, float* d_reg,
+                         float* d_dep, float* out_uvd /* or NULL */, float* out_terms /* or NULL */, void* stream);
 
 /* The lifter's input from a step's image-(u,v) joints (the live caller's glue between the path and Pose2Mesh,
  * ros_demo.py:148-157: get_bbox -> process_bbox -> j2d_processing (rot 0, no flip) -> / input_shape -> (x - mean) / std):
