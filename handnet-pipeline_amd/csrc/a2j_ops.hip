@@ -1,5 +1,7 @@
-// HBM-bound helpers of the A2J / ResNet path: 3x3/2 max pooling, depth -> NHWC packing
-// and the softmax-weighted anchor aggregation (a2j/anchor.py:57-82).
+// HBM-bound helpers of the A2J / ResNet path: 3x3/2 max pooling, depth -> NHWC packing, the softmax-weighted anchor
+// aggregation (a2j/anchor.py:57-82) with its criterion (anchor.py:99-153) and the criterion's backward -- three kernels over
+// ONE head sweep (AggMap, joint_max, sums<NQ>, joint_totals<NQ> below) --, the joint conversion, the lifter's input, the
+// all-gather records and the stem image.
 #include "hn_common.h"
 
 #include <float.h>
@@ -49,13 +51,6 @@ __global__ __launch_bounds__(256) void pack_depth_kernel(const float* __restrict
   }
 }
 
-// kJointSplit workgroups per crop, each owning a contiguous range of joints (the joints are independent; one workgroup
-// per crop was 28 us of the batch-1 frame on one CU).  Thread (g, a, jl): anchor-in-cell a, joint j = j0 + jl; the G
-// thread groups take the cells p = g, g+G, ... (a single group walked all fh*fw cells with two dependent loads each: 60 us
-// of pure latency per launch).
-// Pass 1: per-joint max of the logits (exact, order independent).
-// Pass 2: e = exp(x - max); partial sums of e, e*(anchor+offset), e*depth per (group, anchor, joint), then
-// combined through LDS in a fixed order (group-major, then anchor): bitwise reproducible, and independent of the joint split.
 // crop-(u,v,d) of one joint -> image (u,v,d) and / or camera xyz in millimetres (a2j/a2j.py:17-34 convert_joints +
 // datasets3d/a2jdataset.py:31-38 uvd2xyz).  ONE function for the stand-alone kernel and the aggregation's epilogue: the two are
 // bit-identical by construction.  (Every operation is a single rounding in the reference's order; nothing here can contract
@@ -144,11 +139,226 @@ __device__ __forceinline__ void loss_terms_one(const LossSpec& ls, long joint_ro
   o[1] = hi;
 }
 
-// a2j_aggregate_kernel and a2j_loss_aggregate_kernel: ONE body (a2j_aggregate_body.h) with a compile-time switch, the same flags
-#define A2J_AGG_LOSS 0
-#include "a2j_aggregate_body.h"
-#define A2J_AGG_LOSS 1
-#include "a2j_aggregate_body.h"
+// ---------------------------------------------------------------------------------------
+// The head sweep of a2j_aggregate_kernel, a2j_loss_aggregate_kernel and a2j_loss_grad_kernel, written once.
+// kJointSplit workgroups per crop, each owning a contiguous range of joints (the joints are independent; one workgroup
+// per crop was 28 us of the batch-1 frame on one CU).  Thread (g, a, jl): anchor-in-cell a, joint j = j0 + jl; the G
+// thread groups take the cells p = g, g+G, ... (a single group walked all fh*fw cells with two dependent loads each: 60 us
+// of pure latency per launch).
+// joint_max: per-joint max of the logits (exact, order independent).
+// sums<NQ>: e = exp(x - max); partial sums of e, e*(anchor+offset), e*depth (and, NQ == 6, e*anchor) per (group, anchor, joint),
+// then combined through LDS in a fixed order (group-major here, anchor order in joint_totals<NQ>): bitwise reproducible,
+// independent of the joint split, and the same bytes in all three kernels.
+// Both cell loops fetch kBatch (14: three rounds for the 41 cells a thread owns on an 11 x 11 map) cells' operands before they use
+// any (same operations in the same order): written as load -> use per cell, each of the 2 x 41 iterations waited for its own L2
+// round trip -- 27 us per launch.
+// ---------------------------------------------------------------------------------------
+constexpr int kBatch = 14;
+
+struct AggMap {
+  int k, j0, jn;      // crop; first joint and joints of this workgroup (the last one may have fewer, or none)
+  int AJ, AW;         // channels per cell in memory; thread slots per cell group
+  int g, cl, a, jl;   // cell group, slot in it = (anchor, joint of the workgroup)
+  int c;              // channel in memory
+  int cells;
+  bool active;
+  const float *cls, *reg, *dep;   // the crop's slices of the heads
+  __device__ __forceinline__ AggMap(const float* cls_, const float* reg_, const float* dep_, int fh, int fw, int J, int Jw, int G) {
+    k = blockIdx.x;
+    j0 = blockIdx.y * Jw;
+    jn = min(Jw, J - j0);
+    AJ = kAnchorsPerCell * J;
+    AW = kAnchorsPerCell * Jw;
+    g = threadIdx.x / AW, cl = threadIdx.x - g * AW;
+    a = cl / Jw, jl = cl - a * Jw;
+    c = a * J + j0 + jl;
+    cells = fh * fw;
+    active = g < G && jl < jn;
+    cls = cls_ + (long)k * cells * AJ;
+    dep = dep_ + (long)k * cells * AJ;
+    reg = reg_ + (long)k * cells * AJ * 2;
+  }
+  // this thread's element of cell p in the crop's slice of cls / dep.  (p >= 0 and AJ > 0, said with unsigned operands: ONE
+  // 32 x 32 -> 64 bit multiply.  The signed 64-bit product is two, and the second one's addend pair has a don't-care half that
+  // the register allocator once put on the destination of a load in flight: the first sweep then waited out a third of its
+  // loads one by one)
+  __device__ __forceinline__ long at(int p) const { return (long)((unsigned long)(unsigned)p * (unsigned)AJ) + c; }
+};
+
+// A row with valid != 1 (uniform per workgroup): 0 = no crop (zeros; the loss's reduction leaves the row out), 2 = non-finite
+// crop (NaN, as the reference's network returns for it: every cell of the 11 x 11 maps sees every pixel of the crop).  The
+// workgroup's joints of every [n,J,3] output given and of the [n,J,8] terms; nullptr: not an output of the caller.
+__device__ __forceinline__ float row_fill(int valid_k) { return valid_k == 0 ? 0.f : __builtin_nanf(""); }
+__device__ __forceinline__ void fill_row(const AggMap& m, int J, float fill, float* uvd, float* image_uvd, float* xyz_mm, float* terms) {
+  const long row = (long)m.k * J + m.j0;
+  if ((int)threadIdx.x < m.jn * 3) {
+    if (uvd) uvd[row * 3 + threadIdx.x] = fill;
+    if (image_uvd) image_uvd[row * 3 + threadIdx.x] = fill;
+    if (xyz_mm) xyz_mm[row * 3 + threadIdx.x] = fill;
+  }
+  if (terms && (int)threadIdx.x < m.jn * kLossTerms) terms[row * kLossTerms + threadIdx.x] = fill;
+}
+
+// the maximum of this thread's joint over all cells and anchors; lds: AW * G floats, free again on return
+__device__ __forceinline__ float joint_max(const AggMap& m, int Jw, int G, float* lds) {
+  float mx = -FLT_MAX;
+  if (m.active)
+    for (int pb = m.g; pb < m.cells; pb += kBatch * G) {
+      float v[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int p = pb + u * G;
+        v[u] = p < m.cells ? m.cls[m.at(p)] : -FLT_MAX;
+      }
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) mx = fmaxf(mx, v[u]);
+    }
+  if (m.g < G) lds[m.g * m.AW + m.cl] = mx;
+  __syncthreads();
+  if ((int)threadIdx.x < m.AW) {   // (group 0's threads: slot cl = threadIdx.x) maximum over the groups, then over the anchors below
+    float mm = lds[threadIdx.x];
+    for (int gg = 1; gg < G; ++gg) mm = fmaxf(mm, lds[gg * m.AW + threadIdx.x]);
+    lds[threadIdx.x] = mm;
+  }
+  __syncthreads();
+  float mj = -FLT_MAX;
+  if (m.active)
+    for (int aa = 0; aa < kAnchorsPerCell; ++aa) mj = fmaxf(mj, lds[aa * Jw + m.jl]);
+  __syncthreads();
+  return mj;
+}
+
+// the NQ sums of every (anchor, joint) slot over all cells: on return plane q of lds ([NQ][AW], group 0's) holds them, summed
+// over the groups 0 .. G-1 in that order; lds: [G][NQ][AW] floats
+template <int NQ>
+__device__ __forceinline__ void sums(const AggMap& m, float mj, int fw, int stride, int G, float* lds) {
+  static_assert(NQ == 4 || NQ == 6, "s, s0, s1, sd and, for the criterion, sa0, sa1");
+  const int AW = m.AW, cl = m.cl;
+  if (m.active) {
+    float s = 0.f, s0 = 0.f, s1 = 0.f, sd = 0.f;
+    [[maybe_unused]] float sa0 = 0.f, sa1 = 0.f;   // e * anchor
+    const float p0 = 2.f + 4.f * (float)(m.a >> 2), p1 = 2.f + 4.f * (float)(m.a & 3);
+    for (int pb = m.g; pb < m.cells; pb += kBatch * G) {
+      float vc[kBatch], vd[kBatch];
+      float2 vr[kBatch];
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int p = pb + u * G;
+        const long q = m.at(p < m.cells ? p : m.g);   // (clamped: the tail batch's extra cells are not used)
+        vc[u] = m.cls[q];
+        vr[u] = *reinterpret_cast<const float2*>(m.reg + q * 2);
+        vd[u] = m.dep[q];
+      }
+#pragma unroll
+      for (int u = 0; u < kBatch; ++u) {
+        const int p = pb + u * G;
+        if (p < m.cells) {
+          const int hh = p / fw, ww = p - hh * fw;
+          const float e = expf(vc[u] - mj);
+          const float a0 = (float)(hh * stride) + p0, a1 = (float)(ww * stride) + p1;
+          s += e;
+          s0 += e * (a0 + vr[u].x);
+          s1 += e * (a1 + vr[u].y);
+          sd += e * vd[u];
+          if constexpr (NQ == 6) {
+            sa0 += e * a0;
+            sa1 += e * a1;
+          }
+        }
+      }
+    }
+    float* o = lds + (long)m.g * NQ * AW;
+    o[cl] = s;
+    o[AW + cl] = s0;
+    o[2 * AW + cl] = s1;
+    o[3 * AW + cl] = sd;
+    if constexpr (NQ == 6) {
+      o[4 * AW + cl] = sa0;
+      o[5 * AW + cl] = sa1;
+    }
+  }
+  __syncthreads();
+  // fixed-order combination in two steps: thread (quantity q, anchor a, joint jl) of the first NQ * AW sums its slot over the
+  // groups 0 .. G-1, then joint_totals sums the 16 anchors of a joint (G + 16 dependent additions instead of 16 G)
+  for (int s4 = threadIdx.x; s4 < NQ * AW; s4 += blockDim.x) {
+    float acc = lds[s4];
+    for (int gg = 1; gg < G; ++gg) acc += lds[(long)gg * NQ * AW + s4];
+    lds[s4] = acc;   // (group 0's slot: only this thread reads or writes it here)
+  }
+  __syncthreads();
+}
+
+// joint jj's totals over its 16 anchors, in anchor order: t[q] of plane q
+template <int NQ>
+struct JointTotals {
+  float t[NQ];
+};
+template <int NQ>
+__device__ __forceinline__ JointTotals<NQ> joint_totals(const float* lds, int AW, int Jw, int jj) {
+  JointTotals<NQ> r;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) r.t[q] = 0.f;
+  for (int aa = 0; aa < kAnchorsPerCell; ++aa) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) r.t[q] += lds[q * AW + aa * Jw + jj];
+  }
+  return r;
+}
+
+// The aggregation (NQ == 4) and, with the criterion's terms behind the same sweep (NQ == 6; hn_a2j_aggregate_loss_f32, DESIGN.md
+// section 9o), the loss form: two more running sums (e * anchor) and six LDS planes per group instead of four.
+template <int NQ>
+__device__ __forceinline__ void aggregate_row(const float* __restrict__ cls, const float* __restrict__ reg,
+                                              const float* __restrict__ dep, const int* __restrict__ valid, int fh, int fw, int J,
+                                              int Jw, int stride, int G, float* __restrict__ out, const ConvertSpec& cs,
+                                              const LossSpec& ls, float* lds) {
+  constexpr bool kLoss = NQ == 6;
+  const AggMap m(cls, reg, dep, fh, fw, J, Jw, G);
+  if (m.jn <= 0) return;
+  if (valid && valid[m.k] != 1) {
+    const bool convert = cs.box || cs.box_f32;
+    fill_row(m, J, row_fill(valid[m.k]), out, convert ? cs.image_uvd : nullptr, convert && cs.has_paras ? cs.xyz_mm : nullptr,
+             kLoss ? ls.terms : nullptr);
+    return;
+  }
+  const float mj = joint_max(m, Jw, G, lds);
+  sums<NQ>(m, mj, fw, stride, G, lds);
+  if ((int)threadIdx.x < m.jn) {
+    const int jj = threadIdx.x;
+    const JointTotals<NQ> tt = joint_totals<NQ>(lds, m.AW, Jw, jj);
+    const long joint_row = (long)m.k * J + m.j0 + jj;
+    const float t = tt.t[0];
+    float* o = out + joint_row * 3;
+    float ku = tt.t[1] / t;
+    const float kv = tt.t[2] / t, kd = tt.t[3] / t;
+    if constexpr (!kLoss)   // (the loss form's entry takes no mirror flags: gt is in the coordinates of the crop as cut)
+      if (cs.mirror && cs.mirror[m.k]) ku = cs.crop_w - ku;   // (one fp32 subtraction, before anything else sees the value)
+    o[0] = ku;
+    o[1] = kv;
+    o[2] = kd;
+    // convert_joints + uvd2xyz in the aggregation's epilogue (what every caller does next: ros_demo.py:289,
+    // 329-330, a2j/a2j.py:341-348) -- from the registers that hold the joint, no second launch
+    if (cs.box || cs.box_f32) convert_one(cs, m.k, joint_row, ku, kv, kd);
+    if constexpr (kLoss) loss_terms_one(ls, joint_row, tt.t[4] / t, tt.t[5] / t, ku, kv, kd);
+  }
+}
+
+// (two kernels and not one template's instantiations: each has a name of its own in the build's resource record)
+__global__ __launch_bounds__(1024) void a2j_aggregate_kernel(const float* __restrict__ cls, const float* __restrict__ reg,
+                                                             const float* __restrict__ dep, const int* __restrict__ valid, int fh,
+                                                             int fw, int J, int Jw, int stride, int G, float* __restrict__ out,
+                                                             const ConvertSpec cs) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // [G][4][A*Jw]
+  aggregate_row<4>(cls, reg, dep, valid, fh, fw, J, Jw, stride, G, out, cs, LossSpec{}, lds);
+}
+
+__global__ __launch_bounds__(1024) void a2j_loss_aggregate_kernel(const float* __restrict__ cls, const float* __restrict__ reg,
+                                                                  const float* __restrict__ dep, const int* __restrict__ valid,
+                                                                  int fh, int fw, int J, int Jw, int stride, int G,
+                                                                  float* __restrict__ out, const ConvertSpec cs, const LossSpec ls) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // [G][6][A*Jw]
+  aggregate_row<6>(cls, reg, dep, valid, fh, fw, J, Jw, stride, G, out, cs, ls, lds);
+}
 
 // what the criterion's backward (hn_a2j_loss_grad_f32; DESIGN.md section 9r, tests/loss_grad_ref.py) adds to the kernel's arguments
 struct GradSpec {
@@ -168,9 +378,8 @@ __device__ __forceinline__ float clip1(float x) { return x != x ? x : fminf(fmax
 // the derivative of |x|: sign(0) = 0 as torch's, a NaN stays NaN
 __device__ __forceinline__ float sign1(float x) { return x > 0.f ? 1.f : x < 0.f ? -1.f : x; }
 
-// The criterion's backward in the aggregation's sweep: grid, thread <-> (group, anchor, joint) map, cell batches and LDS
-// combination of a2j_loss_aggregate_kernel (phases one and two below are its lines: the same maximum and six sums through the same
-// chains in the same order, so the divided uvd and the eight terms are the loss entry's bytes), then
+// The criterion's backward in the aggregation's sweep: a2j_loss_aggregate_kernel's grid, AggMap, joint_max, sums<6> and
+// joint_totals<6> (so the divided uvd and the eight terms are the loss entry's bytes), then
 //   the thread that owns a joint: n = rows with valid != 0 (counted here, per workgroup), the coefficients
 //     ga_c = wa / n / (2J) clip(Ea_c - g_c),  gr_c = wr R sf / n / (2J) clip(Er_c - g_c),  gd = wr R / n / J sign(Ed - g_d)
 //     and t, Ea, Er, Ed into LDS (mj is there since the first phase);
@@ -184,19 +393,12 @@ __global__ __launch_bounds__(1024) void a2j_loss_grad_kernel(const float* __rest
   constexpr int NQ = 6;
   extern __shared__ __attribute__((aligned(16))) float lds[];  // [G][NQ][A*Jw], then [kGradJoint][Jw]
   __shared__ int wave_rows[16];
-  const int k = blockIdx.x;
-  const int j0 = blockIdx.y * Jw;
-  const int jn = min(Jw, J - j0);
-  if (jn <= 0) return;
-  const int AJ = kAnchorsPerCell * J;
-  const int AW = kAnchorsPerCell * Jw;
-  const int g = threadIdx.x / AW, cl = threadIdx.x - g * AW;
-  const int a = cl / Jw, jl = cl - a * Jw;
-  const bool active = g < G && jl < jn;
-  const int c = a * J + j0 + jl;
-  const int cells = fh * fw;
-  if (valid && valid[k] != 1) {  // uniform per workgroup: the row's slice of the gradients (and of the forward outputs) is 0 or NaN
-    const float fill = valid[k] == 0 ? 0.f : __builtin_nanf("");
+  const AggMap m(cls, reg, dep, fh, fw, J, Jw, G);
+  if (m.jn <= 0) return;
+  const int k = m.k, j0 = m.j0, jn = m.jn, AJ = m.AJ, AW = m.AW, g = m.g, a = m.a, jl = m.jl, c = m.c, cells = m.cells;
+  const bool active = m.active;
+  if (valid && valid[k] != 1) {  // the row's slice of the gradients (and of the forward outputs) is 0 or NaN
+    const float fill = row_fill(valid[k]);
     if (active)
       for (int p = g; p < cells; p += G) {
         const long q = ((long)k * cells + p) * AJ + c;
@@ -204,8 +406,7 @@ __global__ __launch_bounds__(1024) void a2j_loss_grad_kernel(const float* __rest
         *reinterpret_cast<float2*>(gs.d_reg + q * 2) = make_float2(fill, fill);
         gs.d_dep[q] = fill;
       }
-    if (gs.uvd && (int)threadIdx.x < jn * 3) gs.uvd[((long)k * J + j0) * 3 + threadIdx.x] = fill;
-    if (gs.terms && (int)threadIdx.x < jn * kLossTerms) gs.terms[((long)k * J + j0) * kLossTerms + threadIdx.x] = fill;
+    fill_row(m, J, fill, gs.uvd, nullptr, nullptr, gs.terms);
     return;
   }
   {  // rows that count in the batch means: this thread's share, then its wave's (read behind the barriers below)
@@ -215,99 +416,19 @@ __global__ __launch_bounds__(1024) void a2j_loss_grad_kernel(const float* __rest
     for (int o = 32; o > 0; o >>= 1) rows += __shfl_xor(rows, o);
     if ((threadIdx.x & 63) == 0) wave_rows[threadIdx.x >> 6] = rows;
   }
-  const float* clsk = cls + (long)k * cells * AJ;
-  const float* depk = dep + (long)k * cells * AJ;
-  const float* regk = reg + (long)k * cells * AJ * 2;
+  const float *clsk = m.cls, *depk = m.dep, *regk = m.reg;
 
-  constexpr int kBatch = 14;
-  float mx = -FLT_MAX;
-  if (active)
-    for (int pb = g; pb < cells; pb += kBatch * G) {
-      float v[kBatch];
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) {
-        const int p = pb + u * G;
-        v[u] = p < cells ? clsk[(long)p * AJ + c] : -FLT_MAX;
-      }
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) mx = fmaxf(mx, v[u]);
-    }
-  if (g < G) lds[g * AW + cl] = mx;
-  __syncthreads();
-  if ((int)threadIdx.x < AW) {
-    float m = lds[threadIdx.x];
-    for (int gg = 1; gg < G; ++gg) m = fmaxf(m, lds[gg * AW + threadIdx.x]);
-    lds[threadIdx.x] = m;
-  }
-  __syncthreads();
-  float mj = -FLT_MAX;
-  if (active)
-    for (int aa = 0; aa < kAnchorsPerCell; ++aa) mj = fmaxf(mj, lds[aa * Jw + jl]);
+  const float mj = joint_max(m, Jw, G, lds);
   float* jv = lds + (long)G * NQ * AW;   // [kGradJoint][Jw]: behind the planes
   if ((int)threadIdx.x < jn) jv[threadIdx.x] = mj;   // (thread jl = group 0, anchor 0 of its joint; read in the third sweep)
-  __syncthreads();
-
-  if (active) {
-    const float p0 = 2.f + 4.f * (float)(a >> 2), p1 = 2.f + 4.f * (float)(a & 3);
-    float s = 0.f, s0 = 0.f, s1 = 0.f, sd = 0.f;
-    float sa0 = 0.f, sa1 = 0.f;   // e * anchor
-    for (int pb = g; pb < cells; pb += kBatch * G) {
-      float vc[kBatch], vd[kBatch];
-      float2 vr[kBatch];
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) {
-        const int p = pb + u * G;
-        const long q = (long)(p < cells ? p : g) * AJ + c;   // (clamped: the tail batch's extra cells are not used)
-        vc[u] = clsk[q];
-        vr[u] = *reinterpret_cast<const float2*>(regk + q * 2);
-        vd[u] = depk[q];
-      }
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) {
-        const int p = pb + u * G;
-        if (p < cells) {
-          const int hh = p / fw, ww = p - hh * fw;
-          const float e = expf(vc[u] - mj);
-          const float a0 = (float)(hh * stride) + p0, a1 = (float)(ww * stride) + p1;
-          s += e;
-          s0 += e * (a0 + vr[u].x);
-          s1 += e * (a1 + vr[u].y);
-          sd += e * vd[u];
-          sa0 += e * a0;
-          sa1 += e * a1;
-        }
-      }
-    }
-    float* o = lds + (long)g * NQ * AW;
-    o[cl] = s;
-    o[AW + cl] = s0;
-    o[2 * AW + cl] = s1;
-    o[3 * AW + cl] = sd;
-    o[4 * AW + cl] = sa0;
-    o[5 * AW + cl] = sa1;
-  }
-  __syncthreads();
-  for (int s4 = threadIdx.x; s4 < NQ * AW; s4 += blockDim.x) {
-    float acc = lds[s4];
-    for (int gg = 1; gg < G; ++gg) acc += lds[(long)gg * NQ * AW + s4];
-    lds[s4] = acc;
-  }
-  __syncthreads();
+  sums<NQ>(m, mj, fw, stride, G, lds);
   if ((int)threadIdx.x < jn) {
     const int jj = threadIdx.x;
-    float t = 0.f, t0 = 0.f, t1 = 0.f, td = 0.f;
-    float ta0 = 0.f, ta1 = 0.f;
-    for (int aa = 0; aa < kAnchorsPerCell; ++aa) {
-      t += lds[aa * Jw + jj];
-      t0 += lds[AW + aa * Jw + jj];
-      t1 += lds[2 * AW + aa * Jw + jj];
-      td += lds[3 * AW + aa * Jw + jj];
-      ta0 += lds[4 * AW + aa * Jw + jj];
-      ta1 += lds[5 * AW + aa * Jw + jj];
-    }
+    const JointTotals<NQ> tt = joint_totals<NQ>(lds, AW, Jw, jj);
     const long joint_row = (long)k * J + j0 + jj;
-    const float ku = t0 / t, kv = t1 / t, kd = td / t;
-    const float e0 = ta0 / t, e1 = ta1 / t;
+    const float t = tt.t[0];
+    const float ku = tt.t[1] / t, kv = tt.t[2] / t, kd = tt.t[3] / t;
+    const float e0 = tt.t[4] / t, e1 = tt.t[5] / t;
     if (gs.uvd) {
       float* o = gs.uvd + joint_row * 3;
       o[0] = ku;
@@ -467,6 +588,38 @@ __global__ __launch_bounds__(256) void convert_joints_kernel(const float* __rest
 
 }  // namespace
 
+// the conversion as the entries take it (paras: host (fx, fy, cx, cy) or null; opts: host or null = no clamps, no per-sample
+// operands) -> the kernels' ConvertSpec
+static int convert_spec(ConvertSpec& cs, const int64_t* crop_box, float crop_w, float crop_h, const float* paras,
+                        const hn_convert_opts* opts, const int32_t* mirror, float* out_image_uvd, float* out_xyz_mm) {
+  cs.box = (const long long*)crop_box;
+  cs.crop_w = crop_w;
+  cs.crop_h = crop_h;
+  cs.box_f32 = opts ? opts->sample_box : nullptr;
+  cs.sample_paras = opts ? opts->sample_paras : nullptr;
+  cs.has_paras = (paras || cs.sample_paras) ? 1 : 0;
+  cs.fx = paras ? paras[0] : 1.f;
+  cs.fy = paras ? paras[1] : 1.f;
+  cs.cx = paras ? paras[2] : 0.f;
+  cs.cy = paras ? paras[3] : 0.f;
+  cs.clamp_kp = opts ? opts->clamp_keypoints : 0;
+  cs.clamp_h = opts ? opts->clamp_box_h : 0;
+  cs.clamp_w = opts ? opts->clamp_box_w : 0;
+  HN_CHECK_ARG((cs.clamp_h > 0) == (cs.clamp_w > 0), "clamp_box_h and clamp_box_w are given together");
+  cs.image_uvd = out_image_uvd;
+  cs.xyz_mm = out_xyz_mm;
+  cs.mirror = mirror;
+  return HN_OK;
+}
+
+// the head checks of the four aggregation entries; who: "" or "<the entry's name>: "
+static int check_heads(const char* who, int k, int fh, int fw, int joints, int stride) {
+  HN_CHECK_ARG(joints > 0 && joints * kAnchorsPerCell <= 1024, "%sjoints must be in [1, 64]", who);
+  HN_CHECK_ARG(fh > 0 && fw > 0, "%sbad dims: fh * fw must not be 0", who);
+  HN_CHECK_ARG(k >= 0 && stride > 0, "%sbad dims", who);
+  return HN_OK;
+}
+
 extern "C" int hn_convert_joints_f32(const float* kp, const int64_t* crop_box, const int32_t* valid, int n, int joints,
                                      float crop_w, float crop_h, const float* paras, float* out, void* stream) {
   HN_CHECK_ARG(kp && crop_box && out, "hn_convert_joints_f32: null pointer");
@@ -474,16 +627,8 @@ extern "C" int hn_convert_joints_f32(const float* kp, const int64_t* crop_box, c
   if (n == 0) return HN_OK;
   const int total = n * joints;
   ConvertSpec cs{};
-  cs.box = (const long long*)crop_box;
-  cs.crop_w = crop_w;
-  cs.crop_h = crop_h;
-  cs.has_paras = paras ? 1 : 0;
-  cs.fx = paras ? paras[0] : 1.f;
-  cs.fy = paras ? paras[1] : 1.f;
-  cs.cx = paras ? paras[2] : 0.f;
-  cs.cy = paras ? paras[3] : 0.f;
-  cs.image_uvd = paras ? nullptr : out;
-  cs.xyz_mm = paras ? out : nullptr;
+  if (const int st = convert_spec(cs, crop_box, crop_w, crop_h, paras, nullptr, nullptr, paras ? nullptr : out, paras ? out : nullptr))
+    return st;
   hipLaunchKernelGGL(convert_joints_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, kp, valid, n, joints, cs);
   HN_CHECK_LAUNCH("convert_joints_kernel");
   return HN_OK;
@@ -499,14 +644,8 @@ extern "C" int hn_convert_joints_samples_f32(const float* kp, const float* box_f
   if (n == 0) return HN_OK;
   const int total = n * joints;
   ConvertSpec cs{};
-  cs.box_f32 = box_f32;
-  cs.sample_paras = sample_paras;
-  cs.crop_w = crop_w;
-  cs.crop_h = crop_h;
-  cs.has_paras = sample_paras ? 1 : 0;
-  cs.fx = cs.fy = 1.f;
-  cs.image_uvd = out_image_uvd;
-  cs.xyz_mm = out_xyz_mm;
+  const hn_convert_opts samples{0, 0, 0, 0, box_f32, sample_paras};
+  if (const int st = convert_spec(cs, nullptr, crop_w, crop_h, nullptr, &samples, nullptr, out_image_uvd, out_xyz_mm)) return st;
   hipLaunchKernelGGL(convert_joints_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, kp, valid, n, joints, cs);
   HN_CHECK_LAUNCH("convert_joints_kernel");
   return HN_OK;
@@ -572,8 +711,7 @@ static int launch_aggregate(const float* cls, const float* reg, const float* dep
 extern "C" int hn_a2j_aggregate_f32(const float* cls, const float* reg, const float* dep, const int32_t* valid,
                                     int k, int fh, int fw, int joints, int stride, float* out, void* stream) {
   HN_CHECK_ARG(cls && reg && dep && out, "hn_a2j_aggregate_f32: null pointer");
-  HN_CHECK_ARG(k >= 0 && fh > 0 && fw > 0 && stride > 0, "bad dims");
-  HN_CHECK_ARG(joints > 0 && joints * kAnchorsPerCell <= 1024, "joints must be in [1, 64]");
+  if (const int st = check_heads("", k, fh, fw, joints, stride)) return st;
   if (k == 0) return HN_OK;
   return launch_aggregate(cls, reg, dep, valid, k, fh, fw, joints, stride, out, ConvertSpec{}, stream);
 }
@@ -587,27 +725,11 @@ static int aggregate_convert_run(const float* cls, const float* reg, const float
   HN_CHECK_ARG(out_image_uvd || out_xyz_mm, "hn_a2j_aggregate_convert_f32: no converted output requested");
   HN_CHECK_ARG(!out_xyz_mm || paras || (opts && opts->sample_paras),
                "hn_a2j_aggregate_convert_f32: camera xyz needs the intrinsics (fx, fy, cx, cy)");
-  HN_CHECK_ARG(k >= 0 && fh > 0 && fw > 0 && stride > 0 && crop_w > 0.f && crop_h > 0.f, "bad dims");
-  HN_CHECK_ARG(joints > 0 && joints * kAnchorsPerCell <= 1024, "joints must be in [1, 64]");
+  HN_CHECK_ARG(crop_w > 0.f && crop_h > 0.f, "bad dims");
+  if (const int st = check_heads("", k, fh, fw, joints, stride)) return st;
   if (k == 0) return HN_OK;
   ConvertSpec cs{};
-  cs.box = (const long long*)crop_box;
-  cs.crop_w = crop_w;
-  cs.crop_h = crop_h;
-  cs.box_f32 = opts ? opts->sample_box : nullptr;
-  cs.sample_paras = opts ? opts->sample_paras : nullptr;
-  cs.has_paras = (paras || cs.sample_paras) ? 1 : 0;
-  cs.fx = paras ? paras[0] : 1.f;
-  cs.fy = paras ? paras[1] : 1.f;
-  cs.cx = paras ? paras[2] : 0.f;
-  cs.cy = paras ? paras[3] : 0.f;
-  cs.clamp_kp = opts ? opts->clamp_keypoints : 0;
-  cs.clamp_h = opts ? opts->clamp_box_h : 0;
-  cs.clamp_w = opts ? opts->clamp_box_w : 0;
-  HN_CHECK_ARG((cs.clamp_h > 0) == (cs.clamp_w > 0), "clamp_box_h and clamp_box_w are given together");
-  cs.image_uvd = out_image_uvd;
-  cs.xyz_mm = out_xyz_mm;
-  cs.mirror = mirror;
+  if (const int st = convert_spec(cs, crop_box, crop_w, crop_h, paras, opts, mirror, out_image_uvd, out_xyz_mm)) return st;
   return launch_aggregate(cls, reg, dep, valid, k, fh, fw, joints, stride, out_uvd, cs, stream);
 }
 
@@ -618,9 +740,7 @@ extern "C" int hn_a2j_aggregate_loss_f32(const float* cls, const float* reg, con
                                          float* out_xyz_mm, float* out_terms, float* out_sample, float* out_batch, void* stream) {
   HN_CHECK_ARG(cls && reg && dep && gt && out_uvd && out_terms && out_sample && out_batch,
                "hn_a2j_aggregate_loss_f32: null pointer");
-  HN_CHECK_ARG(joints > 0 && joints * kAnchorsPerCell <= 1024, "hn_a2j_aggregate_loss_f32: joints must be in [1, 64]");
-  HN_CHECK_ARG(fh > 0 && fw > 0, "hn_a2j_aggregate_loss_f32: fh * fw must not be 0");
-  HN_CHECK_ARG(k >= 0 && stride > 0, "hn_a2j_aggregate_loss_f32: bad dims");
+  if (const int st = check_heads("hn_a2j_aggregate_loss_f32: ", k, fh, fw, joints, stride)) return st;
   HN_CHECK_ARG((uintptr_t)out_terms % 16 == 0, "hn_a2j_aggregate_loss_f32: out_terms must be 16-byte aligned");
   ConvertSpec cs{};
   if (crop_box || (opts && opts->sample_box)) {   // the conversion, as hn_a2j_aggregate_convert_f32 takes it; absent: none
@@ -628,22 +748,7 @@ extern "C" int hn_a2j_aggregate_loss_f32(const float* cls, const float* reg, con
     HN_CHECK_ARG(!out_xyz_mm || paras || (opts && opts->sample_paras),
                  "hn_a2j_aggregate_loss_f32: camera xyz needs the intrinsics (fx, fy, cx, cy)");
     HN_CHECK_ARG(crop_w > 0.f && crop_h > 0.f, "hn_a2j_aggregate_loss_f32: bad crop size");
-    cs.box = (const long long*)crop_box;
-    cs.crop_w = crop_w;
-    cs.crop_h = crop_h;
-    cs.box_f32 = opts ? opts->sample_box : nullptr;
-    cs.sample_paras = opts ? opts->sample_paras : nullptr;
-    cs.has_paras = (paras || cs.sample_paras) ? 1 : 0;
-    cs.fx = paras ? paras[0] : 1.f;
-    cs.fy = paras ? paras[1] : 1.f;
-    cs.cx = paras ? paras[2] : 0.f;
-    cs.cy = paras ? paras[3] : 0.f;
-    cs.clamp_kp = opts ? opts->clamp_keypoints : 0;
-    cs.clamp_h = opts ? opts->clamp_box_h : 0;
-    cs.clamp_w = opts ? opts->clamp_box_w : 0;
-    HN_CHECK_ARG((cs.clamp_h > 0) == (cs.clamp_w > 0), "clamp_box_h and clamp_box_w are given together");
-    cs.image_uvd = out_image_uvd;
-    cs.xyz_mm = out_xyz_mm;
+    if (const int st = convert_spec(cs, crop_box, crop_w, crop_h, paras, opts, nullptr, out_image_uvd, out_xyz_mm)) return st;
   } else {
     HN_CHECK_ARG(!out_image_uvd && !out_xyz_mm, "hn_a2j_aggregate_loss_f32: converted outputs need boxes (crop_box or opts->sample_box)");
   }
@@ -662,9 +767,7 @@ extern "C" int hn_a2j_loss_grad_f32(const float* cls, const float* reg, const fl
                                     const float* upstream, float* d_cls, float* d_reg, float* d_dep, float* out_uvd,
                                     float* out_terms, void* stream) {
   HN_CHECK_ARG(cls && reg && dep && gt && d_cls && d_reg && d_dep, "hn_a2j_loss_grad_f32: null pointer");
-  HN_CHECK_ARG(joints > 0 && joints * kAnchorsPerCell <= 1024, "hn_a2j_loss_grad_f32: joints must be in [1, 64]");
-  HN_CHECK_ARG(fh > 0 && fw > 0, "hn_a2j_loss_grad_f32: fh * fw must not be 0");
-  HN_CHECK_ARG(k >= 0 && stride > 0, "hn_a2j_loss_grad_f32: bad dims");
+  if (const int st = check_heads("hn_a2j_loss_grad_f32: ", k, fh, fw, joints, stride)) return st;
   HN_CHECK_ARG((long)fh * fw * kAnchorsPerCell * joints * 2 < (1L << 31),
                "hn_a2j_loss_grad_f32: one crop's reg slice (fh * fw * 32 * joints) must be below 2^31 elements");
   HN_CHECK_ARG((uintptr_t)reg % 8 == 0 && (uintptr_t)d_reg % 8 == 0, "hn_a2j_loss_grad_f32: reg and d_reg must be 8-byte aligned");
@@ -703,15 +806,8 @@ extern "C" int hn_a2j_aggregate_convert_mirror_f32(const float* cls, const float
 // rounding only; the tests compare with a function-by-function fp64 restatement of the caller's chain).
 // ---------------------------------------------------------------------------------------
 namespace {
-__global__ __launch_bounds__(64) void joints2d_standardize_kernel(const float* __restrict__ uvd, const int* __restrict__ valid,
-                                                                  int J, float* __restrict__ out) {
-  const int img = blockIdx.x, lane = threadIdx.x;
-  float* o = out + (long)img * J * 2;
-  if (valid && valid[img] != 1) {
-    for (int i = lane; i < J * 2; i += 64) o[i] = 0.f;
-    return;
-  }
-  const float* p = uvd + (long)img * J * 3;
+// one frame's row p [J][3] -> o [J][2], by one wave; flip: column 0 negated (the gated kernel's mirrored rows)
+__device__ __forceinline__ void standardize_row(const float* __restrict__ p, int J, int lane, bool flip, float* __restrict__ o) {
   // every lane computes both axes' statistics itself (J <= 64 values each: 2 x 21 loads that hit the same cache line)
   double m0 = 0.0, m1 = 0.0;
   for (int j = 0; j < J; ++j) {
@@ -728,9 +824,21 @@ __global__ __launch_bounds__(64) void joints2d_standardize_kernel(const float* _
   }
   const double s0 = sqrt(v0 / J), s1 = sqrt(v1 / J);
   for (int j = lane; j < J; j += 64) {
-    o[j * 2 + 0] = (float)(((double)p[j * 3 + 0] - m0) / s0);
+    const float x = (float)(((double)p[j * 3 + 0] - m0) / s0);
+    o[j * 2 + 0] = flip ? -x : x;
     o[j * 2 + 1] = (float)(((double)p[j * 3 + 1] - m1) / s1);
   }
+}
+
+__global__ __launch_bounds__(64) void joints2d_standardize_kernel(const float* __restrict__ uvd, const int* __restrict__ valid,
+                                                                  int J, float* __restrict__ out) {
+  const int img = blockIdx.x, lane = threadIdx.x;
+  float* o = out + (long)img * J * 2;
+  if (valid && valid[img] != 1) {
+    for (int i = lane; i < J * 2; i += 64) o[i] = 0.f;
+    return;
+  }
+  standardize_row(uvd + (long)img * J * 3, J, lane, false, o);
 }
 }  // namespace
 
@@ -748,7 +856,7 @@ extern "C" int hn_joints2d_standardize_f32(const float* image_uvd, const int32_t
 // The lifter's input with the live caller's skip rule (include/handnet_hip.h): ros_demo.py:288-300 drops a hand when
 // process_bbox(get_bbox(joints2d)) is None (pose2mesh/lib/coord_utils.py:21-49).  One wave per slot: the bounding box from
 // exact wave min / max reductions, the rule in fp32 one rounding per numpy operation (no contraction: this file is built with
-// the compiler's default), then joints2d_standardize_kernel's statistics for the accepted slots, restated line by line.
+// the compiler's default), then standardize_row for the accepted slots.
 // ---------------------------------------------------------------------------------------
 namespace {
 __device__ __forceinline__ void wave_minmax(float& lo, float& hi) {
@@ -808,27 +916,7 @@ __global__ __launch_bounds__(64) void lifter_input_gated_kernel(const float* __r
     for (int i = lane; i < J * 2; i += 64) o[i] = 0.f;
     return;
   }
-  // joints2d_standardize_kernel's body from here on: the same operations in the same order (bit-identical rows)
-  double m0 = 0.0, m1 = 0.0;
-  for (int j = 0; j < J; ++j) {
-    m0 += (double)p[j * 3 + 0];
-    m1 += (double)p[j * 3 + 1];
-  }
-  m0 /= J;
-  m1 /= J;
-  double v0 = 0.0, v1 = 0.0;
-  for (int j = 0; j < J; ++j) {
-    const double a = (double)p[j * 3 + 0] - m0, b = (double)p[j * 3 + 1] - m1;
-    v0 += a * a;
-    v1 += b * b;
-  }
-  const double s0 = sqrt(v0 / J), s1 = sqrt(v1 / J);
-  const bool flip = mirror && mirror[img];
-  for (int j = lane; j < J; j += 64) {
-    const float x = (float)(((double)p[j * 3 + 0] - m0) / s0);
-    o[j * 2 + 0] = flip ? -x : x;
-    o[j * 2 + 1] = (float)(((double)p[j * 3 + 1] - m1) / s1);
-  }
+  standardize_row(p, J, lane, mirror && mirror[img], o);   // (joints2d_standardize_kernel's rows, bit for bit)
 }
 }  // namespace
 

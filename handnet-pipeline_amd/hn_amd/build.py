@@ -58,9 +58,10 @@ EXTRA_FLAGS = {"fcos_post.hip": ["-ffp-contract=off", "-fno-slp-vectorize"], "gr
 # (plain, deep-k, multi, mixed -- the deep-k kernel's name once slipped through per-kernel entries), the others are the
 # remaining files with LDS-DMA / counted waits (tests/test_build_cpu.py keeps this list in step with the sources).
 NO_SPILL_KERNELS = ("conv_igemm_f16x3_", "conv3x3_halo_kernel", "conv_stem_pool_direct_kernel", "conv3x3_thin", "conv1x1_stream_kernel")
-# Plain compiler-scheduled loads, but batches of 14 cells' operands under 1024 threads' 128 registers: a VGPR spill or scratch
-# would put memory traffic where the batching removed it, so the build refuses either (SGPR spills go to VGPR lanes: allowed).
-NO_SCRATCH_KERNELS = ("a2j_loss_grad_kernel",)
+# Plain compiler-scheduled loads, but batches of 14 cells' operands under 1024 threads' 128 registers (the A2J head sweep the
+# three kernels share): a VGPR spill or scratch would put memory traffic where the batching removed it, so the build refuses
+# either (SGPR spills go to VGPR lanes: allowed).
+NO_SCRATCH_KERNELS = ("a2j_aggregate_kernel", "a2j_loss_aggregate_kernel", "a2j_loss_grad_kernel")
 
 
 def _check_resources(src: Path, remarks: str, objdir: Path) -> None:

@@ -1627,6 +1627,24 @@ def _convert_arg(convert, k, joints, device):
     return box, float(convert.get("crop", 176)), pp, opts, img, xyz
 
 
+def _a2j_heads(cls, reg, dep, joints, gt=None, valid=None):
+    """The argument checks a2j_aggregate, a2j_loss and a2j_loss_grad share: cls/dep [K,fh,fw,16*J], reg [K,fh,fw,16*J*2], gt
+    [K,J,3] (where the caller takes one), valid [K] int32 or None, all contiguous fp32 / int32 on the device -> (k, fh, fw)."""
+    _req(cls, name="cls"); _req(reg, name="reg"); _req(dep, name="dep")
+    if gt is not None:
+        _req(gt, name="gt")
+    if cls.dim() != 4 or reg.dim() != 4:
+        raise ValueError("bad head shapes")
+    k, fh, fw, aj = cls.shape
+    if joints < 1 or aj != 16 * joints or reg.shape[3] != 2 * aj or dep.shape != cls.shape or reg.shape[:3] != cls.shape[:3]:
+        raise ValueError("bad head shapes")
+    if gt is not None and tuple(gt.shape) != (k, joints, 3):
+        raise ValueError("gt must be [K,J,3]")
+    if valid is not None and _req(valid, torch.int32, "valid").numel() != k:
+        raise ValueError("valid must hold one flag per crop")
+    return k, fh, fw
+
+
 def a2j_aggregate(cls, reg, dep, joints=21, stride=16, valid=None, out=None, convert=None):
     """cls/dep [K,fh,fw,16*J], reg [K,fh,fw,16*J*2] -> [K,J,3].
     convert: optional dict -- convert_joints + uvd2xyz in the SAME launch (hn_a2j_aggregate_convert_f32):
@@ -1637,16 +1655,11 @@ def a2j_aggregate(cls, reg, dep, joints=21, stride=16, valid=None, out=None, con
       else sees the value (hn_a2j_aggregate_convert_mirror_f32).
     Then returns (crop_uvd, image_uvd [K,J,3], xyz_mm [K,J,3] or None), bit-identical to convert_joints() on crop_uvd."""
     lib = _lib.load()
-    _req(cls, name="cls"); _req(reg, name="reg"); _req(dep, name="dep")
-    k, fh, fw, aj = cls.shape
-    if aj != 16 * joints or reg.shape[3] != 2 * aj or dep.shape != cls.shape:
-        raise ValueError("bad head shapes")
+    k, fh, fw = _a2j_heads(cls, reg, dep, joints, valid=valid)
     if out is None:
         out = torch.empty((k, joints, 3), device=cls.device, dtype=torch.float32)
     if k == 0:
         return out
-    if valid is not None:
-        _req(valid, torch.int32, "valid")
     if convert is not None:
         box, crop, pp, opts, img, xyz = _convert_arg(convert, k, joints, cls.device)
         mirror = convert.get("mirror")
@@ -1678,21 +1691,12 @@ def a2j_loss(cls, reg, dep, gt, joints=21, stride=16, spatial_factor=0.5, reg_lo
     valid: rows with 0 are left out of the batch values, rows with 2 make them NaN.  convert: a2j_aggregate's dict without
     mirror.  out: a preallocated uvd."""
     lib = _lib.load()
-    _req(cls, name="cls"); _req(reg, name="reg"); _req(dep, name="dep"); _req(gt, name="gt")
-    if cls.dim() != 4 or reg.dim() != 4:
-        raise ValueError("bad head shapes")
-    k, fh, fw, aj = cls.shape
-    if joints < 1 or aj != 16 * joints or reg.shape[3] != 2 * aj or dep.shape != cls.shape or reg.shape[:3] != cls.shape[:3]:
-        raise ValueError("bad head shapes")
-    if tuple(gt.shape) != (k, joints, 3):
-        raise ValueError("gt must be [K,J,3]")
+    k, fh, fw = _a2j_heads(cls, reg, dep, joints, gt, valid)
     dev = cls.device
     if out is None:
         out = torch.empty((k, joints, 3), device=dev, dtype=torch.float32)
     elif tuple(_req(out, name="out").shape) != (k, joints, 3):
         raise ValueError("out must be [K,J,3]")
-    if valid is not None and _req(valid, torch.int32, "valid").numel() != k:
-        raise ValueError("valid must hold one flag per crop")
     terms = torch.empty((k, joints, 8), device=dev, dtype=torch.float32)
     sample = torch.empty((k, 2), device=dev, dtype=torch.float32)
     # (no crop at all: nothing is launched, and the batch values are the mean of nothing)
@@ -1722,16 +1726,7 @@ def a2j_loss_grad(cls, reg, dep, gt, joints=21, stride=16, spatial_factor=0.5, r
     nothing here synchronises.  Rows with valid == 0 get zero gradients and are not counted in the batch mean, rows with
     valid == 2 get NaN.  want_forward: also return a2j_loss's uvd [K,J,3] and terms [K,J,8] of the same heads, bit for bit."""
     lib = _lib.load()
-    _req(cls, name="cls"); _req(reg, name="reg"); _req(dep, name="dep"); _req(gt, name="gt")
-    if cls.dim() != 4 or reg.dim() != 4:
-        raise ValueError("bad head shapes")
-    k, fh, fw, aj = cls.shape
-    if joints < 1 or aj != 16 * joints or reg.shape[3] != 2 * aj or dep.shape != cls.shape or reg.shape[:3] != cls.shape[:3]:
-        raise ValueError("bad head shapes")
-    if tuple(gt.shape) != (k, joints, 3):
-        raise ValueError("gt must be [K,J,3]")
-    if valid is not None and _req(valid, torch.int32, "valid").numel() != k:
-        raise ValueError("valid must hold one flag per crop")
+    k, fh, fw = _a2j_heads(cls, reg, dep, joints, gt, valid)
     if upstream is not None and _req(upstream, name="upstream").numel() != 2:
         raise ValueError("upstream must hold (wa, wr)")
     d_cls, d_reg, d_dep = torch.empty_like(cls), torch.empty_like(reg), torch.empty_like(dep)

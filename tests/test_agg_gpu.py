@@ -105,8 +105,8 @@ def test_fused_epilogue_is_convert_joints_on_the_returned_crop_uvd(name):
 
 
 def test_refusals_launch_nothing():
-    """65 joints, a cls whose last dimension is not 16 * joints, fh = 0: refused before any launch (the sentinel-filled output
-    comes back untouched)."""
+    """65 joints, a cls whose last dimension is not 16 * joints, fh = 0, a valid shorter than K, a reg of another K: refused
+    before any launch (the sentinel-filled output comes back untouched)."""
     from hn_amd import ops
 
     def heads(k, fh, fw, joints, aj=None):
@@ -121,3 +121,12 @@ def test_refusals_launch_nothing():
             ops.a2j_aggregate(*args, joints=joints, out=out)
         torch.cuda.synchronize()
         assert bool((out == SENTINEL).all()), joints
+    # fewer flags than crops (the kernel would read past the end of valid), and reg with another K: ops.a2j_loss's refusals
+    out = torch.full((2, 21, 3), SENTINEL, device="cuda")
+    cls, reg, dep = heads(2, 2, 2, 21)
+    with pytest.raises(ValueError, match="one flag per crop"):
+        ops.a2j_aggregate(cls, reg, dep, joints=21, valid=torch.ones(1, dtype=torch.int32, device="cuda"), out=out)
+    with pytest.raises(ValueError, match="bad head shapes"):
+        ops.a2j_aggregate(cls, reg[:1], dep, joints=21, out=out)
+    torch.cuda.synchronize()
+    assert bool((out == SENTINEL).all())

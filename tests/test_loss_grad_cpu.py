@@ -215,9 +215,10 @@ def test_the_c_entry_is_exported_under_abi_36_and_refuses_bad_arguments():
         assert call(**kw) == 1 and word in lib.hn_last_error(), (kw, lib.hn_last_error())
     assert call(k=0) == 0                                          # no crop: nothing is launched
     rows = (build.CSRC / "build" / "a2j_ops.resources.txt").read_text().splitlines()
-    row = [r for r in rows if "a2j_loss_grad_kernel" in r]
-    assert len(row) == 1 and " vgpr_spill 0 " in row[0] and " scratch 0 " in row[0], row
-    assert "a2j_loss_grad_kernel" in build.NO_SCRATCH_KERNELS
+    for kernel in ("a2j_aggregate_kernel", "a2j_loss_aggregate_kernel", "a2j_loss_grad_kernel"):   # the three of the one sweep
+        row = [r for r in rows if kernel in r]
+        assert len(row) == 1 and " vgpr_spill 0 " in row[0] and " scratch 0 " in row[0], row
+        assert kernel in build.NO_SCRATCH_KERNELS
 
 
 def test_the_python_surface():
