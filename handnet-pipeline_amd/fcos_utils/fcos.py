@@ -9,10 +9,11 @@ descending score; with `ext=True` (the class default, used by trainval_net_fcos.
 detections_per_img` are accepted and IGNORED: post-processing hard-codes score > 0.7 and
 NMS IoU 0.3 (fcos.py:600,635).
 
-The criterion is available forward only, as an opt-in: after `device_loss()`, `model.train(); model(images, targets)` returns the
-reference's loss dict (fcos.py:523-570 the matching, :44-178 the six terms) computed on the device from the detector's own head
-tensors, and `loss_step` is the same for a validation loop in either mode (hn_amd.ops.fcos_loss).  There
-is no backward pass and no optimizer; without the opt-in, train mode and targets raise as before.
+The criterion is an opt-in: after `device_loss()`, `model.train(); model(images, targets)` returns the reference's loss dict
+(fcos.py:523-570 the matching, :44-178 the six terms) computed on the device from the detector's own head tensors, and
+`loss_step` is the same for a validation loop in either mode (hn_amd.ops.fcos_loss).  `head_grads` adds the
+criterion's backward at those head tensors in one more launch (hn_amd.ops.fcos_loss_grad).  There is no
+backward pass through the towers or the backbone and no optimizer; without the opt-in, train mode and targets raise as before.
 """
 from __future__ import annotations
 
@@ -117,6 +118,18 @@ class FCOS(EngineOwner):
         the network image by image (FCOSEngine.forward_heads_each), so that an image's terms and fg are the bytes of that
         image alone on the same canvas, whatever else the list holds.  want_terms: also return the per-image sums [N, 6] before
         any factor or division."""
+        return self._loss_step(images, targets, want_terms, False)
+
+    def head_grads(self, images: List[torch.Tensor], targets):
+        """loss_step(images, targets) and the criterion's backward at the engine's own head tensors in one more launch
+        (ops.fcos_loss_grad) -> (losses, fg, (d_cls_lr, d_reg_ctr, d_ext or None)): losses and fg are
+        loss_step's bytes, the gradients are those of the sum of the dict's values (what trainval_net_fcos.py:56-57
+        back-propagates) with respect to the per-level head tensors, in their layouts ([N,h,w,C+2], [N,h,w,5], [N,h,w,8]) and
+        on the device.  Equal-size batches and lists of differently sized images take loss_step's paths.  Nothing is copied to
+        the host and nothing waits."""
+        return self._loss_step(images, targets, False, True)
+
+    def _loss_step(self, images, targets, want_terms, head_grads):
         dev = self._require_gpu()
         eng = self.engine()
         batch = self._batch(images)
@@ -131,11 +144,19 @@ class FCOS(EngineOwner):
                 new = list(zip(oh, ow))
             ratios = ops.fcos_target_ratios([tuple(i.shape[-2:]) for i in images], new)
             targets = ops.pack_fcos_targets(targets, ratios, num_classes=self.num_classes, ext=self.ext, device=dev)
+        ext = eng._ext_levels if self.ext else None
+        grads = None
         with ops.on_device(dev):
-            res = ops.fcos_loss(cls_lr, reg_ctr, strides, self.num_classes, targets, ext=eng._ext_levels if self.ext else None,
-                                radius=self.center_sampling_radius)
+            if head_grads:
+                *grads, res = ops.fcos_loss_grad(cls_lr, reg_ctr, strides, self.num_classes, targets, ext=ext,
+                                                 radius=self.center_sampling_radius, want_forward=True)
+            else:
+                res = ops.fcos_loss(cls_lr, reg_ctr, strides, self.num_classes, targets, ext=ext,
+                                    radius=self.center_sampling_radius)
         keys = ops.FCOS_LOSS_KEYS if self.ext else ops.FCOS_LOSS_KEYS[:4]
         losses = {k: res.losses[i] for i, k in enumerate(keys)}
+        if head_grads:
+            return losses, res.fg, tuple(grads)
         return (losses, res.fg, res.terms) if want_terms else (losses, res.fg)
 
     @staticmethod

@@ -175,6 +175,8 @@ SIGNATURES = {
     "hn_fcos_loss_ws_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "hn_fcos_loss_f32": (C.c_int, [C.POINTER(FcosLevels), C.POINTER(VP), C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, C.c_float,
                                    VP, VP, VP, VP, VP, C.c_int64, VP]),
+    "hn_fcos_loss_grad_f32": (C.c_int, [C.POINTER(FcosLevels), C.POINTER(VP), C.c_int, C.c_int, VP, VP, VP, VP, C.c_int, C.c_float,
+                                        VP, VP, VP, VP, VP, C.c_int64, VP, C.POINTER(VP), C.POINTER(VP), C.POINTER(VP), VP]),
     "hn_fcos_nms_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "hn_fcos_nms": (C.c_int, [VP] * 6 + [C.c_int, C.c_int, C.c_double, C.c_float, C.c_float] + [VP] * 9),
     "hn_fcos_nms_ratios": (C.c_int, [VP] * 6 + [C.c_int, C.c_int, C.c_double, VP] + [VP] * 9),

@@ -61,7 +61,8 @@ NO_SPILL_KERNELS = ("conv_igemm_f16x3_", "conv3x3_halo_kernel", "conv_stem_pool_
 # Plain compiler-scheduled loads, but batches of 14 cells' operands under 1024 threads' 128 registers (the A2J head sweep the
 # three kernels share): a VGPR spill or scratch would put memory traffic where the batching removed it, so the build refuses
 # either (SGPR spills go to VGPR lanes: allowed).
-NO_SCRATCH_KERNELS = ("a2j_aggregate_kernel", "a2j_loss_aggregate_kernel", "a2j_loss_grad_kernel")
+# fcos_loss_grad_kernel: one point per thread, 1024 threads, every intermediate in registers; its stores are the traffic.
+NO_SCRATCH_KERNELS = ("a2j_aggregate_kernel", "a2j_loss_aggregate_kernel", "a2j_loss_grad_kernel", "fcos_loss_grad_kernel")
 
 
 def _check_resources(src: Path, remarks: str, objdir: Path) -> None:

@@ -478,6 +478,22 @@ class FCOSEngine:
             return [cat(l, 0) for l in levels], [cat(l, 1) for l in levels], strides, ([g[2] for g in geom], [g[3] for g in geom], ph, pw)
 
     @ops.device_guarded
+    def head_grads(self, images, targets, radius=1.5, upstream=None):
+        """The heads, the criterion and its backward at this engine's own head tensors (ops.fcos_loss_grad; DESIGN.md section
+        9s) -> (losses, fg, (d_cls_lr, d_reg_ctr, d_ext or None)), all on the device: losses = the reference's dict (0-d fp32
+        tensors, four keys without ext) and fg int32 [N] are the bytes ops.fcos_loss gives on the same heads, the gradients are
+        per-level lists in the heads' layouts.  images: [N,3,H,W] (the batched forms) or a list of [3,h_i,w_i] images of
+        different sizes (forward_heads_each); targets: an ops.FcosTargets on the canvas's scale.  This is where a backward pass
+        through the towers would start; there is none here."""
+        heads = self.forward_heads if torch.is_tensor(images) else self.forward_heads_each
+        cls_lr, reg_ctr, strides, _ = heads(images)
+        *grads, res = ops.fcos_loss_grad(cls_lr, reg_ctr, strides, self.num_classes, targets,
+                                         ext=self._ext_levels if self.ext else None, radius=radius, upstream=upstream,
+                                         want_forward=True)
+        keys = ops.FCOS_LOSS_KEYS if self.ext else ops.FCOS_LOSS_KEYS[:4]
+        return {k: res.losses[i] for i, k in enumerate(keys)}, res.fg, tuple(grads)
+
+    @ops.device_guarded
     def detect(self, images, cand=None, det=None, nms_scratch=None):
         """Full detector on the device -> ops.Detections (fixed capacity, score-ordered).  images: [N,3,H,W], or a
         list of [3,h_i,w_i] tensors of different sizes (each resized on its own, boxes rescaled per image)."""

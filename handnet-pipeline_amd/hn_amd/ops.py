@@ -1320,13 +1320,9 @@ def alloc_fcos_loss(n, points, device, want_matched=False) -> FcosLoss:
                     torch.empty((n, points), device=device, dtype=torch.int32) if want_matched else None)
 
 
-def fcos_loss(cls_lr, reg_ctr, strides, num_classes, targets: FcosTargets, ext=None, radius=1.5, want_matched=False,
-              out: FcosLoss | None = None) -> FcosLoss:
-    """The FCOS criterion, forward only, on the detector's head tensors (hn_fcos_loss_f32; fcos_utils/fcos.py:44-178,523-570,
-    DESIGN.md section 9p): cls_lr[l] [N,h,w,C+2], reg_ctr[l] [N,h,w,5] and, for the ext terms, ext[l] [N,h,w,8] per level;
-    targets as pack_fcos_targets builds them (boxes already on the canvas's scale) -> FcosLoss, everything on the device and
-    nothing waited for.  Two launches with a fixed summation order: the same bytes on every run, and row i of a batch is the
-    row of image i alone.  Every refusal happens before a launch."""
+def _fcos_loss_args(cls_lr, reg_ctr, strides, num_classes, targets, ext, want_matched, out):
+    """The argument checks fcos_loss and fcos_loss_grad share -> (level table, ext pointer array or None, n, points, G, out,
+    workspace, its bytes); every refusal happens here, before a launch."""
     lib = _lib.load()
     nl = len(cls_lr)
     if nl == 0 or len(reg_ctr) != nl or len(strides) != nl or (ext is not None and len(ext) != nl):
@@ -1368,18 +1364,69 @@ def fcos_loss(cls_lr, reg_ctr, strides, num_classes, targets: FcosTargets, ext=N
             raise ValueError("out.matched must be int32 [N,P]")
     nbytes = lib.hn_fcos_loss_ws_bytes(n, points)
     ws = torch.empty((nbytes // 8,), device=dev, dtype=torch.float64)
+    return lv, arr, n, points, g, out, ws, nbytes
+
+
+def _fcos_loss_call(entry, name, num_classes, n, points, g, launch):
+    """the profile bracket fcos_loss and fcos_loss_grad share: stage "fcos_loss", one record under `name`"""
     global PROFILE_STAGE
     prev, PROFILE_STAGE = PROFILE_STAGE, "fcos_loss"
     try:
         timer = _profile_start()
-        check(lib.hn_fcos_loss_f32(C.byref(lv), arr, n, int(num_classes), ptr(targets.boxes), ptr(targets.labels), ptr(targets.info),
-                                   ptr(targets.count), g, float(radius), ptr(out.terms), ptr(out.fg), ptr(out.losses),
-                                   ptr(out.matched) if want_matched else None, ptr(ws), nbytes, _stream()), "hn_fcos_loss_f32")
+        check(launch(), entry)
         if timer is not None:
-            _profile_stop(timer, lambda: (("f32", "fcos_loss"), 0, (n, points, int(num_classes), g)))
+            _profile_stop(timer, lambda: (("f32", name), 0, (n, points, int(num_classes), g)))
     finally:
         PROFILE_STAGE = prev
+
+
+def fcos_loss(cls_lr, reg_ctr, strides, num_classes, targets: FcosTargets, ext=None, radius=1.5, want_matched=False,
+              out: FcosLoss | None = None) -> FcosLoss:
+    """The FCOS criterion's forward on the detector's head tensors (hn_fcos_loss_f32; fcos_utils/fcos.py:44-178,523-570,
+    DESIGN.md section 9p): cls_lr[l] [N,h,w,C+2], reg_ctr[l] [N,h,w,5] and, for the ext terms, ext[l] [N,h,w,8] per level;
+    targets as pack_fcos_targets builds them (boxes already on the canvas's scale) -> FcosLoss, everything on the device and
+    nothing waited for.  Two launches with a fixed summation order: the same bytes on every run, and row i of a batch is the
+    row of image i alone.  Every refusal happens before a launch.  The backward at the heads is fcos_loss_grad."""
+    lib = _lib.load()
+    lv, arr, n, points, g, out, ws, nbytes = _fcos_loss_args(cls_lr, reg_ctr, strides, num_classes, targets, ext, want_matched, out)
+    _fcos_loss_call("hn_fcos_loss_f32", "fcos_loss", num_classes, n, points, g, lambda: lib.hn_fcos_loss_f32(
+        C.byref(lv), arr, n, int(num_classes), ptr(targets.boxes), ptr(targets.labels), ptr(targets.info), ptr(targets.count), g,
+        float(radius), ptr(out.terms), ptr(out.fg), ptr(out.losses), ptr(out.matched) if want_matched else None, ptr(ws), nbytes,
+        _stream()))
     return out
+
+
+def fcos_loss_grad(cls_lr, reg_ctr, strides, num_classes, targets: FcosTargets, ext=None, radius=1.5, upstream=None,
+                   want_forward=False, out=None):
+    """The FCOS criterion's backward at the detector heads (hn_fcos_loss_grad_f32): fcos_loss's arguments
+    and refusals -> per-level lists (d_cls_lr, d_reg_ctr, d_ext or None), the gradient of sum_k upstream[k] * losses[k] at the
+    tensors as they are handed in (the regressions and the ext (mag, dx, dy) are a ReLU's outputs: the gradient is at those
+    outputs).  upstream: six fp32 weights ON THE DEVICE in FCOS_LOSS_KEYS order (None: ones; without ext [4:] is ignored); the
+    kernel reads them, so the call sits inside a captured step.  The matching and the divisor max(1, sum fg) are constants.
+    The forward's two launches, then one more; every element is written once, the same bytes on every run.  want_forward: also
+    return the FcosLoss, the bytes fcos_loss gives.  out: (d_cls_lr, d_reg_ctr, d_ext or None) lists to write into."""
+    lib = _lib.load()
+    lv, arr, n, points, g, res, ws, nbytes = _fcos_loss_args(cls_lr, reg_ctr, strides, num_classes, targets, ext, False, None)
+    dev = cls_lr[0].device
+    if upstream is not None and (tuple(_req(upstream, name="upstream").shape) != (6,) or upstream.device != dev):
+        raise ValueError("fcos_loss_grad: upstream must be fp32 [6] on the heads' device")
+    heads = (cls_lr, reg_ctr, ext)
+    if out is None:
+        out = tuple(None if h is None else [torch.empty_like(t) for t in h] for h in heads)
+    else:
+        if len(out) != 3 or (out[2] is None) != (ext is None):
+            raise ValueError("fcos_loss_grad: out must be (d_cls_lr, d_reg_ctr, d_ext or None)")
+        for h, o in zip(heads, out):
+            if h is not None and (len(o) != len(h) or any(_req(t, name="out").shape != s.shape or t.device != dev for t, s in zip(o, h))):
+                raise ValueError("fcos_loss_grad: out must hold tensors of the heads' shapes on their device")
+    nl = len(cls_lr)
+    arrays = [None if o is None else (C.c_void_p * nl)(*[t.data_ptr() for t in o]) for o in out]
+    _fcos_loss_call("hn_fcos_loss_grad_f32", "fcos_loss_grad", num_classes, n, points, g, lambda: lib.hn_fcos_loss_grad_f32(
+        C.byref(lv), arr, n, int(num_classes), ptr(targets.boxes), ptr(targets.labels), ptr(targets.info), ptr(targets.count), g,
+        float(radius), ptr(res.terms), ptr(res.fg), ptr(res.losses), None, ptr(ws), nbytes, ptr(upstream), arrays[0], arrays[1],
+        arrays[2], _stream()))
+    grads = (out[0], out[1], out[2])
+    return grads + (res,) if want_forward else grads
 
 
 def fcos_nms(cand: Candidates, iou_thresh, ratio_h, ratio_w, scratch=None, out: Detections | None = None,

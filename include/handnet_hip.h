@@ -43,7 +43,8 @@ extern "C" {
  * hn_conv2d_nhwc_f16x3_grouped_carry, hn_conv2d_f16x3_grouped_carry_applies and hn_affine_split_f32_levels_streams, the evaluator's hn_hpe_accumulate_f32, the
  * detector evaluation's hn_det_ap_accumulate_f32, the A2J criterion's hn_a2j_aggregate_loss_f32, and the FCOS criterion's
  * hn_fcos_loss_f32 and hn_fcos_loss_ws_bytes, and the held objects' hn_hand_objects_f32, hn_hand_objects_scratch_bytes and
- * hn_draw_object_labels_u8, and the A2J criterion's backward hn_a2j_loss_grad_f32). */
+ * hn_draw_object_labels_u8, and the A2J criterion's backward hn_a2j_loss_grad_f32, and the FCOS criterion's backward
+ * hn_fcos_loss_grad_f32). */
 #define HN_ABI_VERSION 36
 int hn_abi_version(void);
 const char* hn_last_error(void);
@@ -507,7 +508,7 @@ int hn_fcos_ext_gather(const hn_fcos_levels* lv, const float* const* ext, const 
                        int32_t* det_contacts /* [n][cap] */, float* det_dxdymags /* [n][cap][3] */,
                        void* stream);
 
-/* The FCOS criterion, forward only (fcos_utils/fcos.py:523-570 the matching, :44-178 the six terms), on
+/* The FCOS criterion's forward (fcos_utils/fcos.py:523-570 the matching, :44-178 the six terms), on
  * the head tensors of hn_fcos_candidates plus, with the ext heads, ext[l] as hn_fcos_ext_gather takes it (NULL: no ext terms).
  * Ground truth per image, padded to G rows (device memory): gt_boxes ALREADY SCALED to the canvas, gt_info = (contactstate,
  * handside, mag, dx, dy), gt_count clamped to [0, G] by the kernel (a count of 0: all background, zero dxdy targets).
@@ -525,6 +526,20 @@ int hn_fcos_loss_f32(const hn_fcos_levels* lv, const float* const* ext /* or NUL
                      const float* gt_info /* [n][G][5] */, const int32_t* gt_count /* [n] */, int G, float radius,
                      float* terms, int32_t* fg, float* losses, int32_t* matched /* or NULL */, void* ws, int64_t ws_bytes,
                      void* stream);
+
+/* The FCOS criterion's backward at the heads: hn_fcos_loss_f32's arguments, workspace and outputs (terms,
+ * fg, losses and matched get the bytes hn_fcos_loss_f32 gives), then one more launch on the same stream that writes the gradient
+ * of sum_k upstream[k] * losses[k] at cls_lr, reg_ctr and ext into d_cls_lr[l], d_reg_ctr[l] and d_ext[l] (device tensors in the
+ * layouts of the heads; d_ext NULL exactly when ext is, otherwise 16-byte aligned).  upstream: six fp32 weights in DEVICE memory
+ * (read by the kernel, no host read), NULL = ones; without ext upstream[4] and [5] are ignored.  The matching and the divisor
+ * max(1, sum fg) are constants.  Every gradient element is written exactly once, zeros included (no memset, no atomics): the
+ * same bytes on every run.  Every refusal (hn_fcos_loss_f32's, a null gradient level, d_ext without ext) happens before any
+ * launch. */
+int hn_fcos_loss_grad_f32(const hn_fcos_levels* lv, const float* const* ext /* or NULL */, int n, int num_classes,
+                          const float* gt_boxes, const int32_t* gt_labels, const float* gt_info, const int32_t* gt_count, int G,
+                          float radius, float* terms, int32_t* fg, float* losses, int32_t* matched /* or NULL */, void* ws,
+                          int64_t ws_bytes, const float* upstream /* [6] or NULL */, float* const* d_cls_lr,
+                          float* const* d_reg_ctr, float* const* d_ext /* or NULL */, void* stream);
 
 int64_t hn_fcos_nms_scratch_bytes(int n, int cap);
 int hn_fcos_nms(const float* cand_boxes, const float* cand_scores, const int32_t* cand_labels,
