@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void spmm_csr_kernel(const int* __restrict__ i
 
 // One thread = 4 features of one (batch, vertex) row: x2 = 2*(L x1) - x0, then hi/lo fp16 of x0, x1, x2 are
 // written at channels [0,F), [F,2F), [2F,3F) of the row's S32 record (32-channel blocks of hi[32] | lo[32]);
-// threads with f >= F zero the padding channels [3F, Cpad).
+// threads with f >= F zero the padding channels [3F, Cpad).  Range contract: a part that fails |v| <= 65504 is noted.
 __device__ __forceinline__ void store_split4(_Float16* row16, int ch, const f32x4& v) {
   f16x4 hi, lo;
 #pragma unroll
@@ -52,7 +52,7 @@ __device__ __forceinline__ void store_split4(_Float16* row16, int ch, const f32x
 __global__ __launch_bounds__(256) void cheby3_basis_kernel(const int* __restrict__ indptr, const int* __restrict__ indices,
                                                            const float* __restrict__ values, const float* __restrict__ x0,
                                                            const float* __restrict__ x1, _Float16* __restrict__ out16,
-                                                           int B, int V, int F, int Cpad) {
+                                                           int B, int V, int F, int Cpad, int* __restrict__ range_flag) {
   const int F4 = F >> 2, P4 = (Cpad - 3 * F) >> 2;  // real and padding float4 columns per row
   const int W4 = F4 + P4;
   const long total = (long)B * V * W4;
@@ -78,6 +78,12 @@ __global__ __launch_bounds__(256) void cheby3_basis_kernel(const int* __restrict
     f32x4 a2;
 #pragma unroll
     for (int q = 0; q < 4; ++q) a2[q] = 2.f * acc[q] - a0[q];
+    if (range_flag) {   // f16x3 range contract: the three parts are split below (one NaN-propagating maximum, one comparison)
+      float m = 0.f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) m = hn::max_nan(m, hn::max_nan(hn::range_mag(a0[q], a1[q]), fabsf(a2[q])));
+      if (hn::range_bad(m)) *range_flag = 1;
+    }
     store_split4(row16, c * 4, a0);
     store_split4(row16, F + c * 4, a1);
     store_split4(row16, 2 * F + c * 4, a2);
@@ -140,7 +146,7 @@ struct GraphConvParams {
   int rows, V, Fin, Fout, K, Fi, relu, up, out_split;
   int w_frag;              // 1: the filter bank is stored in MFMA fragment order (a wave's load is one contiguous KB)
   int nt_pow2;             // column tiles of ONE workgroup (a power of two <= 4; blockIdx.y = column group); k slices = 16 / nt_pow2
-  int* range_flag;
+  int* range_flag;         // the step's flag words, or null while the check is off: phase 1 notes the basis, the epilogue an S32 output
 };
 
 // One round of the gathers of a basis row: NL neighbours of L from entry le and NQ neighbours of 2 L L - I from entry qe, all
@@ -254,12 +260,14 @@ __global__ __launch_bounds__(kGcWaves * 64) void graph_conv_fused_kernel(const G
       }
     }
     const f32x4* parts[3] = {&a0, &a1, &a2};
+    float mag = 0.f;   // f16x3 range contract: the three parts become MFMA operands as fp16 pairs (rows behind p.rows: zeros)
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
       f16x4 h, l;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const float val = (*parts[t])[q];
+        mag = hn::max_nan(mag, fabsf(val));
         h[q] = (_Float16)val;
         l[q] = (_Float16)(val - (float)h[q]);
       }
@@ -267,6 +275,7 @@ __global__ __launch_bounds__(kGcWaves * 64) void graph_conv_fused_kernel(const G
       *reinterpret_cast<f16x4*>(hi_pl + r * ldk + k) = h;
       *reinterpret_cast<f16x4*>(lo_pl + r * ldk + k) = l;
     }
+    if (hn::range_bad(mag) && p.range_flag) *p.range_flag = 1;
   }
   const int padk = p.K - 3 * p.Fin;      // zero channels behind the basis (K is a multiple of 32)
   for (int i = tid; i < kGcRows * (padk >> 2); i += kGcWaves * 64) {
@@ -368,7 +377,7 @@ extern "C" int hn_graph_conv_cheby3_f16x3(const hn_graph_csr* L, const hn_graph_
   p.x = x; p.w16 = (const _Float16*)w16; p.bias = bias; p.xin = xin; p.y = y;
   p.rows = batch * L->v; p.V = L->v; p.Fin = fin; p.Fout = fout; p.K = (3 * fin + 31) / 32 * 32; p.Fi = fi;
   p.relu = relu ? 1 : 0; p.up = up; p.out_split = out_split ? 1 : 0; p.w_frag = w_frag ? 1 : 0;
-  p.range_flag = out_split ? hn::range_flag_ptr() : nullptr;
+  p.range_flag = hn::range_flag_ptr();   // (phase 1 notes the basis whatever the output type)
   // column tiles per workgroup: at most 4 (a CU pulls its workgroup's share of the filter bank through ONE 64 B/clk vector
   // memory path: the whole 768 x 256 bank per workgroup was 17 of a layer's 25 us; with four column groups every workgroup
   // repeats the basis gather -- 3.5 us, in parallel on other CUs -- and reads a quarter of the bank, its sixteen waves
@@ -393,12 +402,13 @@ extern "C" int hn_graph_conv_cheby3_f16x3(const hn_graph_csr* L, const hn_graph_
 namespace {
 // fp32 rows [rows][f] -> S32 rows of cpad channels (zero padding behind f): the operand of the lifter's first Linear
 __global__ __launch_bounds__(256) void pad_split_rows_kernel(const float* __restrict__ x, _Float16* __restrict__ out16, long rows,
-                                                             int f, int cpad) {
+                                                             int f, int cpad, int* __restrict__ range_flag) {
   const long total = rows * cpad;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int c = (int)(i % cpad);
     const long r = i / cpad;
     const float v = c < f ? x[r * f + c] : 0.f;
+    if (range_flag) hn::range_note(range_flag, v);
     const _Float16 h = (_Float16)v;
     _Float16* o = out16 + r * 2 * cpad + (c >> 5) * 64 + (c & 31);
     o[0] = h;
@@ -712,7 +722,7 @@ extern "C" int hn_pad_split_rows_f32(const float* x, int64_t rows, int f, int cp
   HN_CHECK_ARG(x && out16, "hn_pad_split_rows_f32: null pointer");
   HN_CHECK_ARG(rows > 0 && f > 0 && cpad >= f && cpad % 32 == 0, "bad dims (cpad: a multiple of 32 >= f)");
   hipLaunchKernelGGL(pad_split_rows_kernel, dim3(grid_for(rows * cpad)), dim3(256), 0, (hipStream_t)stream, x, (_Float16*)out16,
-                     (long)rows, f, cpad);
+                     (long)rows, f, cpad, hn::range_flag_ptr());
   HN_CHECK_LAUNCH("pad_split_rows_kernel");
   return HN_OK;
 }
@@ -747,7 +757,7 @@ extern "C" int hn_cheby3_basis_split(const int32_t* indptr, const int32_t* indic
   HN_CHECK_ARG(cpad >= 3 * f && cpad % 32 == 0, "cpad must be a multiple of 32 and >= 3*f");
   const long total = (long)batch * v * ((cpad - 2 * f) / 4);
   hipLaunchKernelGGL(cheby3_basis_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, indptr, indices,
-                     values, x0, x1, (_Float16*)out16, batch, v, f, cpad);
+                     values, x0, x1, (_Float16*)out16, batch, v, f, cpad, hn::range_flag_ptr());
   HN_CHECK_LAUNCH("cheby3_basis_kernel");
   return HN_OK;
 }

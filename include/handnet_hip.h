@@ -70,7 +70,8 @@ int hn_clock_sample(int micros, float* mhz, void* stream);
  * A value that is stored in the split format must be finite and |v| <= 65504 (hi = fp16(v) would be +-inf).
  * While hn_range_check_enable(1) is in force (the engines' default; HN_CHECK_RANGE=0 turns it off for A/B timing) every
  * launch of a split PRODUCER (f16x3 conv epilogue / split-K tail, hn_affine_split_f32, hn_fcos_preprocess_split / _list,
- * hn_stem_image_nhwc4) sets a sticky per-device flag word when it meets such a value:
+ * hn_stem_image_nhwc4, and the lifter's hn_graph_conv_cheby3_f16x3 -- its in-kernel basis and its S32 output --,
+ * hn_cheby3_basis_split and hn_pad_split_rows_f32) sets a sticky per-device flag word when it meets such a value:
  *   HN_RANGE_ACTIVATION        an intermediate activation (results would be inf / NaN or -- ReLU maps NaN to 0 -- silently
  *                              wrong: this model needs the exact f32 mode)
  *   HN_RANGE_INPUT             a finite INPUT value beyond the range (preprocessed RGB; a depth crop: depth is metres)
@@ -797,7 +798,8 @@ int hn_nonfinite_count_f32(const float* x, int64_t count, int32_t* flag, void* s
  *   hn_spmm_csr_f32        y = L x
  *   hn_cheby3_basis_split  x2 = 2 L x1 - x0; out16 = S32 rows [x0 | x1 | x2 | 0-pad] of cpad channels
  *                          (order k-major: channel k*f + i; the reference's (i, k) order is absorbed by
- *                          permuting the Linear's columns at load time, hn_amd/pose2mesh_engine.py)
+ *                          permuting the Linear's columns at load time, hn_amd/pose2mesh_engine.py); range contract:
+ *                          notes HN_RANGE_ACTIVATION for an x0, x1 or x2 value that fails |v| <= 65504
  *   hn_feat_interp_add_f32 out[r*up + u][:] = y[r][:] + interp_linear(xin[r][:], fi -> fo), u < up
  *                          (F.interpolate(mode='linear') along the feature axis + nn.Upsample(2) on vertices)
  * ------------------------------------------------------------------------------------ */
@@ -812,7 +814,9 @@ int hn_spmm_csr_f32(const int32_t* indptr, const int32_t* indices, const float* 
  * [fout][K/32][2][32] over K = pad32(3*fin) k-major channels (as hn_cheby3_basis_split's operand) -- or, with w_frag = 1, the
  * same values in MFMA fragment order [ceil(fout/16)][K/32][2 (hi, lo)][64 lanes][8]: element i of lane l = column 16*nt +
  * (l & 15), channel 32*kt + 8*(l >> 4) + i, zero behind fout (a wave's load is then one contiguous KB); xin fp32 [batch][v][fi]
- * or NULL; y fp32 [batch][v*up][fout], or S32 rows when out_split (fout % 32 == 0).  fout <= 256. */
+ * or NULL; y fp32 [batch][v*up][fout], or S32 rows when out_split (fout % 32 == 0).  fout <= 256.
+ * Range contract: the three basis parts become fp16 pairs inside the kernel, so a value of x, L x or L2 x that fails
+ * |v| <= 65504 is noted (HN_RANGE_ACTIVATION) whatever the output type; with out_split the stored values are noted as well. */
 typedef struct hn_graph_csr {
   const int32_t* indptr;   /* [v + 1] */
   const int32_t* indices;  /* ascending per row */
@@ -825,7 +829,8 @@ int hn_graph_conv_cheby3_f16x3(const hn_graph_csr* L, const hn_graph_csr* L2, co
 /* Glue of the lifter as single launches: fp32 rows [rows][f] -> S32 rows of cpad channels, zero padded (the operand of
  * PoseNet's first Linear from the [batch][2J] joints); pose_combine (pose2mesh_net.py:20) = [pose2d | pose3d / 1000 | 0] per
  * joint as fp32 [batch*J][fpad] (the padded input of the first graph convolution; pose3d rows may be padded: PoseNet's last
- * Linear is run with 64 output columns so that it takes the vectorised / split-K form of the convolution kernel). */
+ * Linear is run with 64 output columns so that it takes the vectorised / split-K form of the convolution kernel).
+ * hn_pad_split_rows_f32 notes HN_RANGE_ACTIVATION for a value of x that fails |v| <= 65504 (the zero padding cannot). */
 int hn_pad_split_rows_f32(const float* x, int64_t rows, int f, int cpad, void* out16, void* stream);
 /* The last lines of the live caller's mesh path (ros_demo.py:162,332-337): out[i][k][:] = ((mesh[i][perm[k]][:] * 1000 +
  * xyz_mm[i][0][:]) / 1000) * (1, -1, -1) -- the real mesh's vertices in original order (perm = graph_perm_reverse[:v], int64
