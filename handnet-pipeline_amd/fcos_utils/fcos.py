@@ -12,8 +12,11 @@ NMS IoU 0.3 (fcos.py:600,635).
 The criterion is an opt-in: after `device_loss()`, `model.train(); model(images, targets)` returns the reference's loss dict
 (fcos.py:523-570 the matching, :44-178 the six terms) computed on the device from the detector's own head tensors, and
 `loss_step` is the same for a validation loop in either mode (hn_amd.ops.fcos_loss).  `head_grads` adds the
-criterion's backward at those head tensors in one more launch (hn_amd.ops.fcos_loss_grad).  There is no
-backward pass through the towers or the backbone and no optimizer; without the opt-in, train mode and targets raise as before.
+criterion's backward at those head tensors in one more launch (hn_amd.ops.fcos_loss_grad), and
+`output_grads` carries it through the output convolutions to the gradients of their weights and biases under the reference's
+parameter names (hn_amd.ops.conv3x3_thin_backward_levels); after a step on those parameters,
+`refresh_outputs()` repacks them into the engine.  There is no backward pass through the towers or the backbone and no optimizer
+on the device; without the opt-in, train mode and targets raise as before.
 """
 from __future__ import annotations
 
@@ -129,21 +132,78 @@ class FCOS(EngineOwner):
         the host and nothing waits."""
         return self._loss_step(images, targets, False, True)
 
+    # the reference's modules behind the engine's output banks, in the banks' row order
+    _OUTPUT_BANKS = (("cls_out", ("head.classification_head.cls_logits", "head.classification_head.hand_lr_layer")),
+                     ("reg_out", ("head.regression_head.bbox_reg", "head.regression_head.bbox_ctrness")),
+                     ("ext_out", ("head.classification_head.hand_dydx_layer", "head.classification_head.hand_contact_state_layer")))
+
+    def _output_banks(self):
+        return [(bank, names) for bank, names in self._OUTPUT_BANKS if self.ext or bank != "ext_out"]
+
+    def output_grads(self, images: List[torch.Tensor], targets, assign: bool = False):
+        """head_grads(images, targets) carried on through the output convolutions (FCOSEngine.output_grads; DESIGN.md section
+        9t) -> (losses, fg, grads): losses and fg are head_grads' bytes; grads maps the reference's parameter names -- .weight
+        [Cout,Cin,3,3] and .bias [Cout] of head.classification_head.cls_logits / hand_lr_layer, head.regression_head.bbox_reg /
+        bbox_ctrness and, with ext, head.classification_head.hand_dydx_layer / hand_contact_state_layer -- to the gradient of
+        the sum of the dict's values, on the device: the engine bank's rows un-concatenated and permuted to the reference's
+        layout.  assign: also set .grad of the module's own parameters, so that torch.optim.SGD over them followed by
+        refresh_outputs() is a fine-tuning step of the output layers (a linear probe on frozen towers).  There is no backward
+        through the towers or the backbone."""
+        dev = self._require_gpu()
+        eng = self.engine()
+        batch = self._batch(images)
+        if torch.is_tensor(batch):
+            oh, ow = eng.geometry(*batch.shape[-2:])[:2]
+        else:
+            oh, ow = zip(*[g[2:] for g in eng.list_geometry(batch)[0]])
+        targets = self._packed_targets(images, batch, targets, oh, ow, dev)
+        losses, fg, _, param_grads, _ = eng.output_grads(batch, targets, radius=self.center_sampling_radius)
+        grads = {}
+        params = dict(self.named_parameters())
+        for bank, names in self._output_banks():
+            d_w, d_b = param_grads[bank]
+            row = 0
+            for name in names:
+                cout = params[name + ".weight"].shape[0]
+                grads[name + ".weight"] = d_w[row:row + cout].permute(0, 3, 1, 2).contiguous()
+                grads[name + ".bias"] = d_b[row:row + cout].clone()
+                row += cout
+        if assign:
+            for key, g in grads.items():
+                params[key].grad = g
+        return losses, fg, grads
+
+    def refresh_outputs(self):
+        """Repack the module's CURRENT values of the output layers' parameters (those output_grads names) into the engine's
+        cls_out / reg_out / ext_out banks, with the f16x3 range check; the engine itself is kept, not rebuilt, and the banks' tensors keep
+        their addresses (the values are copied into them), so a HandNet that shares this engine and its captured graphs run with
+        the new weights from their next step on.  A value beyond
+        the fp16 range raises and leaves the engine's banks as they were."""
+        eng = self.engine()
+        params = dict(self.named_parameters())
+        sd = {name + k: params[name + k] for _, names in self._output_banks() for name in names for k in (".weight", ".bias")}
+        eng.refresh_outputs(sd)
+        return self
+
+    def _packed_targets(self, images, batch, targets, oh, ow, dev):
+        """The reference's list of target dicts, scaled per image like torchvision's transform scales them -> ops.FcosTargets on
+        the canvas's scale (an ops.FcosTargets passes through).  oh, ow: the resized size, one pair for an equal-size batch, one
+        per image for a list of different sizes."""
+        if isinstance(targets, ops.FcosTargets):
+            return targets
+        if len(targets) != len(images):
+            raise ValueError("one target dict per image")
+        new = [(oh, ow)] * len(images) if torch.is_tensor(batch) else list(zip(oh, ow))
+        ratios = ops.fcos_target_ratios([tuple(i.shape[-2:]) for i in images], new)
+        return ops.pack_fcos_targets(targets, ratios, num_classes=self.num_classes, ext=self.ext, device=dev)
+
     def _loss_step(self, images, targets, want_terms, head_grads):
         dev = self._require_gpu()
         eng = self.engine()
         batch = self._batch(images)
         heads = eng.forward_heads if torch.is_tensor(batch) else eng.forward_heads_each
         cls_lr, reg_ctr, strides, (oh, ow, _, _) = heads(batch)
-        if not isinstance(targets, ops.FcosTargets):
-            if len(targets) != len(images):
-                raise ValueError("one target dict per image")
-            if torch.is_tensor(batch):
-                new = [(oh, ow)] * len(images)
-            else:
-                new = list(zip(oh, ow))
-            ratios = ops.fcos_target_ratios([tuple(i.shape[-2:]) for i in images], new)
-            targets = ops.pack_fcos_targets(targets, ratios, num_classes=self.num_classes, ext=self.ext, device=dev)
+        targets = self._packed_targets(images, batch, targets, oh, ow, dev)
         ext = eng._ext_levels if self.ext else None
         grads = None
         with ops.on_device(dev):

@@ -217,6 +217,10 @@ SIGNATURES = {
     "hn_conv3x3_thin_affine_f16x3_levels": (C.c_int, [C.POINTER(ThinLevels), C.POINTER(ThinAffine), C.c_int, C.c_int, C.c_int,
                                                       VP, VP, C.c_int, VP]),
     "hn_conv3x3_thin_uses_flat": (C.c_int, [C.POINTER(ThinLevels), C.c_int, C.c_int, C.c_int]),
+    # the output convolutions' backward: weight, bias and input gradients (new functions under ABI 36)
+    "hn_conv3x3_thin_backward_ws_bytes": (C.c_int64, [C.POINTER(ThinLevels), C.c_int, C.c_int, C.c_int, c_i32p]),
+    "hn_conv3x3_thin_backward_f32": (C.c_int, [C.POINTER(ThinLevels), C.c_int, C.c_int, C.c_int, C.c_int, c_i32p, c_i32p]
+                                     + [C.POINTER(VP)] * 5 + [C.c_int, C.c_int, VP, C.c_int64, VP]),
     "hn_convert_joints_f32": (C.c_int, [VP, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, VP, VP]),
     "hn_convert_joints_samples_f32": (C.c_int, [VP, VP, VP, VP, C.c_int, C.c_int, C.c_float, C.c_float, VP, VP, VP]),
     "hn_a2j_aggregate_convert_f32": (C.c_int, [VP, VP, VP, VP] + [C.c_int] * 5 + [VP, C.c_float, C.c_float, c_f32p,

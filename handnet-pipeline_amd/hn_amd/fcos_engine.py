@@ -135,6 +135,13 @@ class FCOSEngine:
         self.tower_carry = fm["tower_carry"]
         self.tower_carry_force = False
         self.tower_tile = 0   # development / tests: HN_TILE_* id of the tower layers' launches in heads_grouped (0 = the heuristic)
+        # output_grads: a list that receives, per heads() call, the S32 activations that feed the output convolutions
+        # ({"cls": [per level], "reg": [per level]}); None (always, outside that call): nothing is kept
+        self._capture = None
+
+    def _keep(self, kind, a):
+        if self._capture is not None:
+            self._capture[-1][kind].append(a)
 
     # -----------------------------------------------------------------------------------
     def _conv(self, x, cw: ConvW, relu=False, out_f32=False, **kw):
@@ -245,6 +252,7 @@ class FCOSEngine:
         for cw, (g, b) in zip(self.cls_tower, self.cls_gn):
             x, sc, sh = self._conv_gn(self._act(x, sc, sh), cw, g, b, 32, n, fh * fw, key)
         a = self._act(x, sc, sh)
+        self._keep("cls", a)
         cls_lr = self._out_conv(a, self.cls_out)
         ext = self._out_conv(a, self.ext_out, relu_cols=3) if self.ext else None
         return cls_lr, ext
@@ -254,7 +262,9 @@ class FCOSEngine:
         x, sc, sh = t0[..., 256:], sc[:, 256:], sh[:, 256:]
         for cw, (g, b) in zip(self.reg_tower, self.reg_gn):
             x, sc, sh = self._conv_gn(self._act(x, sc, sh), cw, g, b, 32, n, fh * fw, key)
-        return self._out_conv(self._act(x, sc, sh), self.reg_out, relu_cols=4)
+        a = self._act(x, sc, sh)
+        self._keep("reg", a)
+        return self._out_conv(a, self.reg_out, relu_cols=4)
 
     def head_level(self, feat, key=0):
         """One FPN level -> (cls_lr [N,h,w,C+2], reg_ctr [N,h,w,5], ext [N,h,w,8] or None) raw fp32 conv outputs."""
@@ -276,6 +286,8 @@ class FCOSEngine:
             sc, sh = ops.groupnorm_finalize_rows32(part, g2, b2, n, hw, 64)
         a = self._act(t0, sc, sh)
         ac, ar = a[:, :, :, :8], a[:, :, :, 8:]
+        self._keep("cls", ac)
+        self._keep("reg", ar)
         cls_lr = self._out_conv(ac, self.cls_out)
         ext = self._out_conv(ac, self.ext_out, relu_cols=3) if self.ext else None
         reg_ctr = self._out_conv(ar, self.reg_out, relu_cols=4)
@@ -356,7 +368,7 @@ class FCOSEngine:
 
     def _head_outputs(self, t, aff, L):
         ops.PROFILE_STAGE = "head_outputs"
-        if (self.thin_outputs and self.fuse_last_gn and self.terms == 3 and not self.ext
+        if (self.thin_outputs and self.fuse_last_gn and self.terms == 3 and not self.ext and self._capture is None
                 and ops.thin_affine_applies(t, self.cls_out) and ops.thin_affine_applies(t, self.reg_out)):
             # the last GroupNorm apply pass happens on the head-output kernels' fragments (no 8 bytes per element round trip)
             cls_lr = ops.conv3x3_thin_affine_levels(t, aff, 0, self.cls_out)
@@ -365,6 +377,9 @@ class FCOSEngine:
         ops.PROFILE_STAGE = "towers"
         a = ops.to_split_levels(t, aff, relu=True)
         ac, ar = [x[:, :, :, :8] for x in a], [x[:, :, :, 8:] for x in a]
+        for c, r in zip(ac, ar):
+            self._keep("cls", c)
+            self._keep("reg", r)
         ops.PROFILE_STAGE = "head_outputs"
         if self.thin_outputs and self.terms == 3:   # <= 16 output channels: the thin-N kernels (csrc/conv3x3_thin.hip)
             # one launch for the two (ext: three) filter banks where they run the tap kernel (a single frame); else one each
@@ -383,6 +398,8 @@ class FCOSEngine:
         streams so that the tail of one convolution's grid (e.g. 1700 workgroups on 512 slots at the
         stride-16 level) is filled by another chain's workgroups."""
         ops.PROFILE_STAGE = "towers"
+        if self._capture is not None:
+            self._capture.append({"cls": [], "reg": []})
         if (self.head_streams <= 1 and self.group_towers and self.precision == "f16x3" and 2 * len(feats) <= 6
                 and all(f.shape[1] * f.shape[2] >= 32 for f in feats)):
             return self.heads_grouped(feats)
@@ -483,15 +500,96 @@ class FCOSEngine:
         9s) -> (losses, fg, (d_cls_lr, d_reg_ctr, d_ext or None)), all on the device: losses = the reference's dict (0-d fp32
         tensors, four keys without ext) and fg int32 [N] are the bytes ops.fcos_loss gives on the same heads, the gradients are
         per-level lists in the heads' layouts.  images: [N,3,H,W] (the batched forms) or a list of [3,h_i,w_i] images of
-        different sizes (forward_heads_each); targets: an ops.FcosTargets on the canvas's scale.  This is where a backward pass
-        through the towers would start; there is none here."""
+        different sizes (forward_heads_each); targets: an ops.FcosTargets on the canvas's scale.  output_grads carries these
+        gradients on through the output convolutions."""
         heads = self.forward_heads if torch.is_tensor(images) else self.forward_heads_each
         cls_lr, reg_ctr, strides, _ = heads(images)
+        return self._grads_at_heads(cls_lr, reg_ctr, strides, targets, radius, upstream)
+
+    def _grads_at_heads(self, cls_lr, reg_ctr, strides, targets, radius, upstream):
         *grads, res = ops.fcos_loss_grad(cls_lr, reg_ctr, strides, self.num_classes, targets,
                                          ext=self._ext_levels if self.ext else None, radius=radius, upstream=upstream,
                                          want_forward=True)
         keys = ops.FCOS_LOSS_KEYS if self.ext else ops.FCOS_LOSS_KEYS[:4]
         return {k: res.losses[i] for i, k in enumerate(keys)}, res.fg, tuple(grads)
+
+    @ops.device_guarded
+    def output_grads(self, images, targets, radius=1.5, upstream=None, want_inputs=False):
+        """head_grads plus the backward of the output convolutions (ops.conv3x3_thin_backward_levels) on
+        the engine's own tensors -> (losses, fg, head_grads, param_grads, d_towers): the first three are head_grads' bytes;
+        param_grads = {"cls_out": (dW, db), "reg_out": ..., "ext_out": ... with ext} in the engine's layout (dW [Cout,3,3,256]
+        over the concatenated rows of the bank, ONE sum over levels and images); d_towers = per level fp32 [N,h,w,512], the
+        gradient at the ReLU'd activations of the last tower layer, cls half then reg half like the engine's stacked tower
+        tensor (the cls half holds the ext bank's share too).  This is where the GroupNorm / 256 -> 256 backward would start;
+        there is none yet.  For this call the heads keep the S32 activations that feed the output convolutions, and where the
+        last GroupNorm apply is fused into the thin kernel the unfused, bit-identical path runs; inference is untouched.
+        images / targets as head_grads takes them (a list of different sizes: image by image, concatenated per level).
+        want_inputs: also return {"a_cls", "a_reg", "cls_lr", "reg_ctr", "ext"}, what the backward read.  f16x3 engines only;
+        with ext the cls and ext banks must have at most 16 columns together (num_classes <= 6)."""
+        if self.precision != "f16x3" or self.terms != 3:
+            raise RuntimeError("output_grads needs the f16x3 engine (the backward reads the S32 activations)")
+        if self.ext and self.cls_out.cout + self.ext_out.cout > 16:   # (refused here, before the heads run)
+            raise ValueError(f"output_grads: the cls and ext banks have {self.cls_out.cout} + {self.ext_out.cout} output columns, "
+                             "more than the 16 the backward kernel takes on one map (with ext: num_classes <= 6)")
+        batched = torch.is_tensor(images)
+        self._capture = []
+        try:
+            cls_lr, reg_ctr, strides, _ = (self.forward_heads if batched else self.forward_heads_each)(images)
+        finally:
+            cap, self._capture = self._capture, None
+        losses, fg, grads = self._grads_at_heads(cls_lr, reg_ctr, strides, targets, radius, upstream)
+        levels = range(len(cls_lr))
+        # (the image-by-image path: one capture per image, concatenated per level like forward_heads_each does)
+        join = lambda kind, l: cap[0][kind][l] if len(cap) == 1 else torch.cat([c[kind][l] for c in cap])   # noqa: E731
+        a_cls, a_reg = [join("cls", l) for l in levels], [join("reg", l) for l in levels]
+        ext = self._ext_levels if self.ext else None
+        d_towers = [torch.empty(tuple(t.shape[:3]) + (512,), device=t.device, dtype=torch.float32) for t in cls_lr]
+        prev, ops.PROFILE_STAGE = ops.PROFILE_STAGE, "head_outputs"
+        try:
+            cls_members = [(self.cls_out, 0, cls_lr, grads[0])] + ([(self.ext_out, 3, ext, grads[2])] if self.ext else [])
+            pg_cls, _ = ops.conv3x3_thin_backward_levels(a_cls, cls_members, dx_out=d_towers, dx_channel_offset=0)
+            pg_reg, _ = ops.conv3x3_thin_backward_levels(a_reg, [(self.reg_out, 4, reg_ctr, grads[1])], dx_out=d_towers,
+                                                         dx_channel_offset=256)
+        finally:
+            ops.PROFILE_STAGE = prev
+        param_grads = {"cls_out": pg_cls[0], "reg_out": pg_reg[0]}
+        if self.ext:
+            param_grads["ext_out"] = pg_cls[1]
+        out = (losses, fg, grads, param_grads, d_towers)
+        if want_inputs:
+            out += (dict(a_cls=a_cls, a_reg=a_reg, cls_lr=cls_lr, reg_ctr=reg_ctr, ext=ext),)
+        return out
+
+    def refresh_outputs(self, sd):
+        """Repack the output convolutions from the reference-layout values in sd (cls_logits, hand_lr_layer, bbox_reg,
+        bbox_ctrness and, with ext, hand_dydx_layer, hand_contact_state_layer: .weight / .bias) into cls_out / reg_out /
+        ext_out, the way the constructor packs them (pack_conv, concat_cout, split_f16x3 with its range check).  The new values
+        are COPIED INTO the banks' existing tensors (w, bias, w16): every address stays what it was, so whatever holds this
+        engine -- launch plans keyed by weight addresses, a HandNetEngine's captured graphs with the banks' addresses baked in
+        -- reads the new weights from its next launch or replay on.  Every bank is built and checked before any is written: a
+        refusal leaves the engine as it was.  Nothing else is rebuilt."""
+        c, r = "head.classification_head", "head.regression_head"
+
+        def bank(*names):
+            return concat_cout([pack_conv(sd[n + ".weight"].detach().cpu(), sd[n + ".bias"].detach().cpu(), pad=1)
+                                for n in names]).to(self.device)
+
+        cls_out = bank(c + ".cls_logits", c + ".hand_lr_layer")
+        reg_out = bank(r + ".bbox_reg", r + ".bbox_ctrness")
+        ext_out = bank(c + ".hand_dydx_layer", c + ".hand_contact_state_layer") if self.ext else None
+        pairs = [(self.cls_out, cls_out), (self.reg_out, reg_out)] + ([(self.ext_out, ext_out)] if self.ext else [])
+        fields = lambda cw: (cw.w, cw.bias, cw.w16)                      # noqa: E731
+        for old, new in pairs:
+            if any((a is None) != (b is None) or (a is not None and (a.shape != b.shape or a.dtype != b.dtype))
+                   for a, b in zip(fields(old), fields(new))):
+                raise ValueError("refresh_outputs: the values do not have the engine's shapes")
+        # (inference mode: the banks may be inference tensors -- an engine first built under torch.inference_mode() -- and
+        # those take an in-place write only there; ordinary tensors take it too)
+        with torch.inference_mode(), ops.on_device(self.device):
+            for old, new in pairs:
+                for a, b in zip(fields(old), fields(new)):
+                    if a is not None:
+                        a.copy_(b)
 
     @ops.device_guarded
     def detect(self, images, cand=None, det=None, nms_scratch=None):

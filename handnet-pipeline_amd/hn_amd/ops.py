@@ -791,6 +791,83 @@ def conv3x3_thin_affine_levels(ts, affines, ch0, cw, relu_cols=0):
     return outs
 
 
+def conv3x3_thin_backward_levels(a16s, members, *, want_dx=True, dx_out=None, dx_channel_offset=0):
+    """The backward of conv3x3_thin_levels for the one or two filter banks that read one map (hn_conv3x3_thin_backward_f32;
+    DESIGN.md section 9t): a16s = the S32 inputs the forward read [N,h_l,w_l,Cin/32,2,32] (channel slices allowed), members =
+    [(cw, relu_cols, ys, gs), ...] with cw.w [Cout,3,3,Cin] fp32 (Cout <= 16, at most 16 columns together), ys = the forward's
+    own outputs and gs = the upstream gradients, fp32 [N,h_l,w_l,Cout] per level -> ([(dW [Cout,3,3,Cin], db [Cout]), ...],
+    dA levels or None).  The ReLU mask is torch's on the stored result: a gradient passes where column >= relu_cols or y > 0.
+    dW and db are ONE sum over all levels and images.  dA (want_dx) is fp32 [N,h_l,w_l,Cin], the gradient at float(hi) +
+    float(lo), summed over the members; dx_out = per-level fp32 tensors [N,h_l,w_l,C >= dx_channel_offset + Cin] to write
+    channels dx_channel_offset .. + Cin of instead (the other channels are left alone).  Two launches, every element written
+    once, the same bytes on every run; every refusal happens before a launch."""
+    lib = _lib.load()
+    if not 1 <= len(members) <= 2:
+        raise ValueError("conv3x3_thin_backward_levels: one or two members on a map")
+    if not 1 <= len(a16s) <= _lib.HN_FCOS_MAX_LEVELS:
+        raise ValueError(f"conv3x3_thin_backward_levels: 1..{_lib.HN_FCOS_MAX_LEVELS} levels")
+    cin = members[0][0].w.shape[3]
+    n, xstride = _s32_levels(a16s, cin)
+    dev, nl = a16s[0].device, len(a16s)
+    lv = _thin_levels_of(a16s, inputs=True)
+    couts, relus = (C.c_int32 * len(members))(), (C.c_int32 * len(members))()
+    wp, dwp, dbp = ((C.c_void_p * len(members))() for _ in range(3))
+    yp, gp = ((C.c_void_p * (len(members) * nl))() for _ in range(2))
+    results = []
+    for m, (cw, relu_cols, ys, gs) in enumerate(members):
+        cout, r, s_, c = cw.w.shape
+        if (r, s_) != (3, 3) or cout > 16 or c != cin or not 0 <= int(relu_cols) <= cout:
+            raise ValueError("members need fp32 3x3 filter banks with <= 16 output channels, one input channel count and "
+                             "0 <= relu_cols <= Cout")
+        _req(cw.w, name="w")
+        if len(ys) != nl or len(gs) != nl:
+            raise ValueError("members need one output and one gradient per level")
+        for ts, arr in ((ys, yp), (gs, gp)):
+            if _f32_levels(ts, cout) != (n, cout):
+                raise ValueError("outputs and gradients must be dense fp32 [N,h,w,Cout] tensors of the inputs' batch size")
+            for l, (t, a) in enumerate(zip(ts, a16s)):
+                if tuple(t.shape[1:3]) != tuple(a.shape[1:3]) or t.device != dev:
+                    raise ValueError("outputs and gradients must have the inputs' map sizes and device")
+                arr[m * nl + l] = t.data_ptr()
+        dw = torch.empty((cout, 3, 3, cin), device=dev, dtype=torch.float32)
+        db = torch.empty((cout,), device=dev, dtype=torch.float32)
+        couts[m], relus[m], wp[m], dwp[m], dbp[m] = cout, int(relu_cols), cw.w.data_ptr(), dw.data_ptr(), db.data_ptr()
+        results.append((dw, db))
+    das, dxs = 0, None
+    if want_dx:
+        if dx_out is None:
+            if dx_channel_offset:
+                raise ValueError("dx_channel_offset needs dx_out")
+            dxs = [torch.empty(tuple(a.shape[:3]) + (cin,), device=dev, dtype=torch.float32) for a in a16s]
+        else:
+            dxs = list(dx_out)
+            if len(dxs) != nl or any(tuple(t.shape[:3]) != tuple(a.shape[:3]) or t.device != dev for t, a in zip(dxs, a16s)):
+                raise ValueError("dx_out must hold one tensor per level with the inputs' [N,h,w] on their device")
+            width = dxs[0].shape[3]
+            if _f32_levels([_req(t, name="dx_out") for t in dxs], width) != (n, width) \
+                    or not 0 <= int(dx_channel_offset) <= width - cin:
+                raise ValueError("dx_out must be dense fp32 [N,h,w,C] tensors with dx_channel_offset + Cin <= C")
+        das = dxs[0].shape[3]
+        for l, t in enumerate(dxs):
+            lv.y[l] = t.data_ptr()
+    nbytes = lib.hn_conv3x3_thin_backward_ws_bytes(C.byref(lv), n, cin, len(members), couts)
+    if nbytes < 0:
+        check(1, "hn_conv3x3_thin_backward_ws_bytes")
+    ws = _conv_workspace(dev)
+    if nbytes > 4 * ws.numel():
+        ws = torch.empty(((nbytes + 3) // 4,), device=dev, dtype=torch.float32)
+    timer = _profile_start()
+    check(lib.hn_conv3x3_thin_backward_f32(C.byref(lv), n, cin, 0 if xstride == 2 * cin else xstride, len(members), couts, relus,
+                                           wp, yp, gp, dwp, dbp, das, int(dx_channel_offset) if want_dx else 0, ptr(ws), 4 * ws.numel(), _stream()),
+          "hn_conv3x3_thin_backward_f32")
+    if timer is not None:
+        def describe():
+            rows, cols = _rows(a16s), sum(int(c) for c in couts)
+            return ("f32", "thin-bwd"), rows * cols * 9 * cin * (2 if want_dx else 1), (1, rows, 1, cin, cols, 3, 1, 1)
+        _profile_stop(timer, describe)
+    return results, dxs
+
+
 def thin_uses_flat(xs, cw) -> bool:
     """Would conv3x3_thin_levels(xs, cw) run the P-form kernel (True) or the tap kernel (False)?"""
     cout, _, _, cin = cw.w.shape

@@ -398,6 +398,28 @@ int hn_conv3x3_thin_affine_applies(const hn_thin_levels* lv, int n, int cin, int
 int hn_conv3x3_thin_affine_f16x3_levels(const hn_thin_levels* lv, const hn_thin_affine* aff, int n, int cin, int cout,
                                         const void* w16, const float* bias, int relu_cols, void* stream);
 
+/* The BACKWARD of those output convolutions (csrc/conv3x3_thin_bwd.hip), fp32, for the one or two
+ * filter banks ("members") that read one map: lv->x16[l] = the S32 activation the forward read (a = float(hi) + float(lo);
+ * channel slices: in_pix_stride in halfs, 0 = dense), lv->h / w its sizes, lv->y[l] = where the gradient at that activation
+ * goes (fp32, dx_pix_stride floats per pixel, 0 = dense cin; written at channel dx_channel_offset .. + cin) or NULL on EVERY
+ * level for none.  Per member m: couts[m] <= 16 (at most 16 together), relu_cols[m], w[m] = fp32 [cout][3][3][cin] (the
+ * unsplit bank), and per level y[m * count + l] = the forward's own output and g[m * count + l] = the upstream gradient, both
+ * fp32 [n][h_l][w_l][cout_m] dense.  With gm = g where (column >= relu_cols or y > 0), else 0 (torch's ReLU backward on the
+ * stored result):
+ *   dw[m][co][r][s][ci] = sum over levels, images and pixels of gm[y][x][co] * a[y + r - 1][x + s - 1][ci]   (zero padding)
+ *   db[m][co]           = sum of gm[..][co]
+ *   dA_l[y][x][ci]      = sum over members, co, r, s of gm[y - r + 1][x - s + 1][co] * w[m][co][r][s][ci]
+ * Two launches: a sweep (partial sums per workgroup into `ws`) and a fixed-order reduction.  Every output element is written
+ * exactly once, zeros included; no memset, no atomics; the same bytes on every run.  Every refusal (cin % 32, cout > 16, more
+ * than two members or 16 columns on a map, a null level, a workspace below hn_conv3x3_thin_backward_ws_bytes(), which is
+ * host-only and returns -1 for a problem the call refuses) happens before any launch.  Added under ABI 36: new functions only. */
+int64_t hn_conv3x3_thin_backward_ws_bytes(const hn_thin_levels* lv /* count, h[], w[] */, int n, int cin, int members,
+                                          const int32_t* couts);
+int hn_conv3x3_thin_backward_f32(const hn_thin_levels* lv, int n, int cin, int in_pix_stride, int members, const int32_t* couts,
+                                 const int32_t* relu_cols, const float* const* w, const float* const* y, const float* const* g,
+                                 float* const* dw, float* const* db, int dx_pix_stride, int dx_channel_offset, void* ws,
+                                 int64_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Caller-side ingest, fused: what ros_demo.py:227-231,266-269 does on the host before it calls the network --
  *   bgr8 HWC uint8 -> cv2.COLOR_BGR2RGB -> transpose(2,0,1) -> float32 / 255.0        -> rgb    [n][3][h][w]
