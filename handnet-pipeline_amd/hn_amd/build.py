@@ -42,7 +42,9 @@ ARCH = "gfx950"
 # det_ap.hip: the same for the detector evaluation's fp64 overlaps, association distances and file round trip (tests/ap_ref.py).
 # fcos_loss.hip: the same for the criterion's float32 matching (compared bit for bit) and its terms (tests/fcos_loss_ref.py);
 # without the SLP vectoriser too: it packed the box differences into v_pk_add_f32 with op_sel (the build refused it).
+# crop_stage.hip: fcos_post.hip's flags, which its kernels were written under, for the padded box's fp32 steps (tests/crop_ref.py).
 EXTRA_FLAGS = {"fcos_post.hip": ["-ffp-contract=off", "-fno-slp-vectorize"], "graph_ops.hip": ["-fno-slp-vectorize"],
+               "crop_stage.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
                "mesh_raster.hip": ["-ffp-contract=off"], "label_draw.hip": ["-ffp-contract=off"],
                "rig_ops.hip": ["-ffp-contract=off"], "hand_cloud.hip": ["-ffp-contract=off"],
                "hand_object.hip": ["-ffp-contract=off"],

@@ -1610,6 +1610,17 @@ def track_state(n, k, device):
     return torch.zeros((int(n), 1 + check_max_hands(k), TRACK_WORDS), device=device, dtype=torch.int32)
 
 
+def _slot_out(t, name, shape, dtype, device, wrong_size):
+    """An output of the crop stage: a fresh tensor of `shape` when t is None, else t after _req and -- unless wrong_size is
+    None -- the size check (as many elements as `shape`, else ValueError(wrong_size))."""
+    if t is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    _req(t, dtype, name)
+    if wrong_size is not None and t.numel() != math.prod(shape):
+        raise ValueError(wrong_size)
+    return t
+
+
 def crop_resize_hands(det: Detections, hand_label, depth, max_hands, out_size=176, cpad=4, crop_box=None, has_hand=None,
                       score=None, det_index=None, crops=None, reorder_bgr=False, handed=False, left_side=0, side=None,
                       mirror=None, track=None, track_iou=0.3, track_hold=5, track_id=None, track_age=None):
@@ -1636,61 +1647,40 @@ def crop_resize_hands(det: Detections, hand_label, depth, max_hands, out_size=17
         raise ValueError("depth must be [N,1,H,W] or [N,4,H,W]")
     cap = det.scores.shape[1]
     dev = depth.device
-    if crop_box is None:
-        crop_box = torch.empty((n, k, 4), device=dev, dtype=torch.int64)
-    if has_hand is None:
-        has_hand = torch.empty((n, k), device=dev, dtype=torch.int32)
-    if score is None:
-        score = torch.empty((n, k), device=dev, dtype=torch.float32)
-    if det_index is None:
-        det_index = torch.empty((n, k), device=dev, dtype=torch.int32)
-    if crops is None:
-        crops = torch.empty((n * k, out_size, out_size, cpad), device=dev, dtype=torch.float32)
+    i32 = torch.int32
+    crop_box = _slot_out(crop_box, "crop_box", (n, k, 4), torch.int64, dev, "crop_box must hold four values per slot")
+    has_hand = _slot_out(has_hand, "has_hand", (n, k), i32, dev, "has_hand must hold one value per slot")
+    score = _slot_out(score, "score", (n, k), torch.float32, dev, "score must hold one value per slot")
+    det_index = _slot_out(det_index, "det_index", (n, k), i32, dev, "det_index must hold one value per slot")
+    # (the crops' size follows out_size and cpad, which the C entry judges)
+    crops = _slot_out(crops, "crops", (n * k, out_size, out_size, cpad), torch.float32, dev, None)
+    if handed:
+        side = _slot_out(side, "side", (n, k), i32, dev, "side and mirror must hold one value per slot")
+        mirror = _slot_out(mirror, "mirror", (n, k), i32, dev, "side and mirror must hold one value per slot")
+        _req(det.sides, i32, "det.sides")
     if track is not None:
-        _req(track, torch.int32, "track")
+        _req(track, i32, "track")
         if track.numel() != n * (1 + k) * TRACK_WORDS:
             raise ValueError(f"track must be track_state({n}, {k}): int32 [{n},{1 + k},{TRACK_WORDS}]")
-        if handed:
-            if side is None:
-                side = torch.empty((n, k), device=dev, dtype=torch.int32)
-            if mirror is None:
-                mirror = torch.empty((n, k), device=dev, dtype=torch.int32)
-            _req(side, torch.int32, "side"); _req(mirror, torch.int32, "mirror"); _req(det.sides, torch.int32, "det.sides")
-            if side.numel() != n * k or mirror.numel() != n * k:
-                raise ValueError("side and mirror must hold one value per slot")
-        if track_id is None:
-            track_id = torch.empty((n, k), device=dev, dtype=torch.int32)
-        if track_age is None:
-            track_age = torch.empty((n, k), device=dev, dtype=torch.int32)
-        _req(track_id, torch.int32, "track_id"); _req(track_age, torch.int32, "track_age")
-        if track_id.numel() != n * k or track_age.numel() != n * k:
-            raise ValueError("track_id and track_age must hold one value per slot")
-        check(_lib.load().hn_crop_resize_hands_tracked(
-            ptr(det.boxes), ptr(det.scores), ptr(det.labels), ptr(det.sides) if handed else None, ptr(det.count), cap,
-            int(hand_label), int(left_side), k, ptr(depth), n, c, 1 if reorder_bgr else 0, h, w, out_size, cpad, ptr(crop_box),
-            ptr(has_hand), ptr(score), ptr(det_index), ptr(side) if handed else None, ptr(mirror) if handed else None, ptr(crops),
-            ptr(track), thr_milli, hold, ptr(track_id), ptr(track_age), _stream()), "hn_crop_resize_hands_tracked")
-        head = (crop_box, has_hand, score, det_index, crops) + ((side, mirror) if handed else ())
-        return head + (track_id, track_age)
-    if handed:
-        if side is None:
-            side = torch.empty((n, k), device=dev, dtype=torch.int32)
-        if mirror is None:
-            mirror = torch.empty((n, k), device=dev, dtype=torch.int32)
-        _req(side, torch.int32, "side"); _req(mirror, torch.int32, "mirror"); _req(det.sides, torch.int32, "det.sides")
-        if side.numel() != n * k or mirror.numel() != n * k:
-            raise ValueError("side and mirror must hold one value per slot")
-        check(_lib.load().hn_crop_resize_hands_sided(ptr(det.boxes), ptr(det.scores), ptr(det.labels), ptr(det.sides),
-                                                     ptr(det.count), cap, int(hand_label), int(left_side), k, ptr(depth), n, c,
-                                                     1 if reorder_bgr else 0, h, w, out_size, cpad, ptr(crop_box), ptr(has_hand),
-                                                     ptr(score), ptr(det_index), ptr(side), ptr(mirror), ptr(crops), _stream()),
-              "hn_crop_resize_hands_sided")
-        return crop_box, has_hand, score, det_index, crops, side, mirror
-    check(_lib.load().hn_crop_resize_hands(ptr(det.boxes), ptr(det.scores), ptr(det.labels), ptr(det.count), cap,
-                                           int(hand_label), k, ptr(depth), n, c, 1 if reorder_bgr else 0, h, w, out_size, cpad,
-                                           ptr(crop_box), ptr(has_hand), ptr(score), ptr(det_index), ptr(crops), _stream()),
-          "hn_crop_resize_hands")
-    return crop_box, has_hand, score, det_index, crops
+        track_id = _slot_out(track_id, "track_id", (n, k), i32, dev, "track_id and track_age must hold one value per slot")
+        track_age = _slot_out(track_age, "track_age", (n, k), i32, dev, "track_id and track_age must hold one value per slot")
+    dets = (ptr(det.boxes), ptr(det.scores), ptr(det.labels))
+    stage = (k, ptr(depth), n, c, 1 if reorder_bgr else 0, h, w, out_size, cpad, ptr(crop_box), ptr(has_hand), ptr(score),
+             ptr(det_index))
+    sides = (ptr(det.sides), ptr(side), ptr(mirror)) if handed else (None, None, None)
+    if track is not None:
+        name = "hn_crop_resize_hands_tracked"
+        args = dets + (sides[0], ptr(det.count), cap, int(hand_label), int(left_side)) + stage + sides[1:] + (
+            ptr(crops), ptr(track), thr_milli, hold, ptr(track_id), ptr(track_age))
+    elif handed:
+        name = "hn_crop_resize_hands_sided"
+        args = dets + (sides[0], ptr(det.count), cap, int(hand_label), int(left_side)) + stage + sides[1:] + (ptr(crops),)
+    else:
+        name = "hn_crop_resize_hands"
+        args = dets + (ptr(det.count), cap, int(hand_label)) + stage + (ptr(crops),)
+    check(getattr(_lib.load(), name)(*args, _stream()), name)
+    return ((crop_box, has_hand, score, det_index, crops) + ((side, mirror) if handed else ())
+            + ((track_id, track_age) if track is not None else ()))
 
 
 def stem_image_nhwc4(x, border=3, out=None, valid=None):

@@ -2,7 +2,8 @@
 
 Restates handnet_pipeline/handnet_pipeline.py:58-116 without its per-image Python loop
 and its ~10 device->host syncs per frame: box selection, int truncation, 40 % padding,
-clamping and the nearest-neighbour 176x176 gather run in hn_crop_resize; A2J then runs on
+clamping and the nearest-neighbour 176x176 gather run in hn_crop_resize (csrc/crop_stage.hip:
+the one-slot case of the K-hand stage that forward_hands runs); A2J then runs on
 ALL N frames with a validity mask (frames without a hand produce zero rows), so the whole
 step has a static launch sequence and can be captured into a hipGraph.
 """
@@ -376,47 +377,30 @@ class HandNetEngine:
                                                             reorder_bgr=self.a2j.rgbd)
                 box_rows, has_rows = crop_box, has_hand
             else:
-                side = mirror = track_id = track_age = None
+                # (sides, ids and ages go where the caller wants them -- the live step's buffer -- else behind the scores and ranks
+                # of this step's own record)
+                score = det_index = mirror = None
+                side = None if handed is None else handed[1]
+                track_id, track_age = (None, None) if track is None or track[2] is None else track[2]
+                if record is not None:
+                    own_side, own_track = handed is not None and side is None, track is not None and track[2] is None
+                    views = _hands_tail(record[1], rows, handed=own_side, tracked=own_track)
+                    score, det_index = views[:2]
+                    if own_side:
+                        side = views[2]
+                    if own_track:
+                        track_id, track_age = views[-2:]
+                tracking = {} if track is None else dict(track=self._track_state(n, hands), track_iou=track[0] / 1000.0,
+                                                         track_hold=track[1], track_id=track_id, track_age=track_age)
+                res = ops.crop_resize_hands(
+                    det, self.num_classes - 1, depth.float().contiguous(), hands, CROP, 4, score=score, det_index=det_index,
+                    reorder_bgr=self.a2j.rgbd, handed=handed is not None, left_side=0 if handed is None else handed[0], side=side,
+                    **tracking)
+                crop_box, has_hand, score, det_index, crops = res[:5]
+                if handed is not None:
+                    side, mirror = res[5].view(n, hands), res[6].view(n, hands)
                 if track is not None:
-                    # (sides, ids and ages go where the caller wants them -- the live step's buffer -- else behind the scores
-                    # and ranks of this step's own record)
-                    score = det_index = None
-                    side = None if handed is None else handed[1]
-                    track_id, track_age = track[2] if track[2] is not None else (None, None)
-                    if record is not None:
-                        own_side, own_track = handed is not None and side is None, track[2] is None
-                        views = list(_hands_tail(record[1], rows, handed=own_side, tracked=own_track))
-                        score, det_index = views[:2]
-                        if own_side:
-                            side = views[2]
-                        if own_track:
-                            track_id, track_age = views[-2:]
-                    res = ops.crop_resize_hands(
-                        det, self.num_classes - 1, depth.float().contiguous(), hands, CROP, 4, score=score, det_index=det_index,
-                        reorder_bgr=self.a2j.rgbd, handed=handed is not None, left_side=0 if handed is None else handed[0],
-                        side=side, track=self._track_state(n, hands), track_iou=track[0] / 1000.0, track_hold=track[1],
-                        track_id=track_id, track_age=track_age)
-                    crop_box, has_hand, score, det_index, crops = res[:5]
-                    if handed is not None:
-                        side, mirror = res[5].view(n, hands), res[6].view(n, hands)
                     track_id, track_age = res[-2].view(n, hands), res[-1].view(n, hands)
-                elif handed is None:
-                    score, det_index = _hands_tail(record[1], rows) if record is not None else (None, None)
-                    crop_box, has_hand, score, det_index, crops = ops.crop_resize_hands(
-                        det, self.num_classes - 1, depth.float().contiguous(), hands, CROP, 4, score=score, det_index=det_index,
-                        reorder_bgr=self.a2j.rgbd)
-                else:
-                    # (the sides go where the caller wants them -- the live step's buffer -- else behind the scores and ranks
-                    # of this step's own record)
-                    score, det_index, side = None, None, handed[1]
-                    if record is not None:
-                        views = _hands_tail(record[1], rows, handed=side is None)
-                        score, det_index = views[:2]
-                        side = views[2] if side is None else side
-                    crop_box, has_hand, score, det_index, crops, side, mirror = ops.crop_resize_hands(
-                        det, self.num_classes - 1, depth.float().contiguous(), hands, CROP, 4, score=score, det_index=det_index,
-                        reorder_bgr=self.a2j.rgbd, handed=True, left_side=handed[0], side=side)
-                    side, mirror = side.view(n, hands), mirror.view(n, hands)
                 box_rows, has_rows = crop_box.view(rows, 4), has_hand.view(rows)
             conv = self._convert_spec(box_rows, tuple(depth.shape[-2:]), n, hands)
             unconverted = hands is not None and mirror is not None and conv is None

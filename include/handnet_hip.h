@@ -595,6 +595,10 @@ int hn_nms(const float* boxes, const float* scores, int k, double iou_thresh,
  *   crops [n][out][out][cpad] fp32 NHWC with depth in channel 0, other channels 0.
  * depth is [n][in_ch][h][w] fp32, in_ch = 1 (depth) or 4 (RGB-D; reorder_bgr = 1 applies the
  * reference's channel permutation [2,1,0,3], handnet_pipeline.py:102); crops channel c = image channel.
+ * This is hn_crop_resize_hands with max_hands = 1, by construction: the same two launches, without score and det_index.
+ * crops must be 16-byte aligned (else HN_ERR_ARG): it is written as 16-byte vectors, like the crops of the entries below.
+ * (Until this was checked, a misaligned crops pointer was a misaligned vector store.)  crop_box needs no more than an
+ * int64_t array's own 8 bytes.
  * ------------------------------------------------------------------------------------ */
 int hn_crop_resize(const float* det_boxes, const int32_t* det_labels, const int32_t* det_count,
                    int cap, int hand_label, const float* depth, int n, int in_ch, int reorder_bgr,

@@ -1,6 +1,6 @@
 """The rules of the glue between the detector and the pose network, in numpy, with no torch and no GPU: the padded crop box
-(crop_box_kernel, pad_hand_box), the slot walk (hand_slots_kernel), the nearest-resize gather (crop_gather_kernel,
-hand_crop_gather_kernel), the joint conversion (convert_one) and the lifter's standardisation (joints2d_standardize_kernel,
+(pad_hand_box), the slot walk (hand_slots_kernel; the top-1 crop is its one-slot case), the nearest-resize gather
+(hand_crop_gather_kernel; all three in csrc/crop_stage.hip), the joint conversion (convert_one) and the lifter's standardisation (joints2d_standardize_kernel,
 lifter_input_gated_kernel).  Integers, crops and the fp32 conversion are stated operation for operation, so a kernel is compared
 with them bit for bit; the two float64 references (convert64, standardize64) come with a worst-case bound that is derived here
 from the operations and not from anything a kernel returned.

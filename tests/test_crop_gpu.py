@@ -1,4 +1,5 @@
-"""crop_box_kernel, hand_slots_kernel<SIDED>, crop_gather_kernel and hand_crop_gather_kernel<SIDED> (csrc/fcos_post.hip),
+"""hand_slots_kernel<SIDED> and hand_crop_gather_kernel<SIDED> behind every entry of the crop stage, the top-1 entry as their
+one-slot case (csrc/crop_stage.hip),
 convert_one in its three callers and the lifter's standardisation (csrc/a2j_ops.hip) against the rules of tests/crop_ref.py on the
 cases of tests/crop_cases.py.  Boxes, flags, indices, crops and the fp32 conversion are compared bit for bit, no case excluded;
 the only tolerances are crop_ref's two derived bounds (conversion and standardisation against float64), whose worst ratios are
@@ -164,6 +165,67 @@ def test_box_sweep_top1_and_one_slot():
     torch.cuda.synchronize()
     assert cr.same_bits(box.cpu().numpy(), want["crop_box"][:, 0]) and cr.same_bits(has.cpu().numpy(), want["has_hand"][:, 0])
     assert cr.same_bits(top.cpu().numpy(), crops)
+
+
+CANARY = 0x5A5A5A5A
+
+
+@functools.cache
+def _three_frames():
+    """the top-1 entry's three answers on the sweep's frame at out = 4: frame 0 a hand behind a row of another label, frame 1
+    none below its count, frame 2 a first hand whose padded slice is empty (the hand behind it must not take the slot) ->
+    (tables, depth [3, 1, h, w], the rule's one slot per frame, its crops)"""
+    h, w = cc.SWEEP_H, cc.SWEEP_W
+    boxes = np.array([[(1.0, 2.0, 9.0, 8.0), (10.5, 5.25, 30.75, 20.5), (0.0, 0.0, 5.0, 5.0)],
+                      [(3.0, 3.0, 12.0, 12.0), (4.0, 4.0, 20.0, 20.0), (10.5, 5.25, 30.75, 20.5)],
+                      [cc.OUTSIDE["below"], (10.5, 5.25, 30.75, 20.5), (1.0, 1.0, 6.0, 6.0)]], F)
+    labels = np.array([[1, cc.HAND, cc.HAND], [1, 1, cc.HAND], [cc.HAND, cc.HAND, 1]], np.int32)
+    tables = (boxes, labels, _pack(boxes.reshape(-1, 4), 3)[2], np.zeros((3, 3), np.int32), np.array([3, 2, 3], np.int32))
+    depth = cc.position_depth(1, h, w, n=3)
+    want = _want_slots(*tables, 1, w, h, False)
+    assert want["has_hand"][:, 0].tolist() == [1, 0, 0] and want["det_index"][:, 0].tolist() == [1, -1, -1]
+    return tables, depth, want, _want_crops(depth, want, 4, 4, False)
+
+
+def test_top1_entry_takes_a_crop_box_that_is_only_8_byte_aligned():
+    """hn_crop_resize writes the C caller's own int64 array: crop_box at an address that is 8 mod 16 inside a canary-filled buffer.
+    Boxes, flags and crops are the rule's, and no word around them is written."""
+    from hn_amd import ops
+    tables, depth, want, crops = _three_frames()
+    det, n, (h, w) = _det(*tables), 3, depth.shape[2:]
+    spans = dict(crop_box=(6, 6 + n * 8), has_hand=(32, 32 + n), crops=(40, 40 + n * 4 * 4 * 4))      # int32 words
+    buf = torch.full((spans["crops"][1] + 4,), CANARY, dtype=torch.int32, device="cuda")
+    cut = {name: buf[a:b] for name, (a, b) in spans.items()}
+    box, has, out = cut["crop_box"].view(torch.int64).view(n, 4), cut["has_hand"], cut["crops"].view(torch.float32).view(n, 4, 4, 4)
+    assert box.data_ptr() % 16 == 8 and out.data_ptr() % 16 == 0
+    p = ops.ptr
+    ops.check(ops._lib.load().hn_crop_resize(p(det.boxes), p(det.labels), p(det.count), 3, cc.HAND, p(_gpu(depth)), n, 1, 0, h, w,
+                                             4, 4, p(box), p(has), p(out), ops._stream()), "hn_crop_resize")
+    torch.cuda.synchronize()
+    outside = torch.ones(buf.shape, dtype=torch.bool)
+    for a, b in spans.values():
+        outside[a:b] = False
+    assert bool((buf.cpu()[outside] == CANARY).all()), "a word outside the outputs was written"
+    assert cr.same_bits(box.cpu().numpy(), want["crop_box"][:, 0]) and cr.same_bits(has.cpu().numpy(), want["has_hand"][:, 0])
+    assert cr.same_bits(out.cpu().numpy(), crops)
+
+
+def test_top1_entry_is_the_one_slot_entry():
+    """the same three frames through hn_crop_resize_hands(max_hands = 1) and through hn_crop_resize: the rule's boxes, flags and
+    crops from both, byte for byte; the scores and ranks, which only the first hands out, are the rule's too"""
+    from hn_amd import ops
+    tables, depth, want, crops = _three_frames()
+    det = _det(*tables)
+    one = _hands(det, _gpu(depth), 1, 4)
+    _same(one, want, FIELDS)
+    assert cr.same_bits(one["crops"], crops)
+    o = _outputs(3, 1, 4, 4, False)
+    box, has, top = ops.crop_resize(det, cc.HAND, _gpu(depth), 4, 4, crop_box=o["crop_box"].view(3, 4), has_hand=o["has_hand"].view(3),
+                                    crops=o["crops"])
+    torch.cuda.synchronize()
+    assert box.cpu().numpy().tobytes() == one["crop_box"].tobytes() and has.cpu().numpy().tobytes() == one["has_hand"].tobytes()
+    assert top.cpu().numpy().tobytes() == one["crops"].tobytes()
+    _keep_their_fill({f: o[f] for f in ("score", "det_index")})        # (the top-1 entry has no such outputs)
 
 
 # --------------------------------------------------------------------------------------------------------------------------

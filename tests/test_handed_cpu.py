@@ -180,7 +180,7 @@ def test_resource_report_shows_no_spill_and_no_scratch():
     from hn_amd import _lib, build
     _lib.load()
     want = {"ingest.resources.txt": {"ingest_kernel": 4, "flip_w_kernel": 2},
-            "fcos_post.resources.txt": {"hand_slots_kernel": 2, "hand_crop_gather_kernel": 2},
+            "crop_stage.resources.txt": {"hand_slots_kernel": 2, "hand_crop_gather_kernel": 2},
             "a2j_ops.resources.txt": {"a2j_aggregate_kernel": 1, "lifter_input_gated_kernel": 1},
             "graph_ops.resources.txt": {"mesh_finish_kernel": 1}}
     for name, kernels in want.items():
@@ -191,5 +191,5 @@ def test_resource_report_shows_no_spill_and_no_scratch():
             for r in mine:
                 assert " scratch 0 " in r and "vgpr_spill 0" in r and "sgpr_spill 0" in r, r
     # results compared bit for bit: contraction off for the crop stage's file, and inside mesh_finish_kernel
-    assert "-ffp-contract=off" in build.EXTRA_FLAGS["fcos_post.hip"]
+    assert "-ffp-contract=off" in build.EXTRA_FLAGS["crop_stage.hip"]
     assert "fp contract(off)" in (build.CSRC / "graph_ops.hip").read_text().split("void mesh_finish_kernel")[1].split("}")[0]

@@ -20,6 +20,26 @@ def test_crop_resize_hands_refuses_out_of_range_counts(k):
     assert st == 1 and b"max_hands must be 1..16" in lib.hn_last_error()
 
 
+def test_top1_entry_wants_aligned_crops_and_takes_an_8_byte_aligned_box():
+    """hn_crop_resize stores the crops as 16-byte vectors, like its siblings, and refuses a pointer that would split one; its
+    crop_box is the C caller's own int64 array and needs no more than that.  No launch is reached: the entry checks the
+    addresses before the channel count, so the refusal of five channels tells that the addresses before it were accepted."""
+    from hn_amd import _lib
+    lib = _lib.load()
+    fake = 1 << 20
+
+    def call(crop_box=fake, crops=fake, in_ch=5):
+        return lib.hn_crop_resize(fake, fake, fake, 8, 2, fake, 1, in_ch, 0, 480, 640, 176, 4, crop_box, fake, crops, None)
+    assert call(crops=fake + 8) == 1 and b"16-byte aligned" in lib.hn_last_error()
+    assert call(crops=fake + 4) == 1 and b"16-byte aligned" in lib.hn_last_error()
+    assert call(crop_box=fake + 8) == 1 and b"depth image must have 1..4 channels" in lib.hn_last_error()
+    assert call() == 1 and b"depth image must have 1..4 channels" in lib.hn_last_error()
+    # its siblings still want both at 16 bytes
+    st = lib.hn_crop_resize_hands(fake, fake, fake, fake, 8, 2, 1, fake, 1, 5, 0, 480, 640, 176, 4, fake + 8, fake, fake, fake, fake,
+                                  None)
+    assert st == 1 and b"16-byte aligned" in lib.hn_last_error()
+
+
 @pytest.mark.parametrize("k", [0, 17, 2.5, "2", None])
 def test_python_layers_refuse_out_of_range_counts(k):
     from hn_amd import ops

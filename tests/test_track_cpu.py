@@ -305,9 +305,40 @@ def test_resource_report_shows_no_spill_and_no_scratch():
     """The tracked slot kernel runs from registers, like the plain one: no scratch, no VGPR or SGPR spill, both instantiations."""
     from hn_amd import _lib, build
     _lib.load()
-    rows = (build.CSRC / "build" / "fcos_post.resources.txt").read_text().strip().splitlines()
+    rows = (build.CSRC / "build" / "crop_stage.resources.txt").read_text().strip().splitlines()
     for kernel in ("hand_slots_tracked_kernel", "hand_slots_kernel"):
         mine = [r for r in rows if kernel in r.split(":")[0]]
         assert len(mine) == 2, (kernel, len(mine))
         for r in mine:
             assert " scratch 0 " in r and "vgpr_spill 0" in r and "sgpr_spill 0" in r, r
+
+
+def test_crop_stage_kernels_live_in_one_file_once():
+    """crop_stage.hip holds the stage's three kernels, two instantiations each, all from registers -- and no kernel of the
+    top-1 copies they replaced; fcos_post.hip holds none of the five."""
+    from hn_amd import _lib, build
+    _lib.load()
+    names = lambda f: [r.split(":")[0] for r in (build.CSRC / "build" / f).read_text().strip().splitlines()]
+    rows = (build.CSRC / "build" / "crop_stage.resources.txt").read_text().strip().splitlines()
+    assert len(rows) == 6
+    for kernel in ("hand_slots_kernel", "hand_slots_tracked_kernel", "hand_crop_gather_kernel"):
+        mine = [r for r in rows if kernel in r.split(":")[0]]
+        assert len(mine) == 2, (kernel, len(mine))
+        for r in mine:
+            assert " scratch 0 " in r and "vgpr_spill 0" in r and "sgpr_spill 0" in r, r
+    gone = ("15crop_box_kernel", "18crop_gather_kernel")      # (mangled with their lengths: the second ends the gather's name)
+    assert not [n for n in names("crop_stage.resources.txt") if any(g in n for g in gone)]
+    assert not [n for n in names("fcos_post.resources.txt")
+                if any(k in n for k in gone + ("hand_slots_kernel", "hand_slots_tracked_kernel", "hand_crop_gather_kernel"))]
+    assert build.EXTRA_FLAGS["crop_stage.hip"] == build.EXTRA_FLAGS["fcos_post.hip"] == ["-ffp-contract=off", "-fno-slp-vectorize"]
+
+
+def test_abi_and_bindings_are_unchanged():
+    """The move changes no entry point: ABI 36 and the 136 bound signatures, every one of them exported by the built library."""
+    from hn_amd import _lib
+    lib = _lib.load()
+    assert lib.hn_abi_version() == 36 == _lib.ABI_VERSION
+    assert len(_lib.SIGNATURES) == 136
+    for name in ("hn_crop_resize", "hn_crop_resize_hands", "hn_crop_resize_hands_sided", "hn_crop_resize_hands_tracked",
+                 "hn_track_state_bytes"):
+        assert name in _lib.SIGNATURES and getattr(lib, name) is not None
