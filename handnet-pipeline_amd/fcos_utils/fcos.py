@@ -15,8 +15,10 @@ The criterion is an opt-in: after `device_loss()`, `model.train(); model(images,
 criterion's backward at those head tensors in one more launch (hn_amd.ops.fcos_loss_grad), and
 `output_grads` carries it through the output convolutions to the gradients of their weights and biases under the reference's
 parameter names (hn_amd.ops.conv3x3_thin_backward_levels); after a step on those parameters,
-`refresh_outputs()` repacks them into the engine.  There is no backward pass through the towers or the backbone and no optimizer
-on the device; without the opt-in, train mode and targets raise as before.
+`refresh_outputs()` repacks them into the engine.  `tower_grads` carries the backward on through the four tower layers (GroupNorm
+and 256 -> 256 convolution gradients), so that every parameter of the head has a gradient, and
+`refresh_towers()` is `refresh_outputs()` for them.  There is no backward pass through the FPN or the backbone and no optimizer on
+the device; without the opt-in, train mode and targets raise as before.
 """
 from __future__ import annotations
 
@@ -158,6 +160,10 @@ class FCOS(EngineOwner):
             oh, ow = zip(*[g[2:] for g in eng.list_geometry(batch)[0]])
         targets = self._packed_targets(images, batch, targets, oh, ow, dev)
         losses, fg, _, param_grads, _ = eng.output_grads(batch, targets, radius=self.center_sampling_radius)
+        return losses, fg, self._named_grads(self._named_output_grads(param_grads), assign)
+
+    def _named_output_grads(self, param_grads):
+        """the engine's output banks' (dW, db) -> the reference's names and layouts: rows un-concatenated, [Cout,Cin,3,3]"""
         grads = {}
         params = dict(self.named_parameters())
         for bank, names in self._output_banks():
@@ -168,10 +174,56 @@ class FCOS(EngineOwner):
                 grads[name + ".weight"] = d_w[row:row + cout].permute(0, 3, 1, 2).contiguous()
                 grads[name + ".bias"] = d_b[row:row + cout].clone()
                 row += cout
+        return grads
+
+    def _named_grads(self, grads, assign):
         if assign:
+            params = dict(self.named_parameters())
             for key, g in grads.items():
                 params[key].grad = g
-        return losses, fg, grads
+        return grads
+
+    _TOWERS = (("head.classification_head", "cls_tower", "cls_gn", 0), ("head.regression_head", "reg_tower", "reg_gn", 1))
+
+    def tower_grads(self, images: List[torch.Tensor], targets, assign: bool = False):
+        """output_grads(images, targets) carried on through the towers (FCOSEngine.tower_grads) ->
+        (losses, fg, grads): grads holds output_grads' entries and, under head.classification_head and head.regression_head,
+        conv.{0,3,6,9}.weight [256,256,3,3] / .bias [256] (the tower convolutions) and conv.{1,4,7,10}.weight / .bias [256] (their
+        GroupNorms): the engine's gradients permuted to the reference's layout, the stacked layer 0 (one 256 -> 512 bank, one
+        512-channel GroupNorm) un-concatenated into the two towers' halves.  With it every parameter of the head has a gradient.
+        assign: also set .grad of the module's own parameters, so that an optimizer step over the head followed by
+        refresh_towers() and refresh_outputs() is a fine-tuning step on a frozen backbone.  There is no backward through the FPN
+        or the backbone."""
+        dev = self._require_gpu()
+        eng = self.engine()
+        batch = self._batch(images)
+        if torch.is_tensor(batch):
+            oh, ow = eng.geometry(*batch.shape[-2:])[:2]
+        else:
+            oh, ow = zip(*[g[2:] for g in eng.list_geometry(batch)[0]])
+        targets = self._packed_targets(images, batch, targets, oh, ow, dev)
+        losses, fg, _, param_grads, _, tg, _ = eng.tower_grads(batch, targets, radius=self.center_sampling_radius)
+        grads = self._named_output_grads(param_grads)
+        for head, tower, gn, h in self._TOWERS:
+            rows = slice(256 * h, 256 * (h + 1))
+            convs = [(tg["tower0"][0][rows], tg["tower0"][1][rows])] + list(tg[tower])
+            norms = [(tg["gn0"][0][rows], tg["gn0"][1][rows])] + list(tg[gn])
+            for i, ((d_w, d_b), (d_gamma, d_beta)) in enumerate(zip(convs, norms)):
+                grads[f"{head}.conv.{3 * i}.weight"] = d_w.permute(0, 3, 1, 2).contiguous()
+                grads[f"{head}.conv.{3 * i}.bias"] = d_b.clone()
+                grads[f"{head}.conv.{3 * i + 1}.weight"] = d_gamma.clone()
+                grads[f"{head}.conv.{3 * i + 1}.bias"] = d_beta.clone()
+        return losses, fg, self._named_grads(grads, assign)
+
+    def refresh_towers(self):
+        """Repack the module's CURRENT values of the towers' parameters (the convolutions and GroupNorms tower_grads names) into
+        the engine's tower banks and GroupNorm tensors, with the f16x3 range check; like refresh_outputs() the engine is kept and
+        its tensors keep their addresses.  A value beyond the fp16 range raises and leaves the engine as it was."""
+        params = dict(self.named_parameters())
+        sd = {f"{head}.conv.{j}.{k}": params[f"{head}.conv.{j}.{k}"] for head, _, _, _ in self._TOWERS
+              for i in range(4) for j in (3 * i, 3 * i + 1) for k in ("weight", "bias")}
+        self.engine().refresh_towers(sd)
+        return self
 
     def refresh_outputs(self):
         """Repack the module's CURRENT values of the output layers' parameters (those output_grads names) into the engine's

@@ -283,6 +283,29 @@ SIGNATURES = {
                                  + [C.c_float, C.c_double] + [VP] * 4 + [C.c_int, VP]),
 }
 
+
+
+class GnBwdLevels(C.Structure):  # == struct hn_gn_bwd_levels (include/handnet_hip_train.h)
+    _fields_ = [("count", C.c_int32), ("h", C.c_int32 * HN_FCOS_MAX_LEVELS), ("w", C.c_int32 * HN_FCOS_MAX_LEVELS)] + \
+        [(k, C.c_void_p * HN_FCOS_MAX_LEVELS) for k in ("y", "g", "scale", "shift", "mean", "rstd", "dy")]
+
+
+class WgradLevels(C.Structure):  # == struct hn_wgrad_levels (include/handnet_hip_train.h)
+    _fields_ = [("count", C.c_int32), ("h", C.c_int32 * HN_FCOS_MAX_LEVELS), ("w", C.c_int32 * HN_FCOS_MAX_LEVELS),
+                ("a16", C.c_void_p * HN_FCOS_MAX_LEVELS), ("dy", C.c_void_p * HN_FCOS_MAX_LEVELS)]
+
+
+# the entry points of include/handnet_hip_train.h (the tower layers' backward): a table of their own, bound by the same loop;
+# tests/test_tower_bwd_cpu.py keeps it in step with that header
+TRAIN_SIGNATURES = {
+    "hn_groupnorm_relu_backward_ws_bytes": (C.c_int64, [C.POINTER(GnBwdLevels), C.c_int, C.c_int, C.c_int]),
+    "hn_groupnorm_stats_levels_f32": (C.c_int, [C.POINTER(GnBwdLevels), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, VP,
+                                                C.c_int64, VP]),
+    "hn_groupnorm_relu_backward_f32": (C.c_int, [C.POINTER(GnBwdLevels)] + [C.c_int] * 7 + [VP, VP, VP, VP, C.c_int64, VP]),
+    "hn_conv3x3_wgrad_ws_bytes": (C.c_int64, [C.POINTER(WgradLevels), C.c_int, C.c_int, C.c_int]),
+    "hn_conv3x3_wgrad_f32": (C.c_int, [C.POINTER(WgradLevels)] + [C.c_int] * 5 + [VP, VP, VP, C.c_int64, VP]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -306,7 +329,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
                 raise RuntimeError(f"{path} is missing; run `python __graft_entry__.py build`")
             _build.build_library()
         lib = C.CDLL(str(path))
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()):
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:

@@ -138,10 +138,18 @@ class FCOSEngine:
         # output_grads: a list that receives, per heads() call, the S32 activations that feed the output convolutions
         # ({"cls": [per level], "reg": [per level]}); None (always, outside that call): nothing is kept
         self._capture = None
+        # tower_grads: under _capture, heads_grouped also keeps every tower layer's S32 inputs, raw outputs and GroupNorm tables
+        # (and runs the lock-step schedule, whose tensors are the carried schedule's bit for bit)
+        self._capture_towers = False
+        self._tower_cap = None
 
     def _keep(self, kind, a):
         if self._capture is not None:
             self._capture[-1][kind].append(a)
+
+    def _keep_layer(self, a, y, aff):
+        if self._capture is not None and self._capture_towers:
+            self._capture[-1]["layers"].append({"a": list(a), "y": list(y), "aff": list(aff)})
 
     # -----------------------------------------------------------------------------------
     def _conv(self, x, cw: ConvW, relu=False, out_f32=False, **kw):
@@ -311,7 +319,8 @@ class FCOSEngine:
         # GroupNorm finalize and the affine + ReLU + split pass: ONE launch each over the levels (the library falls back
         # to per-level launches of the apply pass for tensors beyond the caches, where streaming stores win)
         aff = ops.groupnorm_finalize_rows32_levels(parts, self.gn0_gamma, self.gn0_beta, n, hw, 64)
-        if self.tower_carry and (self.tower_carry_force or ops.split_levels_stream(n, hw, 512)):
+        self._keep_layer(feats, t, aff)
+        if self.tower_carry and not self._capture_towers and (self.tower_carry_force or ops.split_levels_stream(n, hw, 512)):
             t, aff = self._towers_carried(t, aff, parts, new_t, n, hw)
             if t is not None:
                 return self._head_outputs(t, aff, L)
@@ -324,6 +333,7 @@ class FCOSEngine:
                                     gn=[(parts[l], 0) for l in range(L)] + [(parts[l], 32) for l in range(L)], gn_units=64,
                                     tile=self.tower_tile)
             aff = ops.groupnorm_finalize_rows32_levels(parts, g2, b2, n, hw, 64)
+            self._keep_layer(a, t, aff)
         return self._head_outputs(t, aff, L)
 
     def _towers_carried(self, t, aff, parts, new_t, n, hw):
@@ -399,7 +409,7 @@ class FCOSEngine:
         stride-16 level) is filled by another chain's workgroups."""
         ops.PROFILE_STAGE = "towers"
         if self._capture is not None:
-            self._capture.append({"cls": [], "reg": []})
+            self._capture.append({"cls": [], "reg": [], "layers": []})
         if (self.head_streams <= 1 and self.group_towers and self.precision == "f16x3" and 2 * len(feats) <= 6
                 and all(f.shape[1] * f.shape[2] >= 32 for f in feats)):
             return self.heads_grouped(feats)
@@ -520,8 +530,7 @@ class FCOSEngine:
         param_grads = {"cls_out": (dW, db), "reg_out": ..., "ext_out": ... with ext} in the engine's layout (dW [Cout,3,3,256]
         over the concatenated rows of the bank, ONE sum over levels and images); d_towers = per level fp32 [N,h,w,512], the
         gradient at the ReLU'd activations of the last tower layer, cls half then reg half like the engine's stacked tower
-        tensor (the cls half holds the ext bank's share too).  This is where the GroupNorm / 256 -> 256 backward would start;
-        there is none yet.  For this call the heads keep the S32 activations that feed the output convolutions, and where the
+        tensor (the cls half holds the ext bank's share too).  tower_grads carries it on through the towers.  For this call the heads keep the S32 activations that feed the output convolutions, and where the
         last GroupNorm apply is fused into the thin kernel the unfused, bit-identical path runs; inference is untouched.
         images / targets as head_grads takes them (a list of different sizes: image by image, concatenated per level).
         want_inputs: also return {"a_cls", "a_reg", "cls_lr", "reg_ctr", "ext"}, what the backward read.  f16x3 engines only;
@@ -537,6 +546,8 @@ class FCOSEngine:
             cls_lr, reg_ctr, strides, _ = (self.forward_heads if batched else self.forward_heads_each)(images)
         finally:
             cap, self._capture = self._capture, None
+        if self._capture_towers:
+            self._tower_cap = cap
         losses, fg, grads = self._grads_at_heads(cls_lr, reg_ctr, strides, targets, radius, upstream)
         levels = range(len(cls_lr))
         # (the image-by-image path: one capture per image, concatenated per level like forward_heads_each does)
@@ -590,6 +601,116 @@ class FCOSEngine:
                 for a, b in zip(fields(old), fields(new)):
                     if a is not None:
                         a.copy_(b)
+
+    def _tower_route_check(self, images):
+        """tower_grads' refusals, before the heads run: the backward walks the tensors of the grouped lock-step route only"""
+        if self.precision != "f16x3" or self.terms != 3:
+            raise RuntimeError("tower_grads needs the f16x3 engine with three terms (the backward reads the S32 activations)")
+        if self.head_streams > 1 or not self.group_towers:
+            raise RuntimeError("tower_grads needs the grouped tower route (head_streams <= 1, group_convs on)")
+        if torch.is_tensor(images):
+            if images.dim() != 4 or images.shape[1] != 3:
+                raise ValueError("expected [N,3,H,W]")
+            _, _, ph, pw = self.geometry(*images.shape[-2:])
+        else:
+            _, ph, pw = self.list_geometry(images)
+        if (ph // 32) * (pw // 32) < 32:
+            raise ValueError(f"tower_grads: the coarsest level of a {ph} x {pw} canvas has fewer than 32 pixels, where the heads "
+                             "leave the grouped route")
+
+    @ops.device_guarded
+    def tower_grads(self, images, targets, radius=1.5, upstream=None, want_inputs=False):
+        """output_grads carried on through the four tower layers (conv3x3 -> GroupNorm -> ReLU, twice: cls and reg) down to the
+        FPN outputs -> output_grads' five results, then tower_param_grads and d_feats:
+        tower_param_grads = {"tower0": (dW [512,3,3,256], db [512]), "cls_tower" / "reg_tower": [(dW [256,3,3,256], db [256])] x 3,
+        "gn0": (d_gamma [512], d_beta [512]), "cls_gn" / "reg_gn": [(d_gamma [256], d_beta [256])] x 3} in the engine's layouts,
+        every one ONE sum over levels and images; d_feats = per level fp32 [N,h,w,256], the gradient at the FPN outputs.
+        Per layer, from the last to the first: the statistics of the layer's raw output (ops.groupnorm_stats_levels), one
+        GroupNorm + ReLU backward over the stacked 512 channels / 64 groups (ops.groupnorm_relu_backward_levels), then per filter
+        bank the weight gradient on the f32 MFMA (ops.conv3x3_wgrad_levels) and the input gradient as a forward convolution with
+        the flipped, transposed bank (ops.conv3x3_dgrad_levels) into that bank's half of the next gradient.  For this call the
+        heads keep every layer's S32 inputs, raw outputs and tables and run the lock-step schedule; inference is untouched.
+        Only the grouped route is supported (f16x3, three terms, head_streams <= 1, grouped towers, every level >= 32 pixels):
+        anything else is refused before the heads run.  images / targets as output_grads takes them.  want_inputs: also return
+        what the backward read and wrote, output_grads' dict plus "feats" and "layers" = per layer {"a", "y", "aff", "stats",
+        "g", "dy"}."""
+        self._tower_route_check(images)
+        self._capture_towers = True
+        try:
+            losses, fg, grads, param_grads, d_towers, inp = self.output_grads(images, targets, radius, upstream, want_inputs=True)
+        finally:
+            cap, self._tower_cap, self._capture_towers = self._tower_cap, None, False
+        if not cap or any(len(c["layers"]) != 4 for c in cap):
+            raise RuntimeError("tower_grads: the heads did not take the grouped route")
+        nl = len(d_towers)
+        if len(cap) == 1:
+            layers = cap[0]["layers"]
+        else:   # the image-by-image path: one capture per image, concatenated per level like forward_heads_each does
+            cat = lambda ts: torch.cat(list(ts))                                                    # noqa: E731
+            layers = [{"a": [cat(c["layers"][k]["a"][l] for c in cap) for l in range(nl)],
+                       "y": [cat(c["layers"][k]["y"][l] for c in cap) for l in range(nl)],
+                       "aff": [(cat(c["layers"][k]["aff"][l][0] for c in cap), cat(c["layers"][k]["aff"][l][1] for c in cap))
+                               for l in range(nl)]} for k in range(4)]
+        from .weights import dgrad_bank
+        dev = d_towers[0].device
+        tg = {"cls_tower": [None] * 3, "reg_tower": [None] * 3, "cls_gn": [None] * 3, "reg_gn": [None] * 3}
+        half = lambda ts, k: [t[..., 256 * k:256 * (k + 1)] for t in ts]                            # noqa: E731
+        prev, ops.PROFILE_STAGE = ops.PROFILE_STAGE, "towers"
+        try:
+            d = d_towers
+            for k in (3, 2, 1, 0):
+                lay = layers[k]
+                gamma = self.gn0_gamma if k == 0 else self.both_gn[k - 1][0]
+                lay["stats"] = ops.groupnorm_stats_levels(lay["y"], 64)
+                lay["g"] = d
+                dys, d_gamma, d_beta = ops.groupnorm_relu_backward_levels(lay["y"], d, lay["aff"], lay["stats"], gamma, 64)
+                lay["dy"] = dys
+                if k == 0:
+                    tg["gn0"] = (d_gamma, d_beta)
+                    tg["tower0"] = ops.conv3x3_wgrad_levels(lay["a"], dys)
+                    d_feats = ops.conv3x3_dgrad_levels(dys, dgrad_bank(self.tower0.w))
+                    break
+                tg["cls_gn"][k - 1], tg["reg_gn"][k - 1] = (d_gamma[:256], d_beta[:256]), (d_gamma[256:], d_beta[256:])
+                d = [torch.empty(tuple(t.shape), device=dev, dtype=torch.float32) for t in dys]
+                for h, (name, tower) in enumerate((("cls_tower", self.cls_tower), ("reg_tower", self.reg_tower))):
+                    tg[name][k - 1] = ops.conv3x3_wgrad_levels([a[:, :, :, 8 * h:8 * (h + 1)] for a in lay["a"]], half(dys, h))
+                    ops.conv3x3_dgrad_levels(half(dys, h), dgrad_bank(tower[k - 1].w), outs=d, out_channel_offset=256 * h)
+        finally:
+            ops.PROFILE_STAGE = prev
+        out = (losses, fg, grads, param_grads, d_towers, tg, d_feats)
+        if want_inputs:
+            out += (dict(inp, feats=layers[0]["a"], layers=layers),)
+        return out
+
+    def refresh_towers(self, sd):
+        """refresh_outputs' twin for the towers: repack the reference-layout values in sd -- head.classification_head.conv.{0,3,6,9}
+        and head.regression_head.conv.{0,3,6,9} (.weight / .bias: the convolutions) and conv.{1,4,7,10} (the GroupNorms) -- into
+        tower0, cls_tower, reg_tower and every GroupNorm tensor, the concatenated copies gn0_gamma / gn0_beta / both_gn included,
+        the way the constructor packs them.  Everything is built and checked first (shapes, the f16x3 range check), then COPIED
+        INTO the existing tensors: addresses, launch plans and captured graphs survive; a refusal leaves the engine as it was."""
+        c, r = "head.classification_head", "head.regression_head"
+        val = lambda k: sd[k].detach().cpu()                                                         # noqa: E731
+        tconv = lambda t, i: pack_conv(val(f"{t}.conv.{3 * i}.weight"), val(f"{t}.conv.{3 * i}.bias"), pad=1)   # noqa: E731
+        gn = lambda t, i, k: val(f"{t}.conv.{3 * i + 1}.{k}").float()                                # noqa: E731
+        convs = [(self.tower0, concat_cout([tconv(c, 0), tconv(r, 0)]).to(self.device))]
+        convs += [(old, tconv(t, i).to(self.device)) for t, tower in ((c, self.cls_tower), (r, self.reg_tower))
+                  for i, old in enumerate(tower, start=1)]
+        pairs = [(a, b) for old, new in convs for a, b in zip((old.w, old.bias, old.w16), (new.w, new.bias, new.w16))]
+        pairs += [(self.gn0_gamma, torch.cat([gn(c, 0, "weight"), gn(r, 0, "weight")])),
+                  (self.gn0_beta, torch.cat([gn(c, 0, "bias"), gn(r, 0, "bias")]))]
+        for i in range(1, 4):
+            gc, bc, gr, br = gn(c, i, "weight"), gn(c, i, "bias"), gn(r, i, "weight"), gn(r, i, "bias")
+            pairs += [(self.cls_gn[i - 1][0], gc), (self.cls_gn[i - 1][1], bc), (self.reg_gn[i - 1][0], gr), (self.reg_gn[i - 1][1], br),
+                      (self.both_gn[i - 1][0], torch.cat([gc, gr])), (self.both_gn[i - 1][1], torch.cat([bc, br]))]
+        for a, b in pairs:
+            if (a is None) != (b is None) or (a is not None and (a.shape != b.shape or a.dtype != b.dtype)):
+                raise ValueError("refresh_towers: the values do not have the engine's shapes")
+            if a is not None and a.dtype == torch.float32 and not bool(torch.isfinite(b).all()):
+                raise ValueError("refresh_towers: non-finite values")
+        with torch.inference_mode(), ops.on_device(self.device):
+            for a, b in pairs:
+                if a is not None:
+                    a.copy_(b)
 
     @ops.device_guarded
     def detect(self, images, cand=None, det=None, nms_scratch=None):

@@ -868,6 +868,171 @@ def conv3x3_thin_backward_levels(a16s, members, *, want_dx=True, dx_out=None, dx
     return results, dxs
 
 
+# ---- the backward of a tower layer: conv3x3 -> GroupNorm -> ReLU (include/handnet_hip_train.h) ----
+_BIG_WORKSPACES = {}
+
+
+def _backward_workspace(device, nbytes):
+    """The convolution workspace where the partial sums fit it, else one grown buffer per (device, stream): the weight
+    gradient's partials are (K ranges) x |dW| floats, beyond the split-K workspace for a 256 -> 256 layer."""
+    ws = _conv_workspace(device)
+    if nbytes <= 4 * ws.numel():
+        return ws
+    key = (device.index, _stream())
+    big = _BIG_WORKSPACES.get(key)
+    if big is None or 4 * big.numel() < nbytes:
+        big = _BIG_WORKSPACES[key] = torch.empty(((nbytes + 3) // 4,), device=device, dtype=torch.float32)
+    return big
+
+
+def _level_count(ts, what):
+    if not 1 <= len(ts) <= _lib.HN_FCOS_MAX_LEVELS:
+        raise ValueError(f"{what}: 1..{_lib.HN_FCOS_MAX_LEVELS} levels")
+
+
+def _gn_levels_arg(ys, groups, what):
+    """The raw fp32 outputs of one layer over the levels -> (hn_gn_bwd_levels with sizes and y stamped, n, c, y stride)."""
+    _level_count(ys, what)
+    c = ys[0].shape[3] if ys[0].dim() == 4 else -1
+    n, ystride = _f32_levels(ys, c)
+    if c % 8 or c > 512 or groups <= 0 or c % groups or (c // groups) % 8:
+        raise ValueError(f"{what}: C must be a multiple of 8, at most 512, and C / groups a multiple of 8 (C {c}, groups {groups})")
+    lv = _lib.GnBwdLevels()
+    lv.count = len(ys)
+    for i, y in enumerate(ys):
+        lv.h[i], lv.w[i], lv.y[i] = y.shape[1], y.shape[2], y.data_ptr()
+    return lv, n, c, ystride
+
+
+def _gn_ws(lv, n, c, groups, device):
+    nbytes = _lib.load().hn_groupnorm_relu_backward_ws_bytes(C.byref(lv), n, c, groups)
+    if nbytes < 0:
+        check(1, "hn_groupnorm_relu_backward_ws_bytes")
+    return _backward_workspace(device, nbytes)
+
+
+def groupnorm_stats_levels(ys, groups, eps=1e-5):
+    """mean and rstd of GroupNorm per (level, image, group) from the raw outputs ys[l] fp32 [N,h_l,w_l,C] (channel slices are
+    fine) -> [(mean [N,G], rstd [N,G])] per level: mean = sum y / M, rstd = 1 / sqrt(sum y^2 / M - mean^2 + eps), fp32 partial
+    sums per 64-pixel chunk in a fixed order, combined in fp64 (hn_groupnorm_stats_levels_f32).  What the forward's finalize
+    computes before it folds the two into its scale / shift tables."""
+    lib = _lib.load()
+    lv, n, c, ystride = _gn_levels_arg(ys, groups, "groupnorm_stats_levels")
+    dev = ys[0].device
+    tables = torch.empty((len(ys), 2, n, groups), device=dev, dtype=torch.float32)
+    for i in range(len(ys)):
+        lv.mean[i], lv.rstd[i] = tables[i, 0].data_ptr(), tables[i, 1].data_ptr()
+    ws = _gn_ws(lv, n, c, groups, dev)
+    check(lib.hn_groupnorm_stats_levels_f32(C.byref(lv), n, c, groups, ystride, float(eps), ptr(ws), 4 * ws.numel(), _stream()),
+          "hn_groupnorm_stats_levels_f32")
+    return [(tables[i, 0], tables[i, 1]) for i in range(len(ys))]
+
+
+def groupnorm_relu_backward_levels(ys, gs, affines, stats, gamma, groups, dy_out=None):
+    """The backward of relu(GroupNorm(y)) over the levels of one tower layer (hn_groupnorm_relu_backward_f32; DESIGN.md section
+    9u): ys[l] = the raw convolution outputs, gs[l] = the gradients at the ReLU'd result, fp32 [N,h_l,w_l,C] (channel slices are
+    fine); affines[l] = the forward's (scale, shift) [N,C] tables; stats[l] = (mean, rstd) [N,G] of groupnorm_stats_levels; gamma
+    [C] -> (dys per level, d_gamma [C], d_beta [C]).  The mask is the sign of fma(y, scale, shift), the forward's own expression.
+    d_gamma and d_beta are ONE sum over levels and images.  dy_out: per-level fp32 tensors (or channel slices) to write instead
+    of fresh ones.  Three launches, every element written once, the same bytes on every run; refusals come before a launch."""
+    lib = _lib.load()
+    what = "groupnorm_relu_backward_levels"
+    lv, n, c, ystride = _gn_levels_arg(ys, groups, what)
+    dev, nl = ys[0].device, len(ys)
+    if len(gs) != nl or len(affines) != nl or len(stats) != nl or (dy_out is not None and len(dy_out) != nl):
+        raise ValueError(f"{what}: one gradient, one (scale, shift) pair and one (mean, rstd) pair per level")
+    _, gstride = _f32_levels(gs, c)
+    dys = [torch.empty(tuple(y.shape), device=dev, dtype=torch.float32) for y in ys] if dy_out is None else list(dy_out)
+    _, dstride = _f32_levels(dys, c)
+    _req(gamma, name="gamma")
+    if tuple(gamma.shape) != (c,):
+        raise ValueError(f"{what}: gamma must hold C values")
+    tstride = affines[0][0].stride(0)
+    for i, (y, g, dy, (scale, shift), (mean, rstd)) in enumerate(zip(ys, gs, dys, affines, stats)):
+        if tuple(g.shape) != tuple(y.shape) or tuple(dy.shape) != tuple(y.shape) or g.device != dev or dy.device != dev:
+            raise ValueError(f"{what}: gradients must have the outputs' shapes and device")
+        _table_stride(scale, shift, n, c, tstride)
+        for t in (mean, rstd):
+            if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (n, groups) or not t.is_contiguous():
+                raise ValueError(f"{what}: mean / rstd must be dense fp32 GPU [N, groups] tables")
+        lv.g[i], lv.dy[i], lv.scale[i], lv.shift[i] = g.data_ptr(), dy.data_ptr(), scale.data_ptr(), shift.data_ptr()
+        lv.mean[i], lv.rstd[i] = mean.data_ptr(), rstd.data_ptr()
+    d_gamma = torch.empty((c,), device=dev, dtype=torch.float32)
+    d_beta = torch.empty((c,), device=dev, dtype=torch.float32)
+    ws = _gn_ws(lv, n, c, groups, dev)
+    timer = _profile_start()
+    check(lib.hn_groupnorm_relu_backward_f32(C.byref(lv), n, c, groups, ystride, gstride, dstride, tstride, ptr(gamma),
+                                             ptr(d_gamma), ptr(d_beta), ptr(ws), 4 * ws.numel(), _stream()),
+          "hn_groupnorm_relu_backward_f32")
+    if timer is not None:
+        def describe():
+            rows = _rows(ys)
+            return ("f32", "gn-bwd"), 0, (1, rows, 1, c, c, 1, 1, 1)
+        _profile_stop(timer, describe)
+    return dys, d_gamma, d_beta
+
+
+def conv3x3_wgrad_levels(a16s, dys):
+    """Weight and bias gradient of a 3x3 / stride 1 / pad 1 convolution on the f32-input MFMA (hn_conv3x3_wgrad_f32; DESIGN.md
+    section 9u): a16s[l] = the S32 inputs the forward read [N,h_l,w_l,Cin/32,2,32], dys[l] = the gradients at its outputs, fp32
+    [N,h_l,w_l,Cout]; both may be channel slices; Cin and Cout multiples of 32, at most 512 -> (dW [Cout,3,3,Cin], db [Cout]),
+    ONE sum over levels and images.  A dW element is one fmaf chain over the pixels of a K range, then the ranges in order; two
+    launches, every element written once, the same bytes on every run."""
+    lib = _lib.load()
+    _level_count(a16s, "conv3x3_wgrad_levels")
+    if len(dys) != len(a16s):
+        raise ValueError("conv3x3_wgrad_levels: one gradient per level")
+    cin, cout = channels(a16s[0]), dys[0].shape[3] if dys[0].dim() == 4 else -1
+    n, astride = _s32_levels(a16s, cin)
+    if _f32_levels(dys, cout)[0] != n:
+        raise ValueError("conv3x3_wgrad_levels: gradients must have the inputs' batch size")
+    dystride = _pixel_stride(dys[0], "dy")
+    if cout % 32 or not 0 < cout <= 512 or not 0 < cin <= 512:
+        raise ValueError(f"conv3x3_wgrad_levels: Cin and Cout must be multiples of 32, at most 512 (Cin {cin}, Cout {cout})")
+    dev = a16s[0].device
+    lv = _lib.WgradLevels()
+    lv.count = len(a16s)
+    for i, (a, dy) in enumerate(zip(a16s, dys)):
+        if tuple(dy.shape[1:3]) != tuple(a.shape[1:3]) or dy.device != dev:
+            raise ValueError("conv3x3_wgrad_levels: gradients must have the inputs' map sizes and device")
+        lv.h[i], lv.w[i], lv.a16[i], lv.dy[i] = a.shape[1], a.shape[2], a.data_ptr(), dy.data_ptr()
+    nbytes = lib.hn_conv3x3_wgrad_ws_bytes(C.byref(lv), n, cin, cout)
+    if nbytes < 0:
+        check(1, "hn_conv3x3_wgrad_ws_bytes")
+    ws = _backward_workspace(dev, nbytes)
+    dw = torch.empty((cout, 3, 3, cin), device=dev, dtype=torch.float32)
+    db = torch.empty((cout,), device=dev, dtype=torch.float32)
+    timer = _profile_start()
+    check(lib.hn_conv3x3_wgrad_f32(C.byref(lv), n, cin, cout, astride, dystride, ptr(dw), ptr(db), ptr(ws), 4 * ws.numel(),
+                                   _stream()), "hn_conv3x3_wgrad_f32")
+    if timer is not None:
+        def describe():
+            rows = _rows(a16s)
+            return ("f32", "wgrad"), rows * cout * 9 * cin, (1, rows, 1, cin, cout, 3, 1, 1)
+        _profile_stop(timer, describe)
+    return dw, db
+
+
+def conv3x3_dgrad_levels(dys, bank, outs=None, out_channel_offset=0):
+    """Input gradient of a 3x3 / stride 1 / pad 1 convolution: the FORWARD convolution of dys[l] (fp32 [N,h_l,w_l,Cout],
+    channel slices are fine) with bank = weights.dgrad_bank(w) [Cin,3,3,Cout] on the exact f32-MFMA kernel, one launch per
+    level -> fp32 [N,h_l,w_l,Cin] per level, or written into channels out_channel_offset .. + Cin of outs[l].  An element is one
+    fmaf chain over its 9 Cout terms."""
+    _level_count(dys, "conv3x3_dgrad_levels")
+    cin = bank.shape[0]
+    if outs is None:
+        if out_channel_offset:
+            raise ValueError("out_channel_offset needs outs")
+        outs = [None] * len(dys)
+    elif len(outs) != len(dys):
+        raise ValueError("conv3x3_dgrad_levels: one output per level")
+    res = []
+    for dy, out in zip(dys, outs):
+        view = None if out is None else out[..., out_channel_offset:out_channel_offset + cin]
+        res.append(conv2d_nhwc(dy, bank, None, pad=1, out=view))
+    return res
+
+
 def thin_uses_flat(xs, cw) -> bool:
     """Would conv3x3_thin_levels(xs, cw) run the P-form kernel (True) or the tap kernel (False)?"""
     cout, _, _, cin = cw.w.shape

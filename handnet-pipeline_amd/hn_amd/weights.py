@@ -136,6 +136,14 @@ def concat_cout(convs) -> ConvW:
     return ConvW(w.contiguous(), b, c0.stride, c0.pad, c0.dil)
 
 
+def dgrad_bank(w: torch.Tensor) -> torch.Tensor:
+    """The filter bank whose FORWARD 3x3 / pad 1 convolution is the input gradient of the convolution with w [Cout,3,3,Cin]:
+    w'[ci, r, s, co] = w[co, 2 - r, 2 - s, ci] (flipped taps, transposed channels), contiguous [Cin,3,3,Cout]."""
+    if w.dim() != 4 or tuple(w.shape[1:3]) != (3, 3):
+        raise ValueError("dgrad_bank needs a [Cout,3,3,Cin] filter bank")
+    return w.flip(1, 2).permute(3, 1, 2, 0).contiguous()
+
+
 def strip_prefix(sd, prefix):
     """Lightning checkpoints store A2J under 'a2j.' (a2j/a2j.py:277)."""
     if any(k.startswith(prefix) for k in sd):
