@@ -17,8 +17,10 @@ criterion's backward at those head tensors in one more launch (hn_amd.ops.fcos_l
 parameter names (hn_amd.ops.conv3x3_thin_backward_levels); after a step on those parameters,
 `refresh_outputs()` repacks them into the engine.  `tower_grads` carries the backward on through the four tower layers (GroupNorm
 and 256 -> 256 convolution gradients), so that every parameter of the head has a gradient, and
-`refresh_towers()` is `refresh_outputs()` for them.  There is no backward pass through the FPN or the backbone and no optimizer on
-the device; without the opt-in, train mode and targets raise as before.
+`refresh_towers()` is `refresh_outputs()` for them.  `fpn_grads` carries it on through the FPN (the 3x3 output convolutions, the
+top-down read and the 1x1 laterals) with `refresh_fpn()` as its refresh: head + FPN on a frozen ResNet-34 is
+a complete step, and the gradient at C3 / C4 / C5 comes out.  The backward stops at the body's outputs: there is none through the
+ResNet body and no optimizer on the device; without the opt-in, train mode and targets raise as before.
 """
 from __future__ import annotations
 
@@ -192,8 +194,14 @@ class FCOS(EngineOwner):
         GroupNorms): the engine's gradients permuted to the reference's layout, the stacked layer 0 (one 256 -> 512 bank, one
         512-channel GroupNorm) un-concatenated into the two towers' halves.  With it every parameter of the head has a gradient.
         assign: also set .grad of the module's own parameters, so that an optimizer step over the head followed by
-        refresh_towers() and refresh_outputs() is a fine-tuning step on a frozen backbone.  There is no backward through the FPN
-        or the backbone."""
+        refresh_towers() and refresh_outputs() is a fine-tuning step on a frozen backbone.  fpn_grads carries the backward on
+        through the FPN; there is none through the ResNet body."""
+        eng, batch, targets = self._grads_args(images, targets)
+        losses, fg, _, param_grads, _, tg, _ = eng.tower_grads(batch, targets, radius=self.center_sampling_radius)
+        return losses, fg, self._named_grads(self._named_tower_grads(param_grads, tg), assign)
+
+    def _grads_args(self, images, targets):
+        """-> (engine, batch, packed targets) the way output_grads prepares them"""
         dev = self._require_gpu()
         eng = self.engine()
         batch = self._batch(images)
@@ -201,8 +209,10 @@ class FCOS(EngineOwner):
             oh, ow = eng.geometry(*batch.shape[-2:])[:2]
         else:
             oh, ow = zip(*[g[2:] for g in eng.list_geometry(batch)[0]])
-        targets = self._packed_targets(images, batch, targets, oh, ow, dev)
-        losses, fg, _, param_grads, _, tg, _ = eng.tower_grads(batch, targets, radius=self.center_sampling_radius)
+        return eng, batch, self._packed_targets(images, batch, targets, oh, ow, dev)
+
+    def _named_tower_grads(self, param_grads, tg):
+        """the engine's output and tower gradients -> the reference's names and layouts"""
         grads = self._named_output_grads(param_grads)
         for head, tower, gn, h in self._TOWERS:
             rows = slice(256 * h, 256 * (h + 1))
@@ -213,7 +223,37 @@ class FCOS(EngineOwner):
                 grads[f"{head}.conv.{3 * i}.bias"] = d_b.clone()
                 grads[f"{head}.conv.{3 * i + 1}.weight"] = d_gamma.clone()
                 grads[f"{head}.conv.{3 * i + 1}.bias"] = d_beta.clone()
+        return grads
+
+    def fpn_grads(self, images: List[torch.Tensor], targets, assign: bool = False):
+        """tower_grads(images, targets) carried on through the FPN (FCOSEngine.fpn_grads) -> (losses, fg,
+        grads): grads holds tower_grads' entries and backbone.fpn.inner_blocks.{0,1,2}.weight [256,Cin,1,1] / .bias [256] (the
+        1x1 laterals, Cin 128 / 256 / 512) and backbone.fpn.layer_blocks.{0,1,2}.weight [256,256,3,3] / .bias [256] (the output
+        convolutions): every parameter the reference trains outside the ResNet body.  assign: also set .grad, so that an optimizer
+        step followed by refresh_fpn(), refresh_towers() and refresh_outputs() is a fine-tuning step of head + FPN on a frozen
+        ResNet-34.  The backward stops at the body's outputs (FCOSEngine.fpn_grads also returns the gradient there)."""
+        eng, batch, targets = self._grads_args(images, targets)
+        res = eng.fpn_grads(batch, targets, radius=self.center_sampling_radius)
+        losses, fg, param_grads, tg, fg_fpn = res[0], res[1], res[3], res[5], res[7]
+        grads = self._named_tower_grads(param_grads, tg)
+        for i in range(3):
+            d_w, d_b = fg_fpn["inner"][i]
+            grads[f"backbone.fpn.inner_blocks.{i}.weight"] = d_w.reshape(d_w.shape[0], d_w.shape[1], 1, 1).clone()
+            grads[f"backbone.fpn.inner_blocks.{i}.bias"] = d_b.clone()
+            d_w, d_b = fg_fpn["layer"][i]
+            grads[f"backbone.fpn.layer_blocks.{i}.weight"] = d_w.permute(0, 3, 1, 2).contiguous()
+            grads[f"backbone.fpn.layer_blocks.{i}.bias"] = d_b.clone()
         return losses, fg, self._named_grads(grads, assign)
+
+    def refresh_fpn(self):
+        """Repack the module's CURRENT values of the FPN's twelve parameters (those fpn_grads names) into the engine's inner and
+        layer banks, with the f16x3 range check; like refresh_towers() the engine is kept and its tensors keep their addresses.  A
+        value beyond the fp16 range raises and leaves the engine as it was."""
+        params = dict(self.named_parameters())
+        sd = {f"backbone.fpn.{b}.{i}.{k}": params[f"backbone.fpn.{b}.{i}.{k}"] for b in ("inner_blocks", "layer_blocks")
+              for i in range(3) for k in ("weight", "bias")}
+        self.engine().refresh_fpn(sd)
+        return self
 
     def refresh_towers(self):
         """Repack the module's CURRENT values of the towers' parameters (the convolutions and GroupNorms tower_grads names) into

@@ -306,6 +306,14 @@ TRAIN_SIGNATURES = {
     "hn_conv3x3_wgrad_f32": (C.c_int, [C.POINTER(WgradLevels)] + [C.c_int] * 5 + [VP, VP, VP, C.c_int64, VP]),
 }
 
+# the entry points of include/handnet_hip_train_fpn.h (the FPN's backward: lateral weight gradient, adjoint of the top-down
+# read): functions only, no struct; tests/test_fpn_bwd_cpu.py keeps it in step with that header
+TRAIN_FPN_SIGNATURES = {
+    "hn_conv1x1_wgrad_ws_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "hn_conv1x1_wgrad_f32": (C.c_int, [VP, VP, C.c_int64] + [C.c_int] * 4 + [VP, VP, VP, C.c_int64, VP]),
+    "hn_upsample_nearest_backward_f32": (C.c_int, [VP] + [C.c_int] * 8 + [VP, VP]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -329,7 +337,7 @@ def load(build_if_missing: bool = True) -> C.CDLL:
                 raise RuntimeError(f"{path} is missing; run `python __graft_entry__.py build`")
             _build.build_library()
         lib = C.CDLL(str(path))
-        for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items()) + list(TRAIN_FPN_SIGNATURES.items()):
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:

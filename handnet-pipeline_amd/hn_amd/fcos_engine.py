@@ -142,6 +142,10 @@ class FCOSEngine:
         # (and runs the lock-step schedule, whose tensors are the carried schedule's bit for bit)
         self._capture_towers = False
         self._tower_cap = None
+        # fpn_grads: backbone() appends, per call, the S32 tensors the FPN read and wrote ({"c": [c3, c4, c5], "lat": [lat3,
+        # lat4, lat5]}) to _fpn_cap; off (always, outside that call): nothing is kept and nothing else differs
+        self._capture_fpn = False
+        self._fpn_cap = None
 
     def _keep(self, kind, a):
         if self._capture is not None:
@@ -194,6 +198,8 @@ class FCOSEngine:
         lat5 = self._conv(c5, self.inner[2])
         lat4 = self._conv(c4, self.inner[1], residual=lat5, res_upsample=True)
         lat3 = self._conv(c3, self.inner[0], residual=lat4, res_upsample=True)
+        if self._capture_fpn and self._fpn_cap is not None:
+            self._fpn_cap.append({"c": [c3, c4, c5], "lat": [lat3, lat4, lat5]})
         if self.precision == "f16x3" and self.group_towers:
             # the three FPN output convs (own weights, own map size) are independent: one grouped launch
             return ops.conv2d_nhwc_grouped([lat3, lat4, lat5], self.layer, pad=1, out_split=True)
@@ -707,6 +713,73 @@ class FCOSEngine:
                 raise ValueError("refresh_towers: the values do not have the engine's shapes")
             if a is not None and a.dtype == torch.float32 and not bool(torch.isfinite(b).all()):
                 raise ValueError("refresh_towers: non-finite values")
+        with torch.inference_mode(), ops.on_device(self.device):
+            for a, b in pairs:
+                if a is not None:
+                    a.copy_(b)
+
+    @ops.device_guarded
+    def fpn_grads(self, images, targets, radius=1.5, upstream=None, want_inputs=False):
+        """tower_grads carried on through the FPN -- the three 3x3 output convolutions, the top-down nearest-neighbour read and
+        the three 1x1 laterals -- down to the outputs of the ResNet body -> tower_grads' seven results,
+        then fpn_param_grads and d_body: fpn_param_grads = {"inner": [(dW [256,Cin_l], db [256])] x 3, "layer": [(dW
+        [256,3,3,256], db [256])] x 3} in the engine's layouts, level order P3, P4, P5; d_body = per level fp32 [N,h,w,Cin_l],
+        the gradient at C3 / C4 / C5 (Cin 128 / 256 / 512).  With G_l = d_feats[l]: the output convolutions' weight gradients are
+        ops.conv3x3_wgrad_levels on (lat_l, G_l), one call per level (each level has its own bank); D3 = dgrad(G3), D4 =
+        dgrad(G4) + upT(D3), D5 = dgrad(G5) + upT(D4), where upT is ops.upsample_nearest_backward and goes in as the f32 kernel's
+        dense residual; the laterals' gradients are ops.conv1x1_wgrad on (c_l, D_l) and dC_l = the 1x1 convolution of D_l with
+        weights.dgrad_bank_1x1.  The S32 rounding of lat_l is passed straight through.  For this call only, backbone() keeps
+        c3..c5 and lat3..lat5; inference is untouched.  Refusals are tower_grads'.  images / targets as tower_grads takes them (a
+        list of different sizes: image by image, concatenated per level).  want_inputs: tower_grads' dict plus, per level, "c",
+        "lat", "D" and "U" (U[l] = upT(D[l - 1]), the residual of D[l]'s launch; None at P3)."""
+        self._tower_route_check(images)
+        self._capture_fpn, self._fpn_cap = True, []
+        try:
+            res = self.tower_grads(images, targets, radius, upstream, want_inputs=True)
+        finally:
+            cap, self._fpn_cap, self._capture_fpn = self._fpn_cap, None, False
+        *res, inp = res
+        d_feats = res[6]
+        nl = len(d_feats)
+        if not cap or nl != 3:
+            raise RuntimeError("fpn_grads: the backbone kept nothing")
+        join = lambda kind, l: cap[0][kind][l] if len(cap) == 1 else torch.cat([c[kind][l] for c in cap])   # noqa: E731
+        cs, lats = [join("c", l) for l in range(nl)], [join("lat", l) for l in range(nl)]
+        from .weights import dgrad_bank, dgrad_bank_1x1
+        prev, ops.PROFILE_STAGE = ops.PROFILE_STAGE, "fpn"
+        try:
+            layer = [ops.conv3x3_wgrad_levels([lats[l]], [d_feats[l]]) for l in range(nl)]
+            ds, ups = [], [None]
+            for l in range(nl):
+                ds.append(ops.conv3x3_dgrad_levels([d_feats[l]], dgrad_bank(self.layer[l].w), residuals=[ups[l]])[0])
+                if l + 1 < nl:
+                    ups.append(ops.upsample_nearest_backward(ds[l], tuple(lats[l + 1].shape[1:3])))
+            inner = [ops.conv1x1_wgrad(cs[l], ds[l]) for l in range(nl)]
+            d_body = [ops.conv2d_nhwc(ds[l], dgrad_bank_1x1(self.inner[l].w)) for l in range(nl)]
+        finally:
+            ops.PROFILE_STAGE = prev
+        out = tuple(res) + ({"inner": inner, "layer": layer}, d_body)
+        if want_inputs:
+            out += (dict(inp, c=cs, lat=lats, D=ds, U=ups),)
+        return out
+
+    def refresh_fpn(self, sd):
+        """refresh_towers' twin for the FPN: repack the reference-layout values in sd -- backbone.fpn.inner_blocks.{0,1,2} and
+        backbone.fpn.layer_blocks.{0,1,2} (.weight / .bias) -- into the six banks of inner and layer, the way the constructor
+        packs them.  Everything is built and checked first (shapes, finiteness, the f16x3 range check), then COPIED INTO the
+        existing tensors: addresses, launch plans and captured graphs survive; a refusal leaves the engine as it was."""
+        f = "backbone.fpn."
+        val = lambda k: sd[k].detach().cpu()                                                         # noqa: E731
+        convs = [(self.inner[i], pack_conv(val(f"{f}inner_blocks.{i}.weight"), val(f"{f}inner_blocks.{i}.bias")).to(self.device))
+                 for i in range(3)]
+        convs += [(self.layer[i], pack_conv(val(f"{f}layer_blocks.{i}.weight"), val(f"{f}layer_blocks.{i}.bias"), pad=1).to(self.device))
+                  for i in range(3)]
+        pairs = [(a, b) for old, new in convs for a, b in zip((old.w, old.bias, old.w16), (new.w, new.bias, new.w16))]
+        for a, b in pairs:
+            if (a is None) != (b is None) or (a is not None and (a.shape != b.shape or a.dtype != b.dtype)):
+                raise ValueError("refresh_fpn: the values do not have the engine's shapes")
+            if a is not None and a.dtype == torch.float32 and not bool(torch.isfinite(b).all()):
+                raise ValueError("refresh_fpn: non-finite values")
         with torch.inference_mode(), ops.on_device(self.device):
             for a, b in pairs:
                 if a is not None:

@@ -1013,11 +1013,12 @@ def conv3x3_wgrad_levels(a16s, dys):
     return dw, db
 
 
-def conv3x3_dgrad_levels(dys, bank, outs=None, out_channel_offset=0):
+def conv3x3_dgrad_levels(dys, bank, outs=None, out_channel_offset=0, residuals=None):
     """Input gradient of a 3x3 / stride 1 / pad 1 convolution: the FORWARD convolution of dys[l] (fp32 [N,h_l,w_l,Cout],
     channel slices are fine) with bank = weights.dgrad_bank(w) [Cin,3,3,Cout] on the exact f32-MFMA kernel, one launch per
     level -> fp32 [N,h_l,w_l,Cin] per level, or written into channels out_channel_offset .. + Cin of outs[l].  An element is one
-    fmaf chain over its 9 Cout terms."""
+    fmaf chain over its 9 Cout terms.  residuals: per level None or a dense fp32 [N,h_l,w_l,Cin] tensor that the epilogue adds
+    after the chain (one more rounding; the FPN's top-down term)."""
     _level_count(dys, "conv3x3_dgrad_levels")
     cin = bank.shape[0]
     if outs is None:
@@ -1026,11 +1027,86 @@ def conv3x3_dgrad_levels(dys, bank, outs=None, out_channel_offset=0):
         outs = [None] * len(dys)
     elif len(outs) != len(dys):
         raise ValueError("conv3x3_dgrad_levels: one output per level")
+    if residuals is None:
+        residuals = [None] * len(dys)
+    elif len(residuals) != len(dys):
+        raise ValueError("conv3x3_dgrad_levels: one residual (or None) per level")
     res = []
-    for dy, out in zip(dys, outs):
+    for dy, out, residual in zip(dys, outs, residuals):
         view = None if out is None else out[..., out_channel_offset:out_channel_offset + cin]
-        res.append(conv2d_nhwc(dy, bank, None, pad=1, out=view))
+        res.append(conv2d_nhwc(dy, bank, None, pad=1, out=view, residual=residual))
     return res
+
+
+# ---- the backward of the FPN: lateral weight gradient, adjoint of the top-down read (include/handnet_hip_train_fpn.h; 9v) ----
+def conv1x1_wgrad(a16, dy):
+    """Weight and bias gradient of a 1x1 / stride 1 convolution on the f32-input MFMA (hn_conv1x1_wgrad_f32; DESIGN.md section
+    9v): a16 = the S32 input the forward read [N,h,w,Cin/32,2,32], dy = the gradient at its output, fp32 [N,h,w,Cout]; both may
+    be channel slices; Cin and Cout multiples of 32, at most 512 -> (dW [Cout,Cin], db [Cout]), ONE sum over images and pixels.
+    A dW element is one fmaf chain over the pixels of a K range, then the ranges in order; two launches, every element written
+    once, the same bytes on every run."""
+    lib = _lib.load()
+    if not is_split(a16) or dy.dim() != 4 or dy.dtype != torch.float32:
+        raise TypeError("conv1x1_wgrad: a16 must be an S32 tensor [N,h,w,Cin/32,2,32] and dy fp32 [N,h,w,Cout]")
+    cin, cout = channels(a16), dy.shape[3]
+    if cout % 32 or not 0 < cout <= 512 or not 0 < cin <= 512:
+        raise ValueError(f"conv1x1_wgrad: Cin and Cout must be multiples of 32, at most 512 (Cin {cin}, Cout {cout})")
+    dev = a16.device
+    if tuple(dy.shape[:3]) != tuple(a16.shape[:3]) or dy.device != dev:
+        raise ValueError("conv1x1_wgrad: the gradient must have the input's batch size, map size and device")
+    rows = _rows([a16])
+    if rows == 0:
+        raise ValueError("conv1x1_wgrad: empty map")
+    n, astride = _s32_levels([a16], cin, "conv1x1_wgrad: a16")
+    dystride = _f32_levels([dy], cout)[1]
+    nbytes = lib.hn_conv1x1_wgrad_ws_bytes(rows, cin, cout)
+    if nbytes < 0:
+        check(1, "hn_conv1x1_wgrad_ws_bytes")
+    ws = _backward_workspace(dev, nbytes)
+    dw = torch.empty((cout, cin), device=dev, dtype=torch.float32)
+    db = torch.empty((cout,), device=dev, dtype=torch.float32)
+    timer = _profile_start()
+    check(lib.hn_conv1x1_wgrad_f32(ptr(a16), ptr(dy), rows, cin, cout, astride, dystride, ptr(dw), ptr(db), ptr(ws), 4 * ws.numel(),
+                                   _stream()), "hn_conv1x1_wgrad_f32")
+    if timer is not None:
+        def describe():
+            return ("f32", "wgrad1x1"), rows * cout * cin, (1, rows, 1, cin, cout, 1, 1, 1)
+        _profile_stop(timer, describe)
+    return dw, db
+
+
+def upsample_nearest_backward(g, size, out=None):
+    """Adjoint of the convolution epilogues' nearest-neighbour read of a coarser map (hn_upsample_nearest_backward_f32; DESIGN.md
+    section 9v): g = the gradient at the fine map, fp32 [N,OH,OW,C] (a channel slice is fine), size = (rh, rw) of the coarse map,
+    rh <= OH, rw <= OW, C % 4 == 0 -> fp32 [N,rh,rw,C]: out[n,s,t] = the sum of g[n,o,p] over floor(o rh / OH) = s and
+    floor(p rw / OW) = t, one fp32 chain in (row, column) order.  out: an fp32 tensor (or channel slice) to write instead of a
+    fresh one.  One launch, every element written once."""
+    lib = _lib.load()
+    if g.dim() != 4 or g.dtype != torch.float32:
+        raise TypeError("upsample_nearest_backward: g must be fp32 [N,OH,OW,C]")
+    n, c = g.shape[0], g.shape[3]
+    rh, rw = (int(v) for v in size)
+    if c <= 0 or c % 4:
+        raise ValueError(f"upsample_nearest_backward: C must be a multiple of 4 (got {c})")
+    if not (0 < rh <= g.shape[1] and 0 < rw <= g.shape[2]):
+        raise ValueError(f"upsample_nearest_backward: the coarse map {rh} x {rw} must be non-empty and no larger than the fine "
+                         f"map {g.shape[1]} x {g.shape[2]}")
+    if n == 0:
+        raise ValueError("upsample_nearest_backward: empty batch")
+    if out is not None and (out.dim() != 4 or tuple(out.shape) != (n, rh, rw, c) or out.device != g.device):
+        raise ValueError("upsample_nearest_backward: out must be fp32 [N,rh,rw,C] on the gradient's device")
+    gstride = _f32_levels([g], c)[1]
+    if out is None:
+        out = torch.empty((n, rh, rw, c), device=g.device, dtype=torch.float32)
+    ostride = _f32_levels([out], c)[1]
+    timer = _profile_start()
+    check(lib.hn_upsample_nearest_backward_f32(ptr(g), n, g.shape[1], g.shape[2], rh, rw, c, gstride, ostride, ptr(out), _stream()),
+          "hn_upsample_nearest_backward_f32")
+    if timer is not None:
+        def describe():
+            return ("f32", "upsample-bwd"), 0, (1, _rows([g]), 1, c, c, 1, 1, 1)
+        _profile_stop(timer, describe)
+    return out
 
 
 def thin_uses_flat(xs, cw) -> bool:

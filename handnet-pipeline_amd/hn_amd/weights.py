@@ -144,6 +144,14 @@ def dgrad_bank(w: torch.Tensor) -> torch.Tensor:
     return w.flip(1, 2).permute(3, 1, 2, 0).contiguous()
 
 
+def dgrad_bank_1x1(w: torch.Tensor) -> torch.Tensor:
+    """dgrad_bank for a 1x1 convolution with w [Cout,1,1,Cin]: w'[ci, 0, 0, co] = w[co, 0, 0, ci] (nothing to flip), contiguous
+    [Cin,1,1,Cout]; its forward 1x1 convolution is the input gradient."""
+    if w.dim() != 4 or tuple(w.shape[1:3]) != (1, 1):
+        raise ValueError("dgrad_bank_1x1 needs a [Cout,1,1,Cin] filter bank")
+    return w.permute(3, 1, 2, 0).contiguous()
+
+
 def strip_prefix(sd, prefix):
     """Lightning checkpoints store A2J under 'a2j.' (a2j/a2j.py:277)."""
     if any(k.startswith(prefix) for k in sd):
